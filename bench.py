@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- frames/s of N-view 512-px PanSt3R panoptic inference on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--variant v2] [--views 50] [--keyframes 16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--variant v2] [--views 50] [--keyframes 16] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one full scene forward (encoder + DINOv2 on every view, sequential keyframe-memory build, render of every
@@ -16,6 +16,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -154,6 +155,44 @@ def full_size_parity(model, dev, ref, imgs, ts, names, amp='fp16', K=2, panoptic
     return res
 
 
+DUMP_BYTES = {'pointmaps': 16 << 20, 'pred_masks': 40 << 20}      # --dump-outputs: float32 budget of the two per-view outputs (+ < 1 MB of scene outputs)
+
+
+def output_sample(res, scene, seed=0, n_views=None):
+    """--dump-outputs: this rank's share of what one scene step returned, as float32 numpy - the arrays a caller of forward_inference_multi_ar receives.
+    pred_logits [1,Q,C] and out_queries [Q,1,d] whole; per view a fixed sample of pixels when the whole tensors exceed DUMP_BYTES: pointmaps [n,7] and
+    pred_masks [Q,n] at the same n pixels of every run (torch.randperm seeded by (seed, view id), sorted; independent of the rank layout).
+    Returns ({'pred_logits', 'out_queries'}, {view_id: (pointmap sample, mask sample)})."""
+    V = n_views or len(res)
+    f32 = lambda t: t.detach().float().cpu().numpy()
+    views = {}
+    for i, (pm, mk) in res.items():
+        pm, mk = pm[0], mk[0]                                  # [H, W, 7], [Q, h, w]
+        pm, mk = pm.reshape(-1, pm.shape[-1]), mk.reshape(mk.shape[0], -1)
+        out = []
+        for t, key, axis in ((pm, 'pointmaps', 0), (mk, 'pred_masks', 1)):
+            P, per_pixel = t.shape[axis], t.numel() // t.shape[axis]
+            n = min(P, DUMP_BYTES[key] // (4 * V * per_pixel))
+            if n < P:
+                g = torch.Generator().manual_seed(seed * 1000003 + i)
+                idx = torch.randperm(P, generator=g)[:n].sort().values.to(t.device)
+                t = t.index_select(axis, idx)
+            out.append(f32(t))
+        views[i] = tuple(out)
+    return {'pred_logits': f32(scene['pred_logits']), 'out_queries': f32(scene['out_queries'])}, views
+
+
+def write_outputs(path, scene, views):
+    """stack the per-view samples in view id order and write DIR/<name>.npy (float32); 64 MB at most"""
+    arrays = dict(scene, pointmaps=np.stack([views[i][0] for i in sorted(views)]), pred_masks=np.stack([views[i][1] for i in sorted(views)]))
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 REAL_STDOUT = 1
 OVERLAP_PICK = {}        # --overlap auto: per measured mode, what the warm-up timing chose
 
@@ -276,8 +315,12 @@ def main():
     ap.add_argument('--stream-bank', action='store_true', help="plan 'broadcast': send the bank per memory update with asynchronous broadcasts beside the build "
                                                                "(opt-in; default = one event-ordered broadcast behind the build, panst3r_amd/scene.py)")
     ap.add_argument('--tune', action='append', default=[], metavar='KNOB=VALUE', help='pst_tune knob for A/B measurements (G256_PP, PAIR, PAIR_RES); results never depend on a knob')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32: '
+                                                           'pred_logits, out_queries whole; pointmaps, pred_masks as a fixed seeded pixel sample, 64 MB at most)')
     ap.add_argument('--launch-selftest', action='store_true', help='only exercise the rank launch / rendezvous / output plumbing (no model work; CPU + gloo when there is no GPU per rank)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # started the way the driver starts `--gpus 1` (plain `python bench.py --gpus N`): become the launcher of N ranks
@@ -333,8 +376,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(amp, steps, warmup, instrument, panoptic_precision=None):
-        """W untimed warm-up steps (the first also captures the three HIP graphs), then EXACTLY `steps` timed steps between two fences."""
+    dumped = {}
+
+    def measure(amp, steps, warmup, instrument, panoptic_precision=None, keep=False):
+        """W untimed warm-up steps (the first also captures the three HIP graphs), then EXACTLY `steps` timed steps between two fences.
+        keep: sample the outputs of the last timed step into `dumped` (after the second fence, before anything runs the scene again)."""
         mk = lambda ov: model.scene_runner(images, V, H, W, names, num_keyframes=K, use_graphs=not args.eager, overlap=ov, amp=amp, plan=args.plan,
                                            panoptic_precision=panoptic_precision, stream_bank=args.stream_bank)
         if args.overlap == 'auto' and not args.eager and world == 1:
@@ -358,13 +404,21 @@ def main():
                 # runs the two branches of stage 2 back-to-back also under --overlap (event durations not inflated by the other branch)
                 timer = hip.KernelTimer()
                 hip.TIMER = timer
-                runner.run(eager=True, serial=True, copy=False)
+                last = runner.run(eager=True, serial=True, copy=False)
             else:
-                runner.run(copy=False)
+                last = runner.run(copy=False)
         marks[steps].record()
         hip.TIMER = None
         fence()
         elapsed = time.perf_counter() - t0
+        if keep:
+            # copy=False: `last` views the runner's buffers, which the next run() overwrites
+            dumped['scene'], dumped['views'] = output_sample(*last, n_views=V)
+            if world > 1:
+                parts = [None] * world
+                dist.all_gather_object(parts, dumped['views'])
+                dumped['views'] = {i: v for p in parts for i, v in p.items()}
+        del last
         pk = OVERLAP_PICK.get(str(amp) + '/' + str(panoptic_precision))
         if pk is not None and pk.get('serial_digest') is not None and 'after_timed_steps_identical' not in pk:
             # outside the timed region: one more replay of the form that was timed, its outputs against the serial scene's bits of the warm-up
@@ -390,7 +444,7 @@ def main():
         del runner
         return elapsed, (per[len(per) // 2] if per else None), timer, coll
 
-    elapsed, median_ms, timer, coll_ms = measure(args.amp, args.steps, args.warmup, not args.no_kernel_timing)
+    elapsed, median_ms, timer, coll_ms = measure(args.amp, args.steps, args.warmup, not args.no_kernel_timing, keep=bool(args.dump_outputs))
 
     if rank == 0:
         fps = V * args.steps / elapsed
@@ -417,6 +471,8 @@ def main():
                        'scene_algorithmic_tflop': round(scene_flops / 1e12, 2),
                        'scene_mfma_frac': round(scene_flops / (elapsed / args.steps) / world / (PEAK_BF16_TFLOPS * 1e12), 4)},
         }
+        if args.dump_outputs:
+            out['dump_outputs'] = {'dir': args.dump_outputs, 'shapes': write_outputs(args.dump_outputs, dumped['scene'], dumped['views'])}
         if use_dist:
             # what the transport did, measured, next to the one-GPU projection of the same plan (profiles/r3_shard_estimate.txt: every rank's stage
             # graphs replayed on ONE GPU, all-gathers counted as zero, the 453 MB bank broadcast ASSUMED at 100 GB/s)
