@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PST_ABI_VERSION 19
+#define PST_ABI_VERSION 20
 
 /* element type codes: every `*_type` / `dtype16` argument below (and the former `*_fp32` flags: 0 and 1 keep their meaning) */
 #define PST_BF16 0   /* bfloat16, raw uint16 */
@@ -58,7 +58,7 @@ typedef struct pst_gemm_params {
   const float* gamma;                /* [N] LayerScale or NULL */
   const float* res;  int64_t ldr;    /* fp32 residual or NULL; row = res_mod ? m % res_mod : out_row(m) */
   int32_t res_mod;
-  int32_t act;                       /* 0 none, 1 GELU(erf), 2 ReLU */
+  int32_t act;                       /* 0 none, 1 GELU(erf), 2 ReLU, 3 GELU(tanh) = 0.5x(1 + tanh(sqrt(2/pi)(x + 0.044715x^3))) (ABI 20; PST_F32 operands only, 16-bit: PST_EINVAL) */
   int32_t out_fp32;                  /* 0: bf16 C, 1: fp32 C */
   int32_t trans_out;                 /* 1: store C^T, i.e. C[n*ldc + m] (bf16 only; feeds attention V^T) */
   /* output row remap: out_row(m) = grp_in ? (m/grp_in)*grp_out + grp_off + m%grp_in : m   (e.g. skip a CLS row) */
@@ -188,6 +188,17 @@ int pst_layernorm(const void* x, int64_t ldx, int in_fp32, void* y, int64_t ldy,
 int pst_layernorm_add(const void* x, int64_t ldx, int in_fp32, const float* add, int64_t ld_add, void* y, int64_t ldy,
                       int out_fp32, const float* gamma, const float* beta, int rows, int D, float eps,
                       int grp_in, int grp_out, int grp_off, void* stream);
+
+/* ---------------------------------------------------------------- SigLIP text tower (ABI 20)
+ * token_embed: out[b L + l, :] = tok[ids[b, l], :] + pos[l, :]  (transformers SiglipTextEmbeddings; reference text_encoder.py:65-79 via
+ * SiglipTextModel).  ids int32 [B, L] contiguous, tok fp32 [vocab, D], pos fp32 [npos, D] (L <= npos), out fp32 rows with leading dim ldo;
+ * D % 4 == 0, 16-byte aligned tables.  An id outside [0, vocab) is never read: its row is written as zeros and, when `status` (int32 on the
+ * device) is not NULL, *status = PST_EINVAL - the caller validates ids beforehand and reads `status` afterwards.
+ * The rest of the tower needs no entry point of its own: pst_gemm in fp32 mode (act 3 for the MLP), pst_attn_fwd in fp32 mode with the
+ * tokenizer's key-padding mask (uint8 [B, Lpad], m_rs = 0, Lpad % 4 == 0, 1 = blocked), pst_layernorm / pst_gemm on the pooled rows
+ * (leading dim L D), pst_l2norm_rows. */
+int pst_token_embed(const int32_t* ids, int B, int L, const float* tok, int vocab, const float* pos, int npos, int D, float* out, int64_t ldo,
+                    int32_t* status, void* stream);
 
 /* rowstats: the producer-side outputs of the LayerNorm fold for a stream that no GEMM produced (first block of a stack): x [rows, D] of
  * element type x_type (PST_F32, or the 16-bit format itself), D % 64 == 0 -> xcopy 16-bit [rows, D] (optional: NULL when x already is

@@ -568,6 +568,9 @@ static int gemm_validate(const pst_gemm_params* pp) {
     return pst::gemm_f32_validate(p);
   }
   if (p.dtype16 != DT_BF16 && p.dtype16 != DT_F16) { set_error("gemm: dtype16 must be PST_BF16, PST_F16 or PST_F32"); return PST_EINVAL; }
+  if (p.act < 0 || p.act > 2) {            // act 3 (tanh GELU) exists in the fp32 mode only: no 16-bit kernel may fall through to another GELU
+    set_error("gemm: act %d not available with 16-bit operands (0 none, 1 GELU(erf), 2 ReLU; 3 = GELU(tanh) needs fp32 operands)", p.act); return PST_EINVAL;
+  }
   if (p.kernel != 0 && p.kernel != 128 && p.kernel != 256) { set_error("gemm: kernel must be 0 (auto), 128 or 256"); return PST_EINVAL; }
   if (p.kernel == 256 && (p.conv_c > 0 || (p.trans_out && pst::gemm256_persistent_class(p) != 3))) {
     set_error("gemm: the 256x256 kernel has no conv mode, and trans_out only in its persistent class (16-bit, ldc %% 8 == 0, N %% 64 == 0)"); return PST_EINVAL;

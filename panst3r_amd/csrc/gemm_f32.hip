@@ -7,7 +7,8 @@
 // TFLOP/s peak = 1 / 16 of the 16-bit rate) on 128 x 128 x 16 block tiles staged through LDS k-major; a scene in this mode is ~12 x slower than with
 // 16-bit operands.  Every epilogue mode the 16-bit model path uses with an fp32 C is here: bias,
 // exact-erf GELU / ReLU, LayerScale, fp32 residual (in place, broadcast row % res_mod), output row remap, fused pixel-shuffle store, transposed
-// store (V^T for the attention kernel), implicit 3x3 conv A operand, strided batch.  Not here (rejected): 16-bit C, fused RoPE (pst_rope2d runs
+// store (V^T for the attention kernel), implicit 3x3 conv A operand, strided batch.  Plus one epilogue of this mode only: act 3 = tanh-approximate GELU
+// (ABI 20, the SigLIP text tower's MLP, which runs in this mode whatever the caller's precision).  Not here (rejected): 16-bit C, fused RoPE (pst_rope2d runs
 // stand-alone in this mode), the LayerNorm-fold producer / consumer arguments (the fold exists to save 16-bit roundings; fp32 has none to save).
 #include "common.h"
 #include "../../include/panst3r_hip.h"
@@ -141,6 +142,10 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const pst_gemm_params p_i
         float x = acc[i][j][r] + bs[r];
         if (p.act == 1) x = 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
         else if (p.act == 2) x = fmaxf(x, 0.f);
+        else if (p.act == 3) {             // tanh GELU, torch.nn.functional.gelu(approximate='tanh') term by term (the SigLIP text tower's MLP)
+          const float inner = 0.7978845608028654f * (x + 0.044715f * (x * x * x));
+          x = 0.5f * x * (1.0f + tanhf(inner));
+        }
         v[r] = x * gm[r];
       }
       if (p.trans_out) {
@@ -172,6 +177,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const pst_gemm_params p_i
 // argument rules of the fp32 mode (the common shape / null checks were done by pst_gemm)
 int gemm_f32_validate(const pst_gemm_params& p) {
   if (!p.out_fp32) { set_error("gemm (fp32 operands): C must be fp32"); return PST_EINVAL; }
+  if (p.act < 0 || p.act > 3) { set_error("gemm (fp32 operands): act %d unknown (0 none, 1 GELU(erf), 2 ReLU, 3 GELU(tanh))", p.act); return PST_EINVAL; }
   if (p.res && p.res_bf16) { set_error("gemm (fp32 operands): the residual must be fp32"); return PST_EINVAL; }
   if (p.rope_hd || p.xcopy || p.stats_out || p.ln_stats) {
     set_error("gemm (fp32 operands): fused RoPE and the LayerNorm-fold arguments belong to the 16-bit path"); return PST_EINVAL;

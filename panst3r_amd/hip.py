@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PST_LIB') or os.path.join(_HERE, 'lib', 'libpanst3r_hip.so')      # PST_LIB: A/B builds of the same ABI (measurement)
-ABI_VERSION = 19
+ABI_VERSION = 20
 STATS_BLOCKS = 128        # PST_STATS_BLOCKS
 _lib = None
 
@@ -44,7 +44,7 @@ EXPORTS = ['pst_abi_version', 'pst_last_error', 'pst_gemm', 'pst_gemm_variant', 
            'pst_patchify', 'pst_dino_preprocess', 'pst_image_prepare', 'pst_patch_rows', 'pst_add_cast', 'pst_l2norm_rows', 'pst_mean4', 'pst_resize_bilinear',
            'pst_attn_mask_from_logits', 'pst_loftup_guidance_gn', 'pst_loftup_minmax', 'pst_minmax_merge', 'pst_groupnorm_stats', 'pst_groupnorm_apply',
            'pst_loftup_lr_pe', 'pst_pp_scores', 'pst_pp_scores_softmax', 'pst_pp_sigmoid', 'pst_pp_argmax', 'pst_pp_argmax_logits', 'pst_pp_select', 'pst_pp_finalize', 'pst_pointmap_activate', 'pst_focal_weiszfeld', 'pst_rigid_moments',
-           'pst_qubo_upsample', 'pst_qubo_workspace_floats', 'pst_qubo_overlap', 'pst_qubo_argmax']
+           'pst_qubo_upsample', 'pst_qubo_workspace_floats', 'pst_qubo_overlap', 'pst_qubo_argmax', 'pst_token_embed']
 
 
 def lib():
@@ -259,7 +259,7 @@ def _rowmajor(t):
 
 
 # ----------------------------------------------------------------------------------------------------------- GEMM
-ACT = {None: 0, 'none': 0, 'gelu': 1, 'relu': 2}
+ACT = {None: 0, 'none': 0, 'gelu': 1, 'relu': 2, 'gelu_tanh': 3}      # 'gelu_tanh' (ABI 20): fp32 operands only (the SigLIP text tower's MLP)
 
 
 def _gemm_params(a, w, out, bias=None, gamma=None, res=None, res_mod=0, act=None, trans_out=False, grp=None, ps=None, conv=None,
@@ -885,6 +885,23 @@ def add_cast(a, out, b=None, b_mod=0):
                               fp(b) if b is not None else 0, b_mod, _ptr(out), i64(_rowmajor(out)), fp(out), rows, D, _stream()),
            'pst_add_cast')
     note_maxabs(out, 'add_cast D=%d out' % D)
+    return out
+
+
+@hbm_timed('token_embed', lambda ids, tok, pos, out, status=None: ids.numel() * (4 + 3 * 4 * tok.shape[1]))
+def token_embed(ids, tok, pos, out, status=None):
+    """out[b L + l] = tok[ids[b, l]] + pos[l]: ids int32 [B, L], tok fp32 [vocab, D], pos fp32 [npos, D], out fp32 [B L, D] rows (the SigLIP text
+    tower's embeddings).  The ids must be in range (the tower checks them on the host); the kernel never reads outside `tok` - an id that is not
+    writes a zero row and PST_EINVAL into the optional int32 device scalar `status`."""
+    _dev(ids, torch.int32); _dev(tok, torch.float32); _dev(pos, torch.float32); _dev(out, torch.float32)
+    if status is not None:
+        _dev(status, torch.int32)
+    assert ids.dim() == 2 and ids.is_contiguous() and tok.is_contiguous() and pos.is_contiguous()
+    B, L = ids.shape
+    D = tok.shape[1]
+    assert pos.shape[1] == D and out.shape[0] >= B * L and out.shape[1] == D
+    _check(lib().pst_token_embed(_ptr(ids), B, L, _ptr(tok), tok.shape[0], _ptr(pos), pos.shape[0], D, _ptr(out), i64(_rowmajor(out)),
+                                 _ptr(status), _stream()), 'pst_token_embed')
     return out
 
 

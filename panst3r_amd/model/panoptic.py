@@ -666,8 +666,11 @@ class MaskTransformer(HipModule):
 
 # =========================================================================================== text + PanopticDecoder
 class TextEncoder(nn.Module):
-    """Fixed-vocabulary text encoder (text_encoder.py:44-47,94-101): cached class embeddings -> unit-norm rows.
-    Live SigLIP inference (fixed_vocab=False) needs HF weights that cannot be fetched offline: set `class_embeddings`."""
+    """Text encoder of the reference (text_encoder.py:32-103): unit-norm class embeddings for the class-logit GEMM.
+    Fixed vocabulary (default): the store `class_embeddings` {class name: pooled SigLIP text embedding}, filled by set_vocab.  With a SigLIP text tower
+    (model/text.py: weights from `load_text_model(path)` or the reference's hub id in the local HF cache) set_vocab embeds unknown classes itself and
+    change_mode(fixed_vocab=False) embeds the classes of every call (memoised per class list and tower).  The tower is not a parameter or buffer: it
+    is not part of the state dict."""
 
     def __init__(self, model_name='siglip', out_dim=768, fixed_vocab=True):
         super().__init__()
@@ -675,25 +678,98 @@ class TextEncoder(nn.Module):
         self.embed_dim = {'siglip': 768, 'siglip2': 768, 'clip': 512}[model_name]
         self.fixed_vocab = True
         self.class_embeddings = {}
+        self._tower = None              # SiglipTextTower, resolved on first need
+        self._live = {}                 # (classes, tower, device) -> pooled rows [Ncls, 768]: live-mode memo, entries never replaced (captured graphs)
 
-    def change_mode(self, fixed_vocab):
-        if not fixed_vocab:
-            raise NotImplementedError('live text-encoder inference is outside the hot path; inject class_embeddings')
+    # ------------------------------------------------------------------ the SigLIP tower
+    def load_text_model(self, path):
+        """Use the SigLIP text tower (weights + tokenizer) in the local directory `path`: a saved SiglipTextModel / Siglip2TextModel, the same keys
+        under `text_model.`, or a full SiglipModel / Siglip2Model checkpoint such as the hub repo the reference loads."""
+        from .text import resolve_tower
+        self._tower = resolve_tower(self.model_name, path)
+        self._new_generation()
+        return self._tower
 
-    def set_vocab(self, classes, embeddings=None, device=None):
-        if embeddings is None:
-            # reference text_encoder.py:44-47 would run the SigLIP text tower; no HF weights offline: the classes must already be in
-            # the fixed-vocabulary store (class_embeddings), else pass the pooled text embeddings
-            unknown = [c for c in classes if c not in self.class_embeddings]
-            if unknown:
-                raise NotImplementedError('no SigLIP text tower in this build: pass embeddings= (pooled text embeddings [Ncls, %d]) or '
-                                          'fill class_embeddings; unknown classes: %s' % (self.embed_dim, unknown[:5]))
-            return
-        self.class_embeddings = {c: e for c, e in zip(classes, embeddings)}
+    def tower(self, required=True):
+        """the text tower in use: loaded by load_text_model, else the reference's hub id from the local HF cache (never the network); None / a
+        NotImplementedError when neither resolves"""
+        if self._tower is None:
+            from .text import resolve_tower
+            self._tower = resolve_tower(self.model_name)
+        if self._tower is None and required:
+            from .text import MODEL_CONFIGS
+            raise NotImplementedError('no SigLIP text tower available: pass set_vocab(..., embeddings=) (pooled text embeddings [Ncls, %d]), fill '
+                                      'class_embeddings, call load_text_model(<local SigLIP directory>), or put %s in the local Hugging Face cache'
+                                      % (self.embed_dim, MODEL_CONFIGS[self.model_name]['hf_model']))
+        return self._tower
+
+    def embed_classes(self, classes, device=None):
+        """pooled text embeddings [Ncls, 768] fp32 of `classes` through the tower (reference embed_classes: template, batches of 32)"""
+        from .text import MODEL_CONFIGS
+        tw = self.tower()
+        cfg = MODEL_CONFIGS[self.model_name]
+        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        return tw.embed_texts([cfg['template'].format(c) for c in classes], cfg['tokenizer_args'], dev)
+
+    def _new_generation(self):
         self._cls_gen = getattr(self, '_cls_gen', 0) + 1       # new vocabulary generation: cached device copies of the old one are
         #                                                        no longer handed out (runners that captured them keep them alive)
 
+    def change_mode(self, fixed_vocab):
+        if not fixed_vocab:
+            try:
+                self.tower()
+            except NotImplementedError as e:
+                raise NotImplementedError('live text-encoder inference (fixed_vocab=False) needs a SigLIP text tower: %s' % e) from None
+        if bool(fixed_vocab) != self.fixed_vocab:
+            self.fixed_vocab = bool(fixed_vocab)
+            self._new_generation()
+
+    def set_vocab(self, classes, embeddings=None, device=None):
+        if embeddings is None:
+            # reference text_encoder.py:87-95: embed the classes with the SigLIP tower and REPLACE the store.  Classes that are all in the store
+            # already need no tower (fixed-vocabulary store filled earlier or injected): validated only
+            unknown = [c for c in classes if c not in self.class_embeddings]
+            if not unknown:
+                return
+            try:
+                self.tower()
+            except NotImplementedError as e:
+                raise NotImplementedError('%s; unknown classes: %s' % (e, unknown[:5])) from None
+            embeddings = self.embed_classes(list(classes), device)
+        self.class_embeddings = {c: e for c, e in zip(classes, embeddings)}
+        self._new_generation()
+
+    def _live_rows(self, classes, device):
+        """live mode: the tower's pooled rows of `classes`, memoised per (class list, tower, device) - a pure function of those"""
+        tw = self.tower()
+        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type == 'cuda' and dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        key = (tuple(classes), tw, str(dev))
+        rows = self._live.get(key)
+        if rows is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('live text-encoder: class list %s first seen inside a graph capture (embed it eagerly first)' % (list(classes)[:5],))
+            rows = self._live[key] = self.embed_classes(list(classes), dev)
+        return rows
+
+    def store_for(self, classes, device=None):
+        """{class: pooled embedding} the classes of a call use: the fixed-vocabulary store, or (fixed_vocab=False) the tower's memoised rows"""
+        if self.fixed_vocab:
+            return self.class_embeddings
+        return dict(zip(classes, self._live_rows(classes, device)))
+
+    def vocab_key(self, classes, device=None):
+        """identity of the class embeddings a call with `classes` uses (runner / graph cache keys): per class the storage address and in-place edit
+        counter, plus the vocabulary generation"""
+        st = self.store_for(classes, device)
+        return (tuple((c, st[c].data_ptr(), st[c]._version) if c in st else (c,) for c in classes), getattr(self, '_cls_gen', 0), self.fixed_vocab)
+
     def forward(self, classes):
+        if not self.fixed_vocab:
+            e = self._live_rows(classes, None)
+            return e / e.norm(dim=-1, keepdim=True)
         assert all(c in self.class_embeddings for c in classes), \
             "Missing classes in vocabulary. 'set_vocab' must be called if using fixed vocabulary"
         e = torch.stack([self.class_embeddings[c] for c in classes])
@@ -701,17 +777,18 @@ class TextEncoder(nn.Module):
 
     def normalized_bf16(self, classes, device):
         """unit-norm class embeddings as the bf16 [Ncls, 768] W operand of the class-logit GEMM (normalised on device)."""
-        assert all(c in self.class_embeddings for c in classes), \
+        store = self.store_for(classes, device)
+        assert all(c in store for c in classes), \
             "Missing classes in vocabulary. 'set_vocab' must be called if using fixed vocabulary"
         # identity of the embeddings in use: vocabulary generation (set_vocab), plus per class the storage address and torch's in-place edit
         # counter - an in-place edit or a direct dict assignment gets fresh device copies too (ADVICE r3)
-        ver = tuple((self.class_embeddings[c].data_ptr(), self.class_embeddings[c]._version) for c in classes)
+        ver = tuple((store[c].data_ptr(), store[c]._version) for c in classes)
         key = (tuple(classes), str(device), adt(), getattr(self, '_cls_gen', 0), ver)
         cache = self.__dict__.setdefault('_cls_cache', {})     # keyed, entries never replaced: a captured graph may hold the address
         if not isinstance(cache, dict):
             cache = self.__dict__['_cls_cache'] = {}
         if key not in cache:
-            raw = torch.stack([self.class_embeddings[c] for c in classes]).float().to(device).contiguous()
+            raw = torch.stack([store[c] for c in classes]).float().to(device).contiguous()
             full = torch.zeros(ceil_to(raw.shape[0], 4), ceil_to(raw.shape[1], 64), dtype=adt(), device=device)
             out = full[:raw.shape[0]]                # up to three zero rows stay behind the classes (MaskTransformer._class_logits: N % 4 == 0)
             out._pst_zero_tail = True

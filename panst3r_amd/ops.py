@@ -117,6 +117,12 @@ def l2norm_rows(x: Tensor, out: Tensor, eps: float) -> None:
     hip.l2norm_rows(x, out, eps)
 
 
+@_op('token_embed', ('out', 'status'))
+def token_embed(ids: Tensor, tok: Tensor, pos: Tensor, out: Tensor, status: Optional[Tensor] = None) -> None:
+    """SigLIP text tower embeddings: out[b L + l] = tok[ids[b, l]] + pos[l] (ids int32, tables and out fp32)"""
+    hip.token_embed(ids, tok, pos, out, status)
+
+
 @_op('split3', ('out',))
 def split3(x: Tensor, out: Tensor) -> None:
     hip.split3(x, out)

@@ -71,12 +71,19 @@ class PanSt3R(nn.Module):
         return mem_batches(n_imgs, self.must3r_params['init_num_views'], self.must3r_params['batch_num_views'])
 
     def set_vocab(self, class_names, device=None, embeddings=None):
-        """Reference signature set_vocab(class_names, device=None) (panst3r.py:298-299).  The reference runs its SigLIP text tower
-        here; offline there are no SigLIP weights, so the pooled text embeddings [Ncls, 768] are passed as `embeddings=` (keyword)
-        or must already be in `panoptic_decoder.text_encoder.class_embeddings` (the reference's fixed-vocabulary store,
-        text_encoder.py:44-47,94-97), in which case this call only validates that every class is known."""
+        """Reference signature set_vocab(class_names, device=None) (panst3r.py:298-299).  Classes that are all in the fixed-vocabulary store
+        `panoptic_decoder.text_encoder.class_embeddings` (text_encoder.py:44-47,94-97) are validated only.  Otherwise the store is REPLACED by
+        `class_names` with either the pooled text embeddings [Ncls, 768] passed as `embeddings=` (keyword) or, as in the reference, what the
+        SigLIP text tower makes of them: see `load_text_encoder` (else the reference's hub id in the local Hugging Face cache)."""
         self.panoptic_decoder.text_encoder.set_vocab(class_names, embeddings, device=device)
         self._runners.clear()
+
+    def load_text_encoder(self, path):
+        """Point the text encoder at a local SigLIP text tower (directory with config.json, the weights and the tokenizer files): set_vocab then
+        embeds new classes, and text_encoder.change_mode(fixed_vocab=False) embeds the classes of every call.  Not part of the state dict."""
+        tower = self.panoptic_decoder.text_encoder.load_text_model(path)
+        self._runners.clear()
+        return tower
 
     # ------------------------------------------------------------------ reference stage methods (panst3r.py:47-86,127-167)
     # The reference runs these under the caller's torch.autocast (panst3r.py:174,204); here `amp=` ('fp16' | 'bf16') selects the 16-bit
@@ -462,7 +469,7 @@ class PanSt3R(nn.Module):
         te = self.panoptic_decoder.text_encoder
         gens = tuple(m.generation for m in self.modules() if isinstance(m, HipModule))
         pver = sum(p._version for p in self.parameters())
-        cver = tuple((c, te.class_embeddings[c].data_ptr(), te.class_embeddings[c]._version) if c in te.class_embeddings else (c,) for c in classes)
+        cver = te.vocab_key(classes, dev)        # fixed store or (live mode) the tower's memoised rows: a new vocabulary is a new signature
         key = (tuple(shapes), num_keyframes, None if keyframes is None else tuple(int(k) for k in keyframes), str(dev),
                amp_dtype(amp, quiet=True), str(amp), gens, pver, cver, getattr(te, '_cls_gen', 0), max_bs, panoptic_precision, bool(streamed))
         ent = self._runners.get(key)
