@@ -326,10 +326,13 @@ class PanSt3R(nn.Module):
     # ------------------------------------------------------------------ reference API
     # range ladder of the 16-bit operand formats: what a call falls back to when its outputs come back non-finite - an activation left the
     # f16 range (65504; the reference warns "fp16 might be unstable", tools/demo_panst3r.py:88-89).  (amp, panoptic_precision) -> the next, range-safer placement.
+    # An explicit panoptic placement the caller chose is kept: only the backbone format moves ('amp' keeps meaning "the backbone's format").
     @staticmethod
     def range_fallback_of(amp, panoptic_precision):
         fmt = amp_dtype(amp, quiet=True)
         if fmt == torch.float16:
+            if panoptic_precision in ('reference', 'fp32', 'bf16', 'amp'):
+                return 'bf16', panoptic_precision
             return 'bf16', None                 # bf16 backbone (fp32 exponent range), panoptic decoder still on f16 operands (every operand there is normalised)
         if fmt == torch.bfloat16 and panoptic_precision in (None, 'auto', 'fp16'):
             return 'bf16', 'amp'                # ... and the panoptic decoder on bf16 operands too

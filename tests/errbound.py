@@ -1,0 +1,319 @@
+"""Per-element error bounds of the HIP kernels, derived from their arithmetic (not fitted to observed errors).
+
+check(got, ref64, bound, what) asserts |got - ref| <= bound at EVERY element (and that got is finite) and returns the largest err / bound ratio.  A global
+rel-L2 lets one wrong tile, one tail row, one dropped key or an intermediate rounded to the wrong format through when it is small in norm; a per-element bound
+derived from the kernel's rounding steps does not.  References are float64 evaluations of the SAME rounded inputs the kernel gets.
+
+Notation: u(f) = unit roundoff of format f (bf16 2^-8, f16 2^-11, fp32 2^-24); tiny(f) = half the smallest subnormal spacing (the absolute error of a rounding
+near zero).  tests/test_errbound.py proves on the CPU, for every bound here, that an emulation of the kernel's rounding path stays below half the bound and that
+the typical kernel mistakes (accumulator through a 16-bit format, P rounded to the wrong format, a dropped key, a negated fragment, wrong LayerNorm eps, ...)
+exceed it.
+
+PST_ERRBOUND_LOG=<path>: every check() appends one JSON line {what, ratio, n} there (the per-family maxima the GPU run reports).
+"""
+import json
+import math
+import os
+
+import torch
+
+LN2 = math.log(2.0)
+LOG2E = 1.0 / LN2
+U32 = 2.0 ** -24
+LAMBDA = 5.0            # probabilistic factor of the attention P-rounding term (sum of independent roundings: a 5-sigma envelope)
+# A round-to-nearest store errs by up to half an ulp, i.e. up to u |y| just above a power of two: every rounding to a storage format is allowed TWO u |y| (one
+# ulp), so that a correct rounding sits at <= 0.5 of the bound and the margin is the same at every element.
+R = 2.0
+
+
+def u(fmt):
+    """unit roundoff of a storage format (torch dtype or one of 'bf16' / 'f16' / 'fp32')"""
+    fmt = _dtype(fmt)
+    return {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11, torch.float32: U32, torch.float64: 2.0 ** -53}[fmt]
+
+
+def tiny(fmt):
+    """half the subnormal spacing: the absolute error of a rounding to fmt near zero"""
+    fmt = _dtype(fmt)
+    return {torch.bfloat16: 2.0 ** -134, torch.float16: 2.0 ** -25, torch.float32: 2.0 ** -150, torch.float64: 0.0}[fmt]
+
+
+def _dtype(fmt):
+    if isinstance(fmt, torch.dtype):
+        return fmt
+    return {'bf16': torch.bfloat16, 'f16': torch.float16, 'fp16': torch.float16, 'fp32': torch.float32}[fmt]
+
+
+def check(got, ref, bound, what):
+    """assert |got - ref| <= bound elementwise (bound broadcasts against ref) and that got is finite; returns max(err / bound)"""
+    got = got.detach().double()
+    ref = ref.detach().double().to(got.device)
+    bound = torch.as_tensor(bound, dtype=torch.float64, device=got.device).expand_as(ref)
+    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
+    fin = torch.isfinite(got)
+    assert bool(fin.all()), '%s: %d non-finite outputs, first at %s' % (what, int((~fin).sum()), tuple(int(i) for i in (~fin).nonzero()[0]))
+    err = (got - ref).abs()
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float('inf')), torch.zeros_like(err)))
+    worst = int(ratio.reshape(-1).argmax())
+    r = float(ratio.reshape(-1)[worst])
+    if os.environ.get('PST_ERRBOUND_LOG'):
+        with open(os.environ['PST_ERRBOUND_LOG'], 'a') as f:
+            f.write(json.dumps(dict(what=what, ratio=r, n=ref.numel())) + '\n')
+    if r > 1.0:
+        idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(worst), ref.shape))
+        nbad = int((err > bound).sum())
+        raise AssertionError('%s: %d of %d elements exceed the error bound; worst at %s: got %.9g ref %.9g |err| %.3g bound %.3g (ratio %.3g)'
+                             % (what, nbad, ref.numel(), idx, float(got[idx]), float(ref[idx]), float(err[idx]), float(bound[idx]), r))
+    return r
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------- GEMM
+GELU_LIP = 1.13          # max |d/dx GELU(x)| (x ~ 2.42): the Lipschitz factor an activation applies to the error of its argument
+GELU_ERF_ABS = 1.5e-7    # |erf error| of Abramowitz-Stegun 7.1.26 (common.h gelu_erf2): 0.5 |x| of it reaches the output
+
+
+def gemm_bound(a, w, out_fmt, bias=None, act=None, gamma=None, res=None, mode='mfma16'):
+    """Per-element bound of C = epilogue(A W^T) for the HIP GEMMs, A [M, K] and W [N, K] the exact operands (16-bit values, or fp32 for the fp32 modes).
+
+    mode 'mfma16' (gemm.hip, gemm256.hip, rowstream.hip, maskhead.hip): products of 16-bit operands are exact in fp32; v_mfma_f32_16x16x32 adds 32 of them
+    into the fp32 accumulator per step, K / 32 steps -> (K/32 + 2) * 2 u32 * sum_k |a_k w_k|.  Epilogue (gemm.hip row_phase / the accumulator-layout
+    epilogue): fmaf(acc, 1, bias) in fp32 (one rounding), GELU(erf) (gelu_erf2) or ReLU, x gamma (one rounding), then
+      - no residual: one rounding to the output format;
+      - fp32 residual, fp32 output: one fp32 add;
+      - residual and 16-bit output: the value is rounded to 16 bit into the LDS C tile, the residual is added in fp32, rounded once more (two roundings).
+    mode 'x3' (split.hip + the 16-bit kernels over 3K: [hi, hi, lo] x [hi, lo, hi]): x = hi + lo with f16 hi / lo -> each operand carries 2^-22 relative
+    (+ 2^-25 absolute, f16 subnormal lo), the dropped lo x lo term 2^-22 |a w|, 3K / 32 accumulation steps.
+    mode 'fp32' (gemm_f32.hip, v_mfma_f32_16x16x4_f32): every product rounded once (u32), K / 4 accumulation steps.
+    Bound = (output / intermediate roundings) + Lip(act) * |gamma| * (accumulation + bias rounding) + activation approximation."""
+    a64, w64 = a.double(), w.double()
+    core = a64 @ w64.T
+    acc = acc_bound(a64.abs() @ w64.abs().T, a.shape[-1], mode, a64.abs().sum(-1, keepdim=True), w64.abs().sum(-1)[None])
+    return gemm_bound_from(core, acc, out_fmt, bias, act, gamma, res)
+
+
+def acc_bound(absprod, K, mode, sum_a=None, sum_w=None):
+    """bound of the fp32 accumulator's error of a K-long dot product (gemm_bound's three modes); absprod = sum_k |a_k w_k|; sum_a / sum_w = sum_k |a_k| /
+    sum_k |w_k| (x3 only: the absolute error of an f16-subnormal lo part)"""
+    if mode == 'mfma16':
+        return 2 * (K / 32 + 2) * U32 * absprod
+    if mode == 'x3':
+        return 2 * (3 * K / 32 + 2) * U32 * absprod + 3 * 2.0 ** -22 * absprod + 2.0 ** -25 * (sum_a + sum_w)
+    if mode == 'fp32':
+        return 2 * (K / 4 + 2) * U32 * absprod + U32 * absprod
+    raise ValueError(mode)
+
+
+def ln_fold_bound(xc, wf, cs, bias, x, eps, out_fmt, act=None):
+    """LayerNorm folded into the consuming GEMM (gemm.hip, ln_fold_prologue / ln_fold_entry in common.h): the raw 16-bit rows xc times the gamma-folded
+    16-bit W (mfma16 accumulator), then out = act(fmaf(acc, rstd, fmaf(-mean rstd, cs, bias))).  mean / rstd come from the fp32 per-64-column (sum, sumsq)
+    partials of the fp32 rows x: one-pass statistics, var = E[x^2] - mean^2 (rownorm_bound's one-pass model).  cs = the fp32 column sums of wf, taken as
+    given.  Returns (float64 reference of the same inputs, bound): the row-norm errors dm (mean) and dr (relative rstd) reach the output as
+    rstd (|acc| dr + |cs| (|mean| dr + dm)), the accumulator's as rstd acc_err, then the GEMM epilogue (gemm_bound_from)."""
+    x64, xc64, wf64, cs64 = x.double(), xc.double(), wf.double(), cs.double()
+    D = x64.shape[-1]
+    nred = D / 16 + 8
+    mean = x64.mean(-1, keepdim=True)
+    var = (x64 * x64).mean(-1, keepdim=True) - mean * mean
+    r = (var + eps).rsqrt()
+    dm = nred * U32 * x64.abs().mean(-1, keepdim=True) + U32 * mean.abs()
+    dv = 2 * nred * U32 * (x64 * x64).mean(-1, keepdim=True) + 2 * U32 * (var + eps) + 2 * dm * mean.abs()
+    dr = dv / (2 * (var + eps)) + 3 * U32
+    raw = xc64 @ wf64.T
+    core = r * raw - (mean * r) * cs64[None]
+    acc = r * (acc_bound(xc64.abs() @ wf64.abs().T, D, 'mfma16') + raw.abs() * dr) + r * cs64.abs()[None] * (mean.abs() * (dr + U32) + dm) \
+        + U32 * ((mean * r) * cs64[None]).abs()
+    ref = core + bias.double()
+    ref = torch.nn.functional.gelu(ref) if act == 'gelu' else ref
+    return ref, gemm_bound_from(core, acc, out_fmt, bias, act)
+
+
+def gemm_bound_from(core, acc, out_fmt, bias=None, act=None, gamma=None, res=None):
+    """the epilogue part of gemm_bound: core = exact A W^T (float64), acc = bound of the accumulator's error (same shape)"""
+    pre = core + (bias.double() if bias is not None else 0.0)
+    err = acc + U32 * pre.abs()                                     # fmaf(acc, 1, bias): one fp32 rounding
+    if act == 'gelu':
+        y = torch.nn.functional.gelu(pre)
+        err = GELU_LIP * err + pre.abs() * (0.5 * GELU_ERF_ABS + 8 * U32)
+    elif act == 'gelu_tanh':
+        y = torch.nn.functional.gelu(pre, approximate='tanh')
+        err = GELU_LIP * err + pre.abs() * 16 * U32
+    elif act == 'relu':
+        y = torch.relu(pre)
+    elif act is None:
+        y = pre
+    else:
+        raise ValueError(act)
+    if gamma is not None:
+        g = gamma.double()
+        y = y * g
+        err = err * g.abs() + U32 * y.abs()
+    uo = u(out_fmt)
+    if res is not None:
+        if _dtype(out_fmt) != torch.float32:
+            err = err + R * uo * (y.abs() + err) + tiny(out_fmt)            # 16-bit value in the LDS C tile, then the residual add
+        y = y + res.double()
+        err = err + U32 * y.abs()
+    return err + R * uo * (y.abs() + err) + tiny(out_fmt)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------- attention
+def attn_ref(q, k, v, mask=None, pre=False):
+    """float64 softmax attention of the given (rounded) operands, [B, H, N, hd]; mask [B, Nq, Nk] True = blocked; a row with every key blocked is 0 (the
+    kernels' l == 0 guard).  pre: q carries hd^-0.5 log2(e) already (softmax of q.k ln 2)."""
+    return attn_bound(q, k, v, mask, pre, 'fp32', 'fp32', _ref_only=True)
+
+
+def attn_bound(q, k, v, mask, pre, out_fmt, p_fmt, nsplit=1, mode='mfma16', _ref_only=False):
+    """Per-element bound of O = softmax(q k^T scale) v for attention.hip (mode 'mfma16'), attn_x3.hip ('x3') and attn_f32.hip ('fp32').
+
+    attention.hip: S - m is one MFMA chain in fp32 on top of -m (hd / 32 steps, :186-197), P = exp2((S - m) c) (v_exp_f32) is rounded to the 16-bit format
+    p_fmt (:269-280); the row sum l is the MFMA sum of the SAME rounded P (:300), O accumulates rounded P times V in fp32; lazy rescaling (:236-258) keeps
+    1 <= P_max <= 2^8; split-K partials are merged in fp32 (:385-394); one rounding to out_fmt at the store (:333).  Because l sums the rounded P, the P
+    rounding moves O by sum_j p_j eps_j (v_j - O) with independent |eps_j| <= u(p_fmt): the probabilistic form LAMBDA * sqrt(sum_j e_j^2 (v_j - O)^2),
+    e_j = max(u(p_fmt) p_j, tiny(p_fmt) p_max) (a subnormal P has an absolute error; P_max >= 1 bounds l from below).  The worst case
+    u(p_fmt) sum_j p_j |v_j - O| would be about sqrt(Nk) times larger and hide a missing key under a near-uniform softmax.
+    Score errors (fp32 accumulation, the scale multiply, exp2) move P_j by the relative eta_j: sum_j p_j eta_j |v_j - O| (worst case, u32-sized).
+    The fp32 P V / l accumulation: 2 (Nk/32 + nsplit + 4) u32 (sum_j p_j |v_j| + |O|).
+    mode 'x3': P, V, Q and K carry 2^-22 (split hi + lo f16 operands), products 3 2^-22.  mode 'fp32': P in fp32, every product rounded (u32).
+    Returns the bound [B, H, Nq, hd] (or with _ref_only the float64 reference)."""
+    B, H, Nq, hd = q.shape
+    Nk = k.shape[2]
+    scale = LN2 if pre else hd ** -0.5
+    c_exp = 1.0 if pre else hd ** -0.5 * LOG2E
+    up, tp = u(p_fmt), tiny(p_fmt)
+    eps_prod = {'mfma16': 0.0, 'x3': 3 * 2.0 ** -22, 'fp32': U32}[mode]
+    eps_v = {'mfma16': 0.0, 'x3': 2 * 2.0 ** -22, 'fp32': 0.0}[mode]
+    if mode == 'x3':
+        up, tp = 2.0 ** -22, 2.0 ** -25
+    nacc_s = hd / (4 if mode == 'fp32' else 32) * (3 if mode == 'x3' else 1) + 3
+    nacc_o = Nk / (4 if mode == 'fp32' else 32) * (3 if mode == 'x3' else 1) + nsplit + 4
+    out = torch.empty(B, H, Nq, hd, dtype=torch.float64, device=q.device)
+    for b in range(B):
+        for h in range(H):
+            q64, k64, v64 = q[b, h].double(), k[b, h].double(), v[b, h].double()
+            raw = q64 @ k64.T
+            s = raw * scale
+            if mask is not None:
+                s = s.masked_fill(mask[b].to(q.device), float('-inf'))
+            dead = torch.isinf(s).all(-1, keepdim=True)
+            p = torch.softmax(s.masked_fill(dead, 0.0), -1).masked_fill(dead, 0.0)
+            if mask is not None:
+                p = p.masked_fill(mask[b].to(q.device), 0.0)
+            ref = p @ v64
+            if _ref_only:
+                out[b, h] = ref
+                continue
+            absv = v64.abs()
+            # P rounding, probabilistic: sqrt(sum_j e_j^2 (v_j - ref)^2) = sqrt(W v^2 - 2 ref (W v) + ref^2 sum W), W = e^2
+            e = torch.maximum(R * up * p, tp * p.amax(-1, keepdim=True)) * (p > 0)
+            W = e * e
+            var = (W @ (v64 * v64) - 2 * ref * (W @ v64) + ref * ref * W.sum(-1, keepdim=True)).clamp_min(0.0)
+            t_p = LAMBDA * var.sqrt()
+            # score error -> relative P error eta_j (worst case)
+            absqk = q64.abs() @ k64.abs().T
+            smax = raw.abs().amax(-1, keepdim=True) + 8.0 / c_exp
+            eta = LN2 * (c_exp * (nacc_s * 2 * U32 * (absqk + smax) + eps_prod * absqk) + U32 * (raw.abs() + smax) * c_exp) + 4 * U32
+            pe = p * eta
+            t_s = pe @ absv + ref.abs() * pe.sum(-1, keepdim=True)
+            pv = p @ absv
+            t_acc = 2 * nacc_o * U32 * (pv + ref.abs()) + eps_v * pv
+            err = t_p + t_s + t_acc
+            out[b, h] = err + R * u(out_fmt) * (ref.abs() + err) + tiny(out_fmt)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------- row norms
+def rownorm_bound(x, gamma, beta, eps, out_fmt, one_pass=False, relu=False, nred=None):
+    """Per-element bound of a LayerNorm-type row normalisation y = (x - mean) rstd gamma + beta over the last axis of x (float64 of the kernel's exact
+    input rows; for GroupNorm pass x reshaped so the last axis is one group and gamma / beta broadcast to it).
+
+    Statistics in fp32 (misc.hip layernorm_kernel :96-124 and layernorm384_kernel: per-lane sequential sums then a lane tree; two passes - mean, then
+    sum (x - mean)^2; one_pass: GroupNorm's (sum, sumsq) statistics, var = E[x^2] - mean^2 - cancellation relative to E[x^2]), each sum with at most
+    nred = D / 16 + 8 rounding steps; rsqrtf; (x - mean) rstd gamma + beta in fp32; one rounding to out_fmt.
+      mean error      dm = nred u32 mean|x| + u32 |mean|
+      variance error  dv = nred u32 (var, or 2 E[x^2] one-pass) + 2 u32 (var + eps)
+      rstd relative   dr = dv / (2 (var + eps)) + 2 u32
+      y error         |gamma| rstd (dm + u32 |x - mean| + |x - mean| dr) + 3 u32 |y|, then the output rounding."""
+    x64 = x.double()
+    D = x64.shape[-1]
+    if nred is None:
+        nred = D / 16 + 8
+    mean = x64.mean(-1, keepdim=True)
+    xc = x64 - mean
+    var = (xc * xc).mean(-1, keepdim=True)
+    r = (var + eps).rsqrt()
+    g = gamma.double() if torch.is_tensor(gamma) else torch.tensor(float(gamma), dtype=torch.float64)
+    bt = beta.double() if torch.is_tensor(beta) else torch.tensor(float(beta), dtype=torch.float64)
+    y = xc * r * g + bt
+    dm = nred * U32 * x64.abs().mean(-1, keepdim=True) + U32 * mean.abs()
+    dv = nred * U32 * (2 * (x64 * x64).mean(-1, keepdim=True) if one_pass else var) + 2 * U32 * (var + eps) + 2 * dm * xc.abs().mean(-1, keepdim=True)
+    dr = dv / (2 * (var + eps)) + 2 * U32
+    err = g.abs() * r * (dm + U32 * xc.abs() + xc.abs() * dr) + 3 * U32 * y.abs()
+    if relu:
+        y = torch.relu(y)
+    return err + R * u(out_fmt) * (y.abs() + err) + tiny(out_fmt)
+
+
+def layernorm_ref(x, gamma, beta, eps):
+    x64 = x.double()
+    return torch.nn.functional.layer_norm(x64, (x64.shape[-1],), gamma.double(), beta.double(), eps)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------- elementwise
+def elementwise_bound(ref, out_fmt, in_abs=None, n_ops=4):
+    """An elementwise op evaluated in fp32 and rounded once: u(out) |ref| + n_ops u32 in_abs (in_abs = the magnitude of the fp32 terms that are combined,
+    e.g. |x| + |partner| for a rotation; default |ref|)."""
+    ref = ref.double()
+    in_abs = ref.abs() if in_abs is None else in_abs.double()
+    err = n_ops * U32 * in_abs
+    return err + R * u(out_fmt) * (ref.abs() + err) + tiny(out_fmt)
+
+
+def rope2d(x, pos, out_fmt, base=100.0):
+    """RoPE-2D (misc.hip / the fused GEMM store, tables of hip.rope_table): x [..., T, hd], integer positions pos [T, 2] (y, x); per head the first hd / 2
+    channels rotate with y, the rest with x, each half a 1-D RoPE over D = hd / 2 with rotate_half pairs (i, i + D/2).  Returns (float64 reference, bound).
+    The kernel: fp32 table (inv_freq = base^(-2i/D) and angle = pos inv_freq in fp32: |d angle| <= 3 u32 |angle|, cos / sin rounded: + u32), one product
+    rounded and one fma: |err| <= (|x| + |partner|) (3 u32 |angle| + 4 u32), then the output rounding."""
+    x64 = x.double()
+    hd = x64.shape[-1]
+    D = hd // 2
+    inv = base ** (-torch.arange(0, D, 2, dtype=torch.float64, device=x64.device) / D)
+    outs, errs = [], []
+    for half in range(2):
+        t = x64[..., half * D:(half + 1) * D]
+        ang = pos[:, half].to(x64.device).double()[:, None] * inv[None]
+        ang = torch.cat([ang, ang], -1)
+        partner = torch.cat([-t[..., D // 2:], t[..., :D // 2]], -1)
+        outs.append(t * ang.cos() + partner * ang.sin())
+        errs.append((t.abs() + partner.abs()) * (3 * U32 * ang.abs() + 4 * U32))
+    ref, err = torch.cat(outs, -1), torch.cat(errs, -1)
+    return ref, err + R * u(out_fmt) * (ref.abs() + err) + tiny(out_fmt)
+
+
+def conv3x3(x, wt, bias, out_fmt, mode='mfma16'):
+    """the implicit-GEMM 3 x 3 convolution (gemm.hip conv mode, padding 1): x NHWC [V, H, W, Cin], wt [Cout, Cin, 3, 3].  A K = 9 Cin dot product per output
+    whose zero-padded taps add nothing: gemm_bound's accumulator model on sum |x| |w| over the taps that exist.  Returns (float64 reference [V H W, Cout],
+    bound)."""
+    V, H, W, Cin = x.shape
+    Cout = wt.shape[0]
+    conv = lambda xx, ww: torch.nn.functional.conv2d(xx.permute(0, 3, 1, 2), ww, padding=1).permute(0, 2, 3, 1).reshape(V * H * W, -1)
+    x64, w64 = x.double(), wt.double()
+    core = conv(x64, w64)
+    sum_a = conv(x64.abs(), torch.ones(1, Cin, 3, 3, dtype=torch.float64, device=x64.device))
+    acc = acc_bound(conv(x64.abs(), w64.abs()), 9 * Cin, mode, sum_a, w64.abs().sum((1, 2, 3))[None])
+    return core + bias.double(), gemm_bound_from(core, acc, out_fmt, bias)
+
+
+def groupnorm(x, n, P, G, gamma, beta, eps, out_fmt, relu=False):
+    """GroupNorm over pixel-major rows x [n P, C] (G groups of C / G channels, per view), statistics of pst_groupnorm_stats: fp32 (sum, sumsq) partials over
+    256-element pieces merged per group - one-pass, nred = P C / (256 G) + 64 steps.  Returns (float64 reference [n P, C], bound)."""
+    C = x.shape[-1]
+    Cg = C // G
+    x64 = x.double()
+    xg = x64.reshape(n, P, G, Cg).permute(0, 2, 1, 3).reshape(n, G, P * Cg)
+    per = lambda t: t.double().to(x64.device).reshape(G, 1, Cg).expand(G, P, Cg).reshape(1, G, P * Cg)
+    back = lambda t: t.reshape(n, G, P, Cg).permute(0, 2, 1, 3).reshape(n * P, C)
+    ref = torch.nn.functional.group_norm(x64.reshape(n, P, C).permute(0, 2, 1), G, gamma.double().to(x64.device), beta.double().to(x64.device), eps)
+    ref = ref.permute(0, 2, 1).reshape(n * P, C)
+    ref = torch.relu(ref) if relu else ref
+    return ref, back(rownorm_bound(xg, per(gamma), per(beta), eps, out_fmt, one_pass=True, relu=relu, nred=P * Cg / 256 + 64))

@@ -138,3 +138,15 @@ def test_torch_ops_registered():
     assert wrappers <= names
     for n in wrappers:
         assert hasattr(hip, n), n
+
+
+def test_range_fallback_ladder_keeps_an_explicit_panoptic_placement():
+    """PanSt3R.range_fallback_of: an f16 overflow moves the backbone to bf16; a panoptic placement the caller chose explicitly stays as it was"""
+    f = PanSt3R.range_fallback_of
+    for pp in (None, 'auto', 'fp16'):
+        assert f('fp16', pp) == ('bf16', None)
+        assert f('bf16', pp) == ('bf16', 'amp')
+    for pp in ('reference', 'fp32', 'bf16', 'amp'):
+        assert f('fp16', pp) == ('bf16', pp)
+        assert f('bf16', pp) is None
+    assert f(False, None) is None

@@ -46,7 +46,10 @@ def scene_parity(built, variant, V, K, amps=('fp16',), want_ref=False):
     import bench
     model, state, names, emb = built
     _, ref, imgs, ts = bench.cpu_baseline(variant, 384, 512, state, names, emb, bench.usable_cores(), V=V, K=K)
-    par = {amp: bench.full_size_parity(model, torch.device(DEV), ref, imgs, ts, names, amp=amp, K=K) for amp in amps}
+    par = {}
+    for amp in amps:
+        par[amp] = bench.full_size_parity(model, torch.device(DEV), ref, imgs, ts, names, amp=amp, K=K)
+        assert model.last_precision == (amp, None), (amp, model.last_precision)      # the format asked for is the one that ran (no silent range fallback)
     return (par, ref) if want_ref else par
 
 
@@ -245,6 +248,7 @@ def golden_parity(built, tag, V, K, amp='fp16'):
         with mt.instrument(log=log):
             pm_h, pan_h = model.forward_inference_multi_ar(inp, ts, names, num_keyframes=K, amp=amp, max_bs=1)
     torch.cuda.synchronize()
+    assert model.last_precision == (amp, None)                  # no silent range fallback to another format
     res = FG.scene_errors(pm_h, pan_h, g)
     res['tolerance'] = dict(bench.TOLERANCE)
     res['within_tolerance'] = bench._within(res)
@@ -256,6 +260,7 @@ def golden_parity(built, tag, V, K, amp='fp16'):
             with mt.instrument(forced=bits):
                 pm_f, pan_f = model.forward_inference_multi_ar(inp, ts, names, num_keyframes=K, amp=amp, max_bs=1)
         torch.cuda.synchronize()
+        assert model.last_precision == (amp, None)
         dm = FG.scene_errors(pm_f, pan_f, g)
         dm['within_tolerance_every_view'] = bench._within(dm, worst=True)
         res['decisions_matched'] = dm
@@ -530,6 +535,7 @@ def test_full_size_mixed_aspect_ratio_and_portrait(full, amp):
     with torch.no_grad():
         pm_o, pan_o = o.forward_inference_multi_ar(imgs, ts, names, num_keyframes=3, outdevice='cpu')
         pm_h, pan_h = model.forward_inference_multi_ar([i.to(DEV) for i in imgs], ts, names, num_keyframes=3, outdevice='cpu', amp=amp)
+    assert model.last_precision == (amp, None)
     rel = lambda a, b: float((a.double() - b.double()).norm() / b.double().norm())
     num = den = agree = npix = 0.0
     for i, (a, b) in enumerate(shapes):

@@ -1,7 +1,9 @@
 """Per-op parity of the HIP kernels (through the C ABI) against plain fp32 torch restatements of the same op.
 
 bf16 MFMA with fp32 accumulate vs fp32 reference on bf16-rounded inputs: tolerance rel-L2 <= 1e-2 (GEMM/attention
-outputs rounded to bf16), <= 1e-5 when the output is fp32 and the op is elementwise.
+outputs rounded to bf16), <= 1e-5 when the output is fp32 and the op is elementwise.  Every anchor test also holds each output element to the error bound
+tests/errbound.py derives from the kernel's arithmetic (float64 reference of the same 16-bit inputs): a wrong tile, tail row, dropped key or an intermediate
+rounded to the wrong format fails there even when it is small in norm.
 """
 import math
 import numpy as np
@@ -10,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
+import errbound as EB
 
 pytestmark = pytest.mark.gpu
 
@@ -43,18 +46,20 @@ def bf(x):
     return x.to(d16())
 
 
-@pytest.mark.parametrize('M,N,K', [(128, 128, 64), (200, 256, 384), (768, 1024, 1024), (1000, 136, 192), (4096, 512, 256), (33, 100, 64)])
+@pytest.mark.parametrize('M,N,K', [(128, 128, 64), (200, 256, 384), (768, 1024, 1024), (1000, 136, 192), (4096, 512, 256), (33, 100, 64),
+                                   (257, 260, 64), (129, 4, 128), (513, 68, 64)])        # tails: M = 256t+1 / 128t+1, N = 4 (mod 64) and N = 4, one k-step
 @pytest.mark.parametrize('act', [None, 'gelu', 'relu'])
 def test_gemm_basic(M, N, K, act):
     from panst3r_amd import hip
     a, w, b = bf(rn(1, M, K)), bf(rn(2, N, K, scale=K ** -0.5)), rn(3, N, scale=0.1)
-    ref = a.float() @ w.float().T + b
+    ref = a.double() @ w.double().T + b.double()
     ref = F.gelu(ref) if act == 'gelu' else (F.relu(ref) if act == 'relu' else ref)
     for out_dtype in (d16(), torch.float32):
         out = torch.full((M, N), float('nan'), dtype=out_dtype, device=dev())
         hip.gemm(a.to(dev()), w.to(dev()), out, bias=b.to(dev()), act=act)
         torch.cuda.synchronize()
         assert rel_l2(out.float().cpu(), ref) < (1e-2 if out_dtype == d16() else 2e-3)
+        EB.check(out.cpu(), ref, EB.gemm_bound(a, w, out_dtype, bias=b, act=act), 'gemm %s out' % out_dtype)
 
 
 def test_gemm_asymmetric_identity():
@@ -116,17 +121,24 @@ def test_gemm_residual_gamma_remap():
     # residual in place on a remapped output (rows 1..96 of each 104-row group), like the DINO patch-embed
     buf = rn(8, 2 * 104, N)
     ref = buf.clone()
-    core = (a.float() @ w.float().T + bias) * gamma
-    for v in range(2):
-        ref[v * 104 + 1: v * 104 + 97] += core[v * 96:(v + 1) * 96]
+    ref = ref.double()
+    core = (a.double() @ w.double().T + bias.double()) * gamma.double()
+    rows = [v * 104 + 1 + i for v in range(2) for i in range(96)]
+    ref[rows] += core
     d = buf.to(dev())
     hip.gemm(a.to(dev()), w.to(dev()), d, bias=bias.to(dev()), gamma=gamma.to(dev()), res=d, grp=(96, 104, 1))
     assert rel_l2(d.cpu(), ref) < 2e-3
+    bound = EB.gemm_bound(a, w, torch.float32, bias=bias, gamma=gamma, res=buf[rows])
+    EB.check(d.cpu()[rows], ref[rows], bound, 'gemm residual remap')
+    untouched = [r for r in range(2 * 104) if r not in set(rows)]
+    assert torch.equal(d.cpu()[untouched], buf[untouched])                    # rows outside the remap keep their residual bits
     # broadcast residual (row % res_mod), like the learned position embedding
     pe = rn(9, 96, N)
     out = torch.zeros(M, N, dtype=torch.float32, device=dev())
     hip.gemm(a.to(dev()), w.to(dev()), out, bias=bias.to(dev()), res=pe.to(dev()), res_mod=96)
-    assert rel_l2(out.cpu(), a.float() @ w.float().T + bias + pe.repeat(2, 1)) < 2e-3
+    ref2 = a.double() @ w.double().T + bias.double() + pe.double().repeat(2, 1)
+    assert rel_l2(out.cpu(), ref2) < 2e-3
+    EB.check(out.cpu(), ref2, EB.gemm_bound(a, w, torch.float32, bias=bias, res=pe.repeat(2, 1)), 'gemm broadcast residual')
 
 
 @pytest.mark.parametrize('M,N,K,kern', [(300, 384, 384, 0), (1024, 2048, 1024, 256), (200, 104, 64, 0)])
@@ -135,13 +147,15 @@ def test_gemm_bf16_residual(M, N, K, kern):
     from panst3r_amd import hip
     a, w, b = bf(rn(100, M, K)), bf(rn(101, N, K, scale=K ** -0.5)), rn(102, N)
     x = bf(rn(103, M, N))
-    ref = a.float() @ w.float().T + b + x.float()
+    ref = a.double() @ w.double().T + b.double() + x.double()
     d = x.clone().to(dev())
     hip.gemm(a.to(dev()), w.to(dev()), d, bias=b.to(dev()), res=d, kernel=kern)
     assert rel_l2(d.float().cpu(), ref) < 6e-3
+    EB.check(d.cpu(), ref, EB.gemm_bound(a, w, d16(), bias=b, res=x), '16-bit residual 16-bit out')
     o32 = torch.zeros(M, N, dtype=torch.float32, device=dev())
     hip.gemm(a.to(dev()), w.to(dev()), o32, bias=b.to(dev()), res=x.to(dev()), kernel=kern)
     assert rel_l2(o32.cpu(), ref) < 2e-3
+    EB.check(o32.cpu(), ref, EB.gemm_bound(a, w, torch.float32, bias=b, res=x), '16-bit residual fp32 out')
 
 
 def test_gemm_trans_out():
@@ -151,9 +165,10 @@ def test_gemm_trans_out():
     ldc = 1544
     out = torch.zeros(N, ldc, dtype=d16(), device=dev())
     hip.gemm(a.to(dev()), w.to(dev()), out, bias=b.to(dev()), trans_out=True)
-    ref = (a.float() @ w.float().T + b).T
+    ref = (a.double() @ w.double().T + b.double()).T
     assert rel_l2(out[:, :M].float().cpu(), ref) < 1e-2
     assert float(out[:, M:].abs().max()) == 0.0
+    EB.check(out[:, :M].cpu(), ref, EB.gemm_bound(a, w, d16(), bias=b).T, 'gemm transposed store')
 
 
 @pytest.mark.parametrize('p,c,h,w', [(2, 8, 3, 5), (16, 7, 2, 3), (2, 512, 4, 6)])
@@ -164,13 +179,16 @@ def test_gemm_pixel_shuffle_store(p, c, h, w):
     N = c * p * p
     Npad = (N + 3) // 4 * 4
     a, wt, b = bf(rn(13, V * h * w, K)), bf(rn(14, N, K, scale=K ** -0.5)), rn(15, N)
-    y = (a.float() @ wt.float().T + b).reshape(V, h, w, N).permute(0, 3, 1, 2)          # [V, c*p*p, h, w] channel-major
+    y = (a.double() @ wt.double().T + b.double()).reshape(V, h, w, N).permute(0, 3, 1, 2)   # [V, c*p*p, h, w] channel-major
     ref = F.pixel_shuffle(y, p).permute(0, 2, 3, 1).contiguous()                          # [V, p*h, p*w, c]
+    yb = EB.gemm_bound(a, wt, torch.float32, bias=b).reshape(V, h, w, N).permute(0, 3, 1, 2)
+    bound = F.pixel_shuffle(yb, p).permute(0, 2, 3, 1).contiguous()
     perm = torch.arange(N).reshape(c, p, p).permute(1, 2, 0).reshape(-1)                  # new row (dy,dx,c) <- old row c*p*p+dy*p+dx
     assert Npad == N
     out = torch.zeros(V, p * h, p * w, c, dtype=torch.float32, device=dev())
     hip.gemm(a.to(dev()), wt[perm].contiguous().to(dev()), out, bias=b[perm].contiguous().to(dev()), ps=(p, c, h, w))
     assert rel_l2(out.cpu(), ref) < 2e-3
+    EB.check(out.cpu(), ref, bound, 'gemm pixel-shuffle store')
 
 
 @pytest.mark.parametrize('Cin,Cout,H,W', [(64, 128, 12, 20), (128, 64, 9, 7)])
@@ -180,11 +198,15 @@ def test_gemm_implicit_conv3x3(Cin, Cout, H, W):
     x = bf(rn(16, V, H, W, Cin))                                  # NHWC
     wt = bf(rn(17, Cout, Cin, 3, 3, scale=(9 * Cin) ** -0.5))
     b = rn(18, Cout)
-    ref = F.conv2d(x.float().permute(0, 3, 1, 2), wt.float(), b, padding=1).permute(0, 2, 3, 1).reshape(V * H * W, Cout)
+    conv = lambda xx, ww: F.conv2d(xx.permute(0, 3, 1, 2), ww, padding=1).permute(0, 2, 3, 1).reshape(V * H * W, Cout)
+    core = conv(x.double(), wt.double())
+    ref = core + b.double()
     wk = wt.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).contiguous()   # [N, tap, c]
     out = torch.zeros(V * H * W, Cout, dtype=torch.float32, device=dev())
     hip.gemm(x.to(dev()), wk.to(dev()), out, bias=b.to(dev()), conv=(Cin, H, W))
     assert rel_l2(out.cpu(), ref) < 2e-3
+    acc = 2 * (9 * Cin / 32 + 2) * EB.U32 * conv(x.double().abs(), wt.double().abs())          # implicit im2col: zero-padded taps add nothing
+    EB.check(out.cpu(), ref, EB.gemm_bound_from(core, acc, torch.float32, bias=b), 'gemm implicit conv3x3')
 
 
 LN2 = 0.6931471805599453
@@ -199,12 +221,15 @@ def _attn_ref(q, k, v, mask=None, pre=False):
 
 
 @pytest.mark.parametrize('B,H,Nq,Nk,hd', [(1, 2, 64, 64, 64), (2, 3, 200, 333, 64), (1, 16, 769, 769, 64), (1, 4, 768, 1536, 96),
-                                          (3, 2, 50, 70, 96), (1, 12, 2304, 768, 64)])
+                                          (3, 2, 50, 70, 96), (1, 12, 2304, 768, 64),
+                                          (1, 2, 65, 577, 96), (2, 2, 129, 1025, 96)])     # tails: one key in the last tile, one row past a 64 / 128-query block
 @pytest.mark.parametrize('masked', [False, True])
 @pytest.mark.parametrize('pre', [False, True])
 def test_attention(B, H, Nq, Nk, hd, masked, pre):
     from panst3r_amd import hip
-    q, k, v = bf(rn(20, B, H, Nq, hd) * (hd ** -0.5 * hip.LOG2E if pre else 1.0)), bf(rn(21, B, H, Nk, hd)), bf(rn(22, B, H, Nk, hd))
+    qr, kr = rn(20, B, H, Nq, hd), rn(21, B, H, Nk, hd)
+    planted = plant_keys(qr, kr, Nk, 1) if Nk % 64 == 1 else []     # one key in the last tile: it (and key 0) dominates one row each
+    q, k, v = bf(qr * (hd ** -0.5 * hip.LOG2E if pre else 1.0)), bf(kr), bf(rn(22, B, H, Nk, hd))
     mask = None
     if masked:
         g = np.random.Generator(np.random.PCG64(5))
@@ -213,6 +238,8 @@ def test_attention(B, H, Nq, Nk, hd, masked, pre):
         mask[:, 0, 64:] = True                                   # a row whose later tiles are fully blocked
         mask[:, 1, :Nk - 1] = True                               # a row whose only open key is the last one
         mask[:, 1, Nk - 1] = False
+        for i, key in enumerate(planted):
+            mask[:, 2 * i + 3, key] = False
     ref = _attn_ref(q.float(), k.float(), v.float(), mask, pre)
     # device layouts: q/k/o token-major [B, N, H*hd]; V transposed [H*hd, B*Nkp] (key contiguous, views side by side)
     Nkp = (Nk + 7) // 8 * 8
@@ -237,14 +264,39 @@ def test_attention(B, H, Nq, Nk, hd, masked, pre):
     got = od.float().cpu().reshape(B, Nq, H, hd).permute(0, 2, 1, 3)
     assert torch.isfinite(got).all()
     assert rel_l2(got, ref) < 1.2e-2
+    check_attention(od.reshape(B, Nq, H, hd).permute(0, 2, 1, 3), q, k, v, mask, pre, 1, 'attention')
 
 
-@pytest.mark.parametrize('H,Nq,Nk,hd,ns,masked', [(12, 768, 6144, 64, 4, False), (8, 200, 3000, 96, 7, True), (2, 70, 1100, 64, 32, False)])
+def check_attention(got, q, k, v, mask, pre, nsplit, what):
+    """per-element bound of tests/errbound.py against the float64 softmax of the same 16-bit operands (evaluated on the GPU)"""
+    q, k, v = q.to(dev()), k.to(dev()), v.to(dev())
+    m = mask.to(dev()) if mask is not None else None
+    ref = EB.attn_ref(q, k, v, m, pre)
+    return EB.check(got, ref, EB.attn_bound(q, k, v, m, pre, d16(), d16(), nsplit=nsplit or 1), what)
+
+
+def plant_keys(qr, kr, Nk, ns):
+    """give the last key of the last tile and the first / last key of every split a large logit in one query row each (rows 3, 5, 7, ...): a key that is
+    dropped or counted twice then moves its row by O(|v|) instead of ~1/Nk.  qr / kr: the unscaled [1, H, N, hd] operands, changed in place."""
+    tiles = (Nk + 63) // 64
+    tps = (tiles + ns - 1) // ns
+    keys = sorted({Nk - 1} | {min(s_ * tps * 64, Nk - 1) for s_ in range(ns)} | {min((s_ + 1) * tps * 64, Nk) - 1 for s_ in range(ns)})
+    for i, key in enumerate(keys):
+        kr[:, :, key] = qr[:, :, 2 * i + 3] * 1.5
+    return keys
+
+
+@pytest.mark.parametrize('H,Nq,Nk,hd,ns,masked', [(12, 768, 6144, 64, 4, False), (8, 200, 3000, 96, 7, True), (2, 70, 1100, 64, 32, False),
+                                                 (2, 129, 513, 96, 8, False), (2, 65, 1025, 96, 16, False), (1, 80, 6144, 96, 4, False)])
 @pytest.mark.parametrize('pre', [False, True])
 def test_attention_split_k(H, Nq, Nk, hd, ns, masked, pre):
-    """flash-decoding split over the key range + combine == unsplit softmax (incl. empty / tail splits and masks)."""
+    """flash-decoding split over the key range + combine == unsplit softmax (incl. empty / tail splits and masks).  Nk = 64t + 1 with 8 / 16 splits: the
+    last non-empty split is one key long; there, and at Nk = 6144, the first / last key of every split and the last key carry planted logits."""
     from panst3r_amd import hip
-    q, k, v = bf(rn(23, 1, H, Nq, hd) * (hd ** -0.5 * hip.LOG2E if pre else 1.0)), bf(rn(24, 1, H, Nk, hd)), bf(rn(25, 1, H, Nk, hd))
+    qr, kr = rn(23, 1, H, Nq, hd), rn(24, 1, H, Nk, hd)
+    if Nk % 64 == 1 or Nq == 80:
+        plant_keys(qr, kr, Nk, ns)
+    q, k, v = bf(qr * (hd ** -0.5 * hip.LOG2E if pre else 1.0)), bf(kr), bf(rn(25, 1, H, Nk, hd))
     mask = None
     if masked:
         g = np.random.Generator(np.random.PCG64(6))
@@ -268,6 +320,7 @@ def test_attention_split_k(H, Nq, Nk, hd, ns, masked, pre):
         got = od.float().cpu().reshape(Nq, H, hd).permute(1, 0, 2)
         assert torch.isfinite(got).all()
         assert rel_l2(got, ref[0]) < 1.2e-2
+        check_attention(od.reshape(1, Nq, H, hd).permute(0, 2, 1, 3), q, k, v, mask, pre, nsplit, 'attention split-K')
 
 
 @pytest.mark.parametrize('pre', [False, True])
@@ -290,6 +343,7 @@ def test_attention_softmax_rescale_spike(pre):
     hip.attention(qd, kd, vt, od, 1, 1, Nq, Nk, hd, (0, 0, hd), (0, 0, hd), (0, 0, vt.stride(0)), (0, 0, hd), prescaled=pre)
     assert rel_l2(od.float().cpu(), ref[0, 0]) < 1.2e-2
     assert rel_l2(od.float().cpu()[7], ref[0, 0, 7]) < 1.2e-2
+    check_attention(od[None, None], q, k, v, None, pre, 1, 'attention rescale spike')
 
 
 def test_attention_fully_masked_rows_are_zero():
@@ -315,6 +369,7 @@ def test_attention_fully_masked_rows_are_zero():
         assert torch.isfinite(got).all() and float(got[:, 3].abs().max()) == 0.0
         keep = [i for i in range(Nq) if i != 3]
         assert rel_l2(got[:, keep], ref[0][:, keep]) < 1.2e-2
+        check_attention(od.reshape(1, Nq, H, hd).permute(0, 2, 1, 3), q, k, v, mask, False, ns, 'attention fully masked rows')
 
 
 @pytest.mark.parametrize('D,eps', [(1024, 1e-6), (768, 1e-6), (384, 1e-5), (48, 1e-5), (2816, 1e-5)])
@@ -322,19 +377,25 @@ def test_layernorm(D, eps):
     from panst3r_amd import hip
     rows = 2 * 37
     x, g, b = rn(40, rows, D) * 3 + 1, 1 + 0.1 * rn(41, D), 0.1 * rn(42, D)
-    ref = F.layer_norm(x, (D,), g, b, eps)
+    x[::9] = rn(47, x[::9].shape[0], D) * 0.01 + 1            # quiet rows (variance 1e-4): there eps moves the output well above the bound
+    ref = EB.layernorm_ref(x, g, b, eps)
     out = torch.zeros(rows, D, dtype=torch.float32, device=dev())
     hip.layernorm(x.to(dev()), g.to(dev()), b.to(dev()), out, eps)
     assert rel_l2(out.cpu(), ref) < 1e-5
+    EB.check(out.cpu(), ref, EB.rownorm_bound(x, g, b, eps, torch.float32), 'layernorm fp32')
     outb = torch.zeros(rows, D + 8, dtype=d16(), device=dev())
     hip.layernorm(bf(x).to(dev()), g.to(dev()), b.to(dev()), outb[:, :D], eps)
     assert rel_l2(outb[:, :D].float().cpu(), F.layer_norm(bf(x).float(), (D,), g, b, eps)) < 5e-3
+    EB.check(outb[:, :D].cpu(), EB.layernorm_ref(bf(x), g, b, eps), EB.rownorm_bound(bf(x), g, b, eps, d16()), 'layernorm 16-bit')
+    assert float(outb[:, D:].abs().max()) == 0.0
     # input row remap: skip a leading CLS row per 38-row group
     xs = rn(43, 2 * 38, D)
     out2 = torch.zeros(rows, D, dtype=torch.float32, device=dev())
     hip.layernorm(xs.to(dev()), g.to(dev()), b.to(dev()), out2, eps, grp=(37, 38, 1))
-    ref2 = F.layer_norm(xs.reshape(2, 38, D)[:, 1:].reshape(rows, D), (D,), g, b, eps)
+    xr = xs.reshape(2, 38, D)[:, 1:].reshape(rows, D)
+    ref2 = F.layer_norm(xr, (D,), g, b, eps)
     assert rel_l2(out2.cpu(), ref2) < 1e-5
+    EB.check(out2.cpu(), EB.layernorm_ref(xr, g, b, eps), EB.rownorm_bound(xr, g, b, eps, torch.float32), 'layernorm row remap')
 
 
 @pytest.mark.parametrize('hd,H', [(64, 16), (64, 12), (96, 4), (16, 2)])
@@ -355,6 +416,9 @@ def test_rope2d(hd, H):
     got = d.float().cpu().reshape(T, 3, H, hd)
     assert rel_l2(got[:, 0].permute(1, 0, 2), ref_q[0]) < 5e-3
     assert rel_l2(got[:, 1].permute(1, 0, 2), ref_k[0]) < 5e-3
+    for i in range(2):
+        r64, bound = EB.rope2d(qk[i, 0], pos[0], d16())                      # float64 angles of the same 16-bit inputs
+        EB.check(got[:, i].permute(1, 0, 2), r64, bound, 'rope2d')
     assert torch.equal(got[:, 2], x.float().reshape(T, 3, H, hd)[:, 2])      # v untouched
 
 
@@ -452,6 +516,10 @@ def test_loftup_guidance_and_groupnorm():
     refn = F.group_norm(got.permute(0, 2, 1).reshape(2, CH, H // 2, W // 2), 1, gamma, beta, 1e-5).permute(0, 2, 3, 1).reshape(2 * P, CH)
     assert rel_l2(out[:, :CH].float().cpu(), refn) < 5e-3
     assert float(out[:, CH:].abs().max()) == 0.0
+    refn64, boundn = EB.groupnorm(got.reshape(2 * P, CH), 2, P, 1, gamma, beta, 1e-5, d16())
+    EB.check(out[:, :CH].cpu(), refn64, boundn, 'groupnorm(1) apply')
+    # the fused path recomputes the Fourier features in the kernel (phases up to e^10 rad: fp32 sin / cos of the same argument is the reference's own
+    # arithmetic, not a rounding of an exact value), so no derived bound applies to it; it is held to the two-kernel path below, which is bounded above
     # fused path: the same features + GroupNorm(1) without the fp32 feature buffer (two recomputing passes)
     out2 = torch.full((2 * P, 256), 7.0, dtype=d16(), device=dev())
     scratch = torch.zeros(2 * (3 * P + 6) + 16, device=dev())
@@ -472,6 +540,9 @@ def test_loftup_guidance_and_groupnorm():
     hip.groupnorm_apply(x.to(dev()), st8, g8.to(dev()), b8.to(dev()), o8, 2, P, Cc, 8, 1e-5, True)
     ref8 = F.relu(F.group_norm(x.reshape(2, P, Cc).permute(0, 2, 1).reshape(2, Cc, H // 2, W // 2), 8, g8, b8, 1e-5))
     assert rel_l2(o8.float().cpu().reshape(2, P, Cc), ref8.permute(0, 2, 3, 1).reshape(2, P, Cc)) < 5e-3
+    ref864, bound8 = EB.groupnorm(x, 2, P, 8, g8, b8, 1e-5, d16(), relu=True)
+    EB.check(o8.cpu(), ref864, bound8, 'groupnorm(8) apply + ReLU')
+    # (the low-resolution positional features below are the same fp32 Fourier-feature arithmetic: held to the oracle module by max-abs, no derived bound)
     # low-res positional features
     lr = ImplicitFeaturizer(False, n_freqs=5, learn_bias=True)
     with torch.no_grad():
@@ -515,6 +586,10 @@ def test_gemm_strided_batch_and_layernorm_add():
     hip.gemm(a[0], w[0], out[0], bias=b[0], act='gelu', batch=(L, a.stride(0), w.stride(0), out.stride(0), b.stride(0)))
     hip.gemm(a[0], w[0], outt[0], bias=b[0], trans_out=True, batch=(L, a.stride(0), w.stride(0), outt.stride(0), b.stride(0)))
     assert torch.equal(out, ref) and torch.equal(outt, reft)
+    for l in range(L):                                          # the anchor of both (the per-problem launches are compared bit for bit above)
+        core = a[l].double() @ w[l].double().T + b[l].double()
+        EB.check(out[l], F.gelu(core), EB.gemm_bound(a[l], w[l], d16(), bias=b[l], act='gelu'), 'gemm strided batch')
+        EB.check(outt[l][:, :M].T, core, EB.gemm_bound(a[l], w[l], d16(), bias=b[l]), 'gemm strided batch transposed')
     with pytest.raises(RuntimeError):
         hip.gemm(a[0], w[0], out[0].float(), res=out[0].float(), batch=(L, a.stride(0), w.stride(0), out.stride(0), b.stride(0)))
     x, add = rn(303, 50, 768).to(dev()), rn(304, 50, 768).to(dev())
@@ -524,6 +599,8 @@ def test_gemm_strided_batch_and_layernorm_add():
     hip.layernorm(x + add, g, bt, y1, 1e-6)
     hip.layernorm(x, g, bt, y2, 1e-6, add=add)
     assert torch.equal(y1, y2)
+    xa = x + add                                                # the kernel's fp32 add: one rounding, the same as torch's
+    EB.check(y2, EB.layernorm_ref(xa, g, bt, 1e-6), EB.rownorm_bound(xa, g, bt, 1e-6, d16()), 'layernorm_add 16-bit')
 
 
 @pytest.mark.parametrize('M,N,K', [(192, 768, 768), (640, 1024, 1024), (200, 3072, 768), (768, 768, 3072), (1536, 1024, 4096)])
@@ -637,13 +714,20 @@ def test_gemm_layernorm_fold_consumer(M, N, D, kern):
     out = torch.full((M, N), float('nan'), dtype=torch.float32, device=dev())
     hip.gemm(xc, wf.to(dev()), out, bias=bfold, ln=(st, cs, eps), kernel=kern)
     assert rel_l2(out.cpu(), ref) < tol, rel_l2(out.cpu(), ref)
+    # per element: the row-norm and GEMM models composed, float64 of the SAME 16-bit rows / folded W (the rel-L2 reference above is the unrounded LN(x) W^T)
+    fold = lambda fmt, act=None: EB.ln_fold_bound(xc, wf.to(dev()), cs, bfold, x.to(dev()), eps, fmt, act)
+    EB.check(out, *fold(torch.float32), 'gemm LN fold consumer fp32')
     out16 = torch.full((M, N), float('nan'), dtype=d16(), device=dev())
     hip.gemm(xc, wf.to(dev()), out16, bias=bfold, ln=(st, cs, eps), act='gelu', kernel=kern)
     assert rel_l2(out16.float().cpu(), F.gelu(ref)) < tol + 4e-3
+    ref16, bound16 = fold(d16(), 'gelu')
+    EB.check(out16, ref16, bound16, 'gemm LN fold consumer 16-bit GELU')
     if kern != 256:
         outt = torch.zeros(N, (M + 7) // 8 * 8 + 8, dtype=d16(), device=dev())
         hip.gemm(xc, wf.to(dev()), outt, bias=bfold, ln=(st, cs, eps), trans_out=True, kernel=kern)
         assert rel_l2(outt[:, :M].float().cpu().T, ref) < tol + 4e-3
+        reft, boundt = fold(d16())
+        EB.check(outt[:, :M].T, reft, boundt, 'gemm LN fold consumer transposed')
 
 
 @pytest.mark.parametrize('M,N,K,kern', [(300, 256, 128, 0), (768, 1024, 1024, 0), (1500, 1024, 4096, 256), (130, 192, 64, 0), (5000, 384, 384, 128),
@@ -666,11 +750,13 @@ def test_gemm_layernorm_fold_producer(M, N, K, kern):
     hip.rowstats(y, xc2, st2)
     assert torch.equal(xc, xc2)
     assert torch.equal(st, st2)                                                # same per-thread order, same DPP tree: bit-identical
+    EB.check(y, a.double() @ w.double().T + b.double() + res.double(), EB.gemm_bound(a, w, torch.float32, bias=b, res=res), 'gemm LN fold producer fp32 stream')
     # 16-bit residual stream (LoftUp blocks): statistics of the stored (rounded) values
     r16 = bf(rn(814, M, N)).to(dev())
     o16 = r16.clone()
     st3 = torch.full((M, N // 64, 2), float('nan'), device=dev())
     hip.gemm(a, w, o16, bias=b, res=o16, stats_out=st3, kernel=kern)
+    EB.check(o16, a.double() @ w.double().T + b.double() + r16.double(), EB.gemm_bound(a, w, d16(), bias=b, res=r16), 'gemm LN fold producer 16-bit stream')
     g = o16.float().reshape(M, N // 64, 64)
     assert rel_l2(st3[..., 0].cpu(), g.sum(-1).cpu()) < 1e-4 and rel_l2(st3[..., 1].cpu(), (g * g).sum(-1).cpu()) < 1e-4
 
@@ -728,6 +814,7 @@ def test_attention_peaked_softmax(H, Nq, Nk, hd, gain):
         got = od.float().cpu().reshape(Nq, H, hd).permute(1, 0, 2)[None]
         assert torch.isfinite(got).all()
         assert rel_l2(got, ref) < (6e-3 if d16() == torch.bfloat16 else 1.5e-3), (ns, rel_l2(got, ref))
+        check_attention(od.reshape(1, Nq, H, hd).permute(0, 2, 1, 3), q, k, v, None, False, ns, 'attention peaked softmax')
 
 
 @pytest.mark.parametrize('M', [16384, 32 * 1200, 32 * 4099])
@@ -807,7 +894,9 @@ def test_groupnorm_apply_streaming_16bit(C, G, P, relu):
     stores): == F.group_norm on the same (rounded) input, statistics from pst_groupnorm_stats."""
     from panst3r_amd import hip
     n = 3
-    x = bf(rn(990, n * P, C) * 1.7 + 0.4).to(dev())
+    x = rn(990, n * P, C) * 1.7 + 0.4
+    x[P:2 * P] = rn(994, P, C) * 0.003                       # a quiet view (zero mean, variance 9e-6): there eps moves the output past the bound
+    x = bf(x).to(dev())
     g, b = 1 + 0.1 * rn(991, C), 0.1 * rn(992, C)
     st = hip.stats_buffer(n, G, dev())
     hip.groupnorm_stats(x, st, n, P, C, G)
@@ -817,6 +906,8 @@ def test_groupnorm_apply_streaming_16bit(C, G, P, relu):
     if relu:
         ref = F.relu(ref)
     assert rel_l2(out.float().cpu(), ref) < (6e-3 if d16() == torch.bfloat16 else 1e-3)
+    ref64, bound = EB.groupnorm(x.cpu(), n, P, G, g, b, 1e-5, d16(), relu)       # one-pass (sum, sumsq) statistics of pst_groupnorm_stats
+    EB.check(out.cpu(), ref64, bound, 'groupnorm apply 16-bit')
 
 
 @pytest.mark.parametrize('C', [256, 384])
@@ -836,6 +927,8 @@ def test_mask_head_streaming_kernel(C, Q, P, n):
         assert torch.equal(out[i], ref), i
     want = torch.einsum('qc,npc->nqp', E.float().cpu(), F_.float().cpu())
     assert rel_l2(out.cpu(), want) < 2e-3
+    for i in range(n):                                      # a K = C dot product per pixel: the GEMM model (float64 on the GPU)
+        EB.check(out[i], E.double() @ F_[i].double().T, EB.gemm_bound(E, F_[i], torch.float32), 'mask head')
     again = torch.empty_like(out)
     for _ in range(5):
         hip.mask_head(E, F_, again)
@@ -1068,7 +1161,7 @@ def test_loftup_minmax_and_merge():
     d2 = half_bilinear(img)
     mm = torch.empty(n, 3, 2, device=dev())
     hip.loftup_minmax(img.to(dev()), mm)
-    close = torch.equal          # the kernel's 2x2 mean IS the nested bilinear, bit for bit
+    close = torch.equal          # the kernel's 2x2 mean IS the nested bilinear, bit for bit (exact comparisons: no error bound is needed here)
     assert close(mm[..., 0].cpu(), d2.amin(dim=(2, 3))) and close(mm[..., 1].cpu(), d2.amax(dim=(2, 3)))
     scope = torch.tensor([0, 0, 1, 0, 1], dtype=torch.int32, device=dev())
     out = hip.minmax_merge(mm, scope, torch.empty_like(mm))
@@ -1160,4 +1253,5 @@ def test_layernorm_384_wide_16bit_rows(rows):
     out = torch.full((rows + 2, D + 8), 7.0, dtype=d16(), device=dev())
     hip.layernorm(x.to(dev()), g.to(dev()), b.to(dev()), out[:rows, :D], 1e-5)
     assert rel_l2(out[:rows, :D].float().cpu(), ref) < 5e-3
+    EB.check(out[:rows, :D].cpu(), EB.layernorm_ref(x, g, b, 1e-5), EB.rownorm_bound(x, g, b, 1e-5, d16()), 'layernorm 384-wide 16-bit')
     assert float((out[rows:].float() - 7.0).abs().max()) == 0.0 and float((out[:, D:].float() - 7.0).abs().max()) == 0.0      # nothing written outside

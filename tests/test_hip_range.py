@@ -6,6 +6,7 @@ SAME weights, tolerances = SURVEY 8(d) (bench.TOLERANCE), unrelaxed:
             (hip.maxabs_telemetry) shows the largest 16-bit value, the 16-bit copy of the decoder's residual stream, at ~0.2 of the f16 range
   S = 3e4   the f16 backbone overflows; the call falls back by itself (PanSt3R.range_fallback_of: fp16 -> bf16 backbone + f16 panoptic decoder), says so in a
             RuntimeWarning, records the placement that ran in `last_precision`, and its outputs are inside the tolerances; range_fallback=False raises.
+            An explicit panoptic placement ('reference': fp32 panoptic decoder) survives the fallback: only the backbone format moves.
 Measured (profiles/r6_range_probe.txt): S = 1e3 fp16 pointmaps 5.4e-4 / masks 2.4e-3 / 99.96 %; bf16 5.0e-3 / 6.7e-3 / 99.87 %; S = 3e4 after the fallback 3.4e-3 / 8.6e-3 / 99.80 %."""
 import warnings
 
@@ -82,6 +83,26 @@ def test_f16_overflow_falls_back_to_a_range_safe_placement_by_itself():
         pm, pan = model.forward_inference_multi_ar(inp, ts, names, num_keyframes=2, amp='fp16', max_bs=1)
     assert any('repeating the call' in str(x.message) for x in w), [str(x.message) for x in w]
     assert model.last_precision == ('bf16', None)
+    assert all(bool(torch.isfinite(t).all()) for t in pm) and all(bool(torch.isfinite(t).all()) for t in pan['pred_masks'])
+    e = bench._scene_errors(pm, pan, ref[0], ref[1])
+    assert bench._within(e), e
+
+
+def test_f16_overflow_fallback_keeps_an_explicit_panoptic_placement():
+    """amp='fp16', panoptic_precision='reference' at S = 3e4: the fallback moves the backbone to bf16 and keeps the caller's fp32 panoptic placement
+    (it used to drop it and put the panoptic decoder on f16 operands)."""
+    import bench
+    from panst3r_amd.panst3r import PanSt3R
+    assert PanSt3R.range_fallback_of('fp16', 'reference') == ('bf16', 'reference')
+    built = build_outlier(3e4)
+    model, _, names, _ = built
+    ref, imgs, ts = oracle(built, 2, 2)
+    inp = [i.to(torch.device(DEV)) for i in imgs]
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter('always')
+        pm, pan = model.forward_inference_multi_ar(inp, ts, names, num_keyframes=2, amp='fp16', max_bs=1, panoptic_precision='reference')
+    assert any('repeating the call' in str(x.message) for x in w), [str(x.message) for x in w]
+    assert model.last_precision == ('bf16', 'reference')
     assert all(bool(torch.isfinite(t).all()) for t in pm) and all(bool(torch.isfinite(t).all()) for t in pan['pred_masks'])
     e = bench._scene_errors(pm, pan, ref[0], ref[1])
     assert bench._within(e), e

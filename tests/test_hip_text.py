@@ -4,6 +4,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import errbound as EB
 import text_tiny as T
 
 pytestmark = pytest.mark.gpu
@@ -109,6 +110,8 @@ def test_gemm_act3_is_tanh_gelu():
         out = hip.gemm(a, w, torch.empty(300, 512, device=DEV), bias=b, act='gelu_tanh')
         erf = hip.gemm(a, w, torch.empty(300, 512, device=DEV), bias=b, act='gelu')
     want = F.gelu(pre, approximate='tanh')
+    ref = F.gelu(a.double() @ w.double().T + b.double(), approximate='tanh')
+    EB.check(out, ref, EB.gemm_bound(a, w, torch.float32, bias=b, act='gelu_tanh', mode='fp32'), 'gemm fp32 tanh GELU')
     assert (out - want).abs().max().item() <= 4e-7 * max(1.0, pre.abs().max().item())        # fp32 rounding of the same pre-activation
     assert (out - erf).abs().max().item() > 1e-4                  # not the erf GELU
     # every 16-bit kernel refuses act 3 instead of computing something else; so does the split-f16 fp32 mode, which runs 16-bit GEMMs
