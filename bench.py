@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- frames/s of N-view 512-px PanSt3R panoptic inference on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--variant v2] [--views 50] [--keyframes 16] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--variant v2] [--views 50] [--keyframes 16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one full scene forward (encoder + DINOv2 on every view, sequential keyframe-memory build, render of every
@@ -9,8 +9,14 @@ view, upscaler, panoptic query decoder, query x pixel masks of every view) on sy
 HBM, random-init full-size weights.  Default workload = BASELINE.json configs[3] (v2 / LoftUp, 50 views, 16
 keyframes, 384x512), which fits one GPU; with --gpus N the SAME scene is view-sharded over N ranks (RCCL all-gathers
 of keyframe tokens, panst3r_amd/scene.py), i.e. strong scaling.  Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the JSON line (with
+the per-kernel / roofline figures of the instrumented last timed step).  --full adds everything that takes runs or
+host work of its own: the other precisions, the API-entry timings, the stand-alone HBM stages, the check of the timed
+form after the timed steps, the CPU baselines and the full-size parity against the oracle (several minutes).
 """
 import argparse
+import gc
 import json
 import os
 import sys
@@ -43,6 +49,30 @@ def usable_cores():
         except Exception:
             pass
     return max(1, min(n, 64))
+
+
+def fill_weights(model, seed, threads):
+    """synthetic.fill_module_(model, seed) on `threads` host threads, into the model wherever it lives: every state-dict entry has a generator of
+    its own (synthetic.fill_value, numpy releases the GIL while it draws), so the entries are independent and the bits are those of the
+    sequential fill (8-15 s on one core for the 0.8 G weights of v2).  Entries on the GPU are sent from pinned memory: pageable host -> HBM
+    copies of the 3.2 GB of v2 weights (model.to) took 0.2 s in some runs and 8-11 s in others on MI355X boxes.  Raises if a parameter or
+    buffer is not a floating state-dict entry (it would keep whatever it held, e.g. after to_empty)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from panst3r_amd.synthetic import fill_value
+    items = sorted(((k, t) for k, t in model.state_dict().items() if t.dtype.is_floating_point), key=lambda kt: -kt[1].numel())
+    filled = {t.data_ptr() for _, t in items}
+    left = [n for n, t in list(model.named_parameters()) + list(model.named_buffers()) if t.data_ptr() not in filled]
+    if left:
+        raise RuntimeError('fill_weights: not filled: %s' % left[:8])
+
+    def one(kt):
+        k, t = kt
+        v = torch.from_numpy(fill_value(k, t.shape, seed)).to(t.dtype)
+        with torch.no_grad():
+            t.copy_(v.pin_memory() if t.is_cuda else v)
+    with ThreadPoolExecutor(max(1, threads)) as ex:
+        list(ex.map(one, items))
+    return model
 
 
 TOLERANCE = {'pointmaps_rel_l2': 2e-2, 'mask_logits_rel_l2': 3e-2, 'mask_sign_agreement': 0.995, 'class_logits_max_abs': 0.05,
@@ -294,13 +324,16 @@ def main():
     ap.add_argument('--height', type=int, default=384)
     ap.add_argument('--width', type=int, default=512)
     ap.add_argument('--amp', default='fp16', choices=['fp16', 'bf16'], help="16-bit MFMA operand format (reference --amp, tools/demo_panst3r.py:88)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-baseline-c2', action='store_true', help='also time the reduced C2 sample (v1, 8 views / 8 keyframes) on the host: ~1 min')
-    ap.add_argument('--no-alt-dtype', action='store_true', help='skip the short measurement of the other 16-bit format')
-    ap.add_argument('--no-depth-parity', action='store_true', help='skip the K = 16 parity scene (16 views = 16 keyframes = BASELINE configs[2]; ~1.5 min of host time)')
-    ap.add_argument('--no-kernel-timing', action='store_true')
-    ap.add_argument('--parity-c4', action='store_true', help='also compare the TIMED configuration itself (v2, 50 views / 16 keyframes, full size) with the oracle on the host: several minutes')
-    ap.add_argument('--parity-c5', action='store_true', help='also compare BASELINE configs[4] (v2, 200 views / 32 keyframes, fp16, full size) with the oracle on the host: ~15 min, ~12 GB of host memory')
+    ap.add_argument('--full', action='store_true', help='after the headline figure, also run every other measurement and check: the other precisions, the API '
+                                                        'entry, the stand-alone HBM stages, the CPU baselines and the full-size parity against the oracle (one GPU; '
+                                                        'several minutes).  A plain run does only what the headline figure needs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baselines, the parity against the oracle and the other precisions')
+    ap.add_argument('--cpu-baseline-c2', action='store_true', help='--full: also time the reduced C2 sample (v1, 8 views / 8 keyframes) on the host: ~1 min')
+    ap.add_argument('--no-alt-dtype', action='store_true', help='--full: skip the short measurements of the other precisions and of the API entry')
+    ap.add_argument('--no-depth-parity', action='store_true', help='--full: skip the K = 16 parity scene (16 views = 16 keyframes = BASELINE configs[2]; ~1.5 min of host time)')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='time the last step as a graph replay too (no per-kernel / roofline figures)')
+    ap.add_argument('--parity-c4', action='store_true', help='--full: also compare the TIMED configuration itself (v2, 50 views / 16 keyframes, full size) with the oracle on the host: several minutes')
+    ap.add_argument('--parity-c5', action='store_true', help='--full: also compare BASELINE configs[4] (v2, 200 views / 32 keyframes, fp16, full size) with the oracle on the host: ~15 min, ~12 GB of host memory')
     ap.add_argument('--c5-views', type=int, default=200, help='views of the --parity-c5 scene (32 keyframes stay: the memory size class of configs[4]; the host oracle costs ~4 s / view)')
     ap.add_argument('--overlap', default='auto', choices=['auto', 'off', 'masked', 'plain'],
                     help="stage 2 of the scene: 'off' = the memory build and the bulk encoder / DINOv2 work back to back on one stream; 'masked' = the build on "
@@ -321,6 +354,9 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    for flag in ('cpu_baseline_c2', 'parity_c4', 'parity_c5'):
+        if getattr(args, flag) and not args.full:
+            ap.error('--%s is a leg of --full' % flag.replace('_', '-'))
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # started the way the driver starts `--gpus 1` (plain `python bench.py --gpus N`): become the launcher of N ranks
@@ -357,13 +393,12 @@ def main():
         hip.tune(getattr(hip, 'TUNE_' + k.upper()), int(v))
 
     V, K, H, W = args.views, args.keyframes, args.height, args.width
-    model = build_from_config(CONFIG_V2 if args.variant == 'v2' else CONFIG_V1).eval()
-    fill_module_(model, seed=1)
+    model = build_from_config(CONFIG_V2 if args.variant == 'v2' else CONFIG_V1).eval().to_empty(device=dev)
+    fill_weights(model, 1, min(usable_cores(), torch.get_num_threads()))         # = fill_module_(model, seed=1), straight into HBM
     names, emb = synth_class_embeddings(100)
-    host_legs = rank == 0 and world == 1 and not args.no_cpu_baseline
-    state = {k: v.clone() for k, v in model.state_dict().items()} if host_legs else None
+    host_legs = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
+    state = {k: v.cpu() for k, v in model.state_dict().items()} if host_legs else None
     model.panoptic_decoder.text_encoder.class_embeddings = {n: e for n, e in zip(names, emb)}
-    model.to(dev)
 
     from panst3r_amd.scene import assign_views, resolve_plan
     args.plan = resolve_plan(args.plan, world, min(K, V))
@@ -381,6 +416,9 @@ def main():
     def measure(amp, steps, warmup, instrument, panoptic_precision=None, keep=False):
         """W untimed warm-up steps (the first also captures the three HIP graphs), then EXACTLY `steps` timed steps between two fences.
         keep: sample the outputs of the last timed step into `dumped` (after the second fence, before anything runs the scene again)."""
+        # the runners of earlier legs sit in reference cycles: their HIP graphs must go now, not in a collection that lands inside one of the
+        # captures below (a graph destroyed while a stream captures aborts the process)
+        gc.collect()
         mk = lambda ov: model.scene_runner(images, V, H, W, names, num_keyframes=K, use_graphs=not args.eager, overlap=ov, amp=amp, plan=args.plan,
                                            panoptic_precision=panoptic_precision, stream_bank=args.stream_bank)
         if args.overlap == 'auto' and not args.eager and world == 1:
@@ -420,10 +458,11 @@ def main():
                 dumped['views'] = {i: v for p in parts for i, v in p.items()}
         del last
         pk = OVERLAP_PICK.get(str(amp) + '/' + str(panoptic_precision))
-        if pk is not None and pk.get('serial_digest') is not None and 'after_timed_steps_identical' not in pk:
+        if args.full and pk is not None and pk.get('serial_digest') is not None and 'after_timed_steps_identical' not in pk:
             # outside the timed region: one more replay of the form that was timed, its outputs against the serial scene's bits of the warm-up
             from panst3r_amd.scene import output_digest
             pk['after_timed_steps_identical'] = output_digest(*runner.run(copy=False)) == pk['serial_digest']
+        if pk is not None and isinstance(pk.get('serial_digest'), int):
             pk['serial_digest'] = '%016x' % (pk['serial_digest'] & (2 ** 64 - 1))
         if world > 1:
             t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -463,7 +502,7 @@ def main():
                        'overlap_auto': OVERLAP_PICK.get(str(args.amp) + '/None'),
                        'overlap_streams': {k[1]: v for k, v in __import__('panst3r_amd.scene', fromlist=['HipBackend']).HipBackend._MASKED_LOG.items()} or None,
                        'overlap': {'auto': 'auto: the serial and the CU-masked two-queue stage 2 are both captured and timed during warm-up, the faster runs '
-                                           '(overlap_auto; bit-identical results, CHECKED in this run: overlap_auto.masked_identical over the trial replays, .after_timed_steps_identical after the timed steps; tests/test_hip_fullsize.py::test_full_size_masked_overlap_equals_serial)',
+                                           '(overlap_auto; bit-identical results, CHECKED in this run: overlap_auto.masked_identical over the trial replays, with --full .after_timed_steps_identical after the timed steps; tests/test_hip_fullsize.py::test_full_size_masked_overlap_equals_serial)',
                                    'off': 'off (one stream)', 'plain': 'memory build || non-keyframe encoder + DINOv2 on two ordinary streams (measurement only)',
                                    'masked': 'memory build on a CU-masked stream || first layers of the two ViT-L towers on the other CUs (panst3r_amd/scene.py)'}[args.overlap],
                        'median_ms_per_graph_step': None if median_ms is None else round(median_ms, 3),
@@ -523,10 +562,12 @@ def main():
             out['kernels'] = {k: {'launches': v['launches'], 'ms': round(v['ms'], 2),
                                   'tflops': round(v['flops'] / max(v['ms'], 1e-9) / 1e9, 1)} for k, v in sorted(summ.items())}
             out['hbm_stages'] = hbm_stage_table(timer, V, H, W, args.variant)
+        if timer is not None and args.full:
             # the same stages stand-alone: one captured HIP graph per stage on scene-sized cold operands, replay timed as a whole (the eager numbers
             # above carry 5-10 us of HIP-event overhead per 20-35 us launch)
             try:
                 from panst3r_amd.stagebench import standalone_hbm_stages
+                gc.collect()            # as in measure(): no graph of the scene runners left to be destroyed during these captures
                 out['hbm_stages_standalone'] = standalone_hbm_stages(dev, args.variant, H, W, torch.float16 if args.amp == 'fp16' else torch.bfloat16)
             except Exception as e:          # a measurement leg must not take the bench line down
                 out['hbm_stages_standalone'] = {'error': repr(e)}
@@ -564,6 +605,7 @@ def main():
 
                 def api(amp, graphs, n, outdevice='cpu'):
                     model.clear_runners()
+                    gc.collect()        # as in measure()
                     for _ in range(2 if graphs else 1):            # warm-up (weights packed; with graphs: first call eager, second captures)
                         model.forward_inference_multi_ar(imgs_all, ts_all, names, num_keyframes=K, max_bs=1, outdevice=outdevice, amp=amp, cache_graphs=graphs)
                     _t.cuda.synchronize()

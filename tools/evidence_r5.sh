@@ -5,14 +5,14 @@ R=gpurun_out
 mkdir -p $R
 timeout 1500 bash tools/pmc_profile.sh r5 > $R/r5_pmc_profile.log 2>&1
 cp $R/r5_pmc_summary.json profiles/r5_pmc_summary.json 2>/dev/null
-timeout 900 python bench.py --cpu-baseline-c2 > $R/r5_bench_default.json 2> $R/r5_bench_default.err
-timeout 300 python bench.py --amp bf16 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_bf16.json 2>/dev/null
-timeout 300 python bench.py --variant v1 --views 8 --keyframes 8 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_config1_v1_8v8k.json 2>/dev/null
-timeout 300 python bench.py --variant v1 --views 8 --keyframes 8 --amp bf16 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_config1_v1_8v8k_bf16.json 2>/dev/null
-timeout 300 python bench.py --views 16 --keyframes 16 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_config2_v2_16v16k.json 2>/dev/null
-timeout 300 python bench.py --views 16 --keyframes 16 --amp bf16 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_config2_v2_16v16k_bf16.json 2>/dev/null
-timeout 400 python bench.py --views 200 --keyframes 32 --steps 5 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_c5_200v32k.json 2>/dev/null
-PST_FORCE_DIST=1 timeout 300 python bench.py --steps 10 --no-cpu-baseline --no-alt-dtype --plan broadcast > $R/r5_bench_rccl_world1_broadcast.json 2>/dev/null
+timeout 900 python bench.py --full --cpu-baseline-c2 > $R/r5_bench_default.json 2> $R/r5_bench_default.err
+timeout 300 python bench.py --full --amp bf16 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_bf16.json 2>/dev/null
+timeout 300 python bench.py --full --variant v1 --views 8 --keyframes 8 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_config1_v1_8v8k.json 2>/dev/null
+timeout 300 python bench.py --full --variant v1 --views 8 --keyframes 8 --amp bf16 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_config1_v1_8v8k_bf16.json 2>/dev/null
+timeout 300 python bench.py --full --views 16 --keyframes 16 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_config2_v2_16v16k.json 2>/dev/null
+timeout 300 python bench.py --full --views 16 --keyframes 16 --amp bf16 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_config2_v2_16v16k_bf16.json 2>/dev/null
+timeout 400 python bench.py --full --views 200 --keyframes 32 --steps 5 --no-cpu-baseline --no-alt-dtype > $R/r5_bench_c5_200v32k.json 2>/dev/null
+PST_FORCE_DIST=1 timeout 300 python bench.py --full --steps 10 --no-cpu-baseline --no-alt-dtype --plan broadcast > $R/r5_bench_rccl_world1_broadcast.json 2>/dev/null
 timeout 200 python tools/build_bench.py 16 > $R/r5_build_bench.txt 2>&1
 timeout 200 python tools/build_bench.py 32 >> $R/r5_build_bench.txt 2>&1
 timeout 600 python tools/shard_estimate.py --plans replicated broadcast > $R/r5_shard_estimate.txt 2>&1

@@ -11,7 +11,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python $ROOT/bench.py --no-cpu-baseline --steps 10 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || true
+timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python $ROOT/bench.py --full --no-cpu-baseline --steps 10 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err || true
 for P in a b c; do
   case $P in a) C="SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES";; b) C="FETCH_SIZE";; c) C="WRITE_SIZE";; esac
   timeout -k 5 400 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/$P -o $P -- python $ROOT/bench.py --no-cpu-baseline --steps 1 --eager --no-kernel-timing --overlap off > /dev/null 2> $OUT/$P.err || true
