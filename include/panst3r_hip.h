@@ -390,6 +390,32 @@ int pst_pointmap_activate(const float* raw, float* pts3d, float* pts3d_local, fl
 int pst_focal_weiszfeld(const float* pts3d_local, const float* pp, float* focal, int nviews, int H, int W, int iters, void* stream);
 int pst_rigid_moments(const float* x, const float* y, const float* conf, double* out, int nviews, int npix, float weight_offset, void* stream);
 
+/* ---------------------------------------------------------------- ASMK retrieval (reference engine/retrieval.py:12-47, panst3r.py:88-125)
+ * The checkpoint's retriever after its head (the head runs on pst_gemm / pst_layernorm in fp32 mode); restated in panst3r_amd/model/retrieval.py
+ * [3P-recalled, parity unpinned].  Deterministic: fixed-order reductions, no atomics.
+ *   retrieval_select     head output x fp32 [sum T_v, D] (view v = rows [in_off[v], in_off[v+1]), maxT >= every T_v <= 16384): per view the
+ *                        out_off[v+1] - out_off[v] (<= T_v) rows of largest L2 norm (ties to the lower token), in that order, L2-normalised
+ *                        (x / max(||x||, 1e-12)) -> out fp32 rows [out_off[v], out_off[v+1]); sel_idx (int32, optional) = the token of each out row
+ *   retrieval_assign     the m (1..8, <= k) nearest centroids of each descriptor in L2: smallest ||c||^2 - 2 x.c, ties to the lower centroid, ascending.
+ *                        x3 = pst_split_operand(descriptors, side 0), c3 = pst_split_operand(centroids, side 1) (f16, K3 = 3 Dpad columns,
+ *                        K3 % 64 == 0), cnorm fp32 [k] (||c||^2 taken in double).  The centroid range is split over nsplit (1 .. ceil(k / 64))
+ *                        workgroup columns; with nsplit > 1 the partial lists go to ws_dist / ws_ids (nsplit x n x m each) and a merge kernel
+ *                        combines them in split order.  -> ids int32 [n, m], dist fp32 [n, m].  The n x k distance matrix is never formed.
+ *   retrieval_aggregate  per group g (a (view, word) pair; members member[gstart[g] .. gstart[g+1]) in ascending descriptor order, word gword[g]):
+ *                        s = fp32 sum of (x[member] - cent[word]) -> sums fp32 [ngroups, D] (optional) and bits uint32 [ngroups, D / 32]
+ *                        (bit j of word w = s[32 w + j] > 0); D % 32 == 0
+ *   retrieval_scores     S[i, j] = sum over the words held by query view i and database view j, ascending, of kappa(1 - 2 popcount(bq XOR bdb) / D),
+ *                        kappa(s) = s^alpha if s >= tau else 0 (integer alpha <= 8 by repeated fp32 products); a view's groups are
+ *                        [*_off[v], *_off[v+1]) sorted by word; max_q >= every query view's group count (<= 16384).  S fp32 [nq_views, ndb_views]. */
+int pst_retrieval_select(const float* x, int64_t ldx, const int32_t* in_off, const int32_t* out_off, int nviews, int maxT, int D, float* out, int64_t ldo,
+                         int32_t* sel_idx, void* stream);
+int pst_retrieval_assign(const void* x3, int64_t ldx, const void* c3, int64_t ldc, const float* cnorm, int n, int k, int K3, int m, int nsplit,
+                         float* ws_dist, int32_t* ws_ids, int32_t* ids, float* dist, int dtype16, void* stream);
+int pst_retrieval_aggregate(const float* x, int64_t ldx, const float* cent, int64_t ldc, const int32_t* member, const int32_t* gstart, const int32_t* gword,
+                            int ngroups, int D, float* sums, uint32_t* bits, void* stream);
+int pst_retrieval_scores(const int32_t* q_off, const int32_t* q_word, const uint32_t* q_bits, const int32_t* db_off, const int32_t* db_word,
+                         const uint32_t* db_bits, int nq_views, int ndb_views, int max_q, int D, float alpha, float tau, float* S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

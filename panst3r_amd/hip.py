@@ -44,7 +44,8 @@ EXPORTS = ['pst_abi_version', 'pst_last_error', 'pst_gemm', 'pst_gemm_variant', 
            'pst_patchify', 'pst_dino_preprocess', 'pst_image_prepare', 'pst_patch_rows', 'pst_add_cast', 'pst_l2norm_rows', 'pst_mean4', 'pst_resize_bilinear',
            'pst_attn_mask_from_logits', 'pst_loftup_guidance_gn', 'pst_loftup_minmax', 'pst_minmax_merge', 'pst_groupnorm_stats', 'pst_groupnorm_apply',
            'pst_loftup_lr_pe', 'pst_pp_scores', 'pst_pp_scores_softmax', 'pst_pp_sigmoid', 'pst_pp_argmax', 'pst_pp_argmax_logits', 'pst_pp_select', 'pst_pp_finalize', 'pst_pointmap_activate', 'pst_focal_weiszfeld', 'pst_rigid_moments',
-           'pst_qubo_upsample', 'pst_qubo_workspace_floats', 'pst_qubo_overlap', 'pst_qubo_argmax', 'pst_token_embed']
+           'pst_qubo_upsample', 'pst_qubo_workspace_floats', 'pst_qubo_overlap', 'pst_qubo_argmax', 'pst_token_embed',
+           'pst_retrieval_select', 'pst_retrieval_assign', 'pst_retrieval_aggregate', 'pst_retrieval_scores']
 
 
 def lib():
@@ -1098,3 +1099,67 @@ def qubo_overlap(probs, Q, P, Wacc):
 def qubo_argmax(probs, sel, P, conf, inst):
     _dev(probs, torch.float32); _dev(sel, torch.int32); _dev(conf, torch.float32); _dev(inst, torch.int32)
     _check(lib().pst_qubo_argmax(_ptr(probs), _ptr(sel), sel.numel(), i64(P), _ptr(conf), _ptr(inst), _stream()), 'pst_qubo_argmax')
+
+
+# ------------------------------------------------------------------ ASMK retrieval (model/retrieval.py restates the algorithm)
+def retrieval_select(x, in_off, out_off, out, max_t, sel_idx=None):
+    """per view v (rows [in_off[v], in_off[v+1]) of the fp32 head output x): the out_off[v+1] - out_off[v] rows of largest norm (ties to the lower
+    token), in that order, L2-normalised into rows [out_off[v], out_off[v+1]) of out; sel_idx (int32, optional) gets their token indices"""
+    _dev(x, torch.float32); _dev(in_off, torch.int32); _dev(out_off, torch.int32); _dev(out, torch.float32)
+    if sel_idx is not None:
+        _dev(sel_idx, torch.int32)
+    assert in_off.is_contiguous() and out_off.is_contiguous() and in_off.numel() == out_off.numel() and x.shape[1] == out.shape[1]
+    _check(lib().pst_retrieval_select(_ptr(x), i64(_rowmajor(x)), _ptr(in_off), _ptr(out_off), in_off.numel() - 1, int(max_t), x.shape[1], _ptr(out),
+                                      i64(_rowmajor(out)), _ptr(sel_idx), _stream()), 'pst_retrieval_select')
+    return out
+
+
+def retrieval_nsplit(n, k):
+    """centroid-range splits of pst_retrieval_assign: about two workgroups per CU over the row tiles (128 rows), at most one split per 64 centroids"""
+    tiles_r, tiles_c = (n + 127) // 128, (k + 63) // 64
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    return max(1, min(tiles_c, (2 * cus + tiles_r - 1) // tiles_r))
+
+
+def retrieval_assign(x3, c3, cnorm, m, ids, dist, nsplit=None):
+    """ids [n, m] / dist [n, m] = the m nearest centroids of each descriptor (ascending ||c||^2 - 2 x.c, ties to the lower index): x3 / c3 the split-f16
+    descriptors (split_operand side 0) and centroids (side 1), cnorm fp32 [k].  The partial lists of the centroid splits live in a workspace of this call."""
+    _dev(x3, X3_FMT); _dev(c3, X3_FMT); _dev(cnorm, torch.float32); _dev(ids, torch.int32); _dev(dist, torch.float32)
+    n, k = x3.shape[0], c3.shape[0]
+    assert x3.shape[1] == c3.shape[1] and cnorm.numel() == k and ids.shape == (n, m) and dist.shape == (n, m) and ids.is_contiguous() and dist.is_contiguous()
+    nsplit = retrieval_nsplit(n, k) if nsplit is None else int(nsplit)
+    ws_d = ws_i = None
+    if nsplit > 1:
+        ws_d = torch.empty(nsplit * n * m, dtype=torch.float32, device=x3.device)
+        ws_i = torch.empty(nsplit * n * m, dtype=torch.int32, device=x3.device)
+    _check(lib().pst_retrieval_assign(_ptr(x3), i64(_rowmajor(x3)), _ptr(c3), i64(_rowmajor(c3)), _ptr(cnorm), n, k, x3.shape[1], int(m), nsplit,
+                                      _ptr(ws_d), _ptr(ws_i), _ptr(ids), _ptr(dist), _tc(x3), _stream()), 'pst_retrieval_assign')
+    return ids, dist
+
+
+def retrieval_aggregate(x, cent, member, gstart, gword, bits, sums=None):
+    """per (view, word) group g: fp32 sum of the residuals x[member] - cent[gword[g]] over members gstart[g] .. gstart[g+1] (ascending) -> packed sign
+    bits [G, D / 32] (int32 storage of the uint32 words; bit j of word w = component 32 w + j) and, optionally, the sums [G, D]"""
+    _dev(x, torch.float32); _dev(cent, torch.float32); _dev(member, torch.int32); _dev(gstart, torch.int32); _dev(gword, torch.int32); _dev(bits, torch.int32)
+    G, D = gword.numel(), x.shape[1]
+    assert cent.shape[1] == D and gstart.numel() == G + 1 and bits.shape == (G, D // 32) and bits.is_contiguous()
+    assert member.is_contiguous() and gstart.is_contiguous() and gword.is_contiguous()
+    if sums is not None:
+        _dev(sums, torch.float32)
+        assert sums.shape == (G, D) and sums.is_contiguous()
+    _check(lib().pst_retrieval_aggregate(_ptr(x), i64(_rowmajor(x)), _ptr(cent), i64(_rowmajor(cent)), _ptr(member), _ptr(gstart), _ptr(gword), G, D,
+                                         _ptr(sums), _ptr(bits), _stream()), 'pst_retrieval_aggregate')
+    return bits
+
+
+def retrieval_scores(q_off, q_word, q_bits, db_off, db_word, db_bits, D, alpha, tau, S, max_q):
+    """S [Vq, Vdb] fp32: ASMK binary-kernel similarity of every query view (groups [q_off[i], q_off[i+1]), sorted by word) against every database view"""
+    for t in (q_off, q_word, q_bits, db_off, db_word, db_bits):
+        _dev(t, torch.int32)
+        assert t.is_contiguous()
+    _dev(S, torch.float32)
+    Vq, Vdb = q_off.numel() - 1, db_off.numel() - 1
+    assert S.shape == (Vq, Vdb) and S.is_contiguous() and q_bits.shape[1] == D // 32 and db_bits.shape[1] == D // 32
+    _check(lib().pst_retrieval_scores(_ptr(q_off), _ptr(q_word), _ptr(q_bits), _ptr(db_off), _ptr(db_word), _ptr(db_bits), Vq, Vdb, int(max(1, max_q)), int(D),
+                                      f32(alpha), f32(tau), _ptr(S), _stream()), 'pst_retrieval_scores')
+    return S

@@ -243,6 +243,27 @@ def qubo_argmax(probs: Tensor, sel: Tensor, P: int, conf: Tensor, inst: Tensor) 
     hip.qubo_argmax(probs, sel, P, conf, inst)
 
 
+@_op('retrieval_select', ('out', 'sel_idx'))
+def retrieval_select(x: Tensor, in_off: Tensor, out_off: Tensor, out: Tensor, max_t: int, sel_idx: Optional[Tensor] = None) -> None:
+    hip.retrieval_select(x, in_off, out_off, out, max_t, sel_idx)
+
+
+@_op('retrieval_assign', ('ids', 'dist'))
+def retrieval_assign(x3: Tensor, c3: Tensor, cnorm: Tensor, m: int, ids: Tensor, dist: Tensor, nsplit: Optional[int] = None) -> None:
+    hip.retrieval_assign(x3, c3, cnorm, m, ids, dist, nsplit=nsplit)
+
+
+@_op('retrieval_aggregate', ('bits', 'sums'))
+def retrieval_aggregate(x: Tensor, cent: Tensor, member: Tensor, gstart: Tensor, gword: Tensor, bits: Tensor, sums: Optional[Tensor] = None) -> None:
+    hip.retrieval_aggregate(x, cent, member, gstart, gword, bits, sums)
+
+
+@_op('retrieval_scores', ('S',))
+def retrieval_scores(q_off: Tensor, q_word: Tensor, q_bits: Tensor, db_off: Tensor, db_word: Tensor, db_bits: Tensor, D: int, alpha: float, tau: float,
+                     S: Tensor, max_q: int) -> None:
+    hip.retrieval_scores(q_off, q_word, q_bits, db_off, db_word, db_bits, D, alpha, tau, S, max_q)
+
+
 def registered_ops():
     """names under torch.ops.panst3r_hip"""
     return list(_REGISTERED)

@@ -367,10 +367,12 @@ class PanSt3R(nn.Module):
                                 panoptic_precision=None, _mm_tables=None):
         """imgs: list[V] of [3,H,W] in [-1,1]; true_shape [V,2]; returns (pointmaps list[V] of [1,H,W,7],
         {'pred_logits' [1,Q,Ncls], 'pred_masks' list[V] of [1,Q,H/2,W/2], 'out_queries' [Q,1,768]}).
-        Keyframes: linspace over the views (panst3r.py:183-186) by default.  `use_retrieval=True` (panst3r.py:179-180) takes the
-        V x V image-similarity matrix as `sim_matrix` - the ASMK retriever that produces it in the reference needs asmk / faiss and
-        is outside this build - and applies the reference's selection (schedule.keyframes_from_similarity: farthest-point sampling
-        on 1 - sim, then the greedy overlap ordering of panst3r.py:105-123).  `keyframes=` passes an explicit list instead.
+        Keyframes: linspace over the views (panst3r.py:183-186) by default.  `use_retrieval=True` (panst3r.py:179-180) selects them from the
+        V x V image-similarity matrix with the reference's selection (schedule.keyframes_from_similarity: farthest-point sampling on 1 - sim, then
+        the greedy overlap ordering of panst3r.py:105-123).  The matrix is `sim_matrix` when given, else what the checkpoint's ASMK retriever
+        (`self.retrieval`, engine.retrieval.PanSt3RRetriever) makes of the encoder tokens of every view (an extra encoder pass: the scene runner
+        encodes again); without either the call raises NotImplementedError.  `keyframes=` passes an explicit list instead (precedence:
+        keyframes= > sim_matrix= > the retriever).
         `max_bs` (reference default None; the demo passes 1): the reference stacks same-shape views in chunks of max_bs and LoftUp's MinMaxScaler
         pools min / max over each chunk (loftup.py:14-19, panst3r.py:212-216,257-261) - None scales all same-shape keyframes
         together and all same-shape other views together, 1 scales every view on its own.  Everything else is chunk-invariant and batched here.
@@ -384,9 +386,13 @@ class PanSt3R(nn.Module):
         graphs (see _runner_for; `clear_runners()` frees them).  Default: one eager pass, nothing kept."""
         if use_retrieval and keyframes is None:
             if sim_matrix is None:
-                raise NotImplementedError('use_retrieval=True needs sim_matrix= (the ASMK / faiss retriever is outside this build, SURVEY 8(f)3)')
-            from .schedule import keyframes_from_similarity
-            keyframes = keyframes_from_similarity(sim_matrix, num_keyframes)
+                if self.retrieval is None:
+                    raise NotImplementedError('use_retrieval=True needs a retriever (model.retrieval, the checkpoint\'s `retrieval` entry) or sim_matrix=')
+                x_must3r, _ = self.forward_must3r_encoder(list(imgs), true_shape, amp=amp)       # every view, per shape group, in the call's format
+                keyframes = self._get_keyframes_retrieval([x.float() for x in x_must3r], num_keyframes)
+            else:
+                from .schedule import keyframes_from_similarity
+                keyframes = keyframes_from_similarity(sim_matrix, num_keyframes)
         V = len(imgs)
         dev = imgs[0].device
         shapes = [tuple(int(s) for s in im.shape[-2:]) for im in imgs]        # multi-AR: views are batched per shape group
@@ -451,6 +457,21 @@ class PanSt3R(nn.Module):
         if not cache_graphs:
             runner.release()                    # a one-off scene keeps no intermediates (stacked inputs, features, mask features) alive
         return pms, panout
+
+    def _get_keyframes_retrieval(self, must3r_x, num_keyframes):
+        """Keyframes through retrieval (reference panst3r.py:88-125): must3r_x = per-view encoder tokens (list of [1, T, D] / [T, D], or [1, V, T, D]).
+        The retriever is parsed from `self.retrieval` on first use and kept (packed on the device) while `self.retrieval` stays the same object."""
+        from .engine.retrieval import PanSt3RRetriever
+        from .schedule import keyframes_from_similarity
+        assert self.retrieval is not None, 'Retrieval model not provided.'
+        if not isinstance(must3r_x, (list, tuple)):
+            must3r_x = [xi for xi in must3r_x.squeeze(0)]
+        cached = getattr(self, '_retriever', None)
+        if cached is None or cached[0] is not self.retrieval:
+            cached = (self.retrieval, PanSt3RRetriever(self.retrieval, backbone=self.must3r_encoder, device=must3r_x[0].device, verbose=self.verbose))
+            self._retriever = cached
+        sim_matrix = cached[1](must3r_x, device=must3r_x[0].device)
+        return keyframes_from_similarity(sim_matrix, num_keyframes)
 
     def _runner_for(self, imgs, shapes, classes, num_keyframes, keyframes, dev, amp, cache_graphs, max_bs=1, panoptic_precision=None, mm_tables=None, streamed=False):
         """The SceneRunner of a call.  Default: a fresh eager runner, dropped after the call (what the reference's per-call execution
