@@ -14,6 +14,20 @@
 
 namespace pst {
 
+// ------------------------------------------------------------------ bilinear source coordinate and blend, shared by every kernel below
+// F.interpolate(mode='bilinear', align_corners=False) on fp32 input: src = scale * (dst + 0.5) - 0.5 with the product ROUNDED before the subtraction,
+// clamped at 0.  Contraction is switched off in it because the compiler otherwise turns the expression into one fma, whose unrounded product moves
+// the tap weight by up to half an ulp of src (2e-6 at column 56 of a 56 -> 93 resize) away from the reference's.  The dyadic ratios (2x, 1x) are exact
+// either way.  One blend function, so that pp_argmax and pp_argmax_logits cannot be contracted differently.
+__device__ __forceinline__ float pp_src(float scale, int dst) {
+#pragma clang fp contract(off)
+  const float prod = scale * ((float)dst + 0.5f);
+  return fmaxf(prod - 0.5f, 0.f);
+}
+__device__ __forceinline__ float pp_blend(float hy, float ly, float hx, float lx, float v00, float v01, float v10, float v11) {
+  return hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+}
+
 // ------------------------------------------------------------------ per-query score / label / keep (:40-47)
 __global__ __launch_bounds__(64) void pp_scores_kernel(const float* logits, int Ncls, float cls_thr, float temperature,
                                                        float* scores, int* labels, int* keep) {
@@ -120,8 +134,8 @@ __global__ __launch_bounds__(256) void pp_argmax_kernel(const float* probs, cons
   const bool valid = pix < H * W;
   const int y = valid ? pix / W : 0, x = valid ? pix - (pix / W) * W : 0;
   // F.interpolate(mode='bilinear', align_corners=False): src = scale * (dst + 0.5) - 0.5 clamped at 0
-  const float sy = fmaxf(((float)Hm / (float)H) * ((float)y + 0.5f) - 0.5f, 0.f);
-  const float sx = fmaxf(((float)Wm / (float)W) * ((float)x + 0.5f) - 0.5f, 0.f);
+  const float sy = pp_src((float)Hm / (float)H, y);
+  const float sx = pp_src((float)Wm / (float)W, x);
   const int y0 = min((int)sy, Hm - 1), x0 = min((int)sx, Wm - 1);
   const int y1 = min(y0 + 1, Hm - 1), x1 = min(x0 + 1, Wm - 1);
   const float ly = fminf(fmaxf(sy - (float)y0, 0.f), 1.f), lx = fminf(fmaxf(sx - (float)x0, 0.f), 1.f);
@@ -144,7 +158,7 @@ __global__ __launch_bounds__(256) void pp_argmax_kernel(const float* probs, cons
     for (int u = 0; u < U; ++u) {
       if (j0 + u >= nk) break;               // uniform
       const int q = qs[u];
-      const float m = hy * (hx * t[u][0] + lx * t[u][1]) + ly * (hx * t[u][2] + lx * t[u][3]);
+      const float m = pp_blend(hy, ly, hx, lx, t[u][0], t[u][1], t[u][2], t[u][3]);
       const unsigned long long ge = __ballot(valid && m >= 0.5f);
       if (lane == 0 && ge) atomicAdd(&cnt[q], __popcll(ge));
       const float p = scores[q] * m;
@@ -206,11 +220,11 @@ __global__ __launch_bounds__(256) void pp_argmax_fused_kernel(const float* logit
   const int ty0 = (blockIdx.x / tiles_x) * PP_TH, tx0 = (blockIdx.x % tiles_x) * PP_TW;
   const float scy = (float)Hm / (float)H, scx = (float)Wm / (float)W;
   // first input row / column any pixel of the tile touches (same formula as the per-pixel one below)
-  const int in_y0 = min((int)fmaxf(scy * ((float)ty0 + 0.5f) - 0.5f, 0.f), Hm - 1);
-  const int in_x0 = min((int)fmaxf(scx * ((float)tx0 + 0.5f) - 0.5f, 0.f), Wm - 1);
+  const int in_y0 = min((int)pp_src(scy, ty0), Hm - 1);
+  const int in_x0 = min((int)pp_src(scx, tx0), Wm - 1);
   const int x = tx0 + (threadIdx.x & (PP_TW - 1)), y = ty0 + (threadIdx.x >> 5);
   const bool valid = y < H && x < W;
-  const float sx = fmaxf(scx * ((float)x + 0.5f) - 0.5f, 0.f), sy = fmaxf(scy * ((float)y + 0.5f) - 0.5f, 0.f);
+  const float sx = pp_src(scx, x), sy = pp_src(scy, y);
   const int x0 = min((int)sx, Wm - 1), x1 = min(x0 + 1, Wm - 1);
   const int y0 = min((int)sy, Hm - 1), y1 = min(y0 + 1, Hm - 1);
   const float lx = fminf(fmaxf(sx - (float)x0, 0.f), 1.f), hx = 1.f - lx;
@@ -256,8 +270,8 @@ __global__ __launch_bounds__(256) void pp_argmax_fused_kernel(const float* logit
       const float a00 = ta[t00], a01 = ta[t01], a10 = ta[t10], a11 = ta[t11];
       const float b00 = tb[t00], b01 = tb[t01], b10 = tb[t10], b11 = tb[t11];
       const float sa = scores[qa], sb = scores[qb];
-      const float ma = hy * (hx * a00 + lx * a01) + ly * (hx * a10 + lx * a11);
-      const float mb = hy * (hx * b00 + lx * b01) + ly * (hx * b10 + lx * b11);
+      const float ma = pp_blend(hy, ly, hx, lx, a00, a01, a10, a11);
+      const float mb = pp_blend(hy, ly, hx, lx, b00, b01, b10, b11);
       const unsigned long long ga = __ballot(valid && ma >= 0.5f);
       const unsigned long long gb = __ballot(valid && mb >= 0.5f && u + 1 < nq);
       if (lane == 0) {
@@ -402,14 +416,14 @@ __global__ __launch_bounds__(256) void qubo_upsample_kernel(const float* logits,
   const int64_t total = (int64_t)Q * H * W;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % W), y = (int)((i / W) % H), q = (int)(i / ((int64_t)W * H));
-    const float fy = fmaxf((y + 0.5f) * sy - 0.5f, 0.f), fx = fmaxf((x + 0.5f) * sx - 0.5f, 0.f);
+    const float fy = pp_src(sy, y), fx = pp_src(sx, x);
     const int y0 = min((int)fy, hm - 1), x0 = min((int)fx, wm - 1);
     const int y1 = min(y0 + 1, hm - 1), x1 = min(x0 + 1, wm - 1);
     const float wy = fy - (float)y0, wx = fx - (float)x0;
     const float* m = logits + (int64_t)q * hm * wm;
     auto sg = [](float v) { return 1.0f / (1.0f + expf(-v)); };
     const float a = sg(m[y0 * wm + x0]), b = sg(m[y0 * wm + x1]), c = sg(m[y1 * wm + x0]), d = sg(m[y1 * wm + x1]);
-    probs[i] = (1.f - wy) * ((1.f - wx) * a + wx * b) + wy * ((1.f - wx) * c + wx * d);
+    probs[i] = pp_blend(1.f - wy, wy, 1.f - wx, wx, a, b, c, d);
   }
 }
 

@@ -317,3 +317,79 @@ def groupnorm(x, n, P, G, gamma, beta, eps, out_fmt, relu=False):
     ref = ref.permute(0, 2, 1).reshape(n * P, C)
     ref = torch.relu(ref) if relu else ref
     return ref, back(rownorm_bound(xg, per(gamma), per(beta), eps, out_fmt, one_pass=True, relu=relu, nred=P * Cg / 256 + 64))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------- output stages
+# postprocess.hip / pointmap.hip (tests/test_hip_pp_stages.py, tests/test_hip_pointmap_stages.py; soundness and tightness: tests/test_pp_stage_checks.py).
+# Division and sqrtf are IEEE-rounded in these builds (hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt; the v_div_scale / v_div_fmas sequence
+# in the ISA): one rounding each.  For the device expf and expm1f the installation carries no accuracy table, so their allowance is MEASURED against the
+# float64 reference, never against a second run of the kernel: twice the largest error seen on the MI355X (profiles/output_kernel_margins.jsonl, rows
+# 'expf_ulp' / 'expm1f_ulp'), a factor of two because the cases sample the argument range rather than cover it.
+#   expf:   conf = 1 + expf(c) of pointmap_activate over c in [0, 80] (131072 logarithmically and linearly spaced arguments; the error of conf in ulps of
+#           exp(c), which includes the rounding of the addition - up to one ulp of exp(c) for c < ln 2): largest 1.764 ulp.
+#   expm1f: x expm1f(d) / d of pointmap_activate on axis-aligned vectors (d = |x| exactly) over d in [1e-12, 88] (the error in ulps of the result, which
+#           includes the roundings of the division and of the product): largest 2.185 ulp.
+# tests/test_hip_pointmap_stages.py::test_device_math_ulps repeats the measurement and fails if twice the observed error exceeds the allowance.
+EXPF_ULP = 3.6           # 2 x 1.764, rounded up
+EXPM1F_ULP = 4.4         # 2 x 2.185, rounded up
+TINY32 = 2.0 ** -149     # absolute error of an fp32 result in the subnormal range
+
+
+def sigmoid_bound(s):
+    """1.0f / (1.0f + expf(-x)) against s = sigmoid(x) (float64): expf moves e = exp(-x) by EXPF_ULP ulps, which reaches s scaled by e / (1 + e) = 1 - s;
+    the addition and the division round once each."""
+    s = torch.as_tensor(s, dtype=torch.float64)
+    return R * U32 * (2.0 + EXPF_ULP * (1.0 - s)) * s + TINY32
+
+
+def blend_bound(m, dm_taps):
+    """m = hy (hx a + lx b) + ly (hx c + lx d) in fp32 with exact fp32 weights: every tap passes through at most four roundings on its way to m (product,
+    sum, product, sum; a contracted fma only removes some), the taps are non-negative: 4 R u32 m, plus the blend of the taps' own errors dm_taps."""
+    return dm_taps + 4 * R * U32 * torch.as_tensor(m, dtype=torch.float64).abs() + TINY32
+
+
+def product_bound(score, m, dm):
+    """score * m in fp32, score an exact fp32 input: |score| dm + one rounding"""
+    return score.abs() * dm + R * U32 * (score * m).abs() + TINY32
+
+
+def softmax_score_bound(arg, darg, ncls):
+    """score = 1 / sum_c expf(arg_c), arg_c <= 0 with max 0 (float64 [Q, Ncls]), darg the bound of the fp32 argument's error.  expf: EXPF_ULP ulps + its
+    argument's error (d exp = exp darg); the sum: ceil(Ncls / 64) sequential adds per lane and 6 tree levels; one division.  Relative to the score the sum's
+    relative error carries over unchanged."""
+    t = arg.exp()
+    dt = t * (EXPF_ULP * R * U32 + darg) + TINY32
+    S = t.sum(-1)
+    nadd = -(-ncls // 64) + 6
+    rel = dt.sum(-1) / S + nadd * R * U32 + R * U32
+    return rel / S + TINY32
+
+
+def chunked_sum_bound(S, nchunk, chunk=256):
+    """sum of non-negative fp32 terms: sequential fp32 sums of at most `chunk` terms (every one of the chunk - 1 additions rounds a partial <= the chunk's sum),
+    the chunk sums then added in double: (chunk R u32 + nchunk 2^-53) S"""
+    return (chunk * R * U32 + nchunk * 2.0 ** -53) * S.abs()
+
+
+def activate_bound(xyz64, ref):
+    """pointmap_activate 'norm_exp': d = sqrtf(x^2 + y^2 + z^2) (each square through <= 3 roundings, the root halves that and rounds once: 2.5 -> 3 R u32
+    relative), s = expm1f(d) / max(d, 1e-8f), out = x s.  The error of d reaches s through kappa = |d g'(d) / g(d)| = d e^d / (e^d - 1) - 1 with
+    g = expm1(d) / d (in the clipped branch s is proportional to d: kappa = 1, and 1e-8f is one rounding away from 1e-8)."""
+    d = xyz64.norm(dim=-1, keepdim=True)
+    kap = torch.where(d < 1e-8, torch.ones_like(d), d * d.exp() / torch.expm1(d).clamp_min(1e-300) - 1.0)
+    kap = torch.where(d == 0, torch.zeros_like(d), kap).clamp_min(0.0)
+    rel = (EXPM1F_ULP + 2.0 + 3.0 * kap + (d < 2e-8).double()) * R * U32
+    return rel * ref.abs() + TINY32
+
+
+def conf_bound(c64):
+    """conf = 1.0f + expf(c): EXPF_ULP ulps of exp(c) and the addition's rounding"""
+    e = c64.exp()
+    return EXPF_ULP * R * U32 * e + R * U32 * (1.0 + e) + TINY32
+
+
+def moments_bound(abs_terms, nadd, dw_terms):
+    """rigid_moments: double sums of nadd additions (+ 3 for the products w y x in double) over terms whose absolute sum is abs_terms, and the single fp32
+    rounding of w = conf + weight_offset: dw_terms = the same moments of |fl32(conf + off) - (conf + off)|, which the CPU computes exactly (0 with offset 0);
+    allowed twice, like every rounding here"""
+    return (nadd + 3) * 2.0 ** -53 * abs_terms + R * dw_terms

@@ -4,28 +4,20 @@ and against golden G6 (generated from the reference's own function).
 Integer outputs: segment ids / query ids / categories must be identical; the panoptic maps are compared pixel by pixel.
 The per-pixel decisions hang on fp32 comparisons (m >= 0.5, m >= 0.25, argmax) of sigmoid + bilinear values whose last
 bit differs between the CPU's and the GPU's expf, so a handful of exact-tie pixels may flip: <= 0.05 % of the pixels are
-allowed to differ as long as the per-query area decisions (the segment list) are identical; conf to 1e-5 elsewhere."""
+allowed to differ as long as the per-query area decisions (the segment list) are identical; conf to 1e-5 elsewhere.
+
+The stages behind this chain are tested one by one, without a pixel allowance, in tests/test_hip_pp_stages.py (float64 references and derived bounds of
+tests/pp_stage_cases.py / tests/errbound.py; a pixel only escapes comparison there when the reference itself cannot decide it).  The allowance stays here
+because this module compares with the fp32 CPU oracle and the reference-generated goldens, whose own expf and rounding order differ from the kernel's: which
+pixels are undecidable between two fp32 evaluations is not known to this test, only that they are few."""
 import numpy as np
 import pytest
 import torch
 
+from pp_stage_cases import blob_scene as _blobs      # the scene generator, shared with the stage tests
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-
-
-def _blobs(seed, Q, ncls, lowres, maxfrac=1.0):
-    g = np.random.Generator(np.random.PCG64(seed))
-    logits = torch.from_numpy(g.standard_normal((1, Q, ncls)).astype(np.float32)) * 2
-    masks = []
-    for (h, w) in lowres:
-        m = torch.from_numpy(g.standard_normal((1, Q, h, w)).astype(np.float32)) * 1.5 - 3.0
-        for q in range(Q):
-            y0, x0 = int(g.integers(0, h - 2)), int(g.integers(0, w - 2))
-            y1 = int(g.integers(y0 + 2, min(h, y0 + max(2, int(h * maxfrac))) + 1))
-            x1 = int(g.integers(x0 + 2, min(w, x0 + max(2, int(w * maxfrac))) + 1))
-            m[0, q, y0:y1, x0:x1] += 6.0
-        masks.append(m)
-    return logits, masks
 
 
 def _compare(res, ref, frac=5e-4):
