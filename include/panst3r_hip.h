@@ -416,6 +416,47 @@ int pst_retrieval_aggregate(const float* x, int64_t ldx, const float* cent, int6
 int pst_retrieval_scores(const int32_t* q_off, const int32_t* q_word, const uint32_t* q_bits, const int32_t* db_off, const int32_t* db_word,
                          const uint32_t* db_bits, int nq_views, int ndb_views, int max_q, int D, float alpha, float tau, float* S, void* stream);
 
+/* ---------------------------------------------------------------- panoptic point cloud (reference tools/demo_panst3r.py:279-300, 622-687: numpy on the host)
+ * The scene's views concatenated in the caller's order, filtered by confidence (stable), coloured and labelled; restated in tests/cloud_ref.py
+ * [restated, parity unpinned].  Integer atomics only, so every result is bit-reproducible.  A device table of pst_cloud_view makes a scene of
+ * mixed shapes ONE launch: view v owns the ceil(npix / 1024) consecutive workgroups that start at first_wg (first_wg of view 0 is 0), nwg = their sum,
+ * offset = the number of points of the views before it (total < 2^31).
+ *   cloud_count           counts[wg] = number of the workgroup's 1024 points with conf >= thr (a NaN confidence is not kept)
+ *   cloud_scan            base[i] = counts[0] + ... + counts[i-1] for i in [0, n]: base[n] = M, the number of kept points.  One workgroup.
+ *   cloud_compact         the kept points in their original order -> rows [0, M) of
+ *                           points fp32 [., 3]        pts3d
+ *                           points_local fp32 [., 3]  x' = ((R00 x + R01 y) + R02 z) + t0 ... of pts3d_local, c2w = rows of [R | t]; every product and sum rounded on its own
+ *                           rgb fp32 [., 3]           img * 0.5f + 0.5f, HWC order
+ *                           pan int32 [.]
+ *                           colors_out fp32 [., 3]    w1 * rgb + w2 * pan_vis (two rounded products, one rounded sum), pan_vis = colors[pan] for
+ *                                                     0 < pan < ncolors (colors fp32 [ncolors, 3], ncolors <= 4096), black otherwise
+ *                           index int64 [.]           offset + pixel: the point's position in the concatenated scene
+ *                         Every output buffer must hold the scene's total number of points (M is only known on the device).
+ *   cloud_segment_median  exact per-axis median of the rows of points_local whose pan id maps to a segment row: row = id2row[id] for 0 < id < ntab
+ *                         (int32 [ntab], -1 = none; other ids take part in nothing), nseg rows.  Radix select, four byte passes.  m_ptr = device
+ *                         pointer to M (base + n), max_points >= M sizes the grid.  Workspaces, all ZEROED by the caller: hist int32
+ *                         [nseg, 3, 2, 256] (16-byte aligned; left zeroed), prefix uint32 / rank int32 [nseg, 3, 2], nan_cnt int32 [nseg, 3].
+ *                         -> count int32 [nseg] (kept points of the segment), median fp32 [nseg, 3]: the middle element for an odd count,
+ *                         (a + b) * 0.5f of the two middle ones for an even count (np.median of float32), NaN for an axis with a NaN or a count of 0. */
+typedef struct pst_cloud_view {
+  const float* conf;          /* [npix] */
+  const float* pts3d;         /* [npix, 3] */
+  const float* pts3d_local;   /* [npix, 3] */
+  const float* img;           /* [3, npix] planes in [-1, 1] */
+  const int32_t* pan;         /* [npix] */
+  int64_t offset;
+  int32_t npix;
+  int32_t first_wg;
+  float c2w[12];
+} pst_cloud_view;
+
+int pst_cloud_count(const pst_cloud_view* views, int nviews, int nwg, float thr, int32_t* counts, void* stream);
+int pst_cloud_scan(const int32_t* counts, int n, int32_t* base, void* stream);
+int pst_cloud_compact(const pst_cloud_view* views, int nviews, int nwg, float thr, const int32_t* base, const float* colors, int ncolors, float w1, float w2,
+                      float* points, float* points_local, float* rgb, int32_t* pan, float* colors_out, int64_t* index, void* stream);
+int pst_cloud_segment_median(const float* points_local, const int32_t* pan, const int32_t* m_ptr, int64_t max_points, const int32_t* id2row, int ntab, int nseg,
+                             int32_t* hist, uint32_t* prefix, int32_t* rank, int32_t* nan_cnt, int32_t* count, float* median, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

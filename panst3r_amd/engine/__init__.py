@@ -5,3 +5,4 @@ from .postprocess import panoptic_inference_v2, panoptic_inference_v1, panoptic_
 from . import pointmaps  # noqa: F401,E402  (pointmap post-processing: postprocess / estimate_focal_knowing_depth / rigid_points_registration)
 from .images import load_images  # noqa: F401,E402
 from .retrieval import PanSt3RRetriever  # noqa: F401,E402  (keyframe selection by retrieval, reference engine/retrieval.py)
+from .cloud import panoptic_point_cloud, PanopticCloud, default_colors, camera_frusta  # noqa: F401,E402  (the scene's labelled point cloud, demo :279-300, :622-687)

@@ -39,13 +39,18 @@ class AttnParams(C.Structure):
                 ('scale', f32), ('zeros', vp), ('nsplit', i32), ('ws', vp), ('ws_bytes', i64), ('dtype16', i32), ('prescaled', i32)]
 
 
+class CloudView(C.Structure):
+    _fields_ = [('conf', vp), ('pts3d', vp), ('pts3d_local', vp), ('img', vp), ('pan', vp), ('offset', i64), ('npix', i32), ('first_wg', i32), ('c2w', f32 * 12)]
+
+
 EXPORTS = ['pst_abi_version', 'pst_last_error', 'pst_gemm', 'pst_gemm_variant', 'pst_gemm_pair', 'pst_gemm_pair_variant', 'pst_tune', 'pst_mask_head', 'pst_mask_head_supported', 'pst_attn_fwd', 'pst_attn_variant', 'pst_attn_pair', 'pst_attn_pair_variant', 'pst_attn_workspace_bytes', 'pst_layernorm', 'pst_layernorm_add',
            'pst_layernorm_add_batch', 'pst_rowstats', 'pst_split3', 'pst_split_operand', 'pst_split2', 'pst_transpose_f32', 'pst_rope2d_split', 'pst_attn_x3', 'pst_attn_x3_variant', 'pst_rope2d',
            'pst_patchify', 'pst_dino_preprocess', 'pst_image_prepare', 'pst_patch_rows', 'pst_add_cast', 'pst_l2norm_rows', 'pst_mean4', 'pst_resize_bilinear',
            'pst_attn_mask_from_logits', 'pst_loftup_guidance_gn', 'pst_loftup_minmax', 'pst_minmax_merge', 'pst_groupnorm_stats', 'pst_groupnorm_apply',
            'pst_loftup_lr_pe', 'pst_pp_scores', 'pst_pp_scores_softmax', 'pst_pp_sigmoid', 'pst_pp_argmax', 'pst_pp_argmax_logits', 'pst_pp_select', 'pst_pp_finalize', 'pst_pointmap_activate', 'pst_focal_weiszfeld', 'pst_rigid_moments',
            'pst_qubo_upsample', 'pst_qubo_workspace_floats', 'pst_qubo_overlap', 'pst_qubo_argmax', 'pst_token_embed',
-           'pst_retrieval_select', 'pst_retrieval_assign', 'pst_retrieval_aggregate', 'pst_retrieval_scores']
+           'pst_retrieval_select', 'pst_retrieval_assign', 'pst_retrieval_aggregate', 'pst_retrieval_scores',
+           'pst_cloud_count', 'pst_cloud_scan', 'pst_cloud_compact', 'pst_cloud_segment_median']
 
 
 def lib():
@@ -1163,3 +1168,63 @@ def retrieval_scores(q_off, q_word, q_bits, db_off, db_word, db_bits, D, alpha, 
     _check(lib().pst_retrieval_scores(_ptr(q_off), _ptr(q_word), _ptr(q_bits), _ptr(db_off), _ptr(db_word), _ptr(db_bits), Vq, Vdb, int(max(1, max_q)), int(D),
                                       f32(alpha), f32(tau), _ptr(S), _stream()), 'pst_retrieval_scores')
     return S
+
+
+# ------------------------------------------------------------------ panoptic point cloud (csrc/cloud.hip; engine/cloud.py holds the public entry point)
+CLOUD_WG = 1024            # points per workgroup of the count / compact passes
+CLOUD_MAX_COLORS = 4096    # colour table rows that fit in LDS
+
+
+def cloud_view_table(views, cams2world, device):
+    """device table of pst_cloud_view for views = [(conf, pts3d, pts3d_local, img, pan)] (contiguous device tensors, which the caller keeps alive)
+    and cams2world = [V, 3, 4] host floats -> (uint8 tensor, number of workgroups, total number of points)"""
+    tab = (CloudView * len(views))()
+    off = wg = 0
+    for e, (conf, pts, loc, img, pan), c2w in zip(tab, views, cams2world):
+        for t, dt in ((conf, torch.float32), (pts, torch.float32), (loc, torch.float32), (img, torch.float32), (pan, torch.int32)):
+            _dev(t, dt)
+            assert t.is_contiguous() and t.device == conf.device
+        n = conf.numel()
+        assert n > 0 and pts.numel() == 3 * n and loc.numel() == 3 * n and img.numel() == 3 * n and pan.numel() == n
+        e.conf, e.pts3d, e.pts3d_local, e.img, e.pan = conf.data_ptr(), pts.data_ptr(), loc.data_ptr(), img.data_ptr(), pan.data_ptr()
+        e.offset, e.npix, e.first_wg = off, n, wg
+        e.c2w[:] = [float(x) for row in c2w for x in row]
+        off += n
+        wg += (n + CLOUD_WG - 1) // CLOUD_WG
+    if off >= 2 ** 31:
+        raise RuntimeError('a scene of %d points exceeds the 2^31 - 1 the cloud kernels index' % off)
+    return torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(device), wg, off
+
+
+def cloud_count(table, nviews, nwg, thr, counts):
+    _dev(table, torch.uint8); _dev(counts, torch.int32)
+    assert table.numel() == nviews * C.sizeof(CloudView) and counts.numel() >= nwg
+    _check(lib().pst_cloud_count(_ptr(table), int(nviews), int(nwg), f32(thr), _ptr(counts), _stream()), 'pst_cloud_count')
+
+
+def cloud_scan(counts, base):
+    _dev(counts, torch.int32); _dev(base, torch.int32)
+    assert base.numel() == counts.numel() + 1
+    _check(lib().pst_cloud_scan(_ptr(counts), counts.numel(), _ptr(base), _stream()), 'pst_cloud_scan')
+
+
+def cloud_compact(table, nviews, nwg, thr, base, colors, w1, w2, points, points_local, rgb, pan, colors_out, index):
+    _dev(table, torch.uint8); _dev(base, torch.int32); _dev(colors, torch.float32); _dev(pan, torch.int32); _dev(index, torch.int64)
+    n = pan.numel()
+    for t in (points, points_local, rgb, colors_out):
+        _dev(t, torch.float32)
+        assert t.is_contiguous() and t.numel() == 3 * n
+    assert table.numel() == nviews * C.sizeof(CloudView) and base.numel() == nwg + 1 and index.numel() == n and colors.is_contiguous() and colors.shape[1] == 3
+    _check(lib().pst_cloud_compact(_ptr(table), int(nviews), int(nwg), f32(thr), _ptr(base), _ptr(colors), colors.shape[0], f32(w1), f32(w2), _ptr(points),
+                                   _ptr(points_local), _ptr(rgb), _ptr(pan), _ptr(colors_out), _ptr(index), _stream()), 'pst_cloud_compact')
+
+
+def cloud_segment_median(points_local, pan, m_ptr, id2row, nseg, count, median):
+    """count int32 [nseg], median fp32 [nseg, 3] of the rows [0, M) of points_local by segment row (id2row int32, -1 = none); m_ptr = one-element int32
+    device tensor holding M"""
+    _dev(points_local, torch.float32); _dev(pan, torch.int32); _dev(m_ptr, torch.int32); _dev(id2row, torch.int32); _dev(count, torch.int32); _dev(median, torch.float32)
+    assert points_local.is_contiguous() and pan.numel() * 3 == points_local.numel() and count.numel() == nseg and median.numel() == 3 * nseg and median.is_contiguous()
+    ws = torch.zeros(nseg * (3 * 2 * 256 + 6 + 6 + 3), dtype=torch.int32, device=pan.device)
+    hist, prefix, rank, nan = ws[:nseg * 1536], ws[nseg * 1536:nseg * 1542], ws[nseg * 1542:nseg * 1548], ws[nseg * 1548:]
+    _check(lib().pst_cloud_segment_median(_ptr(points_local), _ptr(pan), _ptr(m_ptr), i64(pan.numel()), _ptr(id2row), id2row.numel(), int(nseg), _ptr(hist),
+                                          _ptr(prefix), _ptr(rank), _ptr(nan), _ptr(count), _ptr(median), _stream()), 'pst_cloud_segment_median')

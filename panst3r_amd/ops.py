@@ -264,6 +264,27 @@ def retrieval_scores(q_off: Tensor, q_word: Tensor, q_bits: Tensor, db_off: Tens
     hip.retrieval_scores(q_off, q_word, q_bits, db_off, db_word, db_bits, D, alpha, tau, S, max_q)
 
 
+@_op('cloud_count', ('counts',))
+def cloud_count(table: Tensor, nviews: int, nwg: int, thr: float, counts: Tensor) -> None:
+    hip.cloud_count(table, nviews, nwg, thr, counts)
+
+
+@_op('cloud_scan', ('base',))
+def cloud_scan(counts: Tensor, base: Tensor) -> None:
+    hip.cloud_scan(counts, base)
+
+
+@_op('cloud_compact', ('points', 'points_local', 'rgb', 'pan', 'colors_out', 'index'))
+def cloud_compact(table: Tensor, nviews: int, nwg: int, thr: float, base: Tensor, colors: Tensor, w1: float, w2: float, points: Tensor, points_local: Tensor,
+                  rgb: Tensor, pan: Tensor, colors_out: Tensor, index: Tensor) -> None:
+    hip.cloud_compact(table, nviews, nwg, thr, base, colors, w1, w2, points, points_local, rgb, pan, colors_out, index)
+
+
+@_op('cloud_segment_median', ('count', 'median'))
+def cloud_segment_median(points_local: Tensor, pan: Tensor, m_ptr: Tensor, id2row: Tensor, nseg: int, count: Tensor, median: Tensor) -> None:
+    hip.cloud_segment_median(points_local, pan, m_ptr, id2row, nseg, count, median)
+
+
 def registered_ops():
     """names under torch.ops.panst3r_hip"""
     return list(_REGISTERED)

@@ -362,6 +362,30 @@ class PanSt3R(nn.Module):
                 amp, panoptic_precision = nxt
 
     @torch.no_grad()
+    def reconstruct(self, imgs, true_shape, classes, *, postprocess='standard_v2', min_conf_thr=3.0, opacity=0.5, postprocess_kwargs=None, **forward_kwargs):
+        """The body of the demo's `get_reconstructed_scene` (tools/demo_panst3r.py:232-300) in one call, everything on the device:
+        forward_inference_multi_ar (outputs left where they are), the chosen panoptic post-processing ('standard_v2' | 'standard_v1' | 'qubo'),
+        the cameras of the pointmaps and the panoptic point cloud.  `postprocess_kwargs`: thresholds of the chosen post-processing other than its
+        defaults (the demo uses the defaults).  Returns (cloud, cameras, pan_preds): a `PanopticCloud`, the camera frusta
+        (each with its 'focal' and 'cam2world') and the post-processing result.  It only composes the public entry points."""
+        from .engine import panoptic_inference_v2, panoptic_inference_v1, panoptic_inference_qubo, panoptic_point_cloud
+        from .engine.pointmaps import cameras_from_pointmaps
+        fns = {'standard_v2': panoptic_inference_v2, 'standard_v1': panoptic_inference_v1, 'qubo': panoptic_inference_qubo}
+        if postprocess not in fns:
+            raise ValueError('did not recognize postprocess=%r (one of %s)' % (postprocess, sorted(fns)))
+        if forward_kwargs.get('outdevice') is not None:
+            raise ValueError('reconstruct keeps the outputs on the device: outdevice is not an argument of it')
+        pms, panout = self.forward_inference_multi_ar(imgs, true_shape, classes, **forward_kwargs)
+        pan_preds = fns[postprocess](panout['pred_logits'], panout['pred_masks'], true_shape, label_mode=self.panoptic_decoder.label_mode, multi_ar=True,
+                                    **(postprocess_kwargs or {}))
+        x_out, focals, cams2world = cameras_from_pointmaps(pms, true_shape, getattr(self.must3r_decoder, 'pointmaps_activation', 'norm_exp'))
+        dev = pms[0].device
+        cloud = panoptic_point_cloud(x_out, [i.to(dev) for i in imgs], true_shape, pan_preds[0]['pan'], pan_preds[0]['segments_info'], cams2world, focals,
+                                     min_conf_thr=min_conf_thr, opacity=opacity)
+        cameras = [dict(c, cam2world=c2w) for c, c2w in zip(cloud.cameras, cams2world)]
+        return cloud, cameras, pan_preds
+
+    @torch.no_grad()
     def _forward_inference_once(self, imgs, true_shape, classes, num_keyframes=None, use_retrieval=False, max_bs=None,
                                 outdevice=None, amp=False, sim_matrix=None, keyframes=None, check_finite=True, cache_graphs=False,
                                 panoptic_precision=None, _mm_tables=None):
