@@ -457,6 +457,21 @@ int pst_cloud_compact(const pst_cloud_view* views, int nviews, int nwg, float th
 int pst_cloud_segment_median(const float* points_local, const int32_t* pan, const int32_t* m_ptr, int64_t max_points, const int32_t* id2row, int ntab, int nseg,
                              int32_t* hist, uint32_t* prefix, int32_t* rank, int32_t* nan_cnt, int32_t* count, float* median, void* stream);
 
+/* ---------------------------------------------------------------- QUBO mask selection on the device (reference engine/postprocess.py:262-336: numpy on the host)
+ * Minimises E(x) = x^T W x + lambda_reg * mean(x), x in {0,1}^N, by `replicas` independent simulated anneals run at once (the reference's moves,
+ * acceptance rule and geometric schedule; it runs 20 restarts one after the other) and returns the best.  W fp32 [N, N] row-major, symmetric (the -W
+ * of weight_from_masks), 1 <= N <= pst_qubo_anneal_max_n() (200: W is held in the LDS of one CU); a larger N is PST_EINVAL, nothing is written, and the
+ * host annealer remains for it.  1 <= replicas <= 2^20, num_iters >= 0, T0 > 0, T_end > 0.  One wave per replica.
+ * The result is a pure function of the arguments: counter-based random numbers (Philox4x32-10 keyed by `seed`, counter = (move / 2, replica, stream)),
+ * incremental local fields, an exponential made of separately rounded fp32 operations, a fixed evaluation order; the inverse temperature is carried as
+ * beta <- beta * cinv in fp32 (beta0 = fp32(1 / T0), cinv = fp32((T0 / T_end)^(1 / num_iters)), both taken in double on the host).  The operation order
+ * is written out at the top of csrc/qubo_solve.hip and restated bit for bit in tests/qubo_ref.py [restated, own design].
+ *   -> x_all uint8 [replicas, N]  every replica's best state;  e_all fp32 [replicas]  its energy, re-evaluated from scratch in a fixed order
+ *      best_x uint8 [N], best_e fp32 [1]  those of the replica with the smallest (energy, index).  Plain stores, no atomics. */
+int pst_qubo_anneal_max_n(void);
+int pst_qubo_anneal(const float* W, int N, int replicas, int num_iters, float T0, float T_end, float lambda_reg, uint64_t seed, uint8_t* x_all, float* e_all,
+                    uint8_t* best_x, float* best_e, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,12 +119,8 @@ def solve_qubo_simulated_annealing(W, num_iters=10000, T0=0.5, T_end=1e-4, lambd
     return best_x2, best_energy2
 
 
-@torch.no_grad()
-def qubo_weights(views, shapes, device, penalty=1):
-    """`weight_from_masks` (:229-259) with the O(Q^2 x pixels) sums on the GPU: views = list of mask logits [Q,h,w], shapes = true (H, W)
-    per view.  Returns -W as float32 numpy [Q, Q] (what the reference hands to the annealer): diagonal = mask areas, off-diagonal =
-    -(1 + penalty) overlap / 2, normalised by the padded image size and the number of views."""
-    import numpy as np
+def _qubo_overlap_sums(views, shapes, device):
+    """S[a, b] = sum over views and pixels of min(p_a, p_b) of the up-sampled mask probabilities, float64 [Q, Q] on the device"""
     Q = views[0].shape[0]
     Wacc = torch.zeros(Q, Q, dtype=torch.float64, device=device)
     for m, (H, W) in zip(views, shapes):
@@ -132,7 +128,16 @@ def qubo_weights(views, shapes, device, penalty=1):
         hip.qubo_upsample(m, probs, Q, m.shape[-2], m.shape[-1], H, W)
         hip.qubo_overlap(probs, Q, H * W, Wacc)
         del probs
-    S = Wacc.cpu().numpy()
+    return Wacc
+
+
+@torch.no_grad()
+def qubo_weights(views, shapes, device, penalty=1):
+    """`weight_from_masks` (:229-259) with the O(Q^2 x pixels) sums on the GPU: views = list of mask logits [Q,h,w], shapes = true (H, W)
+    per view.  Returns -W as float32 numpy [Q, Q] (what the reference hands to the annealer): diagonal = mask areas, off-diagonal =
+    -(1 + penalty) overlap / 2, normalised by the padded image size and the number of views."""
+    import numpy as np
+    S = _qubo_overlap_sums(views, shapes, device).cpu().numpy()
     Hm, Wm = max(s[0] for s in shapes), max(s[1] for s in shapes)          # the reference pads every view to the largest shape with zeros (:141)
     Wt = -(1 + penalty) * S / 2
     np.fill_diagonal(Wt, np.diag(S))
@@ -141,13 +146,67 @@ def qubo_weights(views, shapes, device, penalty=1):
 
 
 @torch.no_grad()
+def qubo_weights_device(views, shapes, device, penalty=1):
+    """`qubo_weights` without the trip to the host: the same float64 elementwise operations in the same order on the device, then float32.  Every one of
+    them is a single IEEE operation, so the result equals `qubo_weights`' bit for bit (tests/test_hip_qubo_solver.py).  Returns a float32 device tensor."""
+    S = _qubo_overlap_sums(views, shapes, device)
+    Hm, Wm = max(s[0] for s in shapes), max(s[1] for s in shapes)
+    Wt = -(1 + penalty) * S / 2
+    Wt.diagonal().copy_(S.diagonal())
+    Wt = Wt / (Hm * Wm) / len(views)
+    return (-Wt).to(torch.float32).contiguous()
+
+
+QUBO_REPLICAS = 4096       # default of the device solver: how it was chosen is in docs/experiments.md 6g (quality against the reference's own runs, doubled once)
+
+
+@torch.no_grad()
+def solve_qubo_device(W, num_iters=10000, T0=0.5, T_end=1e-4, lambda_reg=1e-3, replicas=QUBO_REPLICAS, seed=0, device=None, return_all=False, energy=True):
+    """The annealer on the GPU (csrc/qubo_solve.hip): `replicas` independent anneals with the reference's moves, acceptance rule and schedule run at once,
+    the best one returned.  W: numpy or a device tensor [N, N] (the -W of `qubo_weights`).  The result is a pure function of the arguments (counter-based
+    random numbers keyed by `seed`; restated bit for bit in tests/qubo_ref.py), not the np.random trajectory of `solve_qubo_simulated_annealing`.
+    Returns (best_x numpy int array [N], best_energy) like the host solver; best_energy is the reference's formula in float64 on best_x, evaluated on
+    the device (W stays there: N + 1 numbers come to the host in one copy), or None with energy=False (N bytes come to the host).  With
+    return_all also every replica's (x uint8 [replicas, N], energy fp32 [replicas]) as device tensors.  N above hip.qubo_anneal_max_n() raises: the
+    host solver (solver='host') remains for such a problem."""
+    import numpy as np
+    if not isinstance(W, torch.Tensor):
+        W = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float32))
+    if not W.is_cuda:
+        W = W.to(torch.device(device if device is not None else 'cuda'))
+    W = W.to(torch.float32).contiguous()
+    N = W.shape[0]
+    replicas = int(replicas)
+    x_all = torch.empty(replicas, N, dtype=torch.uint8, device=W.device)
+    e_all = torch.empty(replicas, dtype=torch.float32, device=W.device)
+    best_x = torch.empty(N, dtype=torch.uint8, device=W.device)
+    best_e = torch.empty(1, dtype=torch.float32, device=W.device)
+    hip.qubo_anneal(W, replicas, num_iters, T0, T_end, lambda_reg, seed, x_all, e_all, best_x, best_e)
+    if energy:                                     # E = x^T W x + lambda mean(x) in float64 (the products are exact: x is 0 / 1), one copy of N + 1 doubles
+        xd = best_x.double()
+        e = (W.double() * xd[:, None] * xd[None, :]).sum() + lambda_reg * xd.mean()
+        both = torch.cat([xd, e.reshape(1)]).cpu().numpy()
+        x, energy = both[:N].astype(np.int64), float(both[N])
+    else:
+        x, energy = best_x.cpu().numpy().astype(np.int64), None                    # N bytes: the only thing the host needs
+    if return_all:
+        return x, energy, x_all, e_all
+    return x, energy
+
+
+@torch.no_grad()
 def panoptic_inference_qubo(mask_cls, mask_pred, true_shape, label_mode='sigmoid', temperature=None, device='cuda', num_redo=20, prob_threshold=0.01,
-                            silent=False, multi_ar=False):
+                            silent=False, multi_ar=False, solver='host', replicas=None, seed=0):
     """Reference signature (engine/postprocess.py:135): QUBO selection of a maximal set of non-overlapping masks, then per-pixel arg-max among
     the selected queries.  Pixel-sized work runs on `device` (a GPU); the annealer and the per-instance bookkeeping are host code as in the
     reference.  Result structure as the reference's (:206-217): 'pan' / 'conf' per view for multi_ar, stacked otherwise; `query_id` is the
-    index among the SELECTED queries, exactly as the reference reports it (:202)."""
+    index among the SELECTED queries, exactly as the reference reports it (:202).
+    solver='host' (default): the reference's annealer in numpy, `num_redo` restarts, its np.random trajectory.  solver='device': the weight matrix is
+    finalised on the device (`qubo_weights_device`), `solve_qubo_device` anneals `replicas` (default QUBO_REPLICAS) independent replicas there with
+    `seed`, and only the selection (Q bytes) comes to the host; `num_redo` is ignored by this solver."""
     import numpy as np
+    if solver not in ('host', 'device'):
+        raise ValueError("solver must be 'host' or 'device', got %r" % (solver,))
     if label_mode != 'sigmoid':         # the reference itself cannot run this combination: :166-167 reads `cur_mask_cls` before any assignment (NameError)
         raise NotImplementedError("panoptic_inference_qubo with label_mode='softmax' fails in the reference too (engine/postprocess.py:166-167); "
                                   "use panoptic_inference_v2 / v1 for softmax-label models")
@@ -169,8 +228,14 @@ def panoptic_inference_qubo(mask_cls, mask_pred, true_shape, label_mode='sigmoid
     cls = mask_cls[0].float().cpu().sigmoid()
     if temperature is not None:
         cls = torch.softmax(cls.sigmoid() / temperature, dim=-1)              # as written in the reference (:158-160)
-    Wneg = qubo_weights(views, shapes, device)
-    solution, _ = solve_qubo_simulated_annealing(Wneg, redo=num_redo, silent=silent)
+    if solver == 'device':
+        if Q > hip.qubo_anneal_max_n():
+            raise RuntimeError("solver='device' takes at most %d queries (got %d); solver='host' remains for this model" % (hip.qubo_anneal_max_n(), Q))
+        solution, _ = solve_qubo_device(qubo_weights_device(views, shapes, device), replicas=QUBO_REPLICAS if replicas is None else replicas, seed=seed,
+                                        energy=False)
+    else:
+        Wneg = qubo_weights(views, shapes, device)
+        solution, _ = solve_qubo_simulated_annealing(Wneg, redo=num_redo, silent=silent)
     sel = np.flatnonzero(np.asarray(solution).astype(bool))
     cls_probs, cls_ids = cls[torch.from_numpy(sel)].max(dim=1)
     sel_dev = torch.from_numpy(sel.astype(np.int32)).to(device)

@@ -50,7 +50,7 @@ EXPORTS = ['pst_abi_version', 'pst_last_error', 'pst_gemm', 'pst_gemm_variant', 
            'pst_loftup_lr_pe', 'pst_pp_scores', 'pst_pp_scores_softmax', 'pst_pp_sigmoid', 'pst_pp_argmax', 'pst_pp_argmax_logits', 'pst_pp_select', 'pst_pp_finalize', 'pst_pointmap_activate', 'pst_focal_weiszfeld', 'pst_rigid_moments',
            'pst_qubo_upsample', 'pst_qubo_workspace_floats', 'pst_qubo_overlap', 'pst_qubo_argmax', 'pst_token_embed',
            'pst_retrieval_select', 'pst_retrieval_assign', 'pst_retrieval_aggregate', 'pst_retrieval_scores',
-           'pst_cloud_count', 'pst_cloud_scan', 'pst_cloud_compact', 'pst_cloud_segment_median']
+           'pst_cloud_count', 'pst_cloud_scan', 'pst_cloud_compact', 'pst_cloud_segment_median', 'pst_qubo_anneal', 'pst_qubo_anneal_max_n']
 
 
 def lib():
@@ -1228,3 +1228,20 @@ def cloud_segment_median(points_local, pan, m_ptr, id2row, nseg, count, median):
     hist, prefix, rank, nan = ws[:nseg * 1536], ws[nseg * 1536:nseg * 1542], ws[nseg * 1542:nseg * 1548], ws[nseg * 1548:]
     _check(lib().pst_cloud_segment_median(_ptr(points_local), _ptr(pan), _ptr(m_ptr), i64(pan.numel()), _ptr(id2row), id2row.numel(), int(nseg), _ptr(hist),
                                           _ptr(prefix), _ptr(rank), _ptr(nan), _ptr(count), _ptr(median), _stream()), 'pst_cloud_segment_median')
+
+
+# ------------------------------------------------------------------ QUBO mask selection (csrc/qubo_solve.hip; engine/postprocess.py holds the public entry points)
+def qubo_anneal_max_n():
+    """the largest problem the device annealer takes (W in the LDS of one CU)"""
+    return int(lib().pst_qubo_anneal_max_n())
+
+
+def qubo_anneal(W, replicas, num_iters, T0, T_end, lambda_reg, seed, x_all, e_all, best_x, best_e):
+    """`replicas` independent simulated anneals of E(x) = x^T W x + lambda_reg mean(x) (W fp32 [N, N]) -> x_all uint8 [replicas, N], e_all fp32 [replicas],
+    best_x uint8 [N], best_e fp32 [1]; a pure function of its arguments (include/panst3r_hip.h).  An N the kernel does not take raises, outputs untouched."""
+    _dev(W, torch.float32); _dev(x_all, torch.uint8); _dev(e_all, torch.float32); _dev(best_x, torch.uint8); _dev(best_e, torch.float32)
+    N = W.shape[0]
+    assert W.dim() == 2 and W.shape[1] == N and all(t.is_contiguous() and t.device == W.device for t in (W, x_all, e_all, best_x, best_e))
+    assert x_all.numel() == replicas * N and e_all.numel() == replicas and best_x.numel() == N and best_e.numel() == 1
+    _check(lib().pst_qubo_anneal(_ptr(W), int(N), int(replicas), int(num_iters), f32(T0), f32(T_end), f32(lambda_reg), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                 _ptr(x_all), _ptr(e_all), _ptr(best_x), _ptr(best_e), _stream()), 'pst_qubo_anneal')

@@ -264,6 +264,12 @@ def retrieval_scores(q_off: Tensor, q_word: Tensor, q_bits: Tensor, db_off: Tens
     hip.retrieval_scores(q_off, q_word, q_bits, db_off, db_word, db_bits, D, alpha, tau, S, max_q)
 
 
+@_op('qubo_anneal', ('x_all', 'e_all', 'best_x', 'best_e'))
+def qubo_anneal(W: Tensor, replicas: int, num_iters: int, T0: float, T_end: float, lambda_reg: float, seed: int, x_all: Tensor, e_all: Tensor, best_x: Tensor,
+                best_e: Tensor) -> None:
+    hip.qubo_anneal(W, replicas, num_iters, T0, T_end, lambda_reg, seed, x_all, e_all, best_x, best_e)
+
+
 @_op('cloud_count', ('counts',))
 def cloud_count(table: Tensor, nviews: int, nwg: int, thr: float, counts: Tensor) -> None:
     hip.cloud_count(table, nviews, nwg, thr, counts)

@@ -366,7 +366,8 @@ class PanSt3R(nn.Module):
         """The body of the demo's `get_reconstructed_scene` (tools/demo_panst3r.py:232-300) in one call, everything on the device:
         forward_inference_multi_ar (outputs left where they are), the chosen panoptic post-processing ('standard_v2' | 'standard_v1' | 'qubo'),
         the cameras of the pointmaps and the panoptic point cloud.  `postprocess_kwargs`: thresholds of the chosen post-processing other than its
-        defaults (the demo uses the defaults).  Returns (cloud, cameras, pan_preds): a `PanopticCloud`, the camera frusta
+        defaults (the demo uses the defaults); with postprocess='qubo', {'solver': 'device'} runs the annealer on the GPU as well (`replicas`, `seed`;
+        engine.solve_qubo_device) instead of the reference's host annealer.  Returns (cloud, cameras, pan_preds): a `PanopticCloud`, the camera frusta
         (each with its 'focal' and 'cam2world') and the post-processing result.  It only composes the public entry points."""
         from .engine import panoptic_inference_v2, panoptic_inference_v1, panoptic_inference_qubo, panoptic_point_cloud
         from .engine.pointmaps import cameras_from_pointmaps
