@@ -43,18 +43,36 @@ class CloudView(C.Structure):
     _fields_ = [('conf', vp), ('pts3d', vp), ('pts3d_local', vp), ('img', vp), ('pan', vp), ('offset', i64), ('npix', i32), ('first_wg', i32), ('c2w', f32 * 12)]
 
 
-EXPORTS = ['pst_abi_version', 'pst_last_error', 'pst_gemm', 'pst_gemm_variant', 'pst_gemm_pair', 'pst_gemm_pair_variant', 'pst_tune', 'pst_mask_head', 'pst_mask_head_supported', 'pst_attn_fwd', 'pst_attn_variant', 'pst_attn_pair', 'pst_attn_pair_variant', 'pst_attn_workspace_bytes', 'pst_layernorm', 'pst_layernorm_add',
-           'pst_layernorm_add_batch', 'pst_rowstats', 'pst_split3', 'pst_split_operand', 'pst_split2', 'pst_transpose_f32', 'pst_rope2d_split', 'pst_attn_x3', 'pst_attn_x3_variant', 'pst_rope2d',
-           'pst_patchify', 'pst_dino_preprocess', 'pst_image_prepare', 'pst_patch_rows', 'pst_add_cast', 'pst_l2norm_rows', 'pst_mean4', 'pst_resize_bilinear',
-           'pst_attn_mask_from_logits', 'pst_loftup_guidance_gn', 'pst_loftup_minmax', 'pst_minmax_merge', 'pst_groupnorm_stats', 'pst_groupnorm_apply',
-           'pst_loftup_lr_pe', 'pst_pp_scores', 'pst_pp_scores_softmax', 'pst_pp_sigmoid', 'pst_pp_argmax', 'pst_pp_argmax_logits', 'pst_pp_select', 'pst_pp_finalize', 'pst_pointmap_activate', 'pst_focal_weiszfeld', 'pst_rigid_moments',
-           'pst_qubo_upsample', 'pst_qubo_workspace_floats', 'pst_qubo_overlap', 'pst_qubo_argmax', 'pst_token_embed',
-           'pst_retrieval_select', 'pst_retrieval_assign', 'pst_retrieval_aggregate', 'pst_retrieval_scores',
-           'pst_cloud_count', 'pst_cloud_scan', 'pst_cloud_compact', 'pst_cloud_segment_median', 'pst_qubo_anneal', 'pst_qubo_anneal_max_n']
+# The C prototypes, one entry per exported function: 'return:arguments' in the type codes of _CODES; tests/test_abi.py checks every entry against the
+# header, and lib() declares them, so a call site passes plain Python numbers and ctypes converts (or refuses) them by the prototype.  The two parameter
+# structs the host fills are declared as pointers to them: only that struct is accepted, by reference.  Every other pointer - device memory (the
+# pst_cloud_view table included) and the stream - is an address: `_ptr` / `_stream` give plain ints or None.
+_CODES = {'i': C.c_int, 'l': C.c_int64, 'u': C.c_uint64, 'f': C.c_float, 'd': C.c_double, 'p': vp, 's': C.c_char_p,
+          'G': C.POINTER(GemmParams), 'A': C.POINTER(AttnParams)}
+SIGNATURES = {
+    'pst_abi_version': 'i:', 'pst_last_error': 's:', 'pst_gemm': 'i:Gp', 'pst_gemm_variant': 's:G', 'pst_gemm_pair': 'i:GGp', 'pst_gemm_pair_variant': 's:GG',
+    'pst_tune': 'i:ii', 'pst_mask_head_supported': 'i:iii', 'pst_mask_head': 'i:plplpliiiiip', 'pst_attn_workspace_bytes': 'l:iiiii', 'pst_attn_fwd': 'i:Ap',
+    'pst_attn_variant': 's:A', 'pst_attn_pair': 'i:AAp', 'pst_attn_pair_variant': 's:AA', 'pst_layernorm': 'i:pliplippiifiiip',
+    'pst_layernorm_add': 'i:pliplplippiifiiip', 'pst_token_embed': 'i:piipipiiplpp', 'pst_rowstats': 'i:pliplpiiiip',
+    'pst_layernorm_add_batch': 'i:pliplplippiifiiiilllp', 'pst_split3': 'i:plpliiip', 'pst_split_operand': 'i:plpliiiiip', 'pst_split2': 'i:plppliiiip',
+    'pst_transpose_f32': 'i:plpliip', 'pst_rope2d_split': 'i:plppppliiiip', 'pst_attn_x3': 'i:Apppilp', 'pst_attn_x3_variant': 's:A',
+    'pst_rope2d': 'i:plppiiiip', 'pst_patchify': 'i:ppliiiiiip', 'pst_dino_preprocess': 'i:ppiiiiip', 'pst_image_prepare': 'i:piipiiiiiip',
+    'pst_patch_rows': 'i:pplpliiiiiiip', 'pst_add_cast': 'i:plipliipliiip', 'pst_l2norm_rows': 'i:plpliifip', 'pst_mean4': 'i:ppiiiiip',
+    'pst_resize_bilinear': 'i:ppiiiiiiip', 'pst_attn_mask_from_logits': 'i:plpliip', 'pst_loftup_guidance_gn': 'i:ppppfpppliiiiipp',
+    'pst_loftup_minmax': 'i:ppiiip', 'pst_minmax_merge': 'i:pppip', 'pst_groupnorm_stats': 'i:plipiiiip', 'pst_groupnorm_apply': 'i:plippppliiiifiip',
+    'pst_loftup_lr_pe': 'i:ppliiiiip', 'pst_pp_scores': 'i:piiffpppp', 'pst_pp_scores_softmax': 'i:piifpppp', 'pst_pp_sigmoid': 'i:pppiip',
+    'pst_pp_argmax': 'i:pppiiiiifppppp', 'pst_pp_argmax_logits': 'i:pppiiiiifppppp', 'pst_pp_select': 'i:pppidppp', 'pst_pp_finalize': 'i:pppiffppp',
+    'pst_qubo_upsample': 'i:ppiiiiip', 'pst_qubo_workspace_floats': 'l:il', 'pst_qubo_overlap': 'i:pilppp', 'pst_qubo_argmax': 'i:ppilppp',
+    'pst_pointmap_activate': 'i:pppplip', 'pst_focal_weiszfeld': 'i:pppiiiip', 'pst_rigid_moments': 'i:ppppiifp', 'pst_retrieval_select': 'i:plppiiiplpp',
+    'pst_retrieval_assign': 'i:plplpiiiiippppip', 'pst_retrieval_aggregate': 'i:plplpppiippp', 'pst_retrieval_scores': 'i:ppppppiiiiffpp',
+    'pst_cloud_count': 'i:piifpp', 'pst_cloud_scan': 'i:pipp', 'pst_cloud_compact': 'i:piifppiffppppppp', 'pst_cloud_segment_median': 'i:ppplpiippppppp',
+    'pst_qubo_anneal_max_n': 'i:', 'pst_qubo_anneal': 'i:piiifffuppppp',
+}
+EXPORTS = list(SIGNATURES)
 
 
 def lib():
-    """Load the shared library (once).  Raises if it has not been built -- there is no CPU fallback."""
+    """Load the shared library (once) and declare every prototype of SIGNATURES on it.  Raises if it has not been built -- there is no CPU fallback."""
     global _lib
     if _lib is not None:
         return _lib
@@ -62,20 +80,12 @@ def lib():
         raise RuntimeError('libpanst3r_hip.so not found at %s -- run `python -m panst3r_amd.build` (hipcc, gfx950). '
                            'The HIP path has no fallback.' % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    L.pst_last_error.restype = C.c_char_p
-    L.pst_gemm_variant.restype = C.c_char_p
-    L.pst_gemm_pair_variant.restype = C.c_char_p
-    L.pst_attn_variant.restype = C.c_char_p
-    L.pst_attn_pair_variant.restype = C.c_char_p
-    L.pst_attn_x3_variant.restype = C.c_char_p
-    L.pst_attn_workspace_bytes.restype = C.c_int64
-    L.pst_qubo_workspace_floats.restype = C.c_int64
-    L.pst_qubo_workspace_floats.argtypes = [C.c_int, C.c_int64]
-    L.pst_abi_version.restype = C.c_int
+    for name, sig in SIGNATURES.items():
+        ret, args = sig.split(':')
+        fn = getattr(L, name)          # AttributeError if a declared symbol is missing
+        fn.restype, fn.argtypes = _CODES[ret], [_CODES[c] for c in args]
     if L.pst_abi_version() != ABI_VERSION:
         raise RuntimeError('libpanst3r_hip.so ABI %d != expected %d; rebuild' % (L.pst_abi_version(), ABI_VERSION))
-    for name in EXPORTS:
-        getattr(L, name)          # AttributeError if a declared symbol is missing
     _lib = L
     return L
 
@@ -88,17 +98,20 @@ def tune(knob, value):
     return int(lib().pst_tune(int(knob), int(value)))
 
 
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError('%s failed (%d): %s' % (what, rc, lib().pst_last_error().decode()))
-
-
 def _stream():
-    return vp(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _ptr(t):
-    return vp(t.data_ptr()) if t is not None else vp(0)
+    return t.data_ptr() if t is not None else None
+
+
+def _call(what, *args):
+    """one launch of the entry point `what` on torch's current stream (every launching entry point takes the stream last); a refusal raises with the
+    library's message.  Scalars go in as plain Python numbers: the declared prototype converts them, and refuses what does not fit its type."""
+    rc = getattr(lib(), what)(*args, _stream())
+    if rc != 0:
+        raise RuntimeError('%s failed (%d): %s' % (what, rc, lib().pst_last_error().decode()))
 
 
 H16 = (torch.bfloat16, torch.float16)        # the two 16-bit storage formats (amp='bf16' / amp='fp16'); all 16-bit operands of a call share one
@@ -237,16 +250,28 @@ def hbm_timed(name, nbytes):
     and recorded with its ALGORITHMIC byte count nbytes(*args) (bench.py reports GB/s per stage against the 8 TB/s HBM peak)."""
     def deco(fn):
         def wrapped(*a, **k):
-            if TIMER is None:
-                return fn(*a, **k)
-            ev = TIMER.bracket(name, 0.0, ('bytes', float(nbytes(*a, **k))))
-            ev[0].record()
-            r = fn(*a, **k)
-            ev[1].record()
-            return r
+            return _timed(name, 0.0, ('bytes', float(nbytes(*a, **k))) if TIMER is not None else None, fn, *a, **k)
         wrapped.__name__, wrapped.__doc__ = fn.__name__, fn.__doc__
         return wrapped
     return deco
+
+
+def _timed(name, flops, tag, fn, *a, **k):
+    """fn(*a, **k); with a KernelTimer installed, bracketed by two HIP events on the launch stream and recorded as (name, flops, tag).  `name` may be a
+    callable: it is asked only when the launch is timed (the kernel's name costs a call into the library)."""
+    if TIMER is None:
+        return fn(*a, **k)
+    ev = TIMER.bracket(name() if callable(name) else name, flops, tag)
+    ev[0].record()
+    r = fn(*a, **k)
+    ev[1].record()
+    return r
+
+
+def _variant(what, unknown, *params):
+    """the name of the kernel the C side dispatches these parameters to (no re-derived rule here); `unknown` for parameters it rejects"""
+    name = getattr(lib(), what)(*params)
+    return name.decode() if name else unknown
 
 _ZERO = {}
 
@@ -352,7 +377,7 @@ def split_operand(x, side, kpad=None, out=None, fmt=None):
     kpad = (K + 63) // 64 * 64 if kpad is None else kpad
     if out is None:
         out = torch.empty(rows, 3 * kpad, dtype=fmt or X3_FMT, device=x.device)
-    _check(lib().pst_split_operand(_ptr(x), i64(_rowmajor(x)), _ptr(out), i64(_rowmajor(out)), rows, K, kpad, int(side), _tc(out), _stream()), 'pst_split_operand')
+    _call('pst_split_operand', _ptr(x), _rowmajor(x), _ptr(out), _rowmajor(out), rows, K, kpad, side, _tc(out))
     return out
 
 
@@ -363,7 +388,7 @@ def split2(x, transpose=False, hi=None, lo=None, fmt=None):
     if hi is None:
         shape = (K, (rows + 7) // 8 * 8) if transpose else (rows, K)
         hi, lo = torch.empty(shape, dtype=fmt or X3_FMT, device=x.device), torch.empty(shape, dtype=fmt or X3_FMT, device=x.device)
-    _check(lib().pst_split2(_ptr(x), i64(_rowmajor(x)), _ptr(hi), _ptr(lo), i64(_rowmajor(hi)), rows, K, int(transpose), _tc(hi), _stream()), 'pst_split2')
+    _call('pst_split2', _ptr(x), _rowmajor(x), _ptr(hi), _ptr(lo), _rowmajor(hi), rows, K, transpose, _tc(hi))
     return hi, lo
 
 
@@ -374,8 +399,7 @@ def rope2d_split(x, pos, table, nheads, hd, fmt=None):
     rows, cols = x.shape[0], nheads * hd
     hi = torch.empty(rows, cols, dtype=fmt or X3_FMT, device=x.device)
     lo = torch.empty(rows, cols, dtype=fmt or X3_FMT, device=x.device)
-    _check(lib().pst_rope2d_split(_ptr(x), i64(_rowmajor(x)), _ptr(pos), _ptr(table), _ptr(hi), _ptr(lo), i64(cols), rows, nheads, hd, _tc(hi), _stream()),
-           'pst_rope2d_split')
+    _call('pst_rope2d_split', _ptr(x), _rowmajor(x), _ptr(pos), _ptr(table), _ptr(hi), _ptr(lo), cols, rows, nheads, hd, _tc(hi))
     return Planes(hi, lo)
 
 
@@ -383,7 +407,7 @@ def transpose_f32(x, out):
     """out[c, r] = x[r, c] (fp32; out row-major with leading dimension >= rows)"""
     _dev(x, torch.float32); _dev(out, torch.float32)
     rows, cols = x.shape
-    _check(lib().pst_transpose_f32(_ptr(x), i64(_rowmajor(x)), _ptr(out), i64(_rowmajor(out)), rows, cols, _stream()), 'pst_transpose_f32')
+    _call('pst_transpose_f32', _ptr(x), _rowmajor(x), _ptr(out), _rowmajor(out), rows, cols)
     return out
 
 
@@ -477,15 +501,8 @@ def gemm(a, w, out, **kw):
         finish()
         return out
     p, flops, tag = _gemm_params(a, w, out, **kw)
-    if TIMER is not None:
-        name = lib().pst_gemm_variant(C.byref(p))          # the C side names the kernel it dispatches to (no re-derived rule here)
-        ev = TIMER.bracket(name.decode() if name else 'gemm?', flops, tag)
-        ev[0].record()
-        _check(lib().pst_gemm(C.byref(p), _stream()), 'pst_gemm')
-        ev[1].record()
-        return out
-    _check(lib().pst_gemm(C.byref(p), _stream()), 'pst_gemm')
-    if MAXABS is not None:
+    _timed(lambda: _variant('pst_gemm_variant', 'gemm?', p), flops, tag, _call, 'pst_gemm', p)
+    if MAXABS is not None and TIMER is None:
         _note_gemm(out, kw, tag)
     return out
 
@@ -530,19 +547,13 @@ def gemm_pair(first, second):
         return o1, o2
     p1, f1, t1 = _gemm_params(a1, w1, o1, **k1)
     p2, f2, t2 = _gemm_params(a2, w2, o2, **k2)
-    if TIMER is not None:
-        name = lib().pst_gemm_pair_variant(C.byref(p1), C.byref(p2))
-        if not name:                                       # not fused: two attributed launches
-            gemm(a1, w1, o1, **k1)
-            gemm(a2, w2, o2, **k2)
-            return o1, o2
-        ev = TIMER.bracket(name.decode(), f1 + f2, t1 + t2)
-        ev[0].record()
-        _check(lib().pst_gemm_pair(C.byref(p1), C.byref(p2), _stream()), 'pst_gemm_pair')
-        ev[1].record()
+    name = _variant('pst_gemm_pair_variant', '', p1, p2) if TIMER is not None else None
+    if name == '':                                         # timed and not fused: two attributed launches
+        gemm(a1, w1, o1, **k1)
+        gemm(a2, w2, o2, **k2)
         return o1, o2
-    _check(lib().pst_gemm_pair(C.byref(p1), C.byref(p2), _stream()), 'pst_gemm_pair')
-    if MAXABS is not None:
+    _timed(name, f1 + f2, t1 + t2, _call, 'pst_gemm_pair', p1, p2)
+    if MAXABS is not None and TIMER is None:
         _note_gemm(o1, k1, t1)
         _note_gemm(o2, k2, t2)
     return o1, o2
@@ -550,7 +561,7 @@ def gemm_pair(first, second):
 
 # ----------------------------------------------------------------------------------------------------------- attention
 def mask_head_supported(Q, P, C):
-    return bool(lib().pst_mask_head_supported(int(Q), int(P), int(C)))
+    return bool(lib().pst_mask_head_supported(Q, P, C))
 
 
 def mask_head(embed, feats, out):
@@ -561,14 +572,8 @@ def mask_head(embed, feats, out):
     P = feats.numel() // (n * C)
     Q = embed.shape[0]
     assert feats.is_contiguous() and out.is_contiguous() and out.numel() == n * Q * P and embed.shape[1] == C and embed.stride(1) == 1
-    ev = None
-    if TIMER is not None:
-        ev = TIMER.bracket('mask_head_kernel', 2.0 * n * Q * P * C, ('bytes', float(n * (C * P * 2 + Q * P * 4))))
-        ev[0].record()
-    _check(lib().pst_mask_head(_ptr(embed), i64(embed.stride(0)), _ptr(feats), i64(P * C), _ptr(out), i64(Q * P), n, Q, P, C, _same16(embed, feats), _stream()),
-           'pst_mask_head')
-    if ev is not None:
-        ev[1].record()
+    _timed('mask_head_kernel', 2.0 * n * Q * P * C, ('bytes', float(n * (C * P * 2 + Q * P * 4))), _call,
+           'pst_mask_head', _ptr(embed), embed.stride(0), _ptr(feats), P * C, _ptr(out), Q * P, n, Q, P, C, _same16(embed, feats))
     return out
 
 
@@ -593,15 +598,20 @@ def auto_nsplit(B, H, Nq, Nk):
 LOG2E = 1.4426950408889634
 
 
-def _attn_params(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides, scale=None, mask=None,
-                 mask_strides=(0, 0), nsplit=None, ws=None, prescaled=False):
-    """pst_attn_params of one hip.attention call (+ the tensors it must keep alive, flops, shape tag)"""
-    _dev(q, *FMT); _dev(k, *FMT); _dev(vt, *FMT); _dev(out, *FMT)
+def attn_workspace_floats(B, H, Nq, Nk, hd, nsplit=None):
+    """fp32 elements of split-K workspace `attention` needs for this call (0 when it does not split)."""
+    ns = auto_nsplit(B, H, Nq, Nk) if nsplit is None else nsplit
+    return ns * B * H * Nq * (hd + 2) if ns > 1 else 0
+
+
+def _attn_struct(fmt, q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides, scale, mask, mask_strides, ns, ws, prescaled):
+    """pst_attn_params of operands in the format code `fmt`, q / k / vt given as addresses, over `ns` key-range splits (+ the workspace the caller
+    must keep alive)"""
     p = AttnParams()
-    p.dtype16 = _fmt(q, k, vt, out)
-    p.Q, (p.q_bs, p.q_hs, p.q_rs) = _ptr(q), q_strides
-    p.K, (p.k_bs, p.k_hs, p.k_rs) = _ptr(k), k_strides
-    p.Vt, (p.v_bs, p.v_hs, p.v_ds) = _ptr(vt), v_strides
+    p.dtype16 = fmt
+    p.Q, (p.q_bs, p.q_hs, p.q_rs) = q, q_strides
+    p.K, (p.k_bs, p.k_hs, p.k_rs) = k, k_strides
+    p.Vt, (p.v_bs, p.v_hs, p.v_ds) = vt, v_strides
     p.O, (p.o_bs, p.o_hs, p.o_rs) = _ptr(out), o_strides
     if mask is not None:
         _dev(mask, torch.uint8)
@@ -609,16 +619,25 @@ def _attn_params(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_stride
     p.B, p.H, p.Nq, p.Nk, p.hd = B, H, Nq, Nk, hd
     p.scale = float(hd ** -0.5 if scale is None else scale)
     p.prescaled = 1 if prescaled else 0
-    p.zeros = _ptr(zeros_page(q.device))
+    p.zeros = _ptr(zeros_page(out.device))
+    if ns > 1:
+        n = attn_workspace_floats(B, H, Nq, Nk, hd, ns)
+        if ws is None:          # caller-owned workspace preferred (C ABI: the caller owns every buffer); else one from torch's caching allocator
+            ws = torch.empty(n, dtype=torch.float32, device=out.device)
+        assert ws.dtype == torch.float32 and ws.numel() >= n
+        p.nsplit, p.ws, p.ws_bytes = ns, _ptr(ws), ws.numel() * 4
+    return p, ws
+
+
+def _attn_params(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides, scale=None, mask=None,
+                 mask_strides=(0, 0), nsplit=None, ws=None, prescaled=False):
+    """pst_attn_params of one hip.attention call (+ the tensors it must keep alive, flops, shape tag)"""
+    _dev(q, *FMT); _dev(k, *FMT); _dev(vt, *FMT); _dev(out, *FMT)
     ns = auto_nsplit(B, H, Nq, Nk) if nsplit is None else nsplit
     if q.dtype == torch.float32 and nsplit is None:
         ns = 1                      # the fp32 kernel does not split the key range
-    if ns > 1:
-        n = ns * B * H * Nq * (hd + 2)
-        if ws is None:          # caller-owned workspace preferred (C ABI: the caller owns every buffer); else one from torch's caching allocator
-            ws = torch.empty(n, dtype=torch.float32, device=q.device)
-        assert ws.dtype == torch.float32 and ws.numel() >= n
-        p.nsplit, p.ws, p.ws_bytes = ns, _ptr(ws), ws.numel() * 4
+    p, ws = _attn_struct(_fmt(q, k, vt, out), _ptr(q), _ptr(k), _ptr(vt), out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides,
+                         scale, mask, mask_strides, ns, ws, prescaled)
     return p, ws, 4.0 * B * H * Nq * Nk * hd, (B, H, Nq, Nk, hd)
 
 
@@ -629,15 +648,9 @@ def attention(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, 
     if (isinstance(q, Planes) or q.dtype == torch.float32) and X3:
         return _attention_x3(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides, scale, mask, mask_strides, nsplit, ws, prescaled)
     p, ws, flops, tag = _attn_params(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides, scale, mask, mask_strides, nsplit, ws, prescaled)
-    if TIMER is not None:
-        name = lib().pst_attn_variant(C.byref(p))
-        ev = TIMER.bracket(name.decode() if name else 'attn?', flops, tag)
-        ev[0].record()
-        _check(lib().pst_attn_fwd(C.byref(p), _stream()), 'pst_attn_fwd')
-        ev[1].record()
-        return out
-    _check(lib().pst_attn_fwd(C.byref(p), _stream()), 'pst_attn_fwd')
-    note_maxabs(out, 'attention hd=%d out' % hd)
+    _timed(lambda: _variant('pst_attn_variant', 'attn?', p), flops, tag, _call, 'pst_attn_fwd', p)
+    if TIMER is None:
+        note_maxabs(out, 'attention hd=%d out' % hd)
     return out
 
 
@@ -674,7 +687,7 @@ def _attention_x3(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strid
         assert a0 % 16 == 0 and n % 4 == 0, 'attention operands must be 16-byte aligned with strides that are multiples of 8'
         hi = torch.empty(n, dtype=X3_FMT, device=dev)
         lo = torch.empty(n, dtype=X3_FMT, device=dev)
-        _check(lib().pst_split2(vp(a0), i64(n), _ptr(hi), _ptr(lo), i64(n), 1, n, 0, _TC[X3_FMT], _stream()), 'pst_split2')
+        _call('pst_split2', a0, n, _ptr(hi), _ptr(lo), n, 1, n, 0, _TC[X3_FMT])
         planes.append((a0, a1, hi, lo))
 
     def plane_ptrs(t):
@@ -686,35 +699,11 @@ def _attention_x3(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strid
                 off = (addr - a0) // 2            # fp32 byte offset -> 16-bit byte offset
                 return hi.data_ptr() + off, lo.data_ptr() + off
         raise AssertionError('attention operand outside the planes')
-    p = AttnParams()
-    p.dtype16 = _TC[X3_FMT]
     (qh, ql), (kh, kl), (vh, vl) = plane_ptrs(q), plane_ptrs(k), plane_ptrs(vt)
-    p.Q, (p.q_bs, p.q_hs, p.q_rs) = vp(qh), q_strides
-    p.K, (p.k_bs, p.k_hs, p.k_rs) = vp(kh), k_strides
-    p.Vt, (p.v_bs, p.v_hs, p.v_ds) = vp(vh), v_strides
-    p.O, (p.o_bs, p.o_hs, p.o_rs) = _ptr(out), o_strides
-    if mask is not None:
-        _dev(mask, torch.uint8)
-        p.mask, (p.m_bs, p.m_rs) = _ptr(mask), mask_strides
-    p.B, p.H, p.Nq, p.Nk, p.hd = B, H, Nq, Nk, hd
-    p.scale = float(hd ** -0.5 if scale is None else scale)
-    p.prescaled = 1 if prescaled else 0
-    p.zeros = _ptr(zeros_page(dev))
-    ns = auto_nsplit(B, H, Nq, Nk) if nsplit is None else nsplit
-    if ns > 1:
-        n = ns * B * H * Nq * (hd + 2)
-        if ws is None:
-            ws = torch.empty(n, dtype=torch.float32, device=dev)
-        assert ws.dtype == torch.float32 and ws.numel() >= n
-        p.nsplit, p.ws, p.ws_bytes = ns, _ptr(ws), ws.numel() * 4
-    ev = None
-    if TIMER is not None:
-        name = lib().pst_attn_x3_variant(C.byref(p))
-        ev = TIMER.bracket(name.decode() if name else 'attn_x3?', 3 * 4.0 * B * H * Nq * Nk * hd, (B, H, Nq, Nk, hd))
-        ev[0].record()
-    _check(lib().pst_attn_x3(C.byref(p), vp(ql), vp(kl), vp(vl), out_type, i64(out_block), _stream()), 'pst_attn_x3')
-    if ev is not None:
-        ev[1].record()
+    p, ws = _attn_struct(_TC[X3_FMT], qh, kh, vh, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides, scale, mask, mask_strides,
+                         auto_nsplit(B, H, Nq, Nk) if nsplit is None else nsplit, ws, prescaled)
+    _timed(lambda: _variant('pst_attn_x3_variant', 'attn_x3?', p), 3 * 4.0 * B * H * Nq * Nk * hd, (B, H, Nq, Nk, hd), _call,
+           'pst_attn_x3', p, ql, kl, vl, out_type, out_block)
     return out
 
 
@@ -728,26 +717,15 @@ def attention_pair(first, second):
         return
     p1, w1, f1, t1 = _attn_params(*a1, **k1)
     p2, w2, f2, t2 = _attn_params(*a2, **k2)
-    if TIMER is not None:
-        name = lib().pst_attn_pair_variant(C.byref(p1), C.byref(p2))
-        if not name:
-            attention(*a1, **k1)
-            attention(*a2, **k2)
-            return
-        ev = TIMER.bracket(name.decode(), f1 + f2, t1 + t2)
-        ev[0].record()
-        _check(lib().pst_attn_pair(C.byref(p1), C.byref(p2), _stream()), 'pst_attn_pair')
-        ev[1].record()
+    name = _variant('pst_attn_pair_variant', '', p1, p2) if TIMER is not None else None
+    if name == '':                                         # timed and not fused: two attributed launches
+        attention(*a1, **k1)
+        attention(*a2, **k2)
         return
-    _check(lib().pst_attn_pair(C.byref(p1), C.byref(p2), _stream()), 'pst_attn_pair')
-    note_maxabs(a1[3], 'attention hd=%d out' % a1[8])
-    note_maxabs(a2[3], 'attention hd=%d out' % a2[8])
-
-
-def attn_workspace_floats(B, H, Nq, Nk, hd, nsplit=None):
-    """fp32 elements of split-K workspace `attention` needs for this call (0 when it does not split)."""
-    ns = auto_nsplit(B, H, Nq, Nk) if nsplit is None else nsplit
-    return ns * B * H * Nq * (hd + 2) if ns > 1 else 0
+    _timed(name, f1 + f2, t1 + t2, _call, 'pst_attn_pair', p1, p2)
+    if TIMER is None:
+        note_maxabs(a1[3], 'attention hd=%d out' % a1[8])
+        note_maxabs(a2[3], 'attention hd=%d out' % a2[8])
 
 
 # ----------------------------------------------------------------------------------------------------------- the rest
@@ -759,11 +737,9 @@ def layernorm_batch(x_all, gamma_all, beta_all, out_all, eps, rows=None, grp=Non
     assert x_all.dim() == 3 and out_all.dim() == 3 and x_all.stride(2) == 1 and out_all.stride(2) == 1 and gamma_all.is_contiguous() and beta_all.is_contiguous()
     rows = out_all.shape[1] if rows is None else rows
     g = grp or (0, 0, 0)
-    _check(lib().pst_layernorm_add_batch(_ptr(x_all), i64(x_all.stride(1)), _tc(x_all),
-                                         _ptr(_dev(add, torch.float32)) if add is not None else vp(0), i64(_rowmajor(add)) if add is not None else i64(0),
-                                         _ptr(out_all), i64(out_all.stride(1)), X3H if split else _tc(out_all),
-                                         _ptr(_dev(gamma_all, torch.float32)), _ptr(_dev(beta_all, torch.float32)), rows, D, f32(eps),
-                                         g[0], g[1], g[2], n, i64(x_all.stride(0)), i64(out_all.stride(0)), i64(D), _stream()), 'pst_layernorm_add_batch')
+    _call('pst_layernorm_add_batch', _ptr(x_all), x_all.stride(1), _tc(x_all), _ptr(_dev(add, torch.float32)) if add is not None else None,
+          _rowmajor(add) if add is not None else 0, _ptr(out_all), out_all.stride(1), X3H if split else _tc(out_all), _ptr(_dev(gamma_all, torch.float32)),
+          _ptr(_dev(beta_all, torch.float32)), rows, D, eps, g[0], g[1], g[2], n, x_all.stride(0), out_all.stride(0), D)
     return out_all
 
 
@@ -777,18 +753,15 @@ def layernorm(x, gamma, beta, out, eps, rows=None, grp=None, add=None, split=Fal
     g = grp or (0, 0, 0)
     if split:
         assert add is None and out.dtype == X3_FMT
-        _check(lib().pst_layernorm(_ptr(x), i64(_rowmajor(x)), _tc(x), _ptr(out), i64(_rowmajor(out)), X3H, _ptr(_dev(gamma, torch.float32)),
-                                   _ptr(_dev(beta, torch.float32)), rows, D, f32(eps), g[0], g[1], g[2], _stream()), 'pst_layernorm')
+        _call('pst_layernorm', _ptr(x), _rowmajor(x), _tc(x), _ptr(out), _rowmajor(out), X3H, _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)),
+              rows, D, eps, g[0], g[1], g[2])
         return out
     if add is not None:
-        _check(lib().pst_layernorm_add(_ptr(x), i64(_rowmajor(x)), _tc(x), _ptr(_dev(add, torch.float32)),
-                                       i64(_rowmajor(add)), _ptr(out), i64(_rowmajor(out)), _tc(out),
-                                       _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)), rows, D, f32(eps),
-                                       g[0], g[1], g[2], _stream()), 'pst_layernorm_add')
+        _call('pst_layernorm_add', _ptr(x), _rowmajor(x), _tc(x), _ptr(_dev(add, torch.float32)), _rowmajor(add), _ptr(out), _rowmajor(out), _tc(out),
+              _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)), rows, D, eps, g[0], g[1], g[2])
         return out
-    _check(lib().pst_layernorm(_ptr(x), i64(_rowmajor(x)), _tc(x), _ptr(out), i64(_rowmajor(out)),
-                               _tc(out), _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)),
-                               rows, D, f32(eps), g[0], g[1], g[2], _stream()), 'pst_layernorm')
+    _call('pst_layernorm', _ptr(x), _rowmajor(x), _tc(x), _ptr(out), _rowmajor(out), _tc(out), _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)),
+          rows, D, eps, g[0], g[1], g[2])
     note_maxabs(out, 'layernorm D=%d out' % D)
     return out
 
@@ -805,8 +778,7 @@ def rowstats(x, xcopy, stats):
         d16 = _tc(x)
     else:
         d16 = _tc(_dev(xcopy, *H16))
-    _check(lib().pst_rowstats(_ptr(x), i64(_rowmajor(x)), _tc(x), _ptr(xcopy), i64(_rowmajor(xcopy) if xcopy is not None else 0), _ptr(stats),
-                              stats.shape[1], rows, D, d16, _stream()), 'pst_rowstats')
+    _call('pst_rowstats', _ptr(x), _rowmajor(x), _tc(x), _ptr(xcopy), (_rowmajor(xcopy) if xcopy is not None else 0), _ptr(stats), stats.shape[1], rows, D, d16)
     note_maxabs(xcopy, 'rowstats D=%d 16-bit copy of the residual stream' % D)
     return xcopy, stats
 
@@ -815,7 +787,7 @@ def split3(x, out):
     """fp32 x [rows, K] -> bf16 out [rows, 3K] = [x_hi | x_hi | x_lo] (operand of a split-precision GEMM, see pack_split3)."""
     _dev(x, torch.float32); _dev(out, *H16)
     rows, K = x.shape
-    _check(lib().pst_split3(_ptr(x), i64(_rowmajor(x)), _ptr(out), i64(_rowmajor(out)), rows, K, _tc(out), _stream()), 'pst_split3')
+    _call('pst_split3', _ptr(x), _rowmajor(x), _ptr(out), _rowmajor(out), rows, K, _tc(out))
     return out
 
 
@@ -830,8 +802,7 @@ def pack_split3(weight, dtype=torch.bfloat16):
 def rope2d_(x, pos, table, nheads, hd):
     """In-place RoPE-2D on the first nheads*hd columns of the row-major bf16 view x; pos int32 [rows,2]."""
     _dev(x, *FMT); _dev(pos, torch.int32); _dev(table, torch.float32)
-    _check(lib().pst_rope2d(_ptr(x), i64(_rowmajor(x)), _ptr(pos), _ptr(table), x.shape[0], nheads, hd, _tc(x), _stream()),
-           'pst_rope2d')
+    _call('pst_rope2d', _ptr(x), _rowmajor(x), _ptr(pos), _ptr(table), x.shape[0], nheads, hd, _tc(x))
     return x
 
 
@@ -847,7 +818,7 @@ def patchify(img, out, p):
     _dev(img, torch.float32); _dev(out, *FMT)
     n, c, h, w = img.shape
     assert img.is_contiguous()
-    _check(lib().pst_patchify(_ptr(img), _ptr(out), i64(_rowmajor(out)), n, c, h, w, p, _tc(out), _stream()), 'pst_patchify')
+    _call('pst_patchify', _ptr(img), _ptr(out), _rowmajor(out), n, c, h, w, p, _tc(out))
     return out
 
 
@@ -855,7 +826,7 @@ def dino_preprocess(img, out):
     _dev(img, torch.float32); _dev(out, torch.float32)
     n, _, h, w = img.shape
     assert img.is_contiguous() and out.is_contiguous()
-    _check(lib().pst_dino_preprocess(_ptr(img), _ptr(out), n, h, w, out.shape[-2], out.shape[-1], _stream()), 'pst_dino_preprocess')
+    _call('pst_dino_preprocess', _ptr(img), _ptr(out), n, h, w, out.shape[-2], out.shape[-1])
     return out
 
 
@@ -865,8 +836,8 @@ def image_prepare(src_u8, out, resized, crop_origin):
     _dev(src_u8, torch.uint8); _dev(out, torch.float32)
     assert src_u8.dim() == 3 and src_u8.shape[2] == 3 and src_u8.is_contiguous() and out.is_contiguous() and out.shape[0] == 3
     Hs, Ws = src_u8.shape[:2]
-    _check(lib().pst_image_prepare(_ptr(src_u8), Hs, Ws, _ptr(out), int(resized[0]), int(resized[1]), int(crop_origin[0]), int(crop_origin[1]),
-                                   out.shape[1], out.shape[2], _stream()), 'pst_image_prepare')
+    _call('pst_image_prepare', _ptr(src_u8), Hs, Ws, _ptr(out), int(resized[0]), int(resized[1]), int(crop_origin[0]), int(crop_origin[1]), out.shape[1],
+          out.shape[2])
     return out
 
 
@@ -877,9 +848,8 @@ def patch_rows(img, enc=None, dino=None, p_enc=16, p_dino=14, dino_transposed=Fa
     assert img.is_contiguous() and (enc is not None or dino is not None)
     n, _, H, W = img.shape
     d16 = _fmt(enc, dino)
-    _check(lib().pst_patch_rows(_ptr(img), _ptr(enc), i64(_rowmajor(enc) if enc is not None else 0), _ptr(dino),
-                                i64(_rowmajor(dino) if dino is not None else 0), n, H, W, p_enc, p_dino, int(dino_transposed), d16, _stream()),
-           'pst_patch_rows')
+    _call('pst_patch_rows', _ptr(img), _ptr(enc), (_rowmajor(enc) if enc is not None else 0), _ptr(dino), (_rowmajor(dino) if dino is not None else 0), n, H, W,
+          p_enc, p_dino, dino_transposed, d16)
     return enc, dino
 
 
@@ -887,9 +857,8 @@ def add_cast(a, out, b=None, b_mod=0):
     _dev(a); _dev(out)
     rows, D = out.shape
     fp = _tc
-    _check(lib().pst_add_cast(_ptr(a), i64(_rowmajor(a)), fp(a), _ptr(b), i64(_rowmajor(b) if b is not None else 0),
-                              fp(b) if b is not None else 0, b_mod, _ptr(out), i64(_rowmajor(out)), fp(out), rows, D, _stream()),
-           'pst_add_cast')
+    _call('pst_add_cast', _ptr(a), _rowmajor(a), fp(a), _ptr(b), (_rowmajor(b) if b is not None else 0), fp(b) if b is not None else 0, b_mod, _ptr(out),
+          _rowmajor(out), fp(out), rows, D)
     note_maxabs(out, 'add_cast D=%d out' % D)
     return out
 
@@ -906,36 +875,33 @@ def token_embed(ids, tok, pos, out, status=None):
     B, L = ids.shape
     D = tok.shape[1]
     assert pos.shape[1] == D and out.shape[0] >= B * L and out.shape[1] == D
-    _check(lib().pst_token_embed(_ptr(ids), B, L, _ptr(tok), tok.shape[0], _ptr(pos), pos.shape[0], D, _ptr(out), i64(_rowmajor(out)),
-                                 _ptr(status), _stream()), 'pst_token_embed')
+    _call('pst_token_embed', _ptr(ids), B, L, _ptr(tok), tok.shape[0], _ptr(pos), pos.shape[0], D, _ptr(out), _rowmajor(out), _ptr(status))
     return out
 
 
 def l2norm_rows(x, out, eps):
     _dev(x, torch.float32); _dev(out, *FMT)
-    _check(lib().pst_l2norm_rows(_ptr(x), i64(_rowmajor(x)), _ptr(out), i64(_rowmajor(out)), x.shape[0], x.shape[1], f32(eps),
-                                 _tc(out), _stream()), 'pst_l2norm_rows')
+    _call('pst_l2norm_rows', _ptr(x), _rowmajor(x), _ptr(out), _rowmajor(out), x.shape[0], x.shape[1], eps, _tc(out))
     return out
 
 
 @hbm_timed('mean4', lambda F, Fm, nimg, Hm, Wm, Cc: Fm.numel() * 2 * 5)
 def mean4(F, Fm, nimg, Hm, Wm, Cc):
     _dev(F, *FMT); _dev(Fm, *FMT)
-    _check(lib().pst_mean4(_ptr(F), _ptr(Fm), nimg, Hm, Wm, Cc, _fmt(F, Fm), _stream()), 'pst_mean4')
+    _call('pst_mean4', _ptr(F), _ptr(Fm), nimg, Hm, Wm, Cc, _fmt(F, Fm))
     return Fm
 
 
 def resize_bilinear(F, Fd, nimg, Hs, Ws, Hd, Wd, Cc):
     _dev(F, *FMT); _dev(Fd, *FMT)
-    _check(lib().pst_resize_bilinear(_ptr(F), _ptr(Fd), nimg, Hs, Ws, Hd, Wd, Cc, _fmt(F, Fd), _stream()), 'pst_resize_bilinear')
+    _call('pst_resize_bilinear', _ptr(F), _ptr(Fd), nimg, Hs, Ws, Hd, Wd, Cc, _fmt(F, Fd))
     return Fd
 
 
 def attn_mask_from_logits(logits, mask):
     _dev(logits, torch.float32); _dev(mask, torch.uint8)
     Q, Nk = logits.shape
-    _check(lib().pst_attn_mask_from_logits(_ptr(logits), i64(_rowmajor(logits)), _ptr(mask), i64(_rowmajor(mask)), Q, Nk, _stream()),
-           'pst_attn_mask_from_logits')
+    _call('pst_attn_mask_from_logits', _ptr(logits), _rowmajor(logits), _ptr(mask), _rowmajor(mask), Q, Nk)
     return mask
 
 
@@ -954,9 +920,8 @@ def loftup_guidance_gn(img, biases, gamma, beta, eps, scratch, stats, out, nf, m
     if mm is not None:
         _dev(mm, torch.float32)
         assert mm.is_contiguous() and tuple(mm.shape) == (n, 3, 2)
-    _check(lib().pst_loftup_guidance_gn(_ptr(img), _ptr(biases), _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)), f32(eps),
-                                        _ptr(scratch), _ptr(stats), _ptr(out), i64(_rowmajor(out)), n, h, w, nf, _tc(out), _ptr(mm), _stream()),
-           'pst_loftup_guidance_gn')
+    _call('pst_loftup_guidance_gn', _ptr(img), _ptr(biases), _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)), eps, _ptr(scratch), _ptr(stats),
+          _ptr(out), _rowmajor(out), n, h, w, nf, _tc(out), _ptr(mm))
     return out
 
 
@@ -965,7 +930,7 @@ def loftup_minmax(img, mm):
     _dev(img, torch.float32); _dev(mm, torch.float32)
     n, c, h, w = img.shape
     assert c == 3 and img.is_contiguous() and mm.is_contiguous() and tuple(mm.shape) == (n, 3, 2)
-    _check(lib().pst_loftup_minmax(_ptr(img), _ptr(mm), n, h, w, _stream()), 'pst_loftup_minmax')
+    _call('pst_loftup_minmax', _ptr(img), _ptr(mm), n, h, w)
     return mm
 
 
@@ -974,23 +939,22 @@ def minmax_merge(mm, scope, out):
     _dev(mm, torch.float32); _dev(scope, torch.int32); _dev(out, torch.float32)
     n = scope.numel()
     assert mm.is_contiguous() and out.is_contiguous() and tuple(mm.shape) == (n, 3, 2) and tuple(out.shape) == (n, 3, 2) and mm.data_ptr() != out.data_ptr()
-    _check(lib().pst_minmax_merge(_ptr(mm), _ptr(scope), _ptr(out), n, _stream()), 'pst_minmax_merge')
+    _call('pst_minmax_merge', _ptr(mm), _ptr(scope), _ptr(out), n)
     return out
 
 
 @hbm_timed('groupnorm_stats', lambda x, stats, nimg, P, Cc, G: nimg * P * Cc * _esz(x))
 def groupnorm_stats(x, stats, nimg, P, Cc, G):
     _dev(x); _dev(stats, torch.float32)
-    _check(lib().pst_groupnorm_stats(_ptr(x), i64(_rowmajor(x)), _tc(x), _ptr(stats), nimg, P, Cc, G, _stream()),
-           'pst_groupnorm_stats')
+    _call('pst_groupnorm_stats', _ptr(x), _rowmajor(x), _tc(x), _ptr(stats), nimg, P, Cc, G)
 
 
 @hbm_timed('groupnorm_apply', lambda x, stats, gamma, beta, out, nimg, P, Cc, G, eps, relu, split=False: nimg * P * (Cc * _esz(x) + out.shape[1] * 2))
 def groupnorm_apply(x, stats, gamma, beta, out, nimg, P, Cc, G, eps, relu, split=False):
     """split=True: `out` f16 [rows, 3 x block] receives the split A operand rows [hi | hi | lo] (PST_X3H) of the conv that follows"""
     _dev(x); _dev(out, *FMT)
-    _check(lib().pst_groupnorm_apply(_ptr(x), i64(_rowmajor(x)), _tc(x), _ptr(stats), _ptr(gamma), _ptr(beta),
-                                     _ptr(out), i64(_rowmajor(out)), nimg, P, Cc, G, f32(eps), int(relu), X3H if split else _tc(out), _stream()), 'pst_groupnorm_apply')
+    _call('pst_groupnorm_apply', _ptr(x), _rowmajor(x), _tc(x), _ptr(stats), _ptr(gamma), _ptr(beta), _ptr(out), _rowmajor(out), nimg, P, Cc, G, eps, relu,
+          X3H if split else _tc(out))
     return out
 
 
@@ -1005,7 +969,7 @@ class Planes:
 
 def loftup_lr_pe(biases, out, col0, nimg, h, w):
     _dev(biases, torch.float32); _dev(out, *FMT)
-    _check(lib().pst_loftup_lr_pe(_ptr(biases), _ptr(out), i64(_rowmajor(out)), col0, nimg, h, w, _tc(out), _stream()), 'pst_loftup_lr_pe')
+    _call('pst_loftup_lr_pe', _ptr(biases), _ptr(out), _rowmajor(out), col0, nimg, h, w, _tc(out))
     return out
 
 
@@ -1013,27 +977,25 @@ def loftup_lr_pe(biases, out, col0, nimg, h, w):
 def pp_scores(logits, cls_threshold, temperature, scores, labels, keep):
     _dev(logits, torch.float32); _dev(scores, torch.float32); _dev(labels, torch.int32); _dev(keep, torch.int32)
     Q, Ncls = logits.shape
-    _check(lib().pst_pp_scores(_ptr(logits), Q, Ncls, C.c_float(cls_threshold), C.c_float(temperature or 0.0), _ptr(scores), _ptr(labels),
-                               _ptr(keep), _stream()), 'pst_pp_scores')
+    _call('pst_pp_scores', _ptr(logits), Q, Ncls, float(cls_threshold), float(temperature or 0.0), _ptr(scores), _ptr(labels), _ptr(keep))
 
 
 def pp_scores_softmax(logits, cls_threshold, scores, labels, keep):
     _dev(logits, torch.float32); _dev(scores, torch.float32); _dev(labels, torch.int32); _dev(keep, torch.int32)
     Q, Ncls = logits.shape
-    _check(lib().pst_pp_scores_softmax(_ptr(logits), Q, Ncls, C.c_float(cls_threshold), _ptr(scores), _ptr(labels), _ptr(keep), _stream()), 'pst_pp_scores_softmax')
+    _call('pst_pp_scores_softmax', _ptr(logits), Q, Ncls, float(cls_threshold), _ptr(scores), _ptr(labels), _ptr(keep))
 
 
 def pp_sigmoid(logits, keep, probs, Q, P):
     _dev(logits, torch.float32); _dev(keep, torch.int32); _dev(probs, torch.float32)
-    _check(lib().pst_pp_sigmoid(_ptr(logits), _ptr(keep), _ptr(probs), Q, P, _stream()), 'pst_pp_sigmoid')
+    _call('pst_pp_sigmoid', _ptr(logits), _ptr(keep), _ptr(probs), Q, P)
 
 
 def pp_argmax(probs, scores, keep, Q, Hm, Wm, H, W, mask_threshold, best_q, best_m, cnt_orig, cnt_mask):
     for t, dt in ((probs, torch.float32), (scores, torch.float32), (keep, torch.int32), (best_q, torch.int32), (best_m, torch.float32),
                   (cnt_orig, torch.int32), (cnt_mask, torch.int32)):
         _dev(t, dt)
-    _check(lib().pst_pp_argmax(_ptr(probs), _ptr(scores), _ptr(keep), Q, Hm, Wm, H, W, C.c_float(mask_threshold), _ptr(best_q), _ptr(best_m),
-                               _ptr(cnt_orig), _ptr(cnt_mask), _stream()), 'pst_pp_argmax')
+    _call('pst_pp_argmax', _ptr(probs), _ptr(scores), _ptr(keep), Q, Hm, Wm, H, W, float(mask_threshold), _ptr(best_q), _ptr(best_m), _ptr(cnt_orig), _ptr(cnt_mask))
 
 
 def pp_fused_fits(Q, Hm, Wm, H, W):
@@ -1048,21 +1010,19 @@ def pp_argmax_logits(logits, scores, keep, Q, Hm, Wm, H, W, mask_threshold, best
     for t, dt in ((logits, torch.float32), (scores, torch.float32), (keep, torch.int32), (best_q, torch.int32), (best_m, torch.float32),
                   (cnt_orig, torch.int32), (cnt_mask, torch.int32)):
         _dev(t, dt)
-    _check(lib().pst_pp_argmax_logits(_ptr(logits), _ptr(scores), _ptr(keep), Q, Hm, Wm, H, W, C.c_float(mask_threshold), _ptr(best_q),
-                                      _ptr(best_m), _ptr(cnt_orig), _ptr(cnt_mask), _stream()), 'pst_pp_argmax_logits')
+    _call('pst_pp_argmax_logits', _ptr(logits), _ptr(scores), _ptr(keep), Q, Hm, Wm, H, W, float(mask_threshold), _ptr(best_q), _ptr(best_m), _ptr(cnt_orig),
+          _ptr(cnt_mask))
 
 
 def pp_select(keep, cnt_orig, cnt_mask, Q, overlap_threshold, keep_out, seg_id):
     for t in (keep, cnt_orig, cnt_mask, keep_out, seg_id):
         _dev(t, torch.int32)
-    _check(lib().pst_pp_select(_ptr(keep), _ptr(cnt_orig), _ptr(cnt_mask), Q, C.c_double(overlap_threshold), _ptr(keep_out), _ptr(seg_id),
-                               _stream()), 'pst_pp_select')
+    _call('pst_pp_select', _ptr(keep), _ptr(cnt_orig), _ptr(cnt_mask), Q, float(overlap_threshold), _ptr(keep_out), _ptr(seg_id))
 
 
 def pp_finalize(best_q, best_m, seg_id, n, mask_threshold, void_confidence, pan, conf):
     _dev(best_q, torch.int32); _dev(best_m, torch.float32); _dev(seg_id, torch.int32); _dev(pan, torch.int32); _dev(conf, torch.float32)
-    _check(lib().pst_pp_finalize(_ptr(best_q), _ptr(best_m), _ptr(seg_id), n, C.c_float(mask_threshold), C.c_float(void_confidence), _ptr(pan),
-                                 _ptr(conf), _stream()), 'pst_pp_finalize')
+    _call('pst_pp_finalize', _ptr(best_q), _ptr(best_m), _ptr(seg_id), n, float(mask_threshold), float(void_confidence), _ptr(pan), _ptr(conf))
 
 
 # ------------------------------------------------------------------ pointmap post-processing
@@ -1071,13 +1031,13 @@ def pointmap_activate(raw, pts3d, pts3d_local, conf, mode=0):
         _dev(t, torch.float32)
         assert t.is_contiguous()
     npix = raw.numel() // 7
-    _check(lib().pst_pointmap_activate(_ptr(raw), _ptr(pts3d), _ptr(pts3d_local), _ptr(conf), i64(npix), int(mode), _stream()), 'pst_pointmap_activate')
+    _call('pst_pointmap_activate', _ptr(raw), _ptr(pts3d), _ptr(pts3d_local), _ptr(conf), npix, mode)
 
 
 def focal_weiszfeld(pts3d_local, pp, focal, H, W, iters=10):
     _dev(pts3d_local, torch.float32); _dev(pp, torch.float32); _dev(focal, torch.float32)
     assert pts3d_local.is_contiguous() and pp.is_contiguous() and focal.numel() * H * W * 3 == pts3d_local.numel()
-    _check(lib().pst_focal_weiszfeld(_ptr(pts3d_local), _ptr(pp), _ptr(focal), focal.numel(), H, W, iters, _stream()), 'pst_focal_weiszfeld')
+    _call('pst_focal_weiszfeld', _ptr(pts3d_local), _ptr(pp), _ptr(focal), focal.numel(), H, W, iters)
     return focal
 
 
@@ -1085,25 +1045,25 @@ def rigid_moments(x, y, conf, out, weight_offset=-1.0):
     _dev(x, torch.float32); _dev(y, torch.float32); _dev(conf, torch.float32); _dev(out, torch.float64)
     V = out.shape[0]
     assert x.is_contiguous() and y.is_contiguous() and conf.is_contiguous() and out.is_contiguous() and out.shape[1] == 16
-    _check(lib().pst_rigid_moments(_ptr(x), _ptr(y), _ptr(conf), _ptr(out), V, conf.numel() // V, C.c_float(weight_offset), _stream()), 'pst_rigid_moments')
+    _call('pst_rigid_moments', _ptr(x), _ptr(y), _ptr(conf), _ptr(out), V, conf.numel() // V, float(weight_offset))
     return out
 
 
 # ------------------------------------------------------------------ QUBO post-processing (engine/postprocess.py:135-336)
 def qubo_upsample(logits, probs, Q, hm, wm, H, W):
     _dev(logits, torch.float32); _dev(probs, torch.float32)
-    _check(lib().pst_qubo_upsample(_ptr(logits), _ptr(probs), Q, hm, wm, H, W, _stream()), 'pst_qubo_upsample')
+    _call('pst_qubo_upsample', _ptr(logits), _ptr(probs), Q, hm, wm, H, W)
 
 
 def qubo_overlap(probs, Q, P, Wacc):
     _dev(probs, torch.float32); _dev(Wacc, torch.float64)
-    ws = torch.empty(int(lib().pst_qubo_workspace_floats(Q, P)), dtype=torch.float32, device=probs.device)
-    _check(lib().pst_qubo_overlap(_ptr(probs), Q, i64(P), _ptr(ws), _ptr(Wacc), _stream()), 'pst_qubo_overlap')
+    ws = torch.empty(lib().pst_qubo_workspace_floats(Q, P), dtype=torch.float32, device=probs.device)
+    _call('pst_qubo_overlap', _ptr(probs), Q, P, _ptr(ws), _ptr(Wacc))
 
 
 def qubo_argmax(probs, sel, P, conf, inst):
     _dev(probs, torch.float32); _dev(sel, torch.int32); _dev(conf, torch.float32); _dev(inst, torch.int32)
-    _check(lib().pst_qubo_argmax(_ptr(probs), _ptr(sel), sel.numel(), i64(P), _ptr(conf), _ptr(inst), _stream()), 'pst_qubo_argmax')
+    _call('pst_qubo_argmax', _ptr(probs), _ptr(sel), sel.numel(), P, _ptr(conf), _ptr(inst))
 
 
 # ------------------------------------------------------------------ ASMK retrieval (model/retrieval.py restates the algorithm)
@@ -1114,8 +1074,8 @@ def retrieval_select(x, in_off, out_off, out, max_t, sel_idx=None):
     if sel_idx is not None:
         _dev(sel_idx, torch.int32)
     assert in_off.is_contiguous() and out_off.is_contiguous() and in_off.numel() == out_off.numel() and x.shape[1] == out.shape[1]
-    _check(lib().pst_retrieval_select(_ptr(x), i64(_rowmajor(x)), _ptr(in_off), _ptr(out_off), in_off.numel() - 1, int(max_t), x.shape[1], _ptr(out),
-                                      i64(_rowmajor(out)), _ptr(sel_idx), _stream()), 'pst_retrieval_select')
+    _call('pst_retrieval_select', _ptr(x), _rowmajor(x), _ptr(in_off), _ptr(out_off), in_off.numel() - 1, int(max_t), x.shape[1], _ptr(out), _rowmajor(out),
+          _ptr(sel_idx))
     return out
 
 
@@ -1137,8 +1097,8 @@ def retrieval_assign(x3, c3, cnorm, m, ids, dist, nsplit=None):
     if nsplit > 1:
         ws_d = torch.empty(nsplit * n * m, dtype=torch.float32, device=x3.device)
         ws_i = torch.empty(nsplit * n * m, dtype=torch.int32, device=x3.device)
-    _check(lib().pst_retrieval_assign(_ptr(x3), i64(_rowmajor(x3)), _ptr(c3), i64(_rowmajor(c3)), _ptr(cnorm), n, k, x3.shape[1], int(m), nsplit,
-                                      _ptr(ws_d), _ptr(ws_i), _ptr(ids), _ptr(dist), _tc(x3), _stream()), 'pst_retrieval_assign')
+    _call('pst_retrieval_assign', _ptr(x3), _rowmajor(x3), _ptr(c3), _rowmajor(c3), _ptr(cnorm), n, k, x3.shape[1], int(m), nsplit, _ptr(ws_d), _ptr(ws_i),
+          _ptr(ids), _ptr(dist), _tc(x3))
     return ids, dist
 
 
@@ -1152,8 +1112,7 @@ def retrieval_aggregate(x, cent, member, gstart, gword, bits, sums=None):
     if sums is not None:
         _dev(sums, torch.float32)
         assert sums.shape == (G, D) and sums.is_contiguous()
-    _check(lib().pst_retrieval_aggregate(_ptr(x), i64(_rowmajor(x)), _ptr(cent), i64(_rowmajor(cent)), _ptr(member), _ptr(gstart), _ptr(gword), G, D,
-                                         _ptr(sums), _ptr(bits), _stream()), 'pst_retrieval_aggregate')
+    _call('pst_retrieval_aggregate', _ptr(x), _rowmajor(x), _ptr(cent), _rowmajor(cent), _ptr(member), _ptr(gstart), _ptr(gword), G, D, _ptr(sums), _ptr(bits))
     return bits
 
 
@@ -1165,8 +1124,8 @@ def retrieval_scores(q_off, q_word, q_bits, db_off, db_word, db_bits, D, alpha, 
     _dev(S, torch.float32)
     Vq, Vdb = q_off.numel() - 1, db_off.numel() - 1
     assert S.shape == (Vq, Vdb) and S.is_contiguous() and q_bits.shape[1] == D // 32 and db_bits.shape[1] == D // 32
-    _check(lib().pst_retrieval_scores(_ptr(q_off), _ptr(q_word), _ptr(q_bits), _ptr(db_off), _ptr(db_word), _ptr(db_bits), Vq, Vdb, int(max(1, max_q)), int(D),
-                                      f32(alpha), f32(tau), _ptr(S), _stream()), 'pst_retrieval_scores')
+    _call('pst_retrieval_scores', _ptr(q_off), _ptr(q_word), _ptr(q_bits), _ptr(db_off), _ptr(db_word), _ptr(db_bits), Vq, Vdb, int(max(1, max_q)), int(D),
+          float(alpha), float(tau), _ptr(S))
     return S
 
 
@@ -1199,13 +1158,13 @@ def cloud_view_table(views, cams2world, device):
 def cloud_count(table, nviews, nwg, thr, counts):
     _dev(table, torch.uint8); _dev(counts, torch.int32)
     assert table.numel() == nviews * C.sizeof(CloudView) and counts.numel() >= nwg
-    _check(lib().pst_cloud_count(_ptr(table), int(nviews), int(nwg), f32(thr), _ptr(counts), _stream()), 'pst_cloud_count')
+    _call('pst_cloud_count', _ptr(table), nviews, nwg, float(thr), _ptr(counts))
 
 
 def cloud_scan(counts, base):
     _dev(counts, torch.int32); _dev(base, torch.int32)
     assert base.numel() == counts.numel() + 1
-    _check(lib().pst_cloud_scan(_ptr(counts), counts.numel(), _ptr(base), _stream()), 'pst_cloud_scan')
+    _call('pst_cloud_scan', _ptr(counts), counts.numel(), _ptr(base))
 
 
 def cloud_compact(table, nviews, nwg, thr, base, colors, w1, w2, points, points_local, rgb, pan, colors_out, index):
@@ -1215,8 +1174,8 @@ def cloud_compact(table, nviews, nwg, thr, base, colors, w1, w2, points, points_
         _dev(t, torch.float32)
         assert t.is_contiguous() and t.numel() == 3 * n
     assert table.numel() == nviews * C.sizeof(CloudView) and base.numel() == nwg + 1 and index.numel() == n and colors.is_contiguous() and colors.shape[1] == 3
-    _check(lib().pst_cloud_compact(_ptr(table), int(nviews), int(nwg), f32(thr), _ptr(base), _ptr(colors), colors.shape[0], f32(w1), f32(w2), _ptr(points),
-                                   _ptr(points_local), _ptr(rgb), _ptr(pan), _ptr(colors_out), _ptr(index), _stream()), 'pst_cloud_compact')
+    _call('pst_cloud_compact', _ptr(table), nviews, nwg, float(thr), _ptr(base), _ptr(colors), colors.shape[0], float(w1), float(w2), _ptr(points),
+          _ptr(points_local), _ptr(rgb), _ptr(pan), _ptr(colors_out), _ptr(index))
 
 
 def cloud_segment_median(points_local, pan, m_ptr, id2row, nseg, count, median):
@@ -1226,14 +1185,14 @@ def cloud_segment_median(points_local, pan, m_ptr, id2row, nseg, count, median):
     assert points_local.is_contiguous() and pan.numel() * 3 == points_local.numel() and count.numel() == nseg and median.numel() == 3 * nseg and median.is_contiguous()
     ws = torch.zeros(nseg * (3 * 2 * 256 + 6 + 6 + 3), dtype=torch.int32, device=pan.device)
     hist, prefix, rank, nan = ws[:nseg * 1536], ws[nseg * 1536:nseg * 1542], ws[nseg * 1542:nseg * 1548], ws[nseg * 1548:]
-    _check(lib().pst_cloud_segment_median(_ptr(points_local), _ptr(pan), _ptr(m_ptr), i64(pan.numel()), _ptr(id2row), id2row.numel(), int(nseg), _ptr(hist),
-                                          _ptr(prefix), _ptr(rank), _ptr(nan), _ptr(count), _ptr(median), _stream()), 'pst_cloud_segment_median')
+    _call('pst_cloud_segment_median', _ptr(points_local), _ptr(pan), _ptr(m_ptr), pan.numel(), _ptr(id2row), id2row.numel(), nseg, _ptr(hist), _ptr(prefix),
+          _ptr(rank), _ptr(nan), _ptr(count), _ptr(median))
 
 
 # ------------------------------------------------------------------ QUBO mask selection (csrc/qubo_solve.hip; engine/postprocess.py holds the public entry points)
 def qubo_anneal_max_n():
     """the largest problem the device annealer takes (W in the LDS of one CU)"""
-    return int(lib().pst_qubo_anneal_max_n())
+    return lib().pst_qubo_anneal_max_n()
 
 
 def qubo_anneal(W, replicas, num_iters, T0, T_end, lambda_reg, seed, x_all, e_all, best_x, best_e):
@@ -1243,5 +1202,5 @@ def qubo_anneal(W, replicas, num_iters, T0, T_end, lambda_reg, seed, x_all, e_al
     N = W.shape[0]
     assert W.dim() == 2 and W.shape[1] == N and all(t.is_contiguous() and t.device == W.device for t in (W, x_all, e_all, best_x, best_e))
     assert x_all.numel() == replicas * N and e_all.numel() == replicas and best_x.numel() == N and best_e.numel() == 1
-    _check(lib().pst_qubo_anneal(_ptr(W), int(N), int(replicas), int(num_iters), f32(T0), f32(T_end), f32(lambda_reg), C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                 _ptr(x_all), _ptr(e_all), _ptr(best_x), _ptr(best_e), _stream()), 'pst_qubo_anneal')
+    _call('pst_qubo_anneal', _ptr(W), N, int(replicas), int(num_iters), float(T0), float(T_end), float(lambda_reg), int(seed) & (2 ** 64 - 1), _ptr(x_all),
+          _ptr(e_all), _ptr(best_x), _ptr(best_e))

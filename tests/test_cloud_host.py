@@ -4,13 +4,13 @@ No GPU needed."""
 import ctypes
 import math
 import os
-import re
 import struct
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import cloud_ref as R
 
 F = np.float32
@@ -159,16 +159,13 @@ def test_cpu_tensors_raise():
 def test_header_exports_and_library_agree_on_the_cloud_symbols():
     from panst3r_amd import hip
     from panst3r_amd.build import build
-    text = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'panst3r_hip.h')).read(), flags=re.S)
-    declared = sorted(set(re.findall(r'\b(pst_cloud_[a-z0-9_]+)\s*\(', text)))
+    declared = sorted(p[0] for p in abi_header.prototypes() if p[0].startswith('pst_cloud_'))
     assert declared == CLOUD_SYMBOLS == sorted(s for s in hip.EXPORTS if s.startswith('pst_cloud_'))
     lib = ctypes.CDLL(build(verbose=False))
     for s in declared:
         assert hasattr(lib, s), s
     assert hip.ABI_VERSION == 20
-    body = re.search(r'typedef struct pst_cloud_view \{(.*?)\} pst_cloud_view;', text, flags=re.S).group(1)
-    names = [re.findall(r'[A-Za-z_][A-Za-z0-9_]*', d)[-1] for d in body.split(';') if d.strip()]
-    names = [n if n != '12' else 'c2w' for n in names]
+    names = [f[0] for f in abi_header.structs()['pst_cloud_view']]
     assert names == [f[0] for f in hip.CloudView._fields_] and ctypes.sizeof(hip.CloudView) == 104
 
 

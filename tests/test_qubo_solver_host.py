@@ -8,11 +8,11 @@ its defaults on three 200 x 200 matrices (tests/golden/make_qubo_solver_golden.p
 import ctypes
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header
 import qubo_ref as R
 
 F = np.float32
@@ -24,10 +24,10 @@ SYMBOLS = ['pst_qubo_anneal', 'pst_qubo_anneal_max_n']
 def test_header_declares_and_library_exports_the_symbols():
     from panst3r_amd.build import build
     from panst3r_amd import hip
-    text = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'panst3r_hip.h')).read(), flags=re.S)
+    declared = {p[0] for p in abi_header.prototypes()}
     lib = ctypes.CDLL(build(verbose=False))
     for s in SYMBOLS:
-        assert re.search(r'\b%s\s*\(' % s, text), s
+        assert s in declared, s
         assert hasattr(lib, s) and s in hip.EXPORTS, s
     assert lib.pst_qubo_anneal_max_n() == R.NMAX == 200
     assert lib.pst_abi_version() == 20                                  # additive: the ABI version stays
