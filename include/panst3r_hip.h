@@ -457,6 +457,45 @@ int pst_cloud_compact(const pst_cloud_view* views, int nviews, int nwg, float th
 int pst_cloud_segment_median(const float* points_local, const int32_t* pan, const int32_t* m_ptr, int64_t max_points, const int32_t* id2row, int ntab, int nseg,
                              int32_t* hist, uint32_t* prefix, int32_t* rank, int32_t* nan_cnt, int32_t* count, float* median, void* stream);
 
+/* ---------------------------------------------------------------- voxel fusion of the point cloud with multi-view label votes (no counterpart in the reference)
+ * The rows [0, M) of a cloud (points fp32 [M, 3], rgb fp32 [M, 3], pan int32 [M], index int64 [M]) fused on a grid of cubic cells; restated in
+ * tests/voxel_ref.py [restated, parity unpinned].  Every step is exact, so the outputs are held to the restatement bit for bit:
+ *   1 cell      inv = fp32(1 / fp64(voxel_size)) (host); per axis t = p * inv (fp32, rounded on its own), c = floor(t).  A point with a non-finite
+ *               coordinate or |c| >= 2^20 on any axis is left out and counted.
+ *   2 position  q = int(floor((t - c) * 65536)) (fp32: the difference is ONE rounded operation - exact for t >= 0, correctly rounded for t < 0, where it
+ *               reaches 1, q = 65536, for a tiny negative t - and the product is exact; 0 <= q <= 65536);
+ *               per voxel the q of each axis are summed as 64-bit integers;
+ *               pos = fp32((fp64(c) + fp64(sum) / fp64(count) * 2^-16) * fp64(voxel_size)), every fp64 operation rounded on its own.
+ *   3 colour    u = floor(clamp(rgb, 0, 1) * 255 + 0.5) in fp32 (a NaN counts as 0), summed as integers; mean = fp32(fp64(sum) / fp64(count) / 255.0);
+ *               colour = w1 * mean + w2 * colors[pan] (two rounded fp32 products, one rounded sum; black for void and ids >= ncolors).
+ *   4 vote      every point votes for its pan id; ids <= 0, ids >= ntab and ids with id2row[id] < 0 are void.  The winner is the non-void id with the
+ *               most votes, ties to the smallest id; a voxel with only void votes gets id 0 and votes = its count.
+ *   5 order     voxels in increasing order of their smallest member row.
+ * Only integer atomics touch shared state: two calls return identical bytes.  M <= 2^30 - 1; capacity = a power of two >= 2 M (<= 2^31), shared by the
+ * two open-addressing tables; every probe loop is bounded by it, and a full table sets status[0] instead of spinning (the caller reads it and raises).
+ * `merge` != 0 merges runs of adjacent lanes with one key inside a wave before the global atomics (same results).  Workspaces set by the caller:
+ *   keys, pair_keys uint64 [capacity] = all ones; first int32 [capacity] = INT32_MAX; pair_cnt int32 [capacity], cnt int32 [M], sums uint64 [M, 6],
+ *   best uint64 [M], status int32 [2] = 0.  Not initialised: point_slot int32 [M], slot_rank int32 [capacity], first_row int32 [M].
+ *   voxel_insert      -> point_slot[i] = the table slot of point i's cell (-1: left out), first[slot] = the smallest member row, status[1] += left out
+ *   voxel_count       counts[wg] = number of first points among the workgroup's 1024 rows; pst_cloud_scan of it gives base, base[n] = Mv
+ *   voxel_rank        -> slot_rank[slot] = the voxel's output row, first_row[row] = its first point
+ *   voxel_accumulate  -> cnt[row], sums[row] = (sum qx, qy, qz, sum r, g, b), the vote counts of the pairs (row << 32 | id) in pair_keys / pair_cnt,
+ *                     point_voxel int32 [M] = the output row of every point (-1: left out)
+ *   voxel_vote        -> best[row] = max over the voxel's pairs of (votes << 32) | (0xFFFFFFFF - id); 0 = no non-void vote
+ *   voxel_emit        rows [0, *mv_ptr) of points, rgb, colors fp32 [., 3], pan, votes int32 [.], first_index int64 [.] (index of the first point);
+ *                     count is cnt itself.  max_voxels >= Mv sizes the grid; every output holds M rows. */
+int pst_voxel_insert(const float* points, int64_t M, float inv, uint64_t* keys, int64_t capacity, int32_t* first, int32_t* point_slot, int32_t* status,
+                     int merge, void* stream);
+int pst_voxel_count(const int32_t* point_slot, const int32_t* first, int64_t M, int32_t* counts, void* stream);
+int pst_voxel_rank(const int32_t* point_slot, const int32_t* first, int64_t M, const int32_t* base, int32_t* slot_rank, int32_t* first_row, void* stream);
+int pst_voxel_accumulate(const float* points, const float* rgb, const int32_t* pan, int64_t M, float inv, const int32_t* point_slot,
+                         const int32_t* slot_rank, const int32_t* id2row, int ntab, int32_t* cnt, uint64_t* sums, uint64_t* pair_keys, int32_t* pair_cnt,
+                         int64_t capacity, int32_t* point_voxel, int32_t* status, int merge, void* stream);
+int pst_voxel_vote(const uint64_t* pair_keys, const int32_t* pair_cnt, int64_t capacity, uint64_t* best, void* stream);
+int pst_voxel_emit(const float* points, const int64_t* index, const int32_t* first_row, const int32_t* mv_ptr, int64_t max_voxels, float inv,
+                   double voxel_size, const int32_t* cnt, const uint64_t* sums, const uint64_t* best, const float* colors, int ncolors, float w1, float w2,
+                   float* out_points, float* out_rgb, int32_t* out_pan, float* out_colors, int32_t* out_votes, int64_t* out_first, void* stream);
+
 /* ---------------------------------------------------------------- QUBO mask selection on the device (reference engine/postprocess.py:262-336: numpy on the host)
  * Minimises E(x) = x^T W x + lambda_reg * mean(x), x in {0,1}^N, by `replicas` independent simulated anneals run at once (the reference's moves,
  * acceptance rule and geometric schedule; it runs 20 restarts one after the other) and returns the best.  W fp32 [N, N] row-major, symmetric (the -W

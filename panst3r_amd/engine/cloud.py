@@ -102,6 +102,11 @@ class PanopticCloud:
         """the demo's opacity slider, and a new colour table"""
         return self._again(min_conf_thr=self.min_conf_thr, opacity=self.opacity if opacity is None else opacity, colors=colors)
 
+    def voxelize(self, voxel_size, **kw):
+        """engine.voxels.voxelize_cloud of this cloud"""
+        from .voxels import voxelize_cloud
+        return voxelize_cloud(self, voxel_size, **kw)
+
     def cpu(self):
         f = lambda t: t.cpu()
         return PanopticCloud(f(self.points), f(self.points_local), f(self.rgb), f(self.pan), f(self.colors), f(self.index), list(self.view_offsets),

@@ -1,0 +1,164 @@
+"""Voxel fusion of a scene's panoptic point cloud on the device: the cloud of `panoptic_point_cloud` concatenates every view's kept pixels, so a
+surface seen by eight views is in it eight times with eight independent 2-D label decisions.  `voxelize_cloud` downsamples it on a grid of cubic
+cells and lets the points of a cell vote on its panoptic id: one point per occupied cell (mean position, mean colour, voted id, agreement), the cell
+of every cloud point, and - projected back - per-view panoptic maps that agree across views.
+
+The reference has no such stage (its viewer shows the raw concatenation): *restated, unpinned*, like the cloud.  tests/voxel_ref.py restates the
+five steps of the contract in include/panst3r_hip.h in numpy; csrc/voxel.hip is held to it bit for bit (integer sums, separately rounded fp32 /
+fp64 operations, integer atomics only)."""
+import math
+
+import numpy as np
+import torch
+
+from .. import hip
+from .cloud import default_colors, ply_colors_u8
+
+
+class VoxelCloud:
+    """For the Mv occupied voxels, ordered by each voxel's first point in cloud order: points [Mv,3] (mean position), rgb [Mv,3] (mean colour), pan [Mv]
+    int32 (voted id), colors [Mv,3], count [Mv] int32 (points of the voxel), votes [Mv] int32 (points that voted for the winner), first_index [Mv] int64
+    (scene index of the voxel's first point); point_voxel [M] int32 (voxel row of every cloud point, -1 for a point left out); segments as the cloud's
+    ('count' = voxels, 'median' over voxel positions); cameras, view_offsets as the cloud's; voxel_size; dropped (points left out)."""
+
+    def __init__(self, points, rgb, pan, colors, count, votes, first_index, point_voxel, segments, cameras, view_offsets, voxel_size, dropped, opacity=None,
+                 point_pan=None, point_index=None, source=None):
+        self.points, self.rgb, self.pan, self.colors, self.count, self.votes, self.first_index = points, rgb, pan, colors, count, votes, first_index
+        self.point_voxel, self.segments, self.cameras, self.view_offsets = point_voxel, segments, cameras, view_offsets
+        self.voxel_size, self.dropped, self.opacity = voxel_size, dropped, opacity
+        self._point_pan, self._point_index, self._source = point_pan, point_index, source
+
+    def __len__(self):
+        return int(self.pan.shape[0])
+
+    def cpu(self):
+        f = lambda t: None if t is None else t.cpu()
+        return VoxelCloud(f(self.points), f(self.rgb), f(self.pan), f(self.colors), f(self.count), f(self.votes), f(self.first_index), f(self.point_voxel),
+                          [dict(s) for s in self.segments], self.cameras, list(self.view_offsets), self.voxel_size, self.dropped, self.opacity,
+                          f(self._point_pan), f(self._point_index))
+
+    def write_ply(self, path):
+        """binary little-endian PLY: the cloud's row (x y z float, red green blue uchar of `colors`, label int) plus `int count`.  The 23-byte rows are
+        packed where the voxels live: one device-to-host copy."""
+        M = len(self)
+        rows = torch.empty(M, 23, dtype=torch.uint8, device=self.pan.device)
+        rows[:, 0:12] = self.points.contiguous().view(torch.uint8).reshape(M, 12)
+        rows[:, 12:15] = ply_colors_u8(self.colors)
+        rows[:, 15:19] = self.pan.contiguous().view(torch.uint8).reshape(M, 4)
+        rows[:, 19:23] = self.count.contiguous().view(torch.uint8).reshape(M, 4)
+        header = ('ply\nformat binary_little_endian 1.0\ncomment panst3r_amd voxel cloud, voxel_size %r\nelement vertex %d\nproperty float x\nproperty float y\n'
+                  'property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nproperty int label\nproperty int count\nend_header\n'
+                  % (self.voxel_size, M))
+        with open(path, 'wb') as f:
+            f.write(header.encode('ascii'))
+            f.write(rows.cpu().numpy().tobytes())
+        return path
+
+    def point_labels(self):
+        """[M] int32: the voted label of every cloud point; a point left out keeps its own"""
+        if self._point_pan is None:
+            raise RuntimeError('this voxel cloud does not hold the labels of its points (it was built by hand)')
+        pv = self.point_voxel.long()
+        if len(self) == 0:
+            return self._point_pan.clone()
+        return torch.where(pv >= 0, self.pan[pv.clamp(min=0)], self._point_pan)
+
+    def consistent_maps(self):
+        """list over views of int32 [H, W]: a kept pixel gets its voxel's voted id, a pixel below the confidence threshold keeps its 2-D id"""
+        if self._source is None:
+            raise RuntimeError('this cloud does not hold its device inputs (it was moved to the CPU or built by hand)')
+        flat = torch.cat([v[4].reshape(-1) for v in self._source.views])
+        flat[self._point_index] = self.point_labels()
+        off = self.view_offsets
+        return [flat[off[v]:off[v + 1]].reshape(self._source.shapes[v]) for v in range(len(off) - 1)]
+
+
+def _check_voxel_size(voxel_size):
+    vs = float(voxel_size)
+    if not (math.isfinite(vs) and vs > 0):
+        raise ValueError('voxel_size must be a positive finite number, got %r' % (voxel_size,))
+    with np.errstate(over='ignore'):
+        inv = float(np.float32(1.0 / vs))
+    if not (math.isfinite(inv) and inv > 0):
+        raise ValueError('voxel_size %r has no positive finite float32 inverse' % (voxel_size,))
+    return vs, inv
+
+
+def check_status(status):
+    """the device status word of one fusion, as it arrives with the result copy: non-zero = an open-addressing table ran full (a kernel gave up instead
+    of spinning) and the outputs are not complete"""
+    if int(status) != 0:
+        raise RuntimeError('voxelize_cloud: an open-addressing table ran full on the device (status %d); no result' % int(status))
+
+
+@torch.no_grad()
+def voxelize_cloud(cloud, voxel_size, *, colors=None, opacity=None):
+    """Fuse a device `PanopticCloud` on a grid of cubic cells of edge `voxel_size` (the unit of `cloud.points`) -> `VoxelCloud`.  Per occupied cell:
+    mean position and colour of its points, the panoptic id most of them carry (ties to the smallest id; void - ids <= 0 or not among the cloud's
+    segments - only wins alone), colour = (1 - opacity) * rgb + opacity * colors[pan] with the cloud's table and opacity unless given.  A point with a
+    non-finite coordinate or a cell index beyond +-2^20 is left out and counted in `dropped`.  Voxels come in the order of their first points.
+    One host sync.  GPU only: a CPU cloud raises."""
+    vs, inv = _check_voxel_size(voxel_size)
+    for t in (cloud.points, cloud.rgb, cloud.pan, cloud.index):
+        if not t.is_cuda:
+            raise RuntimeError('voxelize_cloud got a %s tensor: it runs on the GPU only (no CPU fallback)' % t.device)
+    dev = cloud.pan.device
+    M = len(cloud)
+    src = cloud._source
+    infos = cloud.segments
+    ids = [int(s['id']) for s in infos]
+    ntab = max(ids + [0]) + 1
+    if colors is None:
+        colors = src.colors if src is not None else default_colors(max(ntab, 2))
+    ctab = torch.as_tensor(colors, dtype=torch.float32).reshape(-1, 3).to(dev).contiguous()
+    if not 1 <= ctab.shape[0] <= hip.CLOUD_MAX_COLORS:
+        raise ValueError('the colour table must have 1 .. %d rows, got %d' % (hip.CLOUD_MAX_COLORS, ctab.shape[0]))
+    if ids and max(ids) >= ctab.shape[0]:
+        raise ValueError('segment id %d does not fit the colour table of %d rows' % (max(ids), ctab.shape[0]))
+    if opacity is None:
+        opacity = 0.5 if cloud.opacity is None else cloud.opacity
+    w1, w2 = float(np.float32(1.0 - float(opacity))), float(np.float32(float(opacity)))
+    f3 = lambda n: torch.empty(n, 3, dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    common = dict(cameras=cloud.cameras, view_offsets=list(cloud.view_offsets), voxel_size=vs, opacity=float(opacity), point_pan=cloud.pan,
+                  point_index=cloud.index, source=src)
+    if M == 0:
+        return VoxelCloud(f3(0), f3(0), torch.empty(0, **i32), f3(0), torch.empty(0, **i32), torch.empty(0, **i32), torch.empty(0, dtype=torch.int64, device=dev),
+                          torch.empty(0, **i32), [], dropped=0, **common)
+    row = np.full(ntab, -1, dtype=np.int32)
+    for r, i in enumerate(ids):
+        row[i] = r
+    id2row = torch.from_numpy(row).to(dev)
+    points, rgb, pan, index = cloud.points.float().contiguous(), cloud.rgb.float().contiguous(), cloud.pan.to(torch.int32).contiguous(), cloud.index.contiguous()
+    ws = hip.voxel_workspace(M, dev)
+    nwg = (M + hip.CLOUD_WG - 1) // hip.CLOUD_WG
+    counts, base = torch.empty(nwg, **i32), torch.empty(nwg + 1, **i32)
+    point_voxel = torch.empty(M, **i32)
+    out_points, out_rgb, out_colors = f3(M), f3(M), f3(M)
+    out_pan, out_votes, out_first = torch.empty(M, **i32), torch.empty(M, **i32), torch.empty(M, dtype=torch.int64, device=dev)
+    hip.voxel_insert(points, inv, ws)
+    hip.voxel_count(ws, counts)
+    hip.cloud_scan(counts, base)
+    hip.voxel_rank(ws, base)
+    hip.voxel_accumulate(points, rgb, pan, inv, id2row, ws, point_voxel)
+    hip.voxel_vote(ws)
+    mv = base[nwg:]
+    hip.voxel_emit(points, index, mv, inv, vs, ws, ctab, w1, w2, out_points, out_rgb, out_pan, out_colors, out_votes, out_first)
+    res = torch.cat([mv, ws['status']])
+    S = len(infos)
+    if S:
+        count = torch.empty(S, **i32)
+        median = torch.empty(S, 3, dtype=torch.float32, device=dev)
+        hip.cloud_segment_median(out_points, out_pan, mv, id2row, S, count, median)      # the cloud's median, over voxel positions
+        res = torch.cat([res, count, median.view(torch.int32).reshape(-1)])
+    res = res.cpu().numpy()                                                  # the only host sync: Mv, the status words, the segment table
+    check_status(res[1])
+    Mv, dropped = int(res[0]), int(res[2])
+    segments = []
+    if S:
+        med = res[3 + S:].view(np.float32).reshape(S, 3)
+        for r, s in enumerate(infos):
+            if res[3 + r] > 0:
+                segments.append({'id': s['id'], 'query_id': s.get('query_id'), 'category_id': s.get('category_id'), 'count': int(res[3 + r]), 'median': med[r].copy()})
+    return VoxelCloud(out_points[:Mv], out_rgb[:Mv], out_pan[:Mv], out_colors[:Mv], ws['cnt'][:Mv], out_votes[:Mv], out_first[:Mv], point_voxel, segments,
+                      dropped=dropped, **common)

@@ -67,6 +67,8 @@ SIGNATURES = {
     'pst_retrieval_assign': 'i:plplpiiiiippppip', 'pst_retrieval_aggregate': 'i:plplpppiippp', 'pst_retrieval_scores': 'i:ppppppiiiiffpp',
     'pst_cloud_count': 'i:piifpp', 'pst_cloud_scan': 'i:pipp', 'pst_cloud_compact': 'i:piifppiffppppppp', 'pst_cloud_segment_median': 'i:ppplpiippppppp',
     'pst_qubo_anneal_max_n': 'i:', 'pst_qubo_anneal': 'i:piiifffuppppp',
+    'pst_voxel_insert': 'i:plfplpppip', 'pst_voxel_count': 'i:pplpp', 'pst_voxel_rank': 'i:pplpppp', 'pst_voxel_accumulate': 'i:ppplfpppipppplppip',
+    'pst_voxel_vote': 'i:pplpp', 'pst_voxel_emit': 'i:pppplfdppppiffppppppp',
 }
 EXPORTS = list(SIGNATURES)
 
@@ -1204,3 +1206,72 @@ def qubo_anneal(W, replicas, num_iters, T0, T_end, lambda_reg, seed, x_all, e_al
     assert x_all.numel() == replicas * N and e_all.numel() == replicas and best_x.numel() == N and best_e.numel() == 1
     _call('pst_qubo_anneal', _ptr(W), N, int(replicas), int(num_iters), float(T0), float(T_end), float(lambda_reg), int(seed) & (2 ** 64 - 1), _ptr(x_all),
           _ptr(e_all), _ptr(best_x), _ptr(best_e))
+
+
+# ------------------------------------------------------------------ voxel fusion of the point cloud (csrc/voxel.hip; engine/voxels.py holds the public entry point)
+VOXEL_MERGE = 1            # merge runs of equal keys inside a wave before the global atomics (A/B: tools/voxel_bench.py, docs/experiments.md)
+
+
+def voxel_capacity(M):
+    """slots of the two open-addressing tables: the next power of two >= 2 M"""
+    return 1 << max(1, (2 * int(M) - 1).bit_length())
+
+
+def voxel_workspace(M, device):
+    """the initialised workspaces of one fusion of M points (include/panst3r_hip.h): dict of device tensors"""
+    cap = voxel_capacity(M)
+    i32 = dict(dtype=torch.int32, device=device)
+    i64 = dict(dtype=torch.int64, device=device)
+    return {'cap': cap, 'keys': torch.full((cap,), -1, **i64), 'first': torch.full((cap,), 2 ** 31 - 1, **i32), 'slot_rank': torch.empty(cap, **i32),
+            'point_slot': torch.empty(M, **i32), 'first_row': torch.empty(M, **i32), 'cnt': torch.zeros(M, **i32), 'sums': torch.zeros(M, 6, **i64),
+            'pair_keys': torch.full((cap,), -1, **i64), 'pair_cnt': torch.zeros(cap, **i32), 'best': torch.zeros(M, **i64), 'status': torch.zeros(2, **i32)}
+
+
+def voxel_insert(points, inv, ws, merge=None):
+    _dev(points, torch.float32)
+    M = points.shape[0]
+    assert points.is_contiguous() and points.dim() == 2 and points.shape[1] == 3 and ws['point_slot'].numel() == M and ws['keys'].numel() == ws['cap']
+    _call('pst_voxel_insert', _ptr(points), M, float(inv), _ptr(ws['keys']), ws['cap'], _ptr(ws['first']), _ptr(ws['point_slot']), _ptr(ws['status']),
+          int(VOXEL_MERGE if merge is None else merge))
+
+
+def voxel_count(ws, counts):
+    _dev(counts, torch.int32)
+    M = ws['point_slot'].numel()
+    assert counts.numel() == (M + CLOUD_WG - 1) // CLOUD_WG
+    _call('pst_voxel_count', _ptr(ws['point_slot']), _ptr(ws['first']), M, _ptr(counts))
+
+
+def voxel_rank(ws, base):
+    _dev(base, torch.int32)
+    M = ws['point_slot'].numel()
+    assert base.numel() == (M + CLOUD_WG - 1) // CLOUD_WG + 1
+    _call('pst_voxel_rank', _ptr(ws['point_slot']), _ptr(ws['first']), M, _ptr(base), _ptr(ws['slot_rank']), _ptr(ws['first_row']))
+
+
+def voxel_accumulate(points, rgb, pan, inv, id2row, ws, point_voxel, merge=None):
+    _dev(points, torch.float32); _dev(rgb, torch.float32); _dev(pan, torch.int32); _dev(id2row, torch.int32); _dev(point_voxel, torch.int32)
+    M = pan.numel()
+    assert points.is_contiguous() and rgb.is_contiguous() and points.numel() == 3 * M and rgb.numel() == 3 * M and point_voxel.numel() == M
+    assert ws['point_slot'].numel() == M and pan.is_contiguous() and id2row.is_contiguous()
+    _call('pst_voxel_accumulate', _ptr(points), _ptr(rgb), _ptr(pan), M, float(inv), _ptr(ws['point_slot']), _ptr(ws['slot_rank']), _ptr(id2row), id2row.numel(),
+          _ptr(ws['cnt']), _ptr(ws['sums']), _ptr(ws['pair_keys']), _ptr(ws['pair_cnt']), ws['cap'], _ptr(point_voxel), _ptr(ws['status']),
+          int(VOXEL_MERGE if merge is None else merge))
+
+
+def voxel_vote(ws):
+    _call('pst_voxel_vote', _ptr(ws['pair_keys']), _ptr(ws['pair_cnt']), ws['cap'], _ptr(ws['best']))
+
+
+def voxel_emit(points, index, mv_ptr, inv, voxel_size, ws, colors, w1, w2, out_points, out_rgb, out_pan, out_colors, out_votes, out_first):
+    _dev(points, torch.float32); _dev(index, torch.int64); _dev(mv_ptr, torch.int32); _dev(colors, torch.float32); _dev(out_pan, torch.int32)
+    _dev(out_votes, torch.int32); _dev(out_first, torch.int64)
+    M = index.numel()
+    for t in (out_points, out_rgb, out_colors):
+        _dev(t, torch.float32)
+        assert t.is_contiguous() and t.numel() == 3 * M
+    assert points.is_contiguous() and index.is_contiguous() and colors.is_contiguous() and colors.shape[1] == 3 and ws['first_row'].numel() == M
+    assert out_pan.numel() == M and out_votes.numel() == M and out_first.numel() == M
+    _call('pst_voxel_emit', _ptr(points), _ptr(index), _ptr(ws['first_row']), _ptr(mv_ptr), M, float(inv), float(voxel_size), _ptr(ws['cnt']), _ptr(ws['sums']),
+          _ptr(ws['best']), _ptr(colors), colors.shape[0], float(w1), float(w2), _ptr(out_points), _ptr(out_rgb), _ptr(out_pan), _ptr(out_colors), _ptr(out_votes),
+          _ptr(out_first))

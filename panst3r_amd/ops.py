@@ -291,6 +291,43 @@ def cloud_segment_median(points_local: Tensor, pan: Tensor, m_ptr: Tensor, id2ro
     hip.cloud_segment_median(points_local, pan, m_ptr, id2row, nseg, count, median)
 
 
+# voxel fusion (csrc/voxel.hip): the workspaces of hip.voxel_workspace as separate tensors
+@_op('voxel_insert', ('keys', 'first', 'point_slot', 'status'))
+def voxel_insert(points: Tensor, inv: float, keys: Tensor, first: Tensor, point_slot: Tensor, status: Tensor, merge: int = 1) -> None:
+    hip.voxel_insert(points, inv, {'cap': keys.numel(), 'keys': keys, 'first': first, 'point_slot': point_slot, 'status': status}, merge)
+
+
+@_op('voxel_count', ('counts',))
+def voxel_count(point_slot: Tensor, first: Tensor, counts: Tensor) -> None:
+    hip.voxel_count({'point_slot': point_slot, 'first': first}, counts)
+
+
+@_op('voxel_rank', ('slot_rank', 'first_row'))
+def voxel_rank(point_slot: Tensor, first: Tensor, base: Tensor, slot_rank: Tensor, first_row: Tensor) -> None:
+    hip.voxel_rank({'point_slot': point_slot, 'first': first, 'slot_rank': slot_rank, 'first_row': first_row}, base)
+
+
+@_op('voxel_accumulate', ('cnt', 'sums', 'pair_keys', 'pair_cnt', 'point_voxel', 'status'))
+def voxel_accumulate(points: Tensor, rgb: Tensor, pan: Tensor, inv: float, id2row: Tensor, point_slot: Tensor, slot_rank: Tensor, cnt: Tensor, sums: Tensor,
+                     pair_keys: Tensor, pair_cnt: Tensor, point_voxel: Tensor, status: Tensor, merge: int = 1) -> None:
+    ws = {'cap': pair_keys.numel(), 'point_slot': point_slot, 'slot_rank': slot_rank, 'cnt': cnt, 'sums': sums, 'pair_keys': pair_keys, 'pair_cnt': pair_cnt,
+          'status': status}
+    hip.voxel_accumulate(points, rgb, pan, inv, id2row, ws, point_voxel, merge)
+
+
+@_op('voxel_vote', ('best',))
+def voxel_vote(pair_keys: Tensor, pair_cnt: Tensor, best: Tensor) -> None:
+    hip.voxel_vote({'cap': pair_keys.numel(), 'pair_keys': pair_keys, 'pair_cnt': pair_cnt, 'best': best})
+
+
+@_op('voxel_emit', ('out_points', 'out_rgb', 'out_pan', 'out_colors', 'out_votes', 'out_first'))
+def voxel_emit(points: Tensor, index: Tensor, first_row: Tensor, mv_ptr: Tensor, inv: float, voxel_size: float, cnt: Tensor, sums: Tensor, best: Tensor,
+               colors: Tensor, w1: float, w2: float, out_points: Tensor, out_rgb: Tensor, out_pan: Tensor, out_colors: Tensor, out_votes: Tensor,
+               out_first: Tensor) -> None:
+    hip.voxel_emit(points, index, mv_ptr, inv, voxel_size, {'first_row': first_row, 'cnt': cnt, 'sums': sums, 'best': best}, colors, w1, w2, out_points, out_rgb,
+                   out_pan, out_colors, out_votes, out_first)
+
+
 def registered_ops():
     """names under torch.ops.panst3r_hip"""
     return list(_REGISTERED)

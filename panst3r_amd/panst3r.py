@@ -362,13 +362,16 @@ class PanSt3R(nn.Module):
                 amp, panoptic_precision = nxt
 
     @torch.no_grad()
-    def reconstruct(self, imgs, true_shape, classes, *, postprocess='standard_v2', min_conf_thr=3.0, opacity=0.5, postprocess_kwargs=None, **forward_kwargs):
+    def reconstruct(self, imgs, true_shape, classes, *, postprocess='standard_v2', min_conf_thr=3.0, opacity=0.5, postprocess_kwargs=None, voxel_size=None,
+                    **forward_kwargs):
         """The body of the demo's `get_reconstructed_scene` (tools/demo_panst3r.py:232-300) in one call, everything on the device:
         forward_inference_multi_ar (outputs left where they are), the chosen panoptic post-processing ('standard_v2' | 'standard_v1' | 'qubo'),
         the cameras of the pointmaps and the panoptic point cloud.  `postprocess_kwargs`: thresholds of the chosen post-processing other than its
         defaults (the demo uses the defaults); with postprocess='qubo', {'solver': 'device'} runs the annealer on the GPU as well (`replicas`, `seed`;
         engine.solve_qubo_device) instead of the reference's host annealer.  Returns (cloud, cameras, pan_preds): a `PanopticCloud`, the camera frusta
-        (each with its 'focal' and 'cam2world') and the post-processing result.  It only composes the public entry points."""
+        (each with its 'focal' and 'cam2world') and the post-processing result.  With `voxel_size` (a number, the unit of the pointmaps) the cloud is also
+        fused on a voxel grid with multi-view label votes (engine.voxelize_cloud) and the return value is (cloud, cameras, pan_preds, voxels).
+        It only composes the public entry points."""
         from .engine import panoptic_inference_v2, panoptic_inference_v1, panoptic_inference_qubo, panoptic_point_cloud
         from .engine.pointmaps import cameras_from_pointmaps
         fns = {'standard_v2': panoptic_inference_v2, 'standard_v1': panoptic_inference_v1, 'qubo': panoptic_inference_qubo}
@@ -376,6 +379,9 @@ class PanSt3R(nn.Module):
             raise ValueError('did not recognize postprocess=%r (one of %s)' % (postprocess, sorted(fns)))
         if forward_kwargs.get('outdevice') is not None:
             raise ValueError('reconstruct keeps the outputs on the device: outdevice is not an argument of it')
+        if voxel_size is not None:
+            from .engine.voxels import _check_voxel_size
+            _check_voxel_size(voxel_size)                       # a bad size raises before the forward pass, not after it
         pms, panout = self.forward_inference_multi_ar(imgs, true_shape, classes, **forward_kwargs)
         pan_preds = fns[postprocess](panout['pred_logits'], panout['pred_masks'], true_shape, label_mode=self.panoptic_decoder.label_mode, multi_ar=True,
                                     **(postprocess_kwargs or {}))
@@ -384,6 +390,8 @@ class PanSt3R(nn.Module):
         cloud = panoptic_point_cloud(x_out, [i.to(dev) for i in imgs], true_shape, pan_preds[0]['pan'], pan_preds[0]['segments_info'], cams2world, focals,
                                      min_conf_thr=min_conf_thr, opacity=opacity)
         cameras = [dict(c, cam2world=c2w) for c, c2w in zip(cloud.cameras, cams2world)]
+        if voxel_size is not None:
+            return cloud, cameras, pan_preds, cloud.voxelize(voxel_size)
         return cloud, cameras, pan_preds
 
     @torch.no_grad()
