@@ -496,6 +496,36 @@ int pst_voxel_emit(const float* points, const int64_t* index, const int32_t* fir
                    double voxel_size, const int32_t* cnt, const uint64_t* sums, const uint64_t* best, const float* colors, int ncolors, float w1, float w2,
                    float* out_points, float* out_rgb, int32_t* out_pan, float* out_colors, int32_t* out_votes, int64_t* out_first, void* stream);
 
+/* ---------------------------------------------------------------- z-buffered point rendering of the cloud from any camera (no counterpart in the reference)
+ * The rows [0, M) of a cloud (points fp32 [M, 3] in the world frame, rgb, colors fp32 [M, 3], pan int32 [M]; a panoptic cloud or a voxel cloud) seen
+ * from B pinhole cameras at one output shape (H, W) -> per pixel the nearest point.  The reference's demo hands the cloud to an interactive viewer and has
+ * no such stage; restated in tests/render_ref.py [restated, parity unpinned].  Every step is exact, so the outputs are held to it bit for bit.  Every
+ * fp32 product and sum is rounded on its own, in the order written (contraction off):
+ *   1 camera    host, float64: with the camera-to-world matrix [R | t], W = R^T and s_a = -((R_0a t_0 + R_1a t_1) + R_2a t_2), each rounded to fp32.  The
+ *               device table is float [B, 16] per camera: W00 W01 W02 s0 W10 W11 W12 s1 W20 W21 W22 s2 f cx cy near (f = the focal length in pixels,
+ *               (cx, cy) = the principal point, near > 0).  Device: xc = ((W00 x + W01 y) + W02 z) + s0, likewise yc, zc.
+ *   2 cull      a point is left out if xc, yc or zc is not finite, or zc < near.
+ *   3 project   u = (f xc) / zc + cx, v = (f yc) / zc + cy; px = floor(u), py = floor(v): pixel (i, j) covers [j, j+1) x [i, i+1).  A point whose u or
+ *               v is not finite or beyond +-2^20 is left out.
+ *               THE QUOTIENT is taken in fp64 - fp32(fp64(f xc) / fp64(zc)) - and rounded once, like the voxel contract's fp64 operations.  (For fp32
+ *               operands that equals the correctly rounded fp32 quotient, which is what numpy's float32 division gives.)
+ *   4 footprint the point covers the (2r + 1)^2 pixels around (px, py), clipped to the image: r = min(max_radius, max(radius, floor((f half_size) / zc))),
+ *               the same quotient; half_size >= 0 is fp32(point_size / 2) in world units, rounded on the host.
+ *               0 <= radius, max_radius <= PST_RENDER_MAX_RADIUS (pst_render_max_radius()).
+ *   5 depth     key = (uint64(bits(zc)) << 32) | uint32(row): zc > 0, so its bit pattern orders as an unsigned integer.  64-bit atomicMin of the key
+ *               into zbuf uint64 [B, H, W], which the CALLER clears to all ones: the nearest point wins, equal depths go to the smallest row.  Integer
+ *               atomics only: the result does not depend on scheduling.  `precheck` != 0 reads the cell first (relaxed) and skips an atomic that
+ *               cannot win (same results).
+ *   6 resolve   per pixel of zbuf (npix = B H W): an empty cell gives index -1, depth 0, pan 0, rgb = colors = 0; otherwise index int64 = the winning row,
+ *               depth fp32 = its zc, and pan int32, rgb, colors fp32 [., 3] are that row's.  Plain vector stores.
+ * 1 <= M <= 2^32 - 1 (the row is 32 bits of the key), 1 <= B <= 65535, B H W <= 2^31 - 1.  Nothing can fail on the device: there is no status word. */
+#define PST_RENDER_MAX_RADIUS 16
+int pst_render_max_radius(void);
+int pst_render_splat(const float* points, int64_t M, const float* cams, int ncams, int H, int W, float half_size, int radius, int max_radius, uint64_t* zbuf,
+                     int precheck, void* stream);
+int pst_render_resolve(const uint64_t* zbuf, int64_t npix, int64_t M, const float* rgb, const float* colors, const int32_t* pan, int64_t* index, float* depth,
+                       int32_t* out_pan, float* out_rgb, float* out_colors, void* stream);
+
 /* ---------------------------------------------------------------- QUBO mask selection on the device (reference engine/postprocess.py:262-336: numpy on the host)
  * Minimises E(x) = x^T W x + lambda_reg * mean(x), x in {0,1}^N, by `replicas` independent simulated anneals run at once (the reference's moves,
  * acceptance rule and geometric schedule; it runs 20 restarts one after the other) and returns the best.  W fp32 [N, N] row-major, symmetric (the -W

@@ -107,6 +107,11 @@ class PanopticCloud:
         from .voxels import voxelize_cloud
         return voxelize_cloud(self, voxel_size, **kw)
 
+    def render(self, cams2world, focals, shape, **kw):
+        """engine.render.render_cloud of this cloud"""
+        from .render import render_cloud
+        return render_cloud(self, cams2world, focals, shape, **kw)
+
     def cpu(self):
         f = lambda t: t.cpu()
         return PanopticCloud(f(self.points), f(self.points_local), f(self.rgb), f(self.pan), f(self.colors), f(self.index), list(self.view_offsets),

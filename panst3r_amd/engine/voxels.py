@@ -54,6 +54,11 @@ class VoxelCloud:
             f.write(rows.cpu().numpy().tobytes())
         return path
 
+    def render(self, cams2world, focals, shape, **kw):
+        """engine.render.render_cloud of the voxels; the default point_size is voxel_size, so that neighbouring voxels close up"""
+        from .render import render_cloud
+        return render_cloud(self, cams2world, focals, shape, **kw)
+
     def point_labels(self):
         """[M] int32: the voted label of every cloud point; a point left out keeps its own"""
         if self._point_pan is None:

@@ -69,6 +69,7 @@ SIGNATURES = {
     'pst_qubo_anneal_max_n': 'i:', 'pst_qubo_anneal': 'i:piiifffuppppp',
     'pst_voxel_insert': 'i:plfplpppip', 'pst_voxel_count': 'i:pplpp', 'pst_voxel_rank': 'i:pplpppp', 'pst_voxel_accumulate': 'i:ppplfpppipppplppip',
     'pst_voxel_vote': 'i:pplpp', 'pst_voxel_emit': 'i:pppplfdppppiffppppppp',
+    'pst_render_max_radius': 'i:', 'pst_render_splat': 'i:plpiiifiipip', 'pst_render_resolve': 'i:pllppppppppp',
 }
 EXPORTS = list(SIGNATURES)
 
@@ -1275,3 +1276,35 @@ def voxel_emit(points, index, mv_ptr, inv, voxel_size, ws, colors, w1, w2, out_p
     _call('pst_voxel_emit', _ptr(points), _ptr(index), _ptr(ws['first_row']), _ptr(mv_ptr), M, float(inv), float(voxel_size), _ptr(ws['cnt']), _ptr(ws['sums']),
           _ptr(ws['best']), _ptr(colors), colors.shape[0], float(w1), float(w2), _ptr(out_points), _ptr(out_rgb), _ptr(out_pan), _ptr(out_colors), _ptr(out_votes),
           _ptr(out_first))
+
+
+# ------------------------------------------------------------------ z-buffered rendering of a cloud (csrc/render.hip; engine/render.py holds the public entry points)
+RENDER_PRECHECK = 1        # read the z-buffer cell before the atomic and skip one that cannot win (A/B: tests/diag/render_bench.py, docs/experiments.md)
+RENDER_CAM_FLOATS = 16     # floats per camera of the device table: twelve world-to-camera numbers, f, cx, cy, near
+RENDER_MAX_RADIUS = 16     # PST_RENDER_MAX_RADIUS (pst_render_max_radius() of the built library; tests/test_render_host.py holds the three together)
+
+
+def render_max_radius():
+    """PST_RENDER_MAX_RADIUS: the largest footprint radius the splat kernel takes"""
+    return lib().pst_render_max_radius()
+
+
+def render_splat(points, cams, H, W, half_size, radius, max_radius, zbuf, precheck=None):
+    """atomicMin of every point's key into zbuf int64 [B, H, W] (cleared to all ones by the caller) for the B cameras of cams fp32 [B, 16]"""
+    _dev(points, torch.float32); _dev(cams, torch.float32); _dev(zbuf, torch.int64)
+    B = cams.shape[0]
+    assert points.is_contiguous() and points.dim() == 2 and points.shape[1] == 3 and cams.is_contiguous() and tuple(cams.shape) == (B, RENDER_CAM_FLOATS)
+    assert zbuf.is_contiguous() and tuple(zbuf.shape) == (B, H, W) and cams.device == points.device == zbuf.device
+    _call('pst_render_splat', _ptr(points), points.shape[0], _ptr(cams), B, int(H), int(W), float(half_size), int(radius), int(max_radius), _ptr(zbuf),
+          int(RENDER_PRECHECK if precheck is None else precheck))
+
+
+def render_resolve(zbuf, rgb, colors, pan, index, depth, out_pan, out_rgb, out_colors):
+    """per cell of zbuf: the winner's row, depth, pan, rgb and colours (an empty cell: -1 and zeros)"""
+    _dev(zbuf, torch.int64); _dev(rgb, torch.float32); _dev(colors, torch.float32); _dev(pan, torch.int32)
+    _dev(index, torch.int64); _dev(depth, torch.float32); _dev(out_pan, torch.int32); _dev(out_rgb, torch.float32); _dev(out_colors, torch.float32)
+    n, M = zbuf.numel(), pan.numel()
+    assert all(t.is_contiguous() and t.device == zbuf.device for t in (zbuf, rgb, colors, pan, index, depth, out_pan, out_rgb, out_colors))
+    assert rgb.numel() == 3 * M and colors.numel() == 3 * M and index.numel() == n and depth.numel() == n and out_pan.numel() == n
+    assert out_rgb.numel() == 3 * n and out_colors.numel() == 3 * n
+    _call('pst_render_resolve', _ptr(zbuf), n, M, _ptr(rgb), _ptr(colors), _ptr(pan), _ptr(index), _ptr(depth), _ptr(out_pan), _ptr(out_rgb), _ptr(out_colors))

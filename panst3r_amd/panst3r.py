@@ -371,6 +371,8 @@ class PanSt3R(nn.Module):
         engine.solve_qubo_device) instead of the reference's host annealer.  Returns (cloud, cameras, pan_preds): a `PanopticCloud`, the camera frusta
         (each with its 'focal' and 'cam2world') and the post-processing result.  With `voxel_size` (a number, the unit of the pointmaps) the cloud is also
         fused on a voxel grid with multi-view label votes (engine.voxelize_cloud) and the return value is (cloud, cameras, pan_preds, voxels).
+        Images out of the result: `engine.render_cameras(cloud, cameras)` re-renders the cloud (or the voxels) from the input cameras, and
+        `cloud.render(engine.orbit_cameras(...), focal, (H, W))` from any other - depth, panoptic map and colours per pixel (engine/render.py).
         It only composes the public entry points."""
         from .engine import panoptic_inference_v2, panoptic_inference_v1, panoptic_inference_qubo, panoptic_point_cloud
         from .engine.pointmaps import cameras_from_pointmaps
