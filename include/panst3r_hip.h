@@ -526,6 +526,36 @@ int pst_render_splat(const float* points, int64_t M, const float* cams, int ncam
 int pst_render_resolve(const uint64_t* zbuf, int64_t npix, int64_t M, const float* rgb, const float* colors, const int32_t* pan, int64_t* index, float* depth,
                        int32_t* out_pan, float* out_rgb, float* out_colors, void* stream);
 
+/* ---------------------------------------------------------------- panoptic evaluation against ground truth: PQ / SQ / RQ, mIoU (no counterpart in the reference)
+ * V predicted maps and V ground-truth maps of the same shapes, flattened and concatenated to pred, gt int32 [N] (1 <= N <= 2^31 - 1, both 16-byte
+ * aligned), P predicted and G ground-truth segments (ids unique and > 0 within each list, no crowd regions).  The rules are those of COCO
+ * panopticapi's pq_compute_single_core without iscrowd; restated in tests/eval_ref.py [restated, parity unpinned].  Every step is exact, so the
+ * outputs are held to the restatement bit for bit:
+ *   1 rows      a predicted id i maps to row id2row_p[i] if 0 < i < ntab_p and that entry is in [0, P), else to the VOID ROW P; ground truth maps the
+ *               same way to column id2row_g[i], or to the VOID COLUMN G.  Ids <= 0, ids beyond the table and ids not listed are all void (as
+ *               pst_voxel_accumulate treats them).
+ *   2 slabs     slab s holds the pixels [slab_off[s], slab_off[s + 1]) of the flat maps, slab_off int64 [nslabs + 1] on the device, ascending from 0 to
+ *               N: one slab with every pixel of every view (scope 'scene'), or one slab per view (scope 'view').
+ *   3 counts    counts int32 [nslabs, P+1, G+1], cleared by the CALLER: the number of pixels of slab s with (row p, column g).  int32 atomicAdd only,
+ *               so the result does not depend on scheduling.  nslabs (P+1) (G+1) <= 2^31 - 1.  `merge` != 0 adds runs of equal keys inside a
+ *               wave with one atomic (same results).
+ *   4 areas     pred_area[s,p] = sum_g counts[s,p,g] over all columns, void included (p < P); gt_area[s,g] = sum_p counts[s,p,g] over all rows, void
+ *               included (g < G).  A segment with area 0 in a slab does not exist in that slab.
+ *   5 match     for every g with gt_area > 0 and every p with pred_area > 0 and cat_p[p] == cat_g[g]: inter = counts[s,p,g],
+ *               union = pred_area + gt_area - inter - counts[s,p,G] (the predicted pixels on void ground truth leave the union); the pair matches iff
+ *               2 inter > union, tested in int64 - equality is no match.  Segments of one map are disjoint, so at most one p matches a g and at most
+ *               one g a p.  match int32 [nslabs, G] = the row or -1; iou double [nslabs, G] = (double)inter / (double)union, one IEEE division, or 0.
+ *   6 misses    an existing g without a match is an FN.  An existing p without a match is IGNORED if 2 counts[s,p,G] > pred_area[s,p] (more than half of
+ *               it on void), otherwise an FP.  pred_state int32 [nslabs, P]: 0 absent, 1 matched, 2 FP, 3 ignored.
+ *   7, 8        per-category tp / fp / fn / iou_sum, PQ = iou_sum / (tp + fp / 2 + fn / 2), SQ, RQ, their means, and the semantic mIoU / pixel accuracy
+ *               of the category-merged table are float64 host arithmetic on the copied tables (panst3r_amd/engine/evaluate.py).
+ * Every output of pst_pq_match is written by one thread with plain stores.  cat_p int32 [P], cat_g int32 [G] are device arrays; an operand of P (or G)
+ * rows may be null when P (or G) is 0. */
+int pst_pq_count(const int32_t* pred, const int32_t* gt, int64_t N, const int64_t* slab_off, int nslabs, const int32_t* id2row_p, int ntab_p,
+                 const int32_t* id2row_g, int ntab_g, int P, int G, int32_t* counts, int merge, void* stream);
+int pst_pq_match(const int32_t* counts, int nslabs, int P, int G, const int32_t* cat_p, const int32_t* cat_g, int32_t* pred_area, int32_t* gt_area,
+                 int32_t* match, double* iou, int32_t* pred_state, void* stream);
+
 /* ---------------------------------------------------------------- QUBO mask selection on the device (reference engine/postprocess.py:262-336: numpy on the host)
  * Minimises E(x) = x^T W x + lambda_reg * mean(x), x in {0,1}^N, by `replicas` independent simulated anneals run at once (the reference's moves,
  * acceptance rule and geometric schedule; it runs 20 restarts one after the other) and returns the best.  W fp32 [N, N] row-major, symmetric (the -W

@@ -70,6 +70,7 @@ SIGNATURES = {
     'pst_voxel_insert': 'i:plfplpppip', 'pst_voxel_count': 'i:pplpp', 'pst_voxel_rank': 'i:pplpppp', 'pst_voxel_accumulate': 'i:ppplfpppipppplppip',
     'pst_voxel_vote': 'i:pplpp', 'pst_voxel_emit': 'i:pppplfdppppiffppppppp',
     'pst_render_max_radius': 'i:', 'pst_render_splat': 'i:plpiiifiipip', 'pst_render_resolve': 'i:pllppppppppp',
+    'pst_pq_count': 'i:pplpipipiiipip', 'pst_pq_match': 'i:piiipppppppp',
 }
 EXPORTS = list(SIGNATURES)
 
@@ -1308,3 +1309,31 @@ def render_resolve(zbuf, rgb, colors, pan, index, depth, out_pan, out_rgb, out_c
     assert rgb.numel() == 3 * M and colors.numel() == 3 * M and index.numel() == n and depth.numel() == n and out_pan.numel() == n
     assert out_rgb.numel() == 3 * n and out_colors.numel() == 3 * n
     _call('pst_render_resolve', _ptr(zbuf), n, M, _ptr(rgb), _ptr(colors), _ptr(pan), _ptr(index), _ptr(depth), _ptr(out_pan), _ptr(out_rgb), _ptr(out_colors))
+
+
+# ------------------------------------------------------------------ panoptic evaluation (csrc/evaluate.hip; engine/evaluate.py holds the public entry point)
+EVAL_MERGE = 1                      # add runs of equal (slab, row, column) keys inside a wave with one atomic (A/B: tests/diag/eval_bench.py, docs/experiments.md)
+EVAL_MAX_TABLE_BYTES = 256 << 20    # the largest `counts` table [slabs, P+1, G+1] int32 that panoptic_quality allocates
+EVAL_MAX_ID = 1 << 24               # segment ids are below this (a COCO panoptic id is 24 bits of an RGB triple): bounds the id -> row tables
+
+
+def pq_count(pred, gt, slab_off, id2row_p, id2row_g, P, G, counts, merge=None):
+    """counts int32 [S, P+1, G+1] (cleared by the caller) += the pixels of pred / gt int32 [N] per (slab, row, column); slab_off int64 [S + 1]"""
+    _dev(pred, torch.int32); _dev(gt, torch.int32); _dev(slab_off, torch.int64); _dev(id2row_p, torch.int32); _dev(id2row_g, torch.int32); _dev(counts, torch.int32)
+    N, S = pred.numel(), slab_off.numel() - 1
+    assert all(t.is_contiguous() and t.device == pred.device for t in (pred, gt, slab_off, id2row_p, id2row_g, counts))
+    assert gt.numel() == N and S >= 1 and tuple(counts.shape) == (S, P + 1, G + 1)
+    _call('pst_pq_count', _ptr(pred), _ptr(gt), N, _ptr(slab_off), S, _ptr(id2row_p), id2row_p.numel(), _ptr(id2row_g), id2row_g.numel(), int(P), int(G),
+          _ptr(counts), int(EVAL_MERGE if merge is None else merge))
+
+
+def pq_match(counts, cat_p, cat_g, pred_area, gt_area, match, iou, pred_state):
+    """areas, match / iou per (slab, gt column) and the state per (slab, predicted row) of a counts table [S, P+1, G+1]"""
+    _dev(counts, torch.int32); _dev(cat_p, torch.int32); _dev(cat_g, torch.int32); _dev(pred_area, torch.int32); _dev(gt_area, torch.int32)
+    _dev(match, torch.int32); _dev(iou, torch.float64); _dev(pred_state, torch.int32)
+    S, P, G = counts.shape[0], counts.shape[1] - 1, counts.shape[2] - 1
+    assert all(t.is_contiguous() and t.device == counts.device for t in (counts, cat_p, cat_g, pred_area, gt_area, match, iou, pred_state))
+    assert cat_p.numel() == P and cat_g.numel() == G and tuple(pred_area.shape) == tuple(pred_state.shape) == (S, P)
+    assert tuple(gt_area.shape) == tuple(match.shape) == tuple(iou.shape) == (S, G)
+    nz = lambda t: _ptr(t) if t.numel() else None
+    _call('pst_pq_match', _ptr(counts), S, P, G, nz(cat_p), nz(cat_g), nz(pred_area), nz(gt_area), nz(match), nz(iou), nz(pred_state))

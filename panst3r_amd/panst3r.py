@@ -397,6 +397,13 @@ class PanSt3R(nn.Module):
         return cloud, cameras, pan_preds
 
     @torch.no_grad()
+    def evaluate(self, pan_preds, gt_maps, gt_segments, **kw):
+        """Panoptic quality of a post-processing result against ground truth: `engine.panoptic_quality` of pan_preds[0]'s maps and segments
+        (scope='scene' | 'view', things=).  It only composes."""
+        from .engine import panoptic_quality
+        return panoptic_quality(pan_preds[0]['pan'], pan_preds[0]['segments_info'], gt_maps, gt_segments, **kw)
+
+    @torch.no_grad()
     def _forward_inference_once(self, imgs, true_shape, classes, num_keyframes=None, use_retrieval=False, max_bs=None,
                                 outdevice=None, amp=False, sim_matrix=None, keyframes=None, check_finite=True, cache_graphs=False,
                                 panoptic_precision=None, _mm_tables=None):
