@@ -496,6 +496,59 @@ int pst_voxel_emit(const float* points, const int64_t* index, const int32_t* fir
                    double voxel_size, const int32_t* cnt, const uint64_t* sums, const uint64_t* best, const float* colors, int ncolors, float w1, float w2,
                    float* out_points, float* out_rgb, int32_t* out_pan, float* out_colors, int32_t* out_votes, int64_t* out_first, void* stream);
 
+/* ---------------------------------------------------------------- 3-D connected components of the voxels and label despeckling (no counterpart in the reference)
+ * The rows [0, Mv) of a voxel cloud (pan, count int32 [Mv], rgb fp32 [Mv, 3]) plus cells int32 [Mv, 3]; restated in tests/vcc_ref.py [restated, parity
+ * unpinned].  Everything is integer arithmetic, so the outputs are held to the restatement bit for bit (additive entry points: the ABI version stays).
+ *   cell        a voxel's cell is c = floor(fp32(p * inv)) of its first point, as step 1 of the voxel contract computes it (all members share it);
+ *               |c| < 2^20 on every axis.
+ *   adjacency   two voxels are adjacent under `connectivity` when their cells differ by at most 1 on every axis and the number of axes that differ is
+ *               exactly 1 (6), 1 or 2 (18), 1 to 3 (26).  A neighbour cell with a coordinate outside (-2^20, 2^20) does not exist and is never looked
+ *               up (its key field would wrap).
+ *   component   a maximal set of voxels with one pan > 0 that is connected through adjacent voxels of that id.  A voxel with pan <= 0 (void) belongs to
+ *               none: root = component = -1, never linked, never relabelled.  root[v] = the smallest voxel row of v's component (rows are in the order
+ *               of first points); component[v] = the rank of root[v] among all roots in increasing order, in [0, C).
+ *   table       per component, in that order: root, pan, size (voxels), points (sum of the voxels' count, int64), cell_lo / cell_hi (int32 per-axis min
+ *               and max cell).  The host derives the metric box in fp64: lo = cell_lo * voxel_size, hi = (cell_hi + 1) * voxel_size.
+ *   despeckle   a component is small when size < min_voxels.  For a small component every ordered pair (v, n) - v in it, n adjacent to v under the same
+ *               connectivity, pan[n] > 0, n in a component that is not small - is one vote for pan[n].  The component takes the id with the most votes,
+ *               ties to the smallest id (pst_voxel_vote's (votes << 32) | (0xFFFFFFFF - id), and that kernel); without a vote it becomes void, id 0 (a
+ *               floater).  One round.  colour = w1 * rgb + w2 * colors[pan] as step 3 of the voxel contract blends it.
+ * Integer atomics only; two calls return identical bytes.  Mv <= 2^30 - 1.  capacity = a power of two >= 2 Mv of the cell table (keys uint64 [capacity] =
+ * all ones, rows int32 [capacity] not initialised), pair_capacity = a power of two of the vote table (pair_keys = all ones, pair_cnt = 0; min(ids, 26) Mv
+ * distinct pairs at the most).  Every probe, find and union loop is bounded by the capacity or Mv; status int32 [4] = 0: status[0] collects the bits below
+ * instead of spinning (the caller reads it with the result and raises), status[1] / status[2] = voxels relabelled / turned void by vcc_apply.
+ *   vcc_cells    rows [0, *mv_ptr) of cells from the cloud's points and the fusion's first_row (max_voxels sizes the grid)
+ *   vcc_build    cell key -> row into keys / rows (compare-and-swap claim, plain store of the row); parent[v] = v, -1 for a void voxel
+ *   vcc_link     one voxel per lane, the lexicographically positive half of the neighbourhood (3, 9 or 13 cells); same id: wait-free union in parent
+ *                (find with path halving; the larger root hooked under the smaller with atomicMin, retried from the returned value; parent values only
+ *                decrease, so the root of a finished component is its smallest row)
+ *   vcc_flatten  root[v] = find(v); size int32 [Mv] = 0, points int64 [Mv] = 0, cell_lo int32 [Mv, 3] = INT32_MAX, cell_hi = INT32_MIN, indexed by the
+ *                ROOT's row, by atomicAdd / atomicMin / atomicMax.  `merge` != 0 reduces runs of adjacent lanes with one root inside the wave first.
+ *   vcc_count    counts[wg] = roots among the workgroup's 1024 rows; pst_cloud_scan of it gives base, base[n] = C
+ *   vcc_rank     rank_of[root row] = its rank, the table rows [0, C) (t_*), component int32 [Mv]
+ *   vcc_votes    the votes of the voxels of small components into pair_keys / pair_cnt keyed by (root << 32) | id; pst_voxel_vote then gives best[root]
+ *   vcc_apply    out_pan int32 [Mv], out_colors fp32 [Mv, 3] */
+#define PST_VCC_FULL 1        /* a table ran full */
+#define PST_VCC_DUPLICATE 2   /* two voxels share a cell */
+#define PST_VCC_RANGE 4       /* a cell outside (-2^20, 2^20) */
+#define PST_VCC_LOOP 8        /* a find / union loop reached its bound */
+int pst_vcc_cells(const float* points, const int32_t* first_row, const int32_t* mv_ptr, int64_t max_voxels, float inv, int32_t* cells, void* stream);
+int pst_vcc_build(const int32_t* cells, const int32_t* pan, int64_t Mv, uint64_t* keys, int32_t* rows, int64_t capacity, int32_t* parent, int32_t* status,
+                  void* stream);
+int pst_vcc_link(const int32_t* cells, const int32_t* pan, int64_t Mv, const uint64_t* keys, const int32_t* rows, int64_t capacity, int connectivity,
+                 int32_t* parent, int32_t* status, void* stream);
+int pst_vcc_flatten(const int32_t* parent, const int32_t* count, const int32_t* cells, int64_t Mv, int32_t* root, int32_t* size, int64_t* points,
+                    int32_t* cell_lo, int32_t* cell_hi, int32_t* status, int merge, void* stream);
+int pst_vcc_count(const int32_t* root, int64_t Mv, int32_t* counts, void* stream);
+int pst_vcc_rank(const int32_t* root, const int32_t* pan, int64_t Mv, const int32_t* base, const int32_t* size, const int64_t* points, const int32_t* cell_lo,
+                 const int32_t* cell_hi, int32_t* rank_of, int32_t* component, int32_t* t_root, int32_t* t_pan, int32_t* t_size, int64_t* t_points,
+                 int32_t* t_lo, int32_t* t_hi, void* stream);
+int pst_vcc_votes(const int32_t* cells, const int32_t* pan, const int32_t* root, const int32_t* size, int64_t Mv, const uint64_t* keys, const int32_t* rows,
+                  int64_t capacity, int connectivity, int min_voxels, uint64_t* pair_keys, int32_t* pair_cnt, int64_t pair_capacity, int32_t* status,
+                  void* stream);
+int pst_vcc_apply(const int32_t* pan, const int32_t* root, const int32_t* size, const uint64_t* best, int64_t Mv, int min_voxels, const float* rgb,
+                  const float* colors, int ncolors, float w1, float w2, int32_t* out_pan, float* out_colors, int32_t* status, void* stream);
+
 /* ---------------------------------------------------------------- z-buffered point rendering of the cloud from any camera (no counterpart in the reference)
  * The rows [0, M) of a cloud (points fp32 [M, 3] in the world frame, rgb, colors fp32 [M, 3], pan int32 [M]; a panoptic cloud or a voxel cloud) seen
  * from B pinhole cameras at one output shape (H, W) -> per pixel the nearest point.  The reference's demo hands the cloud to an interactive viewer and has

@@ -15,6 +15,7 @@
 // atomics - the run's first lane inserts, its last lane adds the run's sums (a wave-wide prefix sum, differenced at the run's ends).  Same results.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
+#include "voxel_table.h"
 
 #pragma clang fp contract(off)
 
@@ -25,14 +26,7 @@ __device__ __forceinline__ float vx_addr(float a, float b) { return a + b; }
 __device__ __forceinline__ float vx_subr(float a, float b) { return a - b; }
 
 constexpr int VX_T = 256, VX_PT = 4, VX_WG = VX_T * VX_PT;         // count / rank: the 1024-point workgroups of pst_cloud_scan's callers
-constexpr uint64_t VX_EMPTY = ~0ull;                               // no key is all ones: every 21-bit field is in [1, 2^21 - 1]
-constexpr int VX_LIM = 1 << 20;
 constexpr int VX_MAX_COLORS = 4096;
-
-__device__ __forceinline__ uint64_t vx_hash(uint64_t k) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-  return k;
-}
 
 // cell (as floats, exact integers) and in-cell offset q = floor((t - c) * 65536) in [0, 65536] of a point; false = the point is left out
 __device__ __forceinline__ bool vx_cell(const float* __restrict__ p, float inv, float (&c)[3], int (&q)[3]) {
@@ -50,28 +44,6 @@ __device__ __forceinline__ bool vx_cell(const float* __restrict__ p, float inv, 
 
 __device__ __forceinline__ uint64_t vx_key(const float (&c)[3]) {
   return (uint64_t)((int)c[0] + VX_LIM) | ((uint64_t)((int)c[1] + VX_LIM) << 21) | ((uint64_t)((int)c[2] + VX_LIM) << 42);
-}
-
-// lanes [head, tail] = the run of adjacent lanes that hold this lane's key.  Every lane of the wave must call it.
-__device__ __forceinline__ void vx_run(uint64_t key, int lane, int& head, int& tail) {
-  const uint64_t prev = __shfl_up((unsigned long long)key, 1);
-  const uint64_t heads = __ballot(lane == 0 || prev != key);
-  head = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
-  const uint64_t above = lane == 63 ? 0ull : heads >> (lane + 1);
-  tail = above ? lane + __builtin_ctzll(above) : 63;
-}
-
-// the slot of `key`: claimed if it is not in the table yet.  -1 = the table is full (never: capacity >= 2 M), reported through *status.
-__device__ __forceinline__ int vx_find_or_claim(uint64_t* __restrict__ keys, uint32_t mask, uint64_t key, int32_t* __restrict__ status) {
-  uint32_t h = (uint32_t)vx_hash(key) & mask;
-  for (uint32_t n = 0; n <= mask; ++n) {
-    uint64_t k = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == VX_EMPTY) k = atomicCAS((unsigned long long*)&keys[h], (unsigned long long)VX_EMPTY, (unsigned long long)key);
-    if (k == VX_EMPTY || k == key) return (int)h;
-    h = (h + 1) & mask;
-  }
-  atomicOr(status, 1);
-  return -1;
 }
 
 template <bool MERGE>

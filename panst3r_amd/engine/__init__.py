@@ -6,6 +6,6 @@ from . import pointmaps  # noqa: F401,E402  (pointmap post-processing: postproce
 from .images import load_images  # noqa: F401,E402
 from .retrieval import PanSt3RRetriever  # noqa: F401,E402  (keyframe selection by retrieval, reference engine/retrieval.py)
 from .cloud import panoptic_point_cloud, PanopticCloud, default_colors, camera_frusta  # noqa: F401,E402  (the scene's labelled point cloud, demo :279-300, :622-687)
-from .voxels import voxelize_cloud, VoxelCloud  # noqa: F401,E402  (voxel fusion of the cloud with multi-view label votes; not in the reference)
+from .voxels import voxelize_cloud, VoxelCloud, VoxelComponents, voxel_components, clean_voxel_labels  # noqa: F401,E402  (voxel fusion of the cloud with multi-view label votes; not in the reference)
 from .render import render_cloud, render_cameras, orbit_cameras, CloudRender  # noqa: F401,E402  (the cloud seen from any camera: depth, panoptic map, colours; not in the reference)
 from .evaluate import panoptic_quality  # noqa: F401,E402  (PQ / SQ / RQ and mIoU of panoptic maps against ground truth, per scene or per view; not in the reference)

@@ -71,6 +71,8 @@ SIGNATURES = {
     'pst_voxel_vote': 'i:pplpp', 'pst_voxel_emit': 'i:pppplfdppppiffppppppp',
     'pst_render_max_radius': 'i:', 'pst_render_splat': 'i:plpiiifiipip', 'pst_render_resolve': 'i:pllppppppppp',
     'pst_pq_count': 'i:pplpipipiiipip', 'pst_pq_match': 'i:piiipppppppp',
+    'pst_vcc_cells': 'i:ppplfpp', 'pst_vcc_build': 'i:pplpplppp', 'pst_vcc_link': 'i:pplpplippp', 'pst_vcc_flatten': 'i:ppplppppppip', 'pst_vcc_count': 'i:plpp',
+    'pst_vcc_rank': 'i:pplpppppppppppppp', 'pst_vcc_votes': 'i:pppplppliipplpp', 'pst_vcc_apply': 'i:pppplippiffpppp',
 }
 EXPORTS = list(SIGNATURES)
 
@@ -1277,6 +1279,101 @@ def voxel_emit(points, index, mv_ptr, inv, voxel_size, ws, colors, w1, w2, out_p
     _call('pst_voxel_emit', _ptr(points), _ptr(index), _ptr(ws['first_row']), _ptr(mv_ptr), M, float(inv), float(voxel_size), _ptr(ws['cnt']), _ptr(ws['sums']),
           _ptr(ws['best']), _ptr(colors), colors.shape[0], float(w1), float(w2), _ptr(out_points), _ptr(out_rgb), _ptr(out_pan), _ptr(out_colors), _ptr(out_votes),
           _ptr(out_first))
+
+
+# ------------------------------------------------------------------ connected components of the voxels (csrc/components.hip; engine/voxels.py holds the public entry points)
+VCC_MERGE = 1              # reduce runs of adjacent lanes with one root inside a wave before vcc_flatten's atomics (A/B: tests/diag/vcc_bench.py, docs/experiments.md)
+VCC_FULL, VCC_DUPLICATE, VCC_RANGE, VCC_LOOP = 1, 2, 4, 8      # PST_VCC_*: the bits of status[0]
+
+
+def vcc_cells(points, first_row, mv_ptr, inv, cells):
+    """cells int32 [M, 3]: rows [0, *mv_ptr) = the integer cell of every voxel's first point (first_row: the fusion's workspace)"""
+    _dev(points, torch.float32); _dev(first_row, torch.int32); _dev(mv_ptr, torch.int32); _dev(cells, torch.int32)
+    M = first_row.numel()
+    assert points.is_contiguous() and points.numel() == 3 * M and cells.is_contiguous() and cells.numel() == 3 * M
+    _call('pst_vcc_cells', _ptr(points), _ptr(first_row), _ptr(mv_ptr), M, float(inv), _ptr(cells))
+
+
+def vcc_pair_capacity(Mv, nids):
+    """slots of the vote table: twice the min(nids, 26) Mv distinct (component, id) pairs that can occur, a power of two (2^31 at the most)"""
+    return min(voxel_capacity(max(1, min(int(nids), 26)) * int(Mv)), 1 << 31)
+
+
+def vcc_workspace(Mv, device, pairs=0):
+    """the initialised workspaces of one labelling of Mv voxels (include/panst3r_hip.h): dict of device tensors; pairs > 0 adds the vote table"""
+    cap = voxel_capacity(Mv)
+    i32 = dict(dtype=torch.int32, device=device)
+    i64 = dict(dtype=torch.int64, device=device)
+    ws = {'cap': cap, 'keys': torch.full((cap,), -1, **i64), 'rows': torch.empty(cap, **i32), 'parent': torch.empty(Mv, **i32), 'root': torch.empty(Mv, **i32),
+          'size': torch.zeros(Mv, **i32), 'points': torch.zeros(Mv, **i64), 'lo': torch.full((Mv, 3), 2 ** 31 - 1, **i32), 'hi': torch.full((Mv, 3), -2 ** 31, **i32),
+          'rank_of': torch.empty(Mv, **i32), 'status': torch.zeros(4, **i32)}
+    if pairs:
+        ws.update(pair_cap=pairs, pair_keys=torch.full((pairs,), -1, **i64), pair_cnt=torch.zeros(pairs, **i32), best=torch.zeros(Mv, **i64))
+    return ws
+
+
+def _vcc_voxels(cells, pan):
+    _dev(cells, torch.int32); _dev(pan, torch.int32)
+    Mv = pan.numel()
+    assert cells.is_contiguous() and pan.is_contiguous() and tuple(cells.shape) == (Mv, 3) and cells.device == pan.device
+    return Mv
+
+
+def vcc_build(cells, pan, ws):
+    Mv = _vcc_voxels(cells, pan)
+    assert ws['keys'].numel() == ws['cap'] == ws['rows'].numel() and ws['parent'].numel() == Mv
+    _call('pst_vcc_build', _ptr(cells), _ptr(pan), Mv, _ptr(ws['keys']), _ptr(ws['rows']), ws['cap'], _ptr(ws['parent']), _ptr(ws['status']))
+
+
+def vcc_link(cells, pan, connectivity, ws):
+    Mv = _vcc_voxels(cells, pan)
+    assert ws['parent'].numel() == Mv
+    _call('pst_vcc_link', _ptr(cells), _ptr(pan), Mv, _ptr(ws['keys']), _ptr(ws['rows']), ws['cap'], int(connectivity), _ptr(ws['parent']), _ptr(ws['status']))
+
+
+def vcc_flatten(count, cells, ws, merge=None):
+    _dev(count, torch.int32); _dev(cells, torch.int32)
+    Mv = count.numel()
+    assert count.is_contiguous() and cells.is_contiguous() and cells.numel() == 3 * Mv and all(ws[k].numel() == Mv for k in ('parent', 'root', 'size', 'points'))
+    assert ws['lo'].numel() == 3 * Mv and ws['hi'].numel() == 3 * Mv
+    _call('pst_vcc_flatten', _ptr(ws['parent']), _ptr(count), _ptr(cells), Mv, _ptr(ws['root']), _ptr(ws['size']), _ptr(ws['points']), _ptr(ws['lo']), _ptr(ws['hi']),
+          _ptr(ws['status']), int(VCC_MERGE if merge is None else merge))
+
+
+def vcc_count(ws, counts):
+    _dev(counts, torch.int32)
+    Mv = ws['root'].numel()
+    assert counts.numel() == (Mv + CLOUD_WG - 1) // CLOUD_WG
+    _call('pst_vcc_count', _ptr(ws['root']), Mv, _ptr(counts))
+
+
+def vcc_rank(pan, ws, base, component, table):
+    """component int32 [Mv]; table: dict of root, pan, size int32 [Mv], points int64 [Mv], cell_lo, cell_hi int32 [Mv, 3] - rows [0, C) are written"""
+    _dev(pan, torch.int32); _dev(base, torch.int32); _dev(component, torch.int32)
+    Mv = pan.numel()
+    assert base.numel() == (Mv + CLOUD_WG - 1) // CLOUD_WG + 1 and component.numel() == Mv and ws['root'].numel() == Mv
+    for k in ('root', 'pan', 'size', 'points', 'cell_lo', 'cell_hi'):
+        t = table[k]
+        _dev(t, torch.int64 if k == 'points' else torch.int32)
+        assert t.is_contiguous() and t.numel() == (3 * Mv if k.startswith('cell') else Mv)
+    _call('pst_vcc_rank', _ptr(ws['root']), _ptr(pan), Mv, _ptr(base), _ptr(ws['size']), _ptr(ws['points']), _ptr(ws['lo']), _ptr(ws['hi']), _ptr(ws['rank_of']),
+          _ptr(component), _ptr(table['root']), _ptr(table['pan']), _ptr(table['size']), _ptr(table['points']), _ptr(table['cell_lo']), _ptr(table['cell_hi']))
+
+
+def vcc_votes(cells, pan, connectivity, min_voxels, ws):
+    Mv = _vcc_voxels(cells, pan)
+    assert ws['root'].numel() == Mv and ws['pair_keys'].numel() == ws['pair_cap'] == ws['pair_cnt'].numel()
+    _call('pst_vcc_votes', _ptr(cells), _ptr(pan), _ptr(ws['root']), _ptr(ws['size']), Mv, _ptr(ws['keys']), _ptr(ws['rows']), ws['cap'], int(connectivity),
+          int(min_voxels), _ptr(ws['pair_keys']), _ptr(ws['pair_cnt']), ws['pair_cap'], _ptr(ws['status']))
+
+
+def vcc_apply(pan, min_voxels, rgb, colors, w1, w2, ws, out_pan, out_colors):
+    _dev(pan, torch.int32); _dev(rgb, torch.float32); _dev(colors, torch.float32); _dev(out_pan, torch.int32); _dev(out_colors, torch.float32)
+    Mv = pan.numel()
+    assert all(t.is_contiguous() for t in (pan, rgb, colors, out_pan, out_colors)) and rgb.numel() == 3 * Mv and out_colors.numel() == 3 * Mv and out_pan.numel() == Mv
+    assert colors.dim() == 2 and colors.shape[1] == 3 and ws['root'].numel() == Mv and ws['best'].numel() == Mv
+    _call('pst_vcc_apply', _ptr(pan), _ptr(ws['root']), _ptr(ws['size']), _ptr(ws['best']), Mv, int(min_voxels), _ptr(rgb), _ptr(colors), colors.shape[0], float(w1),
+          float(w2), _ptr(out_pan), _ptr(out_colors), _ptr(ws['status']))
 
 
 # ------------------------------------------------------------------ z-buffered rendering of a cloud (csrc/render.hip; engine/render.py holds the public entry points)

@@ -328,6 +328,53 @@ def voxel_emit(points: Tensor, index: Tensor, first_row: Tensor, mv_ptr: Tensor,
                    out_pan, out_colors, out_votes, out_first)
 
 
+# connected components of the voxels (csrc/components.hip): the workspaces of hip.vcc_workspace as separate tensors
+@_op('vcc_cells', ('cells',))
+def vcc_cells(points: Tensor, first_row: Tensor, mv_ptr: Tensor, inv: float, cells: Tensor) -> None:
+    hip.vcc_cells(points, first_row, mv_ptr, inv, cells)
+
+
+@_op('vcc_build', ('keys', 'rows', 'parent', 'status'))
+def vcc_build(cells: Tensor, pan: Tensor, keys: Tensor, rows: Tensor, parent: Tensor, status: Tensor) -> None:
+    hip.vcc_build(cells, pan, {'cap': keys.numel(), 'keys': keys, 'rows': rows, 'parent': parent, 'status': status})
+
+
+@_op('vcc_link', ('parent', 'status'))
+def vcc_link(cells: Tensor, pan: Tensor, keys: Tensor, rows: Tensor, connectivity: int, parent: Tensor, status: Tensor) -> None:
+    hip.vcc_link(cells, pan, connectivity, {'cap': keys.numel(), 'keys': keys, 'rows': rows, 'parent': parent, 'status': status})
+
+
+@_op('vcc_flatten', ('root', 'size', 'points', 'cell_lo', 'cell_hi', 'status'))
+def vcc_flatten(parent: Tensor, count: Tensor, cells: Tensor, root: Tensor, size: Tensor, points: Tensor, cell_lo: Tensor, cell_hi: Tensor, status: Tensor,
+                merge: int = 1) -> None:
+    hip.vcc_flatten(count, cells, {'parent': parent, 'root': root, 'size': size, 'points': points, 'lo': cell_lo, 'hi': cell_hi, 'status': status}, merge)
+
+
+@_op('vcc_count', ('counts',))
+def vcc_count(root: Tensor, counts: Tensor) -> None:
+    hip.vcc_count({'root': root}, counts)
+
+
+@_op('vcc_rank', ('rank_of', 'component', 't_root', 't_pan', 't_size', 't_points', 't_lo', 't_hi'))
+def vcc_rank(root: Tensor, pan: Tensor, base: Tensor, size: Tensor, points: Tensor, cell_lo: Tensor, cell_hi: Tensor, rank_of: Tensor, component: Tensor,
+             t_root: Tensor, t_pan: Tensor, t_size: Tensor, t_points: Tensor, t_lo: Tensor, t_hi: Tensor) -> None:
+    hip.vcc_rank(pan, {'root': root, 'size': size, 'points': points, 'lo': cell_lo, 'hi': cell_hi, 'rank_of': rank_of}, base, component,
+                 {'root': t_root, 'pan': t_pan, 'size': t_size, 'points': t_points, 'cell_lo': t_lo, 'cell_hi': t_hi})
+
+
+@_op('vcc_votes', ('pair_keys', 'pair_cnt', 'status'))
+def vcc_votes(cells: Tensor, pan: Tensor, root: Tensor, size: Tensor, keys: Tensor, rows: Tensor, connectivity: int, min_voxels: int, pair_keys: Tensor,
+              pair_cnt: Tensor, status: Tensor) -> None:
+    hip.vcc_votes(cells, pan, connectivity, min_voxels, {'cap': keys.numel(), 'keys': keys, 'rows': rows, 'root': root, 'size': size, 'pair_cap': pair_keys.numel(),
+                                                          'pair_keys': pair_keys, 'pair_cnt': pair_cnt, 'status': status})
+
+
+@_op('vcc_apply', ('out_pan', 'out_colors', 'status'))
+def vcc_apply(pan: Tensor, root: Tensor, size: Tensor, best: Tensor, min_voxels: int, rgb: Tensor, colors: Tensor, w1: float, w2: float, out_pan: Tensor,
+              out_colors: Tensor, status: Tensor) -> None:
+    hip.vcc_apply(pan, min_voxels, rgb, colors, w1, w2, {'root': root, 'size': size, 'best': best, 'status': status}, out_pan, out_colors)
+
+
 def registered_ops():
     """names under torch.ops.panst3r_hip"""
     return list(_REGISTERED)

@@ -363,7 +363,7 @@ class PanSt3R(nn.Module):
 
     @torch.no_grad()
     def reconstruct(self, imgs, true_shape, classes, *, postprocess='standard_v2', min_conf_thr=3.0, opacity=0.5, postprocess_kwargs=None, voxel_size=None,
-                    **forward_kwargs):
+                    min_component_voxels=None, **forward_kwargs):
         """The body of the demo's `get_reconstructed_scene` (tools/demo_panst3r.py:232-300) in one call, everything on the device:
         forward_inference_multi_ar (outputs left where they are), the chosen panoptic post-processing ('standard_v2' | 'standard_v1' | 'qubo'),
         the cameras of the pointmaps and the panoptic point cloud.  `postprocess_kwargs`: thresholds of the chosen post-processing other than its
@@ -371,6 +371,8 @@ class PanSt3R(nn.Module):
         engine.solve_qubo_device) instead of the reference's host annealer.  Returns (cloud, cameras, pan_preds): a `PanopticCloud`, the camera frusta
         (each with its 'focal' and 'cam2world') and the post-processing result.  With `voxel_size` (a number, the unit of the pointmaps) the cloud is also
         fused on a voxel grid with multi-view label votes (engine.voxelize_cloud) and the return value is (cloud, cameras, pan_preds, voxels).
+        With `min_component_voxels` as well (only together with `voxel_size`) the voxels' labels are despeckled: every 26-connected same-label component of
+        fewer voxels takes the id of its large neighbours or becomes void (`VoxelCloud.clean_labels`), and the voxels returned are the cleaned ones.
         Images out of the result: `engine.render_cameras(cloud, cameras)` re-renders the cloud (or the voxels) from the input cameras, and
         `cloud.render(engine.orbit_cameras(...), focal, (H, W))` from any other - depth, panoptic map and colours per pixel (engine/render.py).
         It only composes the public entry points."""
@@ -384,6 +386,11 @@ class PanSt3R(nn.Module):
         if voxel_size is not None:
             from .engine.voxels import _check_voxel_size
             _check_voxel_size(voxel_size)                       # a bad size raises before the forward pass, not after it
+        if min_component_voxels is not None:
+            from .engine.voxels import _check_min_voxels
+            if voxel_size is None:
+                raise ValueError('min_component_voxels works on the voxels: it is valid only together with voxel_size')
+            _check_min_voxels(min_component_voxels)
         pms, panout = self.forward_inference_multi_ar(imgs, true_shape, classes, **forward_kwargs)
         pan_preds = fns[postprocess](panout['pred_logits'], panout['pred_masks'], true_shape, label_mode=self.panoptic_decoder.label_mode, multi_ar=True,
                                     **(postprocess_kwargs or {}))
@@ -393,7 +400,8 @@ class PanSt3R(nn.Module):
                                      min_conf_thr=min_conf_thr, opacity=opacity)
         cameras = [dict(c, cam2world=c2w) for c, c2w in zip(cloud.cameras, cams2world)]
         if voxel_size is not None:
-            return cloud, cameras, pan_preds, cloud.voxelize(voxel_size)
+            voxels = cloud.voxelize(voxel_size)
+            return cloud, cameras, pan_preds, voxels if min_component_voxels is None else voxels.clean_labels(min_component_voxels)
         return cloud, cameras, pan_preds
 
     @torch.no_grad()
