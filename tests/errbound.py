@@ -388,6 +388,15 @@ def conf_bound(c64):
     return EXPF_ULP * R * U32 * e + R * U32 * (1.0 + e) + TINY32
 
 
+def select_bound(ref, D):
+    """retrieval.hip select_kernel, out = x / max(sqrtf(key), 1e-12f) against ref = x / max(||x||, 1e-12) (float64 of the same fp32 row).  key = the fp32
+    sum of the D squares: lane l of 64 chains ceil(D / 64) fmas (one rounding each; the terms are non-negative, so every rounding is relative to a partial
+    <= key), a six-step butterfly adds the lanes -> (ceil(D / 64) + 6) u32 relative; the root halves that and rounds once, the division rounds once, and for
+    a clamped row 1e-12f is one rounding away from 1e-12.  Each rounding allowed twice (R), like everywhere here."""
+    n = -(-D // 64)
+    return R * U32 * ((n + 6) / 2.0 + 3.0) * torch.as_tensor(ref, dtype=torch.float64).abs() + TINY32
+
+
 def moments_bound(abs_terms, nadd, dw_terms):
     """rigid_moments: double sums of nadd additions (+ 3 for the products w y x in double) over terms whose absolute sum is abs_terms, and the single fp32
     rounding of w = conf + weight_offset: dw_terms = the same moments of |fl32(conf + off) - (conf + off)|, which the CPU computes exactly (0 with offset 0);

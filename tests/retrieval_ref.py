@@ -251,3 +251,205 @@ def margins(ck, xs):
     ids, _ = assign(desc, cent, m)
     smin = min(float(np.min(np.abs(s))) for ma in (p['ma_q'], p['ma_db']) for lst in aggregate(desc, cent, ids, counts, ma).values() for _, s in lst)
     return (min(gaps) if gaps else 1.0), agap, smin
+
+
+# ---------------------------------------------------------------------------------------------------- kernel-level cases (tests/test_hip_retrieval_kernels.py)
+# Seeded inputs that make the loops of csrc/retrieval.hip repeat, with their float64 answers.  Everything is built from the contract in the docstrings of
+# panst3r_amd/hip.py (retrieval_*) and panst3r_amd/model/retrieval.py; tests/test_retrieval_host.py checks the constructions themselves on the CPU.
+SELECT_TS = [1, 5, 256, 257, 300, 700]      # one launch: a single row, a tiny view, the block width and one more, two views that need a second ranking trip
+SELECT_STEP = 0.998                         # ratio of neighbouring row norms: a relative gap of 2e-3, far above the fp32 error of the ranking key
+
+
+def _unit_rows(g, n, d):
+    x = g.standard_normal((n, d))
+    return x / np.linalg.norm(x, axis=1, keepdims=True)
+
+
+def select_case(seed, nfeat, D, Ts=SELECT_TS):
+    """rows of len(Ts) views whose float64 norms form the ladder 2 SELECT_STEP^rank (rank -> token by a random permutation), with planted exceptions:
+      ties    pairs of bit-identical rows at neighbouring ranks: tokens 3 and 260 of the 300- and 700-token views (either side of 256), and in every view
+              that is cut (T > nsel) a pair at ranks (nsel - 1, nsel), so that exactly one of the two is selected;
+      zeros   the two lowest ranks of the 5-token view are all-zero rows, the rank above them has norm 1e-13 (below the 1e-12 clamp).
+    -> dict(x fp32 [sum T, D], Ts, counts, ties [(view, lower token, higher token)], zeros [(view, token)], tiny [(view, token)])"""
+    g = np.random.Generator(np.random.PCG64(seed))
+    xs, ties, zeros, tiny = [], [], [], []
+    counts = [min(nfeat, T) for T in Ts]
+    for v, (T, nsel) in enumerate(zip(Ts, counts)):
+        perm = g.permutation(T)                                  # perm[rank] = token
+
+        def place(rank, token):
+            j = int(np.nonzero(perm == token)[0][0])
+            perm[rank], perm[j] = perm[j], perm[rank]
+        pairs = []                                               # ranks (r, r + 1) that share one row
+        cut = nsel - 1 if nsel < T else None
+        if T > 260:
+            r = cut if (cut is not None and (T == 300 or nsel < 3)) else (10 if T == 300 else 0)
+            place(r, 260), place(r + 1, 3)
+            pairs.append(r)
+        if cut is not None and cut not in pairs:
+            pairs.append(cut)
+        rows = (2.0 * SELECT_STEP ** np.arange(T))[:, None] * _unit_rows(g, T, D)
+        if T == 5:
+            rows[2] *= 1e-13 / np.linalg.norm(rows[2])
+            rows[3:] = 0.0
+            zeros += [(v, int(perm[3])), (v, int(perm[4]))]
+            tiny.append((v, int(perm[2])))
+        rows = rows.astype(np.float32)
+        for r in pairs:
+            rows[r + 1] = rows[r]
+            ties.append((v, int(min(perm[r], perm[r + 1])), int(max(perm[r], perm[r + 1]))))
+        x = np.empty_like(rows)
+        x[perm] = rows
+        xs.append(x)
+    return dict(x=np.concatenate(xs, 0), Ts=list(Ts), counts=counts, ties=ties, zeros=zeros, tiny=tiny)
+
+
+def select_ref(x, Ts, counts):
+    """per view the counts[v] rows of largest float64 norm, ties to the lower token (the lexsort of `descriptors`), L2-normalised with the 1e-12 clamp
+    -> (tokens int [sum counts], rows float64 [sum counts, D])"""
+    toks, rows, t0 = [], [], 0
+    for T, n in zip(Ts, counts):
+        h = x[t0:t0 + T].astype(np.float64)
+        nrm = np.sqrt((h * h).sum(-1))
+        order = np.lexsort((np.arange(T), -nrm))[:n]
+        toks.append(order)
+        rows.append(h[order] / np.maximum(nrm[order], 1e-12)[:, None])
+        t0 += T
+    return np.concatenate(toks), np.concatenate(rows, 0)
+
+
+def select_f32(x):
+    """the select kernel's fp32 steps on rows x fp32 [n, D]: lane l of 64 adds the squares of columns l, l + 64, ... by fma, a six-step butterfly adds
+    the lanes, one sqrt, the 1e-12f clamp, one division per element -> fp32 [n, D]"""
+    f = np.float32
+    n, D = x.shape
+    pad = np.zeros((n, -(-D // 64) * 64), np.float64)
+    pad[:, :D] = x
+    s = np.zeros((n, 64), f)
+    for c in range(0, pad.shape[1], 64):
+        s = (pad[:, c:c + 64] * pad[:, c:c + 64] + s.astype(np.float64)).astype(f)      # fmaf: the product is exact in float64
+    lanes = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        s = (s + s[:, lanes ^ o]).astype(f)
+    nrm = np.maximum(np.sqrt(s[:, 0]).astype(f), f(1e-12))
+    return (x / nrm[:, None]).astype(f)
+
+
+ASSIGN_K, ASSIGN_D = 321, 64                # 6 centroid tiles of 64, the last one holding a single centroid
+# bit-identical centroid rows (lower, higher): one 16-centroid subtile but two lane groups (4 centroids per lane); two 64-tiles that share a split for
+# nsplit <= 2 and not above; two splits for every nsplit >= 2; the last centroid with one that shares its split up to nsplit = 5 and not for 6
+ASSIGN_PAIRS = [(17, 22), (70, 140), (5, 250), (300, 320)]
+
+
+def assign_case(seed, n, k=ASSIGN_K, D=ASSIGN_D, pairs=ASSIGN_PAIRS):
+    """unit centroids with the rows of `pairs` made bit-identical, and n descriptors: row i < len(pairs) lies 0.05 from pair i (counted from the last
+    pair, so that n = 1 meets the one with centroid k - 1), the others 0.3 from a random centroid -> (x fp32 [n, D], c fp32 [k, D], [(row, lower, higher)])"""
+    g = np.random.Generator(np.random.PCG64(seed))
+    c = _unit_rows(g, k, D).astype(np.float32)
+    for a, b in pairs:
+        c[b] = c[a]
+    x = c[g.integers(0, k, n)].astype(np.float64) + 0.3 * _unit_rows(g, n, D)
+    near = []
+    for i, (a, b) in enumerate(reversed(pairs)):
+        if i < n:
+            x[i] = c[a].astype(np.float64) + 0.05 * _unit_rows(g, 1, D)[0]
+            near.append((i, a, b))
+    return x.astype(np.float32), c, near
+
+
+def pack_bits(b):
+    """bool [G, D] -> uint32 [G, D / 32], bit j of word w = component 32 w + j"""
+    G, D = b.shape
+    return (b.reshape(G, D // 32, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(-1).astype(np.uint32)
+
+
+def unpack_bits(w):
+    """uint32 [G, W] -> bool [G, 32 W]"""
+    w = np.asarray(w).view(np.uint32)
+    return ((w[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(w.shape[0], -1).astype(bool)
+
+
+def aggregate_case(seed, D):
+    """142 descriptors, 6 centroids and five groups (members ascending):
+      0  one member, x = c + 0.5 pattern (a known +-1 pattern: every bit is decided)      1  70 members around their centroid (mixed signs)
+      2  70 members: descriptor 0 of group 0 and 69 of group 1's (a descriptor in several groups)
+      3  one member equal to its centroid bit for bit (zero sums, zero bits)               4  70 members, each c + (0.5 .. 1.5) pattern
+    -> dict(x, cent, member, gstart, gword, patterns {group: bool [D]}, zero_group)"""
+    g = np.random.Generator(np.random.PCG64(seed))
+    cent = g.standard_normal((6, D)).astype(np.float32)
+    x = np.empty((142, D), np.float32)
+    pat = {0: g.random(D) < 0.5, 4: g.random(D) < 0.5}
+    sgn = lambda p: np.where(p, 1.0, -1.0)
+    x[0] = cent[0] + np.float32(0.5) * sgn(pat[0]).astype(np.float32)
+    x[1:71] = cent[1] + 0.2 * g.standard_normal((70, D))
+    x[71] = cent[3]
+    x[72:] = cent[4] + g.uniform(0.5, 1.5, (70, D)) * sgn(pat[4])
+    groups = [[0], list(range(1, 71)), [0] + list(range(2, 71)), [71], list(range(72, 142))]
+    member = np.concatenate(groups).astype(np.int32)
+    gstart = np.concatenate([[0], np.cumsum([len(m) for m in groups])]).astype(np.int32)
+    return dict(x=x, cent=cent, member=member, gstart=gstart, gword=np.array([0, 1, 2, 3, 4], np.int32), patterns=pat, zero_group=3)
+
+
+def aggregate_ref(x, cent, member, gstart, gword):
+    """float64 residual sums [G, D] and the per-element bound of the kernel's fp32 sum (tests/test_hip_retrieval.py: every x - c rounds once, the
+    running sum once per member, each allowed twice)"""
+    u32 = 2.0 ** -24
+    S, B = [], []
+    for gi in range(len(gword)):
+        mem = member[gstart[gi]:gstart[gi + 1]]
+        c = cent[gword[gi]].astype(np.float64)
+        res = x[mem].astype(np.float64) - c
+        S.append(res.sum(0))
+        B.append(2 * (len(mem) + 1) * u32 * np.abs(res).sum(0) + 2 * u32 * (np.abs(x[mem].astype(np.float64)).sum(0) + len(mem) * np.abs(c)))
+    return np.stack(S), np.stack(B)
+
+
+SCORES_Q = [0, 5, 600]                      # words per query view: none, a few, more than one 256-thread fill of the LDS word list
+SCORES_DB = [0, 1, 63, 64, 65, 130, 300]    # groups per database view: 7 views (two trips of the 4-wave loop), either side of the 64-group chunk, 3 and 5 chunks
+
+
+def scores_case(seed, D):
+    """sorted word lists and sign bits of SCORES_Q query and SCORES_DB database views.  Every database view of >= 4 groups holds a word below and a
+    word above every query word and the first and the last word of the 600-word query view; about half of its other words are that view's too.  The
+    bits of a matching database group are the query's with h random flips, h uniform in [0, D]; planted against the 600-word view: h = 0 (first word)
+    and h = D (last word) in the 300-group view, h = D / 4 (s = 0.5 exactly) and h = D / 4 + 1 in the 130-group view, h = D / 8 in the 1-group view.
+    -> dict(qwords, qbits, dwords, dbits (lists per view; bits bool [groups, D]), planted [(db view, word, h)])"""
+    g = np.random.Generator(np.random.PCG64(seed))
+    uni = np.arange(100, 3000)
+    qwords = [np.sort(g.choice(uni, n, replace=False)) for n in SCORES_Q]
+    qbits = [g.random((n, D)) < 0.5 for n in SCORES_Q]
+    big = qwords[2]
+    lo, hi = min(int(w[0]) for w in qwords if len(w)), max(int(w[-1]) for w in qwords if len(w))
+    first, last = int(big[0]), int(big[-1])
+    pos = {int(w): i for i, w in enumerate(big)}
+    dwords, dbits, planted = [], [], []
+    for j, n in enumerate(SCORES_DB):
+        cand = ([first] if n == 1 else [lo - 1 - j, hi + 1 + j, first, last]) if n else []
+        for a, b in zip(g.permutation(big), g.permutation(np.arange(3000 + 10))):
+            cand += [int(a), int(b)]
+        words = []
+        for w in cand:
+            if len(words) < n and w not in words:
+                words.append(w)
+        words = np.sort(np.array(words, dtype=np.int64))
+        bits = g.random((n, D)) < 0.5
+        plant = {1: {first: D // 8}, 130: {first: D // 4, last: D // 4 + 1}, 300: {first: 0, last: D}}.get(n, {})
+        for i, w in enumerate(words):
+            if int(w) in pos:
+                h = plant.get(int(w), int(g.integers(0, D + 1)))
+                bits[i] = qbits[2][pos[int(w)]]
+                flip = g.choice(D, h, replace=False)
+                bits[i, flip] = ~bits[i, flip]
+                if int(w) in plant:
+                    planted.append((j, int(w), h))
+        dwords.append(words)
+        dbits.append(bits)
+    return dict(qwords=qwords, qbits=qbits, dwords=dwords, dbits=dbits, planted=planted)
+
+
+def flat_groups(words, bits, D):
+    """lists per view -> (off int32 [V + 1], word int32 [G], packed bits uint32 [G, D / 32]) as retrieval_scores takes them"""
+    off = np.concatenate([[0], np.cumsum([len(w) for w in words])]).astype(np.int32)
+    word = np.concatenate([np.asarray(w, dtype=np.int32) for w in words]).astype(np.int32)
+    b = np.concatenate([np.asarray(x, dtype=bool).reshape(-1, D) for x in bits], 0)
+    return off, word, pack_bits(b)
