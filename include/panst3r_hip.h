@@ -579,6 +579,54 @@ int pst_render_splat(const float* points, int64_t M, const float* cams, int ncam
 int pst_render_resolve(const uint64_t* zbuf, int64_t npix, int64_t M, const float* rgb, const float* colors, const int32_t* pan, int64_t* index, float* depth,
                        int32_t* out_pan, float* out_rgb, float* out_colors, void* stream);
 
+/* ---------------------------------------------------------------- z-buffered triangle rasterisation of a labelled mesh: ground-truth depth and panoptic maps
+ * A mesh (vertices fp32 [Nv, 3] in the world frame, faces int32 [Nf, 3], one panoptic id per vertex or per face) seen from B pinhole cameras at one shape
+ * (H, W) -> per pixel the nearest face's depth, index and id, and after a per-view minimum-area filter the ground-truth maps pst_pq_count scores
+ * against.  The reference renders them through pyrender / OpenGL (tools/preprocess_scannetpp.py:395-494: SKIP_CULL_FACES | SEG_VERT, znear 0.05, zfar
+ * 20, MIN_INST_AREA 50), which a compute node does not offer; restated in tests/mesh_ref.py [restated, parity unpinned].  Every step is exact, so the
+ * outputs are held to it bit for bit.  Contraction is off: every fp32 and fp64 operation is rounded on its own, in the order written:
+ *   1 camera    host, float64: the rows of [R^T | -R^T t] computed and rounded as step 1 of the render contract, then fx fy cx cy: float [B, 16] per camera
+ *               W00 W01 W02 s0 W10 W11 W12 s1 W20 W21 W22 s2 fx fy cx cy.  near and far are kernel scalars, 0 < near < far, fp32.
+ *   2 vertex    xc, yc, zc as step 1 of the render contract.  u = fp32(fp64(fx xc) / fp64(zc)) + cx, v = fp32(fp64(fy yc) / fp64(zc)) + cy (the
+ *               quotient rule of render step 3).  A vertex is UNUSABLE if any of xc, yc, zc, u, v is not finite, if zc < near, or if |u| or |v| > 2^14.
+ *               Otherwise it is snapped to 1/256 pixel: X = int32(rint(u 256)), Y = int32(rint(v 256)), half to even; the product is exact.
+ *   3 face      a face with an unusable vertex, or with an index outside [0, Nv), is left out whole: THERE IS NO NEAR-PLANE CLIPPING (the reference
+ *               clips; with centimetre-sized faces at near = 0.05 the difference is a rim of pixels).  A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) in
+ *               int64; A == 0 drops the face; if A < 0 corners 1 and 2 are exchanged (and A = -A).  No face culling.
+ *   4 coverage  pixel (i, j) is sampled at P = (256 j + 128, 256 i + 128).  For corner k with the opposite edge a -> b, (a, b) = (1, 2), (2, 0), (0, 1):
+ *               E_k = (Xb - Xa)(Py - Ya) - (Yb - Ya)(Px - Xa) in int64; E0 + E1 + E2 = A.  The pixel is covered iff for every k E_k > 0, or E_k == 0 and
+ *               the edge d = (Xb - Xa, Yb - Ya) has dy < 0 or (dy == 0 and dx > 0) - the top-left rule: a pixel centre on an edge two faces share
+ *               belongs to exactly one of them.  With the bounds of step 2 |E| < 2^47: exact in int64 and in fp64.
+ *               The BOUNDING BOX of a face is the pixels j0 .. j1 x i0 .. i1 whose centres lie in [min X, max X] x [min Y, max Y], clipped to the
+ *               image: j0 = max(0, ceil((min X - 128) / 256)), j1 = min(W - 1, floor((max X - 128) / 256)), likewise i0, i1; an empty box drops the
+ *               face.  Only its pixels are tested (none outside it can be covered).
+ *   5 depth     perspective-correct, fp64: q_k = 1.0 / fp64(zc_k), s = (fp64(E0) q0 + fp64(E1) q1) + fp64(E2) q2, depth = fp32(fp64(A) / s).  A
+ *               sample is left out if depth is not finite, < near or > far.
+ *   6 z-buffer  key = (uint64(bits(depth)) << 32) | uint32(face); 64-bit atomicMin into zbuf uint64 [B, H, W], which the CALLER clears to all ones:
+ *               the nearest face wins, equal depths go to the smallest face index.  Integer atomics only: the result does not depend on scheduling.
+ *               `precheck` != 0 reads the cell first (relaxed) and skips an atomic that cannot win (same results).
+ *   7 resolve   an empty cell gives face -1, depth 0, id 0; otherwise face int64 and depth fp32 come from the key.  With face_ids int32 [Nf] the id
+ *               is face_ids[face].  With vertex_ids int32 [Nv] the E_k of that face at that pixel are recomputed and the id is vertex_ids[corner] of
+ *               the corner with the largest E_k (the nearest corner), ties to the lowest position as listed in `faces`; ids are never blended.
+ *               With neither the id is 0.  Plain vector stores.
+ *   8 area      an id i is LISTED with row id2row[i] if 0 < i < ntab and that entry is in [0, S) (as pst_pq_count maps ids).  counts int32 [B, S],
+ *               cleared by the CALLER: the pixels of every (camera, listed id), int32 atomicAdd only.  pst_mesh_area_apply: out = the id if it is
+ *               listed and its count in that camera is >= min_area, else 0 (min_area = 0 only removes unlisted ids).  out is not pan.
+ * pst_mesh_raster runs two paths with one result (the minimum is order-free): a lane per (camera, face) loops over a bounding box of at most
+ * PST_MESH_LANE_PIXELS pixels; a larger face goes to the list big uint64 [big_capacity] ((camera << 32) | face; big_count uint64 [1], cleared by the
+ * CALLER, counts the appends) and a second launch walks the list one wave per face, the lanes striding over the box.  A full list is no error: the face
+ * is then rasterised by its lane.  big_capacity = 0 (big may be null) keeps everything in the lane path.
+ * 1 <= Nf, Nv <= 2^31 - 1, 1 <= B <= 65535, B H W <= 2^31 - 1, B S <= 2^31 - 1.  Nothing can fail on the device: there is no status word. */
+#define PST_MESH_LANE_PIXELS 64
+int pst_mesh_lane_pixels(void);
+int pst_mesh_raster(const float* vertices, int64_t Nv, const int32_t* faces, int64_t Nf, const float* cams, int ncams, int H, int W, float near_z, float far_z,
+                    uint64_t* zbuf, uint64_t* big, uint64_t* big_count, int64_t big_capacity, int precheck, void* stream);
+int pst_mesh_resolve(const uint64_t* zbuf, int ncams, int H, int W, const float* vertices, int64_t Nv, const int32_t* faces, int64_t Nf, const float* cams,
+                     float near_z, const int32_t* vertex_ids, const int32_t* face_ids, int64_t* face, float* depth, int32_t* pan, void* stream);
+int pst_mesh_area_count(const int32_t* pan, int ncams, int64_t hw, const int32_t* id2row, int ntab, int S, int32_t* counts, void* stream);
+int pst_mesh_area_apply(const int32_t* pan, int ncams, int64_t hw, const int32_t* id2row, int ntab, int S, const int32_t* counts, int min_area, int32_t* out,
+                        void* stream);
+
 /* ---------------------------------------------------------------- panoptic evaluation against ground truth: PQ / SQ / RQ, mIoU (no counterpart in the reference)
  * V predicted maps and V ground-truth maps of the same shapes, flattened and concatenated to pred, gt int32 [N] (1 <= N <= 2^31 - 1, both 16-byte
  * aligned), P predicted and G ground-truth segments (ids unique and > 0 within each list, no crowd regions).  The rules are those of COCO

@@ -70,6 +70,8 @@ SIGNATURES = {
     'pst_voxel_insert': 'i:plfplpppip', 'pst_voxel_count': 'i:pplpp', 'pst_voxel_rank': 'i:pplpppp', 'pst_voxel_accumulate': 'i:ppplfpppipppplppip',
     'pst_voxel_vote': 'i:pplpp', 'pst_voxel_emit': 'i:pppplfdppppiffppppppp',
     'pst_render_max_radius': 'i:', 'pst_render_splat': 'i:plpiiifiipip', 'pst_render_resolve': 'i:pllppppppppp',
+    'pst_mesh_lane_pixels': 'i:', 'pst_mesh_raster': 'i:plplpiiiffppplip', 'pst_mesh_resolve': 'i:piiiplplpfpppppp', 'pst_mesh_area_count': 'i:pilpiipp',
+    'pst_mesh_area_apply': 'i:pilpiipipp',
     'pst_pq_count': 'i:pplpipipiiipip', 'pst_pq_match': 'i:piiipppppppp',
     'pst_vcc_cells': 'i:ppplfpp', 'pst_vcc_build': 'i:pplpplppp', 'pst_vcc_link': 'i:pplpplippp', 'pst_vcc_flatten': 'i:ppplppppppip', 'pst_vcc_count': 'i:plpp',
     'pst_vcc_rank': 'i:pplpppppppppppppp', 'pst_vcc_votes': 'i:pppplppliipplpp', 'pst_vcc_apply': 'i:pppplippiffpppp',
@@ -1406,6 +1408,79 @@ def render_resolve(zbuf, rgb, colors, pan, index, depth, out_pan, out_rgb, out_c
     assert rgb.numel() == 3 * M and colors.numel() == 3 * M and index.numel() == n and depth.numel() == n and out_pan.numel() == n
     assert out_rgb.numel() == 3 * n and out_colors.numel() == 3 * n
     _call('pst_render_resolve', _ptr(zbuf), n, M, _ptr(rgb), _ptr(colors), _ptr(pan), _ptr(index), _ptr(depth), _ptr(out_pan), _ptr(out_rgb), _ptr(out_colors))
+
+
+# ------------------------------------------------------------------ z-buffered rasterisation of a labelled mesh (csrc/mesh.hip; engine/mesh.py holds the public entry points)
+MESH_PRECHECK = 0          # RENDER_PRECHECK's relaxed load before the atomic: OFF here - a mesh has a few samples per pixel, most atomics win, and the load
+                           # only adds to them (0.87 against 0.56 ms for 16 cameras: tests/diag/mesh_bench.py, docs/experiments.md §6l)
+MESH_CAM_FLOATS = 16       # floats per camera of the device table: twelve world-to-camera numbers, fx, fy, cx, cy
+MESH_LANE_PIXELS = 64      # PST_MESH_LANE_PIXELS (pst_mesh_lane_pixels() of the built library; tests/test_mesh_host.py holds the three together)
+MESH_BIG_CAPACITY = 1 << 22    # the most (camera, face) entries the list of large faces gets (8 bytes each); beyond it a large face stays with its lane
+
+
+def mesh_lane_pixels():
+    """PST_MESH_LANE_PIXELS: the largest pixel bounding box one lane rasterises; a larger face goes to the one-wave-per-face path"""
+    return lib().pst_mesh_lane_pixels()
+
+
+def mesh_workspace(B, Nf, device, capacity=None):
+    """the list of large faces of one pst_mesh_raster launch over B cameras and Nf faces: {'big': int64 [capacity], 'count': int64 [1]}.  `count` is
+    cleared before every launch (mesh_raster does it)."""
+    cap = min(int(B) * int(Nf), MESH_BIG_CAPACITY) if capacity is None else int(capacity)
+    return {'big': torch.empty(max(cap, 1), dtype=torch.int64, device=device), 'count': torch.zeros(1, dtype=torch.int64, device=device), 'capacity': cap}
+
+
+def mesh_raster(vertices, faces, cams, H, W, near, far, zbuf, ws, precheck=None):
+    """atomicMin of every covered sample's key into zbuf int64 [B, H, W] (cleared to all ones by the caller) for the B cameras of cams fp32 [B, 16];
+    ws = mesh_workspace(...)"""
+    _dev(vertices, torch.float32); _dev(faces, torch.int32); _dev(cams, torch.float32); _dev(zbuf, torch.int64); _dev(ws['big'], torch.int64); _dev(ws['count'], torch.int64)
+    B = cams.shape[0]
+    assert vertices.is_contiguous() and vertices.dim() == 2 and vertices.shape[1] == 3 and faces.is_contiguous() and faces.dim() == 2 and faces.shape[1] == 3
+    assert cams.is_contiguous() and tuple(cams.shape) == (B, MESH_CAM_FLOATS) and zbuf.is_contiguous() and tuple(zbuf.shape) == (B, H, W)
+    assert cams.device == vertices.device == faces.device == zbuf.device == ws['big'].device == ws['count'].device
+    assert 0 <= ws['capacity'] <= ws['big'].numel() and ws['count'].numel() == 1
+    ws['count'].zero_()
+    _call('pst_mesh_raster', _ptr(vertices), vertices.shape[0], _ptr(faces), faces.shape[0], _ptr(cams), B, int(H), int(W), float(near), float(far), _ptr(zbuf),
+          _ptr(ws['big']), _ptr(ws['count']), ws['capacity'], int(MESH_PRECHECK if precheck is None else precheck))
+
+
+def mesh_resolve(zbuf, vertices, faces, cams, near, vertex_ids, face_ids, face, depth, pan):
+    """per cell of zbuf int64 [B, H, W]: the winning face, its depth and its id (face_ids, the nearest corner's vertex_ids, or 0); an empty cell: -1, 0, 0"""
+    _dev(zbuf, torch.int64); _dev(vertices, torch.float32); _dev(faces, torch.int32); _dev(cams, torch.float32)
+    _dev(face, torch.int64); _dev(depth, torch.float32); _dev(pan, torch.int32)
+    B, H, W = zbuf.shape
+    Nv, Nf = vertices.shape[0], faces.shape[0]
+    ts = [zbuf, vertices, faces, cams, face, depth, pan]
+    for t, n in ((vertex_ids, Nv), (face_ids, Nf)):
+        if t is not None:
+            _dev(t, torch.int32)
+            assert t.numel() == n
+            ts.append(t)
+    assert all(t.is_contiguous() and t.device == zbuf.device for t in ts) and tuple(cams.shape) == (B, MESH_CAM_FLOATS)
+    assert face.numel() == depth.numel() == pan.numel() == zbuf.numel() and vertices.shape[1] == 3 and faces.shape[1] == 3
+    _call('pst_mesh_resolve', _ptr(zbuf), B, H, W, _ptr(vertices), Nv, _ptr(faces), Nf, _ptr(cams), float(near), _ptr(vertex_ids), _ptr(face_ids), _ptr(face),
+          _ptr(depth), _ptr(pan))
+
+
+def _mesh_area_args(pan, id2row, counts):
+    _dev(pan, torch.int32); _dev(id2row, torch.int32); _dev(counts, torch.int32)
+    B, S = counts.shape
+    assert pan.dim() == 3 and pan.shape[0] == B and S >= 1 and all(t.is_contiguous() and t.device == pan.device for t in (pan, id2row, counts))
+    return B, pan.shape[1] * pan.shape[2], S
+
+
+def mesh_area_count(pan, id2row, counts):
+    """counts int32 [B, S] (cleared by the caller) += the pixels of pan int32 [B, H, W] per (camera, listed id)"""
+    B, hw, S = _mesh_area_args(pan, id2row, counts)
+    _call('pst_mesh_area_count', _ptr(pan), B, hw, _ptr(id2row), id2row.numel(), S, _ptr(counts))
+
+
+def mesh_area_apply(pan, id2row, counts, min_area, out):
+    """out = pan where the id is listed and has at least min_area pixels in its camera, else 0"""
+    B, hw, S = _mesh_area_args(pan, id2row, counts)
+    _dev(out, torch.int32)
+    assert out.is_contiguous() and out.shape == pan.shape and out.device == pan.device and out.data_ptr() != pan.data_ptr()
+    _call('pst_mesh_area_apply', _ptr(pan), B, hw, _ptr(id2row), id2row.numel(), S, _ptr(counts), int(min_area), _ptr(out))
 
 
 # ------------------------------------------------------------------ panoptic evaluation (csrc/evaluate.hip; engine/evaluate.py holds the public entry point)
