@@ -627,6 +627,50 @@ int pst_mesh_area_count(const int32_t* pan, int ncams, int64_t hw, const int32_t
 int pst_mesh_area_apply(const int32_t* pan, int ncams, int64_t hw, const int32_t* id2row, int ntab, int S, const int32_t* counts, int min_area, int32_t* out,
                         void* stream);
 
+/* ---------------------------------------------------------------- surface: the pointmap grids triangulated into one labelled mesh (no counterpart in the reference)
+ * Every view's pointmap is a grid, so pixel neighbours are surface neighbours.  The mesh's vertices ARE the rows of the panoptic cloud (points, pan
+ * and colors of pst_cloud_compact: nothing is copied or compacted, a vertex that no face uses is allowed); these entry points only make the faces.
+ * Restated in tests/surface_ref.py [restated, parity unpinned]; integer work and fp32 compares only, so the outputs are held to the restatement bit
+ * for bit.  View v is an H x W grid of npix = H W pixels, pixel (y, x) is scene pixel p = offset + y W + x; N = the scene's pixels, 1 <= N <= 2^30.
+ *   1 rows      row int32 [N]: row[p] = the cloud row i with index[i] == p, or -1 if the confidence filter dropped the pixel (index int64 [M] as
+ *               pst_cloud_compact wrote it: ascending, distinct).
+ *   2 quads     for every view and every (y, x) with 0 <= y < H - 1, 0 <= x < W - 1, corners a = (y, x), b = (y, x + 1), c = (y + 1, x),
+ *               d = (y + 1, x + 1).  The z of a present corner is the THIRD COMPONENT OF pts3d_local AT ITS PIXEL, the depth in the source camera
+ *               (not of the cloud's points_local, which pst_cloud_compact moved to the world frame).
+ *               Four corners present: two candidate triangles, split along the diagonal with the smaller |dz| - diagonal b-c iff
+ *               |z_b - z_c| < |z_a - z_d| (one fp32 subtraction each), so a tie or a NaN takes a-d.
+ *                 a-d: T0 = (a, c, d), T1 = (a, d, b)        b-c: T0 = (a, c, b), T1 = (b, c, d)
+ *               Exactly three present: the one triangle of them, as T0 - missing d: (a, c, b), a: (b, c, d), b: (a, c, d), c: (a, d, b).
+ *               Fewer: nothing.  Every winding faces the source camera: (v1 - v0) x (v2 - v0) has negative z in its frame (x right, y down, z forward).
+ *   3 cut       a candidate is kept iff zmin > 0 && zmax <= zmin * k over its three corners: one fp32 product, NaN fails, equality keeps.
+ *               k = float32(1 + max_depth_ratio) >= 1; k = +inf is "no cut" (zmin > 0 still applies: the product is +inf, never 0 * inf).
+ *   4 face id   the id that at least two of the corners' vertex_ids share, 0 (void) if all three differ.
+ *   5 order     by view, then by quad in raster order (y, then x), then T0 before T1 -> rows [0, F) of faces int32 [., 3] (cloud rows), face_ids int32
+ *               [.], quad int64 [.] (the scene pixel of the face's corner a).  F is only known on the device: every output holds the bound, two
+ *               faces per quad.  A workgroup of PST_SURFACE_WG threads takes that many consecutive quads of one view, one per thread; dims int32
+ *               [nviews, 4] on the device = (H, W, first_wg, 0) per view, where view v owns the ceil((H - 1)(W - 1) / PST_SURFACE_WG) workgroups from
+ *               first_wg on (none for a view without quads) and nwg = their sum.  `views` is the cloud's table (offset, pts3d_local, npix = H W).
+ *               surface_count -> counts int32 [nwg]; pst_cloud_scan -> base int32 [nwg + 1], base[nwg] = F; surface_emit evaluates every quad
+ *               again and stores at base[wg] + the wave's ballots.  No atomics: the order holds by construction.
+ *   6 islands   two faces are connected when they share a vertex row; components are the transitive closure (views never share a vertex).
+ *               surface_link: parent int32 [M] and size int32 [M] are initialised here (parent[v] = v, size = 0), then unite(v0, v1), unite(v0, v2) per
+ *               face (wait-free union-find: the root is the component's smallest vertex row).  surface_components: component int32 [F] = that root,
+ *               size[root] += 1 per face (int32 atomicAdd: a sum of integers).  surface_keep_count / pst_cloud_scan / surface_keep_emit: the faces
+ *               with size[component] >= min_faces (>= 1) in their order, one per thread, PST_SURFACE_WG per workgroup: counts int32 [ceil(F / WG)].
+ *               status int32 [1], zeroed by the caller: PST_VCC_RANGE (a face index outside [0, M)), PST_VCC_LOOP (a bounded loop ran out) - never on
+ *               the faces of surface_emit.  1 <= F <= 2^31 - 256, 1 <= M <= 2^30. */
+#define PST_SURFACE_WG 256
+int pst_surface_rows(const int64_t* index, int64_t M, int64_t N, int32_t* row, void* stream);
+int pst_surface_count(const pst_cloud_view* views, const int32_t* dims, int nviews, int nwg, const int32_t* row, float k, int32_t* counts, void* stream);
+int pst_surface_emit(const pst_cloud_view* views, const int32_t* dims, int nviews, int nwg, const int32_t* row, float k, const int32_t* vertex_ids,
+                     const int32_t* base, int32_t* faces, int32_t* face_ids, int64_t* quad, void* stream);
+int pst_surface_link(const int32_t* faces, int64_t F, int64_t M, int32_t* parent, int32_t* size, int32_t* status, void* stream);
+int pst_surface_components(const int32_t* faces, int64_t F, int64_t M, const int32_t* parent, int32_t* component, int32_t* size, int32_t* status,
+                           void* stream);
+int pst_surface_keep_count(const int32_t* component, const int32_t* size, int64_t F, int min_faces, int32_t* counts, void* stream);
+int pst_surface_keep_emit(const int32_t* faces, const int32_t* face_ids, const int64_t* quad, const int32_t* component, const int32_t* size, int64_t F,
+                          int min_faces, const int32_t* base, int32_t* out_faces, int32_t* out_face_ids, int64_t* out_quad, void* stream);
+
 /* ---------------------------------------------------------------- panoptic evaluation against ground truth: PQ / SQ / RQ, mIoU (no counterpart in the reference)
  * V predicted maps and V ground-truth maps of the same shapes, flattened and concatenated to pred, gt int32 [N] (1 <= N <= 2^31 - 1, both 16-byte
  * aligned), P predicted and G ground-truth segments (ids unique and > 0 within each list, no crowd regions).  The rules are those of COCO

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "../../include/panst3r_hip.h"
 #include "voxel_table.h"
+#include "union_find.h"          // cc_load, cc_find, cc_unite
 
 #pragma clang fp contract(off)
 
@@ -84,37 +85,6 @@ __global__ __launch_bounds__(CC_T) void vcc_build_kernel(const int32_t* __restri
     h = (h + 1) & mask;
   }
   atomicOr(status, CC_FULL);
-}
-
-__device__ __forceinline__ int cc_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// root of x as far as this thread can see, with path halving: parent[x] = its grandparent (atomicMin: values only decrease).  x falls in every step.
-__device__ __forceinline__ int cc_find(int32_t* __restrict__ parent, int x, int bound, int32_t* __restrict__ status) {
-  for (int it = 0; it < bound; ++it) {
-    const int p = cc_load(&parent[x]);
-    if (p == x) return x;
-    const int g = cc_load(&parent[p]);
-    if (g == p) return p;
-    atomicMin(&parent[x], g);
-    x = g;
-  }
-  atomicOr(status, CC_LOOP);
-  return x;
-}
-
-// wait-free union: the larger of the two roots is hooked under the smaller.  When the atomic finds that `hi` was hooked by someone else (old < hi), hi now
-// hangs under min(old, lo) and what is left is to unite old and lo: max(a, b) falls in every round, so there are at most `bound` of them.
-__device__ __forceinline__ void cc_unite(int32_t* __restrict__ parent, int a, int b, int bound, int32_t* __restrict__ status) {
-  a = cc_find(parent, a, bound, status);
-  b = cc_find(parent, b, bound, status);
-  for (int it = 0; it < bound && a != b; ++it) {                    // both finds agree: no atomic
-    const int hi = max(a, b), lo = min(a, b);
-    const int old = atomicMin(&parent[hi], lo);
-    if (old == hi) return;
-    a = cc_find(parent, old, bound, status);
-    b = cc_find(parent, lo, bound, status);
-  }
-  if (a != b) atomicOr(status, CC_LOOP);
 }
 
 __global__ __launch_bounds__(CC_T) void vcc_link_kernel(const int32_t* __restrict__ cells, const int32_t* __restrict__ pan, int Mv, const uint64_t* __restrict__ keys,

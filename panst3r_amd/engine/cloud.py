@@ -112,6 +112,11 @@ class PanopticCloud:
         from .render import render_cloud
         return render_cloud(self, cams2world, focals, shape, **kw)
 
+    def mesh(self, **kw):
+        """engine.surface.panoptic_mesh of this cloud"""
+        from .surface import panoptic_mesh
+        return panoptic_mesh(self, **kw)
+
     def cpu(self):
         f = lambda t: t.cpu()
         return PanopticCloud(f(self.points), f(self.points_local), f(self.rgb), f(self.pan), f(self.colors), f(self.index), list(self.view_offsets),
@@ -176,6 +181,7 @@ class _Source:
         self.id2row = torch.from_numpy(row).to(self.device)
         self.cameras = None if focals is None else camera_frusta(self.shapes, focals, cams2world)
         self.local_pointmaps = bool(local_pointmaps)
+        self.surface_dims = None                                               # (table, workgroups) of the quad kernels, built by engine.surface on first use
 
     def set_colors(self, colors):
         if colors is None:

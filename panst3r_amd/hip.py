@@ -75,6 +75,8 @@ SIGNATURES = {
     'pst_pq_count': 'i:pplpipipiiipip', 'pst_pq_match': 'i:piiipppppppp',
     'pst_vcc_cells': 'i:ppplfpp', 'pst_vcc_build': 'i:pplpplppp', 'pst_vcc_link': 'i:pplpplippp', 'pst_vcc_flatten': 'i:ppplppppppip', 'pst_vcc_count': 'i:plpp',
     'pst_vcc_rank': 'i:pplpppppppppppppp', 'pst_vcc_votes': 'i:pppplppliipplpp', 'pst_vcc_apply': 'i:pppplippiffpppp',
+    'pst_surface_rows': 'i:pllpp', 'pst_surface_count': 'i:ppiipfpp', 'pst_surface_emit': 'i:ppiipfpppppp', 'pst_surface_link': 'i:pllpppp',
+    'pst_surface_components': 'i:pllppppp', 'pst_surface_keep_count': 'i:pplipp', 'pst_surface_keep_emit': 'i:ppppplippppp',
 }
 EXPORTS = list(SIGNATURES)
 
@@ -1509,3 +1511,93 @@ def pq_match(counts, cat_p, cat_g, pred_area, gt_area, match, iou, pred_state):
     assert tuple(gt_area.shape) == tuple(match.shape) == tuple(iou.shape) == (S, G)
     nz = lambda t: _ptr(t) if t.numel() else None
     _call('pst_pq_match', _ptr(counts), S, P, G, nz(cat_p), nz(cat_g), nz(pred_area), nz(gt_area), nz(match), nz(iou), nz(pred_state))
+
+
+# ------------------------------------------------------------------ surface mesh of the pointmap grids (csrc/surface.hip; engine/surface.py holds the public entry points)
+SURFACE_WG = 256                    # PST_SURFACE_WG: quads (count / emit) or faces (islands) per workgroup, one per thread
+SURFACE_MAX_PIXELS = 1 << 30        # scenes beyond this are refused: the face count (two per quad) stays inside int32
+
+
+def surface_dims(shapes, device):
+    """device table int32 [V, 4] = (H, W, first_wg, 0) of the quad kernels for views of the shapes (H, W) -> (tensor, number of workgroups)"""
+    rows, wg = [], 0
+    for H, W in shapes:
+        rows.append((int(H), int(W), wg, 0))
+        wg += (max(H - 1, 0) * max(W - 1, 0) + SURFACE_WG - 1) // SURFACE_WG
+    return torch.tensor(rows, dtype=torch.int32).reshape(-1, 4).to(device), wg
+
+
+def surface_rows(index, N, row):
+    """row int32 [N]: the cloud row of every scene pixel (index int64 [M] of the cloud), -1 for a pixel that was filtered out"""
+    _dev(index, torch.int64); _dev(row, torch.int32)
+    assert index.is_contiguous() and row.is_contiguous() and row.numel() == N and index.numel() <= N
+    _call('pst_surface_rows', _ptr(index) if index.numel() else None, index.numel(), N, _ptr(row))
+
+
+def _surface_quads(table, dims, nviews, nwg, row):
+    _dev(table, torch.uint8); _dev(dims, torch.int32); _dev(row, torch.int32)
+    assert table.numel() == nviews * C.sizeof(CloudView) and dims.is_contiguous() and tuple(dims.shape) == (nviews, 4) and row.is_contiguous() and nwg > 0
+
+
+def surface_count(table, dims, nviews, nwg, row, k, counts):
+    """counts int32 [nwg]: the faces of every workgroup's quads (table: the cloud's view table, dims: `surface_dims`, k = float32(1 + max_depth_ratio) or inf)"""
+    _surface_quads(table, dims, nviews, nwg, row)
+    _dev(counts, torch.int32)
+    assert counts.numel() == nwg
+    _call('pst_surface_count', _ptr(table), _ptr(dims), nviews, nwg, _ptr(row), float(k), _ptr(counts))
+
+
+def surface_emit(table, dims, nviews, nwg, row, k, vertex_ids, base, faces, face_ids, quad):
+    """faces int32 [., 3], face_ids int32 [.], quad int64 [.]: rows [0, base[nwg]) are written; each holds two rows per quad of the scene"""
+    _surface_quads(table, dims, nviews, nwg, row)
+    _dev(vertex_ids, torch.int32); _dev(base, torch.int32); _dev(faces, torch.int32); _dev(face_ids, torch.int32); _dev(quad, torch.int64)
+    cap = face_ids.numel()
+    assert base.numel() == nwg + 1 and cap >= 2 * SURFACE_WG * nwg and quad.numel() == cap and faces.numel() == 3 * cap
+    assert all(t.is_contiguous() for t in (vertex_ids, faces, face_ids, quad))
+    _call('pst_surface_emit', _ptr(table), _ptr(dims), nviews, nwg, _ptr(row), float(k), _ptr(vertex_ids), _ptr(base), _ptr(faces), _ptr(face_ids), _ptr(quad))
+
+
+def surface_workspace(M, device):
+    """parent, size int32 [M] (initialised by surface_link) and the zeroed status word of one labelling of a mesh on M vertex rows"""
+    return {'parent': torch.empty(M, dtype=torch.int32, device=device), 'size': torch.empty(M, dtype=torch.int32, device=device),
+            'status': torch.zeros(1, dtype=torch.int32, device=device)}
+
+
+def _surface_faces(faces, ws):
+    _dev(faces, torch.int32)
+    F, M = faces.shape[0], ws['parent'].numel()
+    assert faces.is_contiguous() and tuple(faces.shape) == (F, 3) and F > 0 and M > 0 and ws['size'].numel() == M
+    return F, M
+
+
+def surface_link(faces, ws):
+    F, M = _surface_faces(faces, ws)
+    _call('pst_surface_link', _ptr(faces), F, M, _ptr(ws['parent']), _ptr(ws['size']), _ptr(ws['status']))
+
+
+def surface_components(faces, ws, component):
+    """component int32 [F] = the smallest vertex row of every face's component; ws['size'][root] = the component's faces"""
+    F, M = _surface_faces(faces, ws)
+    _dev(component, torch.int32)
+    assert component.is_contiguous() and component.numel() == F
+    _call('pst_surface_components', _ptr(faces), F, M, _ptr(ws['parent']), _ptr(component), _ptr(ws['size']), _ptr(ws['status']))
+
+
+def surface_keep_count(component, ws, min_faces, counts):
+    _dev(component, torch.int32); _dev(counts, torch.int32)
+    F = component.numel()
+    assert counts.numel() == (F + SURFACE_WG - 1) // SURFACE_WG
+    _call('pst_surface_keep_count', _ptr(component), _ptr(ws['size']), F, int(min_faces), _ptr(counts))
+
+
+def surface_keep_emit(faces, face_ids, quad, component, ws, min_faces, base, out_faces, out_face_ids, out_quad):
+    """the faces whose component has at least min_faces faces, in their order -> rows [0, base[-1]) of the outputs (each as long as its input)"""
+    F, _ = _surface_faces(faces, ws)
+    for t, dt in ((face_ids, torch.int32), (quad, torch.int64), (component, torch.int32), (base, torch.int32), (out_faces, torch.int32),
+                  (out_face_ids, torch.int32), (out_quad, torch.int64)):
+        _dev(t, dt)
+        assert t.is_contiguous()
+    assert face_ids.numel() == quad.numel() == component.numel() == out_face_ids.numel() == out_quad.numel() == F and out_faces.numel() == 3 * F
+    assert base.numel() == (F + SURFACE_WG - 1) // SURFACE_WG + 1
+    _call('pst_surface_keep_emit', _ptr(faces), _ptr(face_ids), _ptr(quad), _ptr(component), _ptr(ws['size']), F, int(min_faces), _ptr(base), _ptr(out_faces),
+          _ptr(out_face_ids), _ptr(out_quad))

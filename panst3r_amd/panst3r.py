@@ -375,6 +375,7 @@ class PanSt3R(nn.Module):
         fewer voxels takes the id of its large neighbours or becomes void (`VoxelCloud.clean_labels`), and the voxels returned are the cleaned ones.
         Images out of the result: `engine.render_cameras(cloud, cameras)` re-renders the cloud (or the voxels) from the input cameras, and
         `cloud.render(engine.orbit_cameras(...), focal, (H, W))` from any other - depth, panoptic map and colours per pixel (engine/render.py).
+        A surface out of the result: `cloud.mesh()` triangulates the pointmap grids into a labelled mesh on the cloud's rows (engine/surface.py).
         It only composes the public entry points."""
         from .engine import panoptic_inference_v2, panoptic_inference_v1, panoptic_inference_qubo, panoptic_point_cloud
         from .engine.pointmaps import cameras_from_pointmaps

@@ -1,0 +1,235 @@
+"""The surface mesh of the pointmap grids on the GPU (csrc/surface.hip, panst3r_amd/engine/surface.py) against the numpy restatement of
+tests/surface_ref.py: faces, face ids, quads and F BIT FOR BIT - integer work and fp32 compares leave no tolerance to choose - then the islands, and the
+hand-over to the mesh rasteriser, the PLY reader and the evaluation.
+
+Conditions, not measurements: before the GPU is compared, `check_conditions` asserts ON THE RESTATEMENT that the generated scene (surface_ref.scene)
+holds what it was built for - quads with 4, 3 (each pattern), 2 and 0 corners, both diagonals and an exact tie, a quad whose T0 is cut while T1
+survives and the reverse, a triangle at exact equality of the cut (kept) and one a float32 above it (cut), corners with z = 0, z < 0 and NaN, faces
+with three, two and no equal ids, a view with points but no face, a view without a point (at the second threshold), islands of exactly 1, 5 and 6
+faces beside large patches, and two triangles that touch in one vertex only.  (tests/test_surface_host.py runs the same check without a GPU.)"""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import surface_ref as S
+import render_ref as R
+import eval_ref as E
+from panst3r_amd.engine import panoptic_point_cloud, panoptic_quality, load_ply_mesh, PanopticMesh, MeshRender
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+F = np.float32
+KEYS = ('faces', 'face_ids', 'quad')
+OFF = [0] + list(np.cumsum([h * w for h, w in S.SHAPES]))
+NOVEL = S._pose(1, -10, (0.5, -0.1, -0.6))
+
+
+def bits(a):
+    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return np.ascontiguousarray(a).view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+@functools.lru_cache(maxsize=None)
+def scene():
+    return S.scene()
+
+
+@functools.lru_cache(maxsize=None)
+def reference(thr=S.THR, ratio=0.1):
+    """(cloud, mesh) of the scene by the restatements (computed once per setting, shared, never written to)"""
+    return S.of_scene(scene(), thr, ratio)
+
+
+def pixel(view, y, x):
+    return OFF[view] + y * S.SHAPES[view][1] + x
+
+
+def check_conditions():
+    cloud, m = reference()
+    marks = scene()[5]
+    M, faces = len(cloud['index']), m['faces']
+    n, present, has, keep = m['corners'], m['present'], m['has'], m['keep']
+    assert {0, 2, 3, 4} <= set(np.unique(n).tolist())
+    for missing in range(4):                                                   # each of the four three-corner patterns, with a face
+        assert ((n == 3) & ~present[:, missing] & keep[:, 0]).any(), missing
+    assert m['bc'].any() and ((n == 4) & ~m['bc'] & ~m['tie']).any() and m['tie'].any()
+    both = has[:, 0] & has[:, 1]
+    assert (both & ~keep[:, 0] & keep[:, 1]).any() and (both & keep[:, 0] & ~keep[:, 1]).any()
+    with np.errstate(invalid='ignore'):
+        at, above = keep & (m['zmax'] == m['bound']) & (m['zmin'] < m['zmax']), has & ~keep & (m['zmax'] == np.nextafter(m['bound'], F(np.inf)))
+        assert at.any() and above.any()
+        assert (has & (m['zmin'] == 0)).any() and (has & (m['zmin'] < 0)).any() and (has & np.isnan(m['zmin'])).any()
+        assert not (keep & ~(m['zmin'] > 0)).any()
+    ids = cloud['pan'][faces]
+    same = (ids[:, 0] == ids[:, 1]).astype(int) + (ids[:, 0] == ids[:, 2]) + (ids[:, 1] == ids[:, 2])
+    assert (same == 3).any() and (same == 1).any() and (same == 0).any() and (m['face_ids'][same == 0] == 0).all() and (m['face_ids'][same > 0] > 0).any()
+    in_view = lambda a, v: (a >= OFF[v]) & (a < OFF[v + 1])
+    assert in_view(cloud['index'], 3).sum() == 3 and not in_view(m['quad'], 3).any()                   # points, but no face
+    assert all(in_view(m['quad'], v).any() for v in range(3))
+    cloud2, m2 = reference(S.THR_WITHOUT_VIEW0)
+    assert not in_view(cloud2['index'], 0).any() and in_view(cloud2['index'], 1).any() and len(m2['faces']) == len(faces) - in_view(m['quad'], 0).sum() > 0
+    comp = S.face_component(faces, M)
+    size = np.bincount(comp, minlength=M)
+    of = lambda name, dy=0, dx=0: comp[m['quad'] == pixel(1, marks[name][0] + dy, marks[name][1] + dx)]
+    assert size[of('island1')].tolist() == [1] and set(size[of('island5')]) == {5} and set(size[of('island6')]) == {6} and size.max() > 200
+    a, b = of('touch'), of('touch', 1, 1)
+    fa, fb = faces[m['quad'] == pixel(1, *marks['touch'])], faces[m['quad'] == pixel(1, marks['touch'][0] + 1, marks['touch'][1] + 1)]
+    assert len(a) == len(b) == 1 and a[0] == b[0] and size[a[0]] == 2 and len(set(fa[0]) & set(fb[0])) == 1
+    d2, d6 = S.drop_small(m, M, 2), S.drop_small(m, M, 6)
+    assert len(faces) > len(d2['faces']) > len(d6['faces']) > 200
+    assert pixel(1, *marks['island5']) in d2['quad'] and pixel(1, *marks['island5']) not in d6['quad'] and pixel(1, *marks['island6']) in d6['quad']
+    assert len(reference(S.THR, 0.0)[1]['faces']) < len(faces) < len(reference(S.THR, None)[1]['faces'])      # the other two settings differ, in both directions
+    assert 5000 < len(faces) < 2 * sum((h - 1) * (w - 1) for h, w in S.SHAPES)
+
+
+# ---------------------------------------------------------------- the plane of the hole count
+PLANE_SHAPE, NEAR_CAM = (24, 32), np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 1.0], [0, 0, 0, 1]])      # the plane lies at z = 2: half the distance
+
+
+@functools.lru_cache(maxsize=None)
+def plane_reference():
+    sc = S.plane_scene(PLANE_SHAPE)
+    cloud, m = S.of_scene(sc, S.THR)
+    f = S.focal_of(PLANE_SHAPE)
+    splat = R.render(cloud['points'], cloud['rgb'], cloud['colors'], cloud['pan'], [NEAR_CAM], f, PLANE_SHAPE, radius=0)
+    return sc, cloud, m, int((splat['index'] >= 0).sum()), int((S.render(cloud['points'], m, [NEAR_CAM], f, PLANE_SHAPE)['face'] >= 0).sum())
+
+
+def check_plane():
+    sc, cloud, m, splat_hits, mesh_hits = plane_reference()
+    H, W = PLANE_SHAPE
+    assert len(m['faces']) == 2 * (H - 1) * (W - 1)
+    assert 0 < splat_hits < mesh_hits == H * W                                 # the splat leaves holes, the surface none
+
+
+# ---------------------------------------------------------------- the GPU side
+def to_dev(sc):
+    x, im, pan, info, cams = sc[:5]
+    xd = [{k: torch.from_numpy(v).to(DEV) for k, v in d.items()} for d in x]
+    return xd, [torch.from_numpy(i).to(DEV) for i in im], [torch.from_numpy(p).to(DEV) for p in pan], info, [torch.from_numpy(c) for c in cams]
+
+
+def build_cloud(sc, thr):
+    xd, imd, pand, info, camd = to_dev(sc)
+    return panoptic_point_cloud(xd, imd, None, pand, info, camd, [S.focal_of(x['conf'].shape) for x in sc[0]], min_conf_thr=thr)
+
+
+@functools.lru_cache(maxsize=None)
+def device_cloud():
+    cloud = build_cloud(scene(), S.THR)
+    ref = reference()[0]
+    assert np.array_equal(cloud.index.cpu().numpy(), ref['index']) and np.array_equal(cloud.pan.cpu().numpy(), ref['pan'])
+    assert np.array_equal(cloud.points.cpu().numpy(), ref['points'], equal_nan=True)
+    return cloud
+
+
+def assert_same(got, want):
+    assert isinstance(got, PanopticMesh) and len(got) == len(want['faces'])
+    for k in KEYS:
+        g, w = getattr(got, k), want[k]
+        assert tuple(g.shape) == w.shape and g.cpu().numpy().dtype == w.dtype, (k, tuple(g.shape), w.shape, g.dtype, w.dtype)
+        assert np.array_equal(bits(g), bits(w)), (k, int((bits(g) != bits(w)).sum()))
+
+
+@pytest.mark.parametrize('ratio', [0.1, 0.0, None])
+def test_faces_ids_and_quads_equal_the_restatement(ratio):
+    if ratio == 0.1:
+        check_conditions()
+    cloud = device_cloud()
+    mesh = cloud.mesh(max_depth_ratio=ratio)
+    assert_same(mesh, reference(S.THR, ratio)[1])
+    assert mesh.vertices.data_ptr() == cloud.points.data_ptr() and mesh.vertex_ids.data_ptr() == cloud.pan.data_ptr()      # the cloud's rows: no copies
+    assert mesh.colors.data_ptr() == cloud.colors.data_ptr() and mesh.view_offsets == OFF and mesh.cameras is cloud.cameras
+    assert_same(cloud.mesh(max_depth_ratio=ratio), reference(S.THR, ratio)[1])                                           # a second call: the same bytes
+    h = mesh.cpu()
+    assert h.faces.device.type == 'cpu' and np.array_equal(bits(h.quad), bits(mesh.quad))
+
+
+def test_a_view_without_a_point_and_the_empty_mesh():
+    cloud = device_cloud().rethreshold(S.THR_WITHOUT_VIEW0)
+    want_cloud, want = reference(S.THR_WITHOUT_VIEW0)
+    assert np.array_equal(cloud.index.cpu().numpy(), want_cloud['index'])
+    assert_same(cloud.mesh(), want)
+    for empty in (device_cloud().rethreshold(100.0).mesh(), build_cloud(S.grid_scene(2, 2), 1.0).mesh(max_depth_ratio=None).drop_small(3)):
+        assert len(empty) == 0 and tuple(empty.faces.shape) == (0, 3) and empty.faces.dtype == torch.int32 and empty.face_ids.dtype == torch.int32
+        assert empty.quad.dtype == torch.int64 and empty.faces.is_cuda and len(empty.drop_small(2)) == 0 and tuple(empty.face_component().shape) == (0,)
+        assert not empty.render([NOVEL], 20.0, (8, 8)).hit.any()
+    assert len(device_cloud().rethreshold(100.0)) == 0
+
+
+@pytest.mark.parametrize('ratio', [0.1, None])
+def test_islands(ratio):
+    (cloud, m), mesh = reference(S.THR, ratio), device_cloud().mesh(max_depth_ratio=ratio)
+    M = len(cloud['index'])
+    comp = mesh.face_component()
+    assert comp.dtype == torch.int32 and np.array_equal(comp.cpu().numpy(), S.face_component(m['faces'], M))
+    for n in (2, 6):
+        want = S.drop_small(m, M, n)
+        assert len(want['faces']) < len(m['faces'])
+        got = mesh.drop_small(n)
+        assert_same(got, want)
+        assert got.vertices.data_ptr() == mesh.vertices.data_ptr()            # the vertices are untouched
+    assert_same(mesh.drop_small(1), m)
+    assert_same(device_cloud().mesh(max_depth_ratio=ratio).drop_small(2), S.drop_small(m, M, 2))       # without face_component() first
+
+
+def source_views():
+    cams = scene()[4]
+    return [(cams[2], S.focal_of(S.SHAPES[2]), S.SHAPES[2]), (cams[1], S.focal_of(S.SHAPES[1]), S.SHAPES[1]), (NOVEL, 40.0, (48, 64))]
+
+
+@functools.lru_cache(maxsize=None)
+def reference_renders():
+    cloud, m = reference()
+    return [S.render(cloud['points'], m, [c], f, shape) for c, f, shape in source_views()]
+
+
+def test_renders_through_the_mesh_rasteriser_equal_the_restatements():
+    mesh = device_cloud().mesh()
+    for (c, f, shape), want in zip(source_views(), reference_renders()):
+        assert (want['face'] >= 0).sum() > 50
+        got = mesh.render([c], f, shape)
+        assert isinstance(got, MeshRender)
+        for k in ('depth', 'face', 'pan'):
+            g = getattr(got, k)
+            assert tuple(g.shape) == want[k].shape and g.cpu().numpy().dtype == want[k].dtype and np.array_equal(bits(g), bits(want[k])), k
+
+
+def test_the_surface_has_no_holes_where_the_splat_has():
+    check_plane()
+    sc, ref_cloud, m, splat_hits, mesh_hits = plane_reference()
+    cloud = build_cloud(sc, S.THR)
+    f = S.focal_of(PLANE_SHAPE)
+    got_mesh, got_splat = int(cloud.mesh().render([NEAR_CAM], f, PLANE_SHAPE).hit.sum()), int(cloud.render([NEAR_CAM], f, PLANE_SHAPE, radius=0).hit.sum())
+    print('camera at half the distance: the splat hits %d of %d pixels, the surface %d' % (got_splat, PLANE_SHAPE[0] * PLANE_SHAPE[1], got_mesh))
+    assert got_mesh > got_splat and (got_mesh, got_splat) == (mesh_hits, splat_hits)
+
+
+def test_ply_round_trip(tmp_path):
+    mesh = device_cloud().mesh().drop_small(2)
+    path = mesh.write_ply(str(tmp_path / 'surface.ply'))
+    v, f = load_ply_mesh(path)
+    assert np.array_equal(bits(v), bits(mesh.vertices)) and np.array_equal(f.numpy(), mesh.faces.cpu().numpy().astype(np.int64))
+    M, Fn = len(mesh.vertices), len(mesh)
+    raw = open(path, 'rb').read()
+    body = raw[raw.index(b'end_header\n') + 11:]
+    assert len(body) == 19 * M + 17 * Fn
+    vert = np.frombuffer(body, dtype=np.dtype([('xyz', '<f4', (3,)), ('rgb', 'u1', (3,)), ('label', '<i4')]), count=M)
+    face = np.frombuffer(body[19 * M:], dtype=np.dtype([('n', 'u1'), ('v', '<i4', (3,)), ('label', '<i4')]), count=Fn)
+    assert np.array_equal(vert['label'], mesh.vertex_ids.cpu().numpy()) and np.array_equal(face['label'], mesh.face_ids.cpu().numpy()) and (face['n'] == 3).all()
+    cloud_path = device_cloud().write_ply(str(tmp_path / 'cloud.ply'))
+    cloud_raw = open(cloud_path, 'rb').read()
+    assert body[:19 * M] == cloud_raw[cloud_raw.index(b'end_header\n') + 11:]  # exactly the cloud's rows
+
+
+def test_the_render_from_a_source_camera_scores_against_its_own_map():
+    sc = scene()
+    info, gt = sc[3], sc[2][2]
+    c, f, shape = source_views()[0]
+    pred = device_cloud().mesh().render([c], f, shape).pan[0]
+    r = panoptic_quality([pred], info, [gt], info)
+    want = E.panoptic_quality([reference_renders()[0]['pan'][0]], info, [gt], info)
+    print('pq %.3f sq %.3f rq %.3f miou %.3f' % (r['pq'], r['sq'], r['rq'], r['miou']))
+    assert 0 < r['pq'] <= 1 and r['pq'] == want['pq'] and r['miou'] == want['miou'] and E.totals(r) == E.totals(want)
