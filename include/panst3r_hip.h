@@ -309,6 +309,8 @@ int pst_attn_mask_from_logits(const float* logits, int64_t ldl, uint8_t* mask, i
 /* guidance_gn: the same features followed by GroupNorm(1 group, affine) WITHOUT materialising them: a statistics pass and a
  *   normalise-and-store pass both recompute the features per pixel (no fp32 feature round trip through HBM).
  *   y bf16 [nimg*P, ldy], columns [10*nf+3, ldy) zero; scratch >= nimg*(3*P + 6) floats; stats as for pst_loftup_guidance.
+ *   ldy: a multiple of 8, 10*nf+3 <= ldy <= 512; a 16-bit y stages 64 rows of ldy + 8 elements in LDS, which fits the 64 KiB a block may ask for up to
+ *   ldy = 496: a larger 16-bit ldy is PST_EINVAL (fp32 rows use no tile: up to 512).
  *   (loftup.py:117-124: fourier_feat -> first GroupNorm of first_conv)
  *   mm_ext (ABI 17): NULL = every view is scaled with its OWN per-channel min / max (the demo's max_bs=1 convention, tools/demo_panst3r.py:201); else
  *   fp32 [nimg][3][2] (min, max) per (view, channel) to scale with - the reference's MinMaxScaler takes min / max over the whole chunk of views it is

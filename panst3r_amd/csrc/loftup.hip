@@ -374,6 +374,8 @@ extern "C" int pst_minmax_merge(const float* mm, const int32_t* scope, float* ou
   return check_launch("minmax_merge");
 }
 
+constexpr int GUIDANCE_LDS_LIMIT = 64 * 1024;       // dynamic LDS a block may ask for without hipFuncAttributeMaxDynamicSharedMemorySize
+
 extern "C" int pst_loftup_guidance_gn(const float* img, const float* biases, const float* gamma, const float* beta, float eps,
                                       float* scratch, float* stats, void* y, int64_t ldy, int nimg, int H, int W, int nf, int dtype16,
                                       const float* mm_ext, void* stream) {
@@ -381,6 +383,15 @@ extern "C" int pst_loftup_guidance_gn(const float* img, const float* biases, con
   if ((dtype16 != DT_BF16 && dtype16 != DT_F16 && dtype16 != DT_F32) || !img || !biases || !gamma || !beta || !scratch || !stats || !y || nimg <= 0 || H % 2 || W % 2 || nf < 2 || nf > 64 || ldy < CHc ||
       ldy % 8 || ldy > 512 || ((uintptr_t)y & 15)) {
     set_error("loftup_guidance_gn: bad argument (nf=%d ldy=%lld)", nf, (long long)ldy); return PST_EINVAL;
+  }
+  // the apply pass stages 64 rows of 16-bit output in dynamic LDS behind the frequency table (fp32 rows go straight to memory: no tile).  No function
+  // attribute raises this kernel's limit, so a request beyond the default per-block limit cannot be launched: refuse it here
+  const size_t lds0 = ((nf + 4 + 3) & ~3) * sizeof(float);
+  const size_t lds1 = lds0 + (dtype16 == DT_F32 ? 0 : 64 * (size_t)(ldy + 8) * sizeof(bf16_t));
+  if (lds1 > GUIDANCE_LDS_LIMIT) {
+    set_error("loftup_guidance_gn: a 16-bit ldy=%lld needs %zu bytes of LDS, over the limit of %d bytes per block (largest ldy: 496)", (long long)ldy, lds1,
+              GUIDANCE_LDS_LIMIT);
+    return PST_EINVAL;
   }
   hipStream_t s = (hipStream_t)stream;
   const int H2 = H / 2, W2 = W / 2, P = H2 * W2;
@@ -391,11 +402,10 @@ extern "C" int pst_loftup_guidance_gn(const float* img, const float* biases, con
   const int ntile = (P + 63) / 64;
   const int gx = ntile < PST_STATS_BLOCKS ? ntile : PST_STATS_BLOCKS;
   float* part = stats + 2 * nimg;                        // [nimg][gx][2] partial sums behind the result
-  const size_t lds0 = ((nf + 4 + 3) & ~3) * sizeof(float);
   hipLaunchKernelGGL((guidance_px_kernel<false>), dim3(gx, nimg), dim3(256), lds0, s, img2, mmu, biases, part, (const float*)nullptr,
                      (const float*)nullptr, (const float*)nullptr, 0.f, (bf16_t*)nullptr, ldy, H2, W2, nf, dtype16);
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((nimg * 2 + 3) / 4), dim3(256), 0, s, part, stats, nimg, gx, 2);
-  hipLaunchKernelGGL((guidance_px_kernel<true>), dim3(ntile, nimg), dim3(256), lds0 + 64 * (ldy + 8) * sizeof(bf16_t), s, img2, mmu, biases,
+  hipLaunchKernelGGL((guidance_px_kernel<true>), dim3(ntile, nimg), dim3(256), lds1, s, img2, mmu, biases,
                      (float*)nullptr, stats, gamma, beta, eps, (bf16_t*)y, ldy, H2, W2, nf, dtype16);
   return check_launch("loftup_guidance_gn");
 }

@@ -402,3 +402,74 @@ def moments_bound(abs_terms, nadd, dw_terms):
     rounding of w = conf + weight_offset: dw_terms = the same moments of |fl32(conf + off) - (conf + off)|, which the CPU computes exactly (0 with offset 0);
     allowed twice, like every rounding here"""
     return (nadd + 3) * 2.0 ** -53 * abs_terms + R * dw_terms
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------- LoftUp guidance
+# loftup.hip's sincos_cw (Cody-Waite reduction by three fma steps, Cephes polynomials) promises 1e-7 absolute for |x| < 6e4.  Like the device expf above its
+# allowance is MEASURED against float64 sin / cos of the SAME fp32 argument, never against a second run of the kernel: twice the largest error seen on the
+# MI355X (profiles/output_kernel_margins.jsonl, rows 'sincos_cw_abs' over the product's range - coordinates of a 256 x 256 grid times the five lr_pe
+# frequencies up to e^10, biases in [-pi, pi] - and 'sincos_cw_abs_limit' over the documented |x| < 6e4), a factor of two because the cases sample the
+# range.  Largest seen: 8.54e-8 and 8.73e-8, the rounding of the fp32 result included (a replay of the routine's IEEE operations on the host over 6e7
+# random arguments per range finds 9.30e-8 and 9.40e-8: inside the allowance, and inside the routine's promise).  tests/test_hip_guidance.py::test_sincos_cw_error repeats
+# the measurement and fails if twice the observed error exceeds the allowance.
+# A condition, not a measurement: the allowance must stay below 2^-13, one ulp of the smallest phase (2048 rad) at which a one-ulp phase error still matters -
+# otherwise the bound could not tell a correct sine from the sine of a phase that is one ulp off.
+SINCOS_ABS = 1.75e-7     # 2 x 8.73e-8, rounded up
+SINCOS_ABS_MAX = 2.0 ** -13
+
+
+def guidance_nred(P, nf):
+    """rounding steps on the way of one feature into pst_loftup_guidance_gn's (sum, sumsq) (guidance_px_kernel<false>): a thread walks ceil(tiles / 128)
+    tiles; per tile ceil(nf / 4) frequencies x 5 inputs, each step rounding vs + vc (or vs^2 + vc^2 and its two products: counted below) and the
+    accumulation, then the 3 colours; block_reduce: 6 shuffle levels + 3 adds over the waves; reduce_partials_kernel: at most 128 / 64 = 2 serial adds and 6
+    shuffle levels."""
+    ntile = -(-P // 64)
+    trips = -(-ntile // 128)
+    return trips * (2 * 5 * -(-nf // 4) + 3) + 9 + 8
+
+
+def guidance_perturbation(z, s, gamma, delta):
+    """|change of gamma z| when every input of the normalisation moves by at most delta: |gamma| delta (2 + |z|) / (s - delta), s = sqrt(var + eps)
+    (derivation: guidance_bound)"""
+    return gamma.abs() * delta * (2.0 + z.abs()) / (s - delta).clamp_min(1e-300)
+
+
+def guidance_bound(feat64, gamma, beta, eps, nf, out_fmt='fp32', delta=None):
+    """Per-element bound of pst_loftup_guidance_gn's output against float64 GroupNorm(1) of feat64 = guidance_ref.features64 (float64 [n, P, CH]: sin / cos
+    in float64 of the fp32 phases, the scaled colours).  Returns (ref64 [n P, CH], bound, stats64 [n, 2], stats_bound [n, 2]).
+
+    Two terms.  (a) The kernel's arithmetic on ITS features: one-pass fp32 (sum, sumsq) with guidance_nred rounding steps (+ 2 for the squares), rsqrtf,
+    (x - mean) rstd gamma + beta in fp32: rownorm_bound(one_pass=True).  (b) Its features are not feat64 but x + e, |e| <= delta = SINCOS_ABS + u32
+    (sincos_cw's measured error, which includes the rounding of its result, and one more fp32 rounding for the colours' last bit).  With mu the mean,
+    s = sqrt(var + eps), z = (x - mu) / s and y = gamma z + beta:  mu moves by mean(e), at most delta; the standard deviation is 1-Lipschitz in the rms of
+    the perturbation (triangle inequality of the l2 norm of x - mu), so sqrt(var) moves by at most delta and s by no more (d s / d sqrt(var) <= 1).  Then
+        z' - z = (e_i - mean e) / s' + (x - mu) (1 / s' - 1 / s),   |z' - z| <= 2 delta / s' + |z| delta / s',   s' >= s - delta,
+    i.e. to first order |gamma| rstd delta (2 + |z|); the bound keeps the exact denominators.  Term (a) is evaluated at feat64 instead of the kernel's own
+    features: a difference of second order (u32 x delta).
+    The statistics: |sum - S| <= nred u32 sum |x| + N delta;  |sumsq - S2| <= (nred + 2) u32 S2 + N (2 mean|x| delta + delta^2) (Cauchy-free worst case:
+    sum 2 |x| delta), every fp32 step allowed twice (R) like everywhere here."""
+    x = feat64.double()
+    n, P, CH = x.shape
+    delta = SINCOS_ABS + U32 if delta is None else delta
+    nred = guidance_nred(P, nf)
+    N = P * CH
+    flat = x.reshape(n, 1, N)
+    g = gamma.double().to(x.device).reshape(1, 1, CH).expand(n, P, CH).reshape(n, 1, N)
+    bt = beta.double().to(x.device).reshape(1, 1, CH).expand(n, P, CH).reshape(n, 1, N)
+    mean = flat.mean(-1, keepdim=True)
+    var = ((flat - mean) ** 2).mean(-1, keepdim=True)
+    s = (var + eps).sqrt()
+    z = (flat - mean) / s
+    ref = z * g + bt
+    arith = rownorm_bound(flat, g, bt, eps, out_fmt, one_pass=True, nred=nred + 2)
+    pert = guidance_perturbation(z, s, g, delta)
+    bound = arith + pert * (1.0 + R * u(out_fmt))
+    S, S2, A = flat.sum(-1), (flat * flat).sum(-1), flat.abs().sum(-1)
+    stats = torch.cat([S, S2], -1)
+    sb = torch.cat([R * nred * U32 * A + N * delta, R * (nred + 2) * U32 * S2 + 2 * A * delta + N * delta * delta], -1)
+    return ref.reshape(n * P, CH), bound.reshape(n * P, CH), stats, sb
+
+
+def sincos_bound(ref, out_fmt='fp32'):
+    """a value written by sin_cw / cos_cw with nothing in between (pst_loftup_lr_pe): the measured allowance + one rounding to the output format"""
+    return SINCOS_ABS + R * u(out_fmt) * (torch.as_tensor(ref, dtype=torch.float64).abs() + SINCOS_ABS) + tiny(out_fmt)

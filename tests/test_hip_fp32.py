@@ -353,7 +353,6 @@ def test_loftup_guidance_and_groupnorm_f32():
     P, CH = (H // 2) * (W // 2), 10 * nf + 3
     refp = ref.permute(0, 2, 3, 1).reshape(2, P, CH)
     gamma, beta = 1 + 0.1 * rn(82, CH), 0.1 * rn(83, CH)
-    refn = F.group_norm(refp.permute(0, 2, 1).reshape(2, CH, H // 2, W // 2), 1, gamma, beta, 1e-5).permute(0, 2, 3, 1).reshape(2 * P, CH)
     out = torch.full((2 * P, 256), 7.0, dtype=F32, device=DEV)
     scratch = torch.zeros(2 * (3 * P + 6) + 16, device=DEV)
     st = hip.stats_buffer(2, 1, DEV)
@@ -361,10 +360,15 @@ def test_loftup_guidance_and_groupnorm_f32():
     # the kernel follows torch's fp32 arithmetic of ImplicitFeaturizer operation by operation (linspace = fma(step, i, start), correctly rounded
     # exp, phase = two roundings, sin / cos to 1e-7): at phases up to e^10 = 22026 rad any other association differs by ~1e-3 (measured 1.2e-3
     # before), this one by the sin / cos implementations' last bits
-    assert rel_l2(out[:, :CH].cpu(), refn) < 2e-5
+    # held element by element to float64 GroupNorm(1) of float64 sin / cos of the restatement's fp32 phases (tests/guidance_ref.py, bit-equal to the
+    # oracle modules above) under errbound.guidance_bound; the statistics to their own bound
+    import guidance_ref as GR
+    gi = GR.guidance_inputs(img, feat.biases.detach(), nf)
+    assert torch.equal(GR.features32(gi['s_in'], gi['c_in'], gi['col']), refp)
+    ref64, bound64, stats64, sbound = EB.guidance_bound(GR.features64(gi['s_in'], gi['c_in'], gi['col']), gamma, beta, 1e-5, nf)
+    EB.check(out[:, :CH].cpu(), ref64, bound64, 'guidance_gn fp32 rows')
+    EB.check(st[:4].view(2, 2).cpu(), stats64, sbound, 'guidance_gn GroupNorm(1) statistics')
     assert float(out[:, CH:].abs().max()) == 0.0
-    # (no derived bound for this fused path: its reference is the oracle's own fp32 Fourier-feature arithmetic, which the kernel reproduces operation by
-    # operation - see above; the GroupNorm apply that follows it is bounded below)
     out16 = torch.full((2 * P, 256), 7.0, dtype=torch.float16, device=DEV)
     hip.loftup_guidance_gn(d(img), d(feat.biases.detach()), d(gamma), d(beta), 1e-5, scratch, st, out16, nf)
     assert torch.equal(out16.cpu(), out.cpu().half())     # the 16-bit rows are the roundings of the fp32 ones
@@ -388,7 +392,11 @@ def test_loftup_guidance_and_groupnorm_f32():
         refl = lr(torch.zeros(1, 4, 3, 5))[0].permute(1, 2, 0).reshape(15, 20)
     o = torch.zeros(2 * 15, 32, dtype=F32, device=DEV)
     hip.loftup_lr_pe(d(lr.biases.detach()), o, 8, 2, 3, 5)
-    assert float((o[:15, 8:28].cpu() - refl).abs().max()) < 1e-5 and torch.equal(o[:15], o[15:])
+    s_in, c_in = GR.lr_pe_inputs(lr.biases.detach(), 1, 3, 5)
+    assert torch.equal(GR.features32(s_in, c_in)[0], refl)
+    refl64 = GR.features64(s_in, c_in)[0]
+    EB.check(o[:15, 8:28].cpu(), refl64, EB.sincos_bound(refl64), 'lr_pe fp32')
+    assert torch.equal(o[:15], o[15:])
 
 
 # ---------------------------------------------------------------------------------------------------------------- the model in fp32

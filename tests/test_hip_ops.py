@@ -518,16 +518,19 @@ def test_loftup_guidance_and_groupnorm():
     assert float(out[:, CH:].abs().max()) == 0.0
     refn64, boundn = EB.groupnorm(got.reshape(2 * P, CH), 2, P, 1, gamma, beta, 1e-5, d16())
     EB.check(out[:, :CH].cpu(), refn64, boundn, 'groupnorm(1) apply')
-    # the fused path recomputes the Fourier features in the kernel (phases up to e^10 rad: fp32 sin / cos of the same argument is the reference's own
-    # arithmetic, not a rounding of an exact value), so no derived bound applies to it; it is held to the two-kernel path below, which is bounded above
     # fused path: the same features + GroupNorm(1) without the fp32 feature buffer (two recomputing passes)
     out2 = torch.full((2 * P, 256), 7.0, dtype=d16(), device=dev())
     scratch = torch.zeros(2 * (3 * P + 6) + 16, device=dev())
     st2 = hip.stats_buffer(2, 1, dev())
     hip.loftup_guidance_gn(img.to(dev()), feat.biases.detach().to(dev()), gamma.to(dev()), beta.to(dev()), 1e-5, scratch, st2, out2, nf)
-    assert rel_l2(st2[:4].view(2, 2).cpu(), torch.stack([refp.sum((1, 2)), (refp ** 2).sum((1, 2))], -1)) < 1e-3     # GroupNorm(1) statistics
-    refn2 = F.group_norm(refp.permute(0, 2, 1).reshape(2, CH, H // 2, W // 2), 1, gamma, beta, 1e-5).permute(0, 2, 3, 1).reshape(2 * P, CH)
-    assert rel_l2(out2[:, :CH].float().cpu(), refn) < 5e-3 and float((out2[:, :CH].float().cpu() - refn2).abs().max()) < 6e-2
+    # ... held element by element to float64 GroupNorm(1) of float64 sin / cos of the restatement's fp32 phases (tests/guidance_ref.py, which
+    # tests/test_guidance_host.py holds to the oracle modules above bit for bit), under the bound derived in errbound.guidance_bound
+    import guidance_ref as GR
+    gi = GR.guidance_inputs(img, feat.biases.detach(), nf)
+    assert torch.equal(GR.features32(gi['s_in'], gi['c_in'], gi['col']), refp)
+    ref64, bound64, stats64, sbound = EB.guidance_bound(GR.features64(gi['s_in'], gi['c_in'], gi['col']), gamma, beta, 1e-5, nf, out_fmt=d16())
+    EB.check(st2[:4].view(2, 2).cpu(), stats64, sbound, 'guidance_gn GroupNorm(1) statistics')
+    EB.check(out2[:, :CH].float().cpu(), ref64, bound64, 'guidance_gn 16-bit rows')
     assert float(out2[:, CH:].abs().max()) == 0.0
     assert float((out2.float() - out.float()).abs().max()) < 4e-2              # vs the two-kernel path: bf16 rounding only
     # GroupNorm(8) statistics + apply + ReLU on a conv-like map
@@ -542,15 +545,17 @@ def test_loftup_guidance_and_groupnorm():
     assert rel_l2(o8.float().cpu().reshape(2, P, Cc), ref8.permute(0, 2, 3, 1).reshape(2, P, Cc)) < 5e-3
     ref864, bound8 = EB.groupnorm(x, 2, P, 8, g8, b8, 1e-5, d16(), relu=True)
     EB.check(o8.cpu(), ref864, bound8, 'groupnorm(8) apply + ReLU')
-    # (the low-resolution positional features below are the same fp32 Fourier-feature arithmetic: held to the oracle module by max-abs, no derived bound)
-    # low-res positional features
+    # low-res positional features: the same fp32 Fourier-feature arithmetic, held to float64 sin / cos of the restatement's phases
     lr = ImplicitFeaturizer(False, n_freqs=5, learn_bias=True)
     with torch.no_grad():
         lr.biases.copy_(rn(87, 2, 2, 5))
         refl = lr(torch.zeros(1, 4, 3, 5))[0].permute(1, 2, 0).reshape(15, 20)
     o = torch.zeros(2 * 15, 32, dtype=d16(), device=dev())
     hip.loftup_lr_pe(lr.biases.detach().to(dev()), o, 8, 2, 3, 5)
-    assert float((o[:15, 8:28].float().cpu() - refl).abs().max()) < 2e-2
+    s_in, c_in = GR.lr_pe_inputs(lr.biases.detach(), 1, 3, 5)
+    assert torch.equal(GR.features32(s_in, c_in)[0], refl)
+    refl64 = GR.features64(s_in, c_in)[0]
+    EB.check(o[:15, 8:28].float().cpu(), refl64, EB.sincos_bound(refl64, d16()), 'lr_pe 16-bit')
     assert torch.equal(o[:15], o[15:])
 
 
