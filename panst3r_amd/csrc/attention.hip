@@ -148,15 +148,22 @@ __device__ __forceinline__ void attn_body(const pst_attn_params& p, const int bi
   // delivers s - m; the row sum l comes out of the PV MFMA as one more output row with V^T == 1 (lsum: every register of the
   // fragment holds the full 64-key sum of the 16-bit P values the numerator uses) -- no per-score subtract, no per-score add.
   // m_run == NEG marks a row that has not seen an unmasked key yet ("virgin": reference 0, o == l == 0 exactly).
-  f32x4 negm[QF], lsum[QF];
-  float m_run[QF];
+  f32x4 negm[QF];
+  float m_run[QF], lsum[QF];
+  // Range check by tile sums (DESIGN s4): a full, unmasked tile after the first takes no maximum at all.  Its 64 rounded P go through the ones-row MFMA
+  // into a FRESH accumulator (tsum: every register = the row's sum over the tile) before any PV MFMA touches o; a sum <= 2^8 proves every P <= 2^8, so
+  // the tile is committed as it is.  Otherwise (a large score, an overflowed 16-bit P, inf, NaN) the wave computes the SAME tile again on the checked
+  // path below - the K / V tile is still in LDS, no barrier has passed - and the rows whose own sum tripped move their reference.
+  // sum_lim: 2^8, or -1 while the row is virgin: no sum is <= -1, so a virgin row trips every tile and needs no test of its own.
+  float sum_lim[QF];
 #pragma unroll
-  for (int a = 0; a < QF; ++a) { m_run[a] = NEG; negm[a] = f32x4{0.f, 0.f, 0.f, 0.f}; lsum[a] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  for (int a = 0; a < QF; ++a) { m_run[a] = NEG; negm[a] = f32x4{0.f, 0.f, 0.f, 0.f}; lsum[a] = 0.f; sum_lim[a] = -1.0f; }
   bf16x8 ones;
   {
     union { bf16x8 v; uint32_t u[4]; } t;
     t.u[0] = t.u[1] = t.u[2] = t.u[3] = F16 ? 0x3c003c00u : 0x3f803f80u;
     ones = t.v;
+    asm volatile("" : "+v"(ones));       // pinned in four registers: as a known constant it is rebuilt (two moves) in every tile
   }
 
   // PRE: Q already carries scale * log2(e) (folded into the q projection's epilogue): p = exp2(s - m) with no multiply at all
@@ -183,106 +190,140 @@ __device__ __forceinline__ void attn_body(const pst_attn_params& p, const int bi
     // staging and the barriers only - its MFMAs would compete with the co-resident blocks' for nothing (wave-uniform branch; q_wave0 is scalar)
     if (q_wave0 >= p.Nq) continue;
 
-    // ---- S^T - m = K Q^T - m
-    f32x4 s[4][QF];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-#pragma unroll
-      for (int a = 0; a < QF; ++a) s[f][a] = negm[a];
-      const int row = f * 16 + l16;
-#pragma unroll
-      for (int kk = 0; kk < NKK; ++kk) {
-        const int kc = kk * 4 + g;
-        const bf16x8 kf = *(const bf16x8*)(kb_ + row * C::KPITCH + ((kc ^ C::kswz(row)) << 4));
-#pragma unroll
-        for (int a = 0; a < QF; ++a) s[f][a] = H16<F16>::mfma(kf, qf[a][kk], s[f][a]);
-      }
-    }
-
-    // ---- mask, online softmax; P stays in the lane
-    bf16x8 pb[QF][2];
-    float mx[QF];
     const bool tail = (k0 + KT > p.Nk);
+    // wave-uniform (scalar) choice.  The first tile of a key range is checked: every row is virgin there.  Which path a row's tile takes, and whether
+    // the row itself tripped, depends on the launch, the tile and the row's own scores only - never on another row of the wave.
+    bool fast = !Mp && !tail && kt > kt_begin;
+    bool trip[QF];
 #pragma unroll
-    for (int a = 0; a < QF; ++a) {
-      const int q = q_wave0 + a * 16 + l16;
-      if (Mp || tail) {
-        const uint8_t* mrow = Mp ? Mp + (int64_t)min(q, p.Nq - 1) * p.m_rs : nullptr;
+    for (int a = 0; a < QF; ++a) trip[a] = false;
+    bf16x8 pb[QF][2];
+    f32x4 tsum[QF];
+    for (;;) {      // one pass; two when a tile sum trips
+      // the second pass reads its K fragments from LDS again: without this compiler barrier the loads are hoisted out of the loop and the 32 registers
+      // they fill stay live through the whole tile (171 registers at head dim 64: two blocks per CU instead of three)
+      asm volatile("" ::: "memory");
+      // ---- S^T - m = K Q^T - m
+      f32x4 s[4][QF];
 #pragma unroll
-        for (int f = 0; f < 4; ++f) {
-          const int key = k0 + (f >> 1) * 32 + g * 8 + (f & 1) * 4;
-          uint32_t mb = 0;
-          if (mrow && key < p.Nk) mb = *(const uint32_t*)(mrow + key);
+      for (int f = 0; f < 4; ++f) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (key + r >= p.Nk || ((mb >> (8 * r)) & 0xff)) s[f][a][r] = NEG;       // exp2 of it is exactly 0
+        for (int a = 0; a < QF; ++a) s[f][a] = negm[a];
+        const int row = f * 16 + l16;
+#pragma unroll
+        for (int kk = 0; kk < NKK; ++kk) {
+          const int kc = kk * 4 + g;
+          const bf16x8 kf = *(const bf16x8*)(kb_ + row * C::KPITCH + ((kc ^ C::kswz(row)) << 4));
+#pragma unroll
+          for (int a = 0; a < QF; ++a) s[f][a] = H16<F16>::mfma(kf, qf[a][kk], s[f][a]);
         }
       }
-      // two independent v_max3 chains (a dependent VALU chain issues at ~0.6 of the independent rate): 8 instructions, depth 5
-      auto max3 = [](float x, float y, float z) { return fmaxf(fmaxf(x, y), z); };
-      float m0 = max3(s[0][a][0], s[0][a][1], s[0][a][2]), m1 = max3(s[2][a][0], s[2][a][1], s[2][a][2]);
-      m0 = max3(m0, s[0][a][3], s[1][a][0]); m1 = max3(m1, s[2][a][3], s[3][a][0]);
-      m0 = max3(m0, s[1][a][1], s[1][a][2]); m1 = max3(m1, s[3][a][1], s[3][a][2]);
-      mx[a] = fmaxf(max3(m0, m1, s[1][a][3]), s[3][a][3]);
-    }
-    // max over the 4 lanes that share a query column (lane bits 4, 5): two cross-row swaps on the VALU, no LDS round trip
-    bool virgin[QF], need[QF];
-    bool some = false;
+
+      // ---- checked path: mask, row maximum, reference update (the only path of masked tiles, ragged tiles and virgin rows)
+      if (!fast) {
+        // k0 made opaque here: the key-range and mask predicates below do not vary in this loop, so the compiler would hoist all ~45 instructions
+        // of them in front of it, where every fast tile pays them as well
+        int k0c = k0;
+        asm volatile("" : "+s"(k0c));
+        float mx[QF];
 #pragma unroll
-    for (int a = 0; a < QF; ++a) {
-      mx[a] = max_rows(mx[a]);
-      // Lazy rescaling: the reference only moves when a score exceeds it by more than 2^8 in the exp2 domain (softmax is
-      // invariant to the reference; exp values stay <= 256, exact enough in fp32 / 16 bit), and the whole update is skipped
-      // wave-wide unless some query column needs it.  A virgin row takes the first real score it meets as its reference.
-      virgin[a] = m_run[a] == NEG;
-      need[a] = virgin[a] ? (mx[a] > 0.5f * NEG) : (mx[a] > lazy_thr);
-      some = some || need[a];
-    }
-    if (__any(some)) {
+        for (int a = 0; a < QF; ++a) {
+          const int q = q_wave0 + a * 16 + l16;
+          if (Mp || tail) {
+            const uint8_t* mrow = Mp ? Mp + (int64_t)min(q, p.Nq - 1) * p.m_rs : nullptr;
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+              const int key = k0c + (f >> 1) * 32 + g * 8 + (f & 1) * 4;
+              uint32_t mb = 0;
+              if (mrow && key < p.Nk) mb = *(const uint32_t*)(mrow + key);
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (key + r >= p.Nk || ((mb >> (8 * r)) & 0xff)) s[f][a][r] = NEG;       // exp2 of it is exactly 0
+            }
+          }
+          // two independent v_max3 chains (a dependent VALU chain issues at ~0.6 of the independent rate): 8 instructions, depth 5
+          auto max3 = [](float x, float y, float z) { return fmaxf(fmaxf(x, y), z); };
+          float m0 = max3(s[0][a][0], s[0][a][1], s[0][a][2]), m1 = max3(s[2][a][0], s[2][a][1], s[2][a][2]);
+          m0 = max3(m0, s[0][a][3], s[1][a][0]); m1 = max3(m1, s[2][a][3], s[3][a][0]);
+          m0 = max3(m0, s[1][a][1], s[1][a][2]); m1 = max3(m1, s[3][a][1], s[3][a][2]);
+          mx[a] = fmaxf(max3(m0, m1, s[1][a][3]), s[3][a][3]);
+        }
+        // max over the 4 lanes that share a query column (lane bits 4, 5): two cross-row swaps on the VALU, no LDS round trip
+        bool virgin[QF], need[QF];
+        bool some = false;
+#pragma unroll
+        for (int a = 0; a < QF; ++a) {
+          mx[a] = max_rows(mx[a]);
+          // Lazy rescaling: the reference only moves when a score exceeds it by more than 2^8 in the exp2 domain (softmax is invariant to the
+          // reference; exp values stay <= 256, exact enough in fp32 / 16 bit) or when the row's own tile sum tripped and the tile's maximum lies above
+          // the reference at all (a plateau of 64 scores at reference + 3 would otherwise trip every following tile); the whole update is skipped
+          // wave-wide unless some query column needs it.  A virgin row takes the first real score it meets as its reference.
+          virgin[a] = m_run[a] == NEG;
+          need[a] = virgin[a] ? (mx[a] > 0.5f * NEG) : (mx[a] > lazy_thr || (trip[a] && mx[a] > 0.f));
+          some = some || need[a];
+        }
+        if (__builtin_amdgcn_ballot_w64(some) != 0) {
+#pragma unroll
+          for (int a = 0; a < QF; ++a) {
+            const float shift = need[a] ? mx[a] : 0.f;                      // new reference = old + shift
+            const float alpha = virgin[a] ? 1.0f : __builtin_amdgcn_exp2f(-shift * c_exp);
+            const float m_new = need[a] ? (virgin[a] ? 0.f : m_run[a]) + mx[a] : m_run[a];
+            m_run[a] = m_new;
+            if (need[a]) { negm[a] = f32x4{-m_new, -m_new, -m_new, -m_new}; sum_lim[a] = 256.0f; }
+            lsum[a] *= alpha;
+#pragma unroll
+            for (int hf = 0; hf < NHF; ++hf)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) o[hf][a][r] *= alpha;
+#pragma unroll
+            for (int f = 0; f < 4; ++f)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) s[f][a][r] -= shift;
+          }
+        }
+      }
+
+      // ---- P = exp2(S - m) in the 16-bit format; P stays in the lane
 #pragma unroll
       for (int a = 0; a < QF; ++a) {
-        const float shift = need[a] ? mx[a] : 0.f;                      // new reference = old + shift
-        const float alpha = virgin[a] ? 1.0f : __builtin_amdgcn_exp2f(-shift * c_exp);
-        const float m_new = need[a] ? (virgin[a] ? 0.f : m_run[a]) + mx[a] : m_run[a];
-        m_run[a] = m_new;
-        if (need[a]) negm[a] = f32x4{-m_new, -m_new, -m_new, -m_new};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) lsum[a][r] *= alpha;
-#pragma unroll
-        for (int hf = 0; hf < NHF; ++hf)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[hf][a][r] *= alpha;
+        float pv[4][4];
 #pragma unroll
         for (int f = 0; f < 4; ++f)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) s[f][a][r] -= shift;
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < QF; ++a) {
-      float pv[4][4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
+          for (int r = 0; r < 4; ++r) {
 #ifndef PST_ABL_NOEXP
-          pv[f][r] = __builtin_amdgcn_exp2f(PRE ? s[f][a][r] : s[f][a][r] * c_exp);
+            pv[f][r] = __builtin_amdgcn_exp2f(PRE ? s[f][a][r] : s[f][a][r] * c_exp);
 #else
-          pv[f][r] = s[f][a][r];
+            pv[f][r] = s[f][a][r];
 #endif
-        }
+          }
 #pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        union { bf16x8 v; uint32_t u[4]; } pk;
-        pk.u[0] = H16<F16>::pack(pv[2 * kb][0], pv[2 * kb][1]);
-        pk.u[1] = H16<F16>::pack(pv[2 * kb][2], pv[2 * kb][3]);
-        pk.u[2] = H16<F16>::pack(pv[2 * kb + 1][0], pv[2 * kb + 1][1]);
-        pk.u[3] = H16<F16>::pack(pv[2 * kb + 1][2], pv[2 * kb + 1][3]);
-        pb[a][kb] = pk.v;
+        for (int kb = 0; kb < 2; ++kb) {
+          union { bf16x8 v; uint32_t u[4]; } pk;
+          pk.u[0] = H16<F16>::pack(pv[2 * kb][0], pv[2 * kb][1]);
+          pk.u[1] = H16<F16>::pack(pv[2 * kb][2], pv[2 * kb][3]);
+          pk.u[2] = H16<F16>::pack(pv[2 * kb + 1][0], pv[2 * kb + 1][1]);
+          pk.u[3] = H16<F16>::pack(pv[2 * kb + 1][2], pv[2 * kb + 1][3]);
+          pb[a][kb] = pk.v;
+        }
+        // ---- the tile's row sums, 1^T P^T, on their own: the same two MFMAs on both paths, so a row's l does not depend on the path
+        tsum[a] = H16<F16>::mfma(ones, pb[a][0], f32x4{0.f, 0.f, 0.f, 0.f});
+        tsum[a] = H16<F16>::mfma(ones, pb[a][1], tsum[a]);
       }
+      if (!fast) break;
+      uint64_t tripped = 0;
+#pragma unroll
+      for (int a = 0; a < QF; ++a) {
+        trip[a] = !(tsum[a][0] <= sum_lim[a]);          // inf and NaN trip too
+        tripped |= __builtin_amdgcn_ballot_w64(trip[a]);
+      }
+      if (tripped == 0) break;
+      fast = false;
     }
 
-    // ---- O^T += V^T P^T, l += 1^T P^T
+    // ---- l += 1^T P^T, O^T += V^T P^T
+#pragma unroll
+    for (int a = 0; a < QF; ++a) lsum[a] += tsum[a][0];
 #pragma unroll
     for (int hf = 0; hf < NHF; ++hf) {
       const int row = hf * 16 + l16;
@@ -294,10 +335,6 @@ __device__ __forceinline__ void attn_body(const pst_attn_params& p, const int bi
         for (int a = 0; a < QF; ++a) o[hf][a] = H16<F16>::mfma(vf, pb[a][kb], o[hf][a]);
       }
     }
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int a = 0; a < QF; ++a) lsum[a] = H16<F16>::mfma(ones, pb[a][kb], lsum[a]);
   }
 
   // ---- split-K: unnormalised partial O plus (running max, sum) go to the fp32 workspace; attn_combine_kernel merges
@@ -307,7 +344,7 @@ __device__ __forceinline__ void attn_body(const pst_attn_params& p, const int bi
     float* ws_ml = ws_o + (int64_t)nsplit * rows * HD;
 #pragma unroll
     for (int a = 0; a < QF; ++a) {
-      const float l = lsum[a][0];
+      const float l = lsum[a];
       const int q = q_wave0 + a * 16 + l16;
       if (q < p.Nq) {
         const int64_t row = ((int64_t)b * p.H + h) * p.Nq + q;
@@ -323,7 +360,7 @@ __device__ __forceinline__ void attn_body(const pst_attn_params& p, const int bi
   // ---- normalise and store: lane owns q = l16, head-dim rows 16*hf + 4*g + r
 #pragma unroll
   for (int a = 0; a < QF; ++a) {
-    const float l = lsum[a][0];
+    const float l = lsum[a];
     const float inv = l > 0.f ? 1.0f / l : 0.f;           // a row with every key masked: zeros
     const int q = q_wave0 + a * 16 + l16;
     if (q < p.Nq) {
