@@ -7,7 +7,7 @@ derived from the kernel's rounding steps does not.  References are float64 evalu
 Notation: u(f) = unit roundoff of format f (bf16 2^-8, f16 2^-11, fp32 2^-24); tiny(f) = half the smallest subnormal spacing (the absolute error of a rounding
 near zero).  tests/test_errbound.py proves on the CPU, for every bound here, that an emulation of the kernel's rounding path stays below half the bound and that
 the typical kernel mistakes (accumulator through a 16-bit format, P rounded to the wrong format, a dropped key, a negated fragment, wrong LayerNorm eps, ...)
-exceed it.
+exceed it; tests/test_smallops_host.py does the same for the small row and pixel operations at the end of this file.
 
 PST_ERRBOUND_LOG=<path>: every check() appends one JSON line {what, ratio, n} there (the per-family maxima the GPU run reports).
 """
@@ -473,3 +473,62 @@ def guidance_bound(feat64, gamma, beta, eps, nf, out_fmt='fp32', delta=None):
 def sincos_bound(ref, out_fmt='fp32'):
     """a value written by sin_cw / cos_cw with nothing in between (pst_loftup_lr_pe): the measured allowance + one rounding to the output format"""
     return SINCOS_ABS + R * u(out_fmt) * (torch.as_tensor(ref, dtype=torch.float64).abs() + SINCOS_ABS) + tiny(out_fmt)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------- small row / pixel ops
+# misc.hip's l2norm_rows, resize_bilinear and dino_preprocess (tests/test_hip_smallops.py; soundness and tightness: tests/test_smallops_host.py).  mean4,
+# add_cast, patchify, token_embed and attn_mask_from_logits have no bound: their fp32 expressions are fixed by the header and the results are compared exactly.
+def l2norm_nred(D):
+    """fp32 additions on the longest path of l2norm_rows' sum of squares: lane l of 64 adds columns l, l + 64, ... (ceil(D / 64) additions), then the six
+    levels of the wave's butterfly"""
+    return -(-D // 64) + 6
+
+
+def l2norm_bound(ref, D, out_fmt):
+    """y = x * (1 / (sqrtf(S) + eps)) against ref = x / (||x|| + eps) (float64 of the same fp32 row), S the fp32 sum of the D squares.
+
+    S: every square is rounded once (none when the compiler contracts it into an fma) and every one of the nred = l2norm_nred(D) additions on the longest path
+    rounds a partial sum of non-negative terms that is <= S: (nred + 1) u32 relative.  sqrtf halves that and rounds once (IEEE sqrt, see the note on division
+    and sqrtf above).  Adding eps >= 0 rounds once and only dilutes the error of the root (n / (n + eps) <= 1); the reciprocal rounds once; the product rounds
+    once.  So c = the root, the add of eps, the reciprocal and the product = 4 roundings behind half of (nred + 1):
+        |y - ref| <= ((nred + 1) / 2 + 4) u32 |ref|,
+    every rounding allowed twice (R) like everywhere here: (nred + 9) u32 |ref| = |ref| (nred + c') 2^-24 with c' = 2 x 4 + 1, then the output rounding
+    R u(out) |ref| + tiny(out).  Assumes the squares stay in fp32's normal range (|x| > 2^-63 where it matters, ||x||^2 < 2^128)."""
+    ref = torch.as_tensor(ref, dtype=torch.float64)
+    err = R * U32 * ((l2norm_nred(D) + 1) / 2.0 + 4.0) * ref.abs()
+    return err + R * u(out_fmt) * (ref.abs() + err) + tiny(out_fmt)
+
+
+def resize_bound(ref, tapmax, out_fmt, dtaps=0.0, dcoord=0.0):
+    """o = (1 - wy) ((1 - wx) a + wx b) + wy ((1 - wx) d + wx e) in fp32 (misc.hip resize_bilinear_kernel, and dino_pre_kernel with the factors the other way
+    round) against the float64 blend of the same taps with the same fp32 source coordinate.  tapmax = max(|a|, |b|, |d|, |e|).  blend_bound does not fit: it
+    is relative to the result, which only holds for non-negative taps; features are signed, and the result can cancel.
+
+    wx = fx - floor(fx) is exact; 1 - wx rounds once.  Inner blend: the rounding of 1 - wx and of its product with a (2 (1 - wx) |a|), the product with b
+    (wx |b|) and the sum (|top|): at most u32 tapmax (2 (1 - wx) + wx + 1) <= 3 u32 tapmax.  The outer blend does the same to two values <= tapmax and passes
+    the inner errors on with weights that sum to one: 3 more.  6 u32 tapmax, every rounding allowed twice (R); an fma only removes roundings.
+    dtaps:  the error the taps carry themselves (dino_preprocess normalises them in fp32 first: dino_tap_err); the blend is convex, so it passes on unchanged.
+    dcoord: the |change of o| when the compiler contracts (d + 0.5) s - 0.5 into one fma, so that the kernel's coordinate is not the twice-rounded one of the
+            reference (resize_coord_term; 0 where contraction is switched off: dino_pre_kernel).
+    Then the rounding to the output format."""
+    ref = torch.as_tensor(ref, dtype=torch.float64)
+    err = 6 * R * U32 * torch.as_tensor(tapmax, dtype=torch.float64) + R * torch.as_tensor(dtaps, dtype=torch.float64) + torch.as_tensor(dcoord, dtype=torch.float64)
+    return err + R * u(out_fmt) * (ref.abs() + err) + tiny(out_fmt)
+
+
+def resize_coord_term(fy, fx, gy, gx):
+    """resize_bound's dcoord.  fl(fl((d + 0.5) s) - 0.5) and the single rounding of an fma differ by at most the rounding of the product, u32 (f + 0.5), and
+    the two roundings of the differences, 2 u32 f - together <= 3 u32 (f + 0.5) per axis.  The bilinear interpolant is continuous and piecewise linear; along
+    an axis its slope is a convex combination of differences of neighbouring source pixels, at most g = the largest such difference of the image and channel
+    (of the whole plane: a coordinate next to an integer may fall into the neighbouring cell, whose taps are not the reference's four).  So o moves by at most
+    3 u32 ((fy + 0.5) gy + (fx + 0.5) gx).  A worst case in its own right (the roundings are bounded by their full size): not doubled again."""
+    as64 = lambda t: torch.as_tensor(t, dtype=torch.float64)
+    return 3 * U32 * ((as64(fy) + 0.5) * as64(gy) + (as64(fx) + 0.5) * as64(gx))
+
+
+def dino_tap_err(t, nv, std):
+    """resize_bound's dtaps for dino_preprocess: nv = ((v 0.5 + 0.5) - mean) / std in fp32, mean and std the fp32 constants.  v 0.5 is exact; t = v 0.5 + 0.5
+    rounds once (u32 |t|), t - mean rounds once (u32 |t - mean|) and the division once (u32 |nv|), the first two divided by std:
+    u32 (|t| / std + 2 |nv|) - three roundings per tap."""
+    t, nv = torch.as_tensor(t, dtype=torch.float64), torch.as_tensor(nv, dtype=torch.float64)
+    return U32 * (t.abs() / torch.as_tensor(std, dtype=torch.float64) + 2 * nv.abs())
