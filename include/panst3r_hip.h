@@ -673,6 +673,62 @@ int pst_surface_keep_count(const int32_t* component, const int32_t* size, int64_
 int pst_surface_keep_emit(const int32_t* faces, const int32_t* face_ids, const int64_t* quad, const int32_t* component, const int32_t* size, int64_t F,
                           int min_faces, const int32_t* base, int32_t* out_faces, int32_t* out_face_ids, int64_t* out_quad, void* stream);
 
+/* ---------------------------------------------------------------- score3d: a mesh's surface as points, and the nearest point within a radius (no counterpart in the reference)
+ * The two primitives of engine/score3d.py (F-score, chamfer and a 3-D panoptic quality of a reconstruction against a ground-truth mesh, point to
+ * point).  Restated in tests/nearest_ref.py [restated, parity unpinned]: the sampler as written here, the search by brute force over all pairs.  Every
+ * step is exact, so the outputs are held to the restatement bit for bit.  Contraction is off: every fp32 and fp64 operation is rounded on its own, in the
+ * order written.  Additive to ABI 20.
+ * MESH SURFACE SAMPLER  vertices fp32 [Nv, 3], faces int32 [F, 3], spacing > 0 fp32, 1 <= max_subdiv <= PST_MESH_SAMPLE_MAX_SUBDIV:
+ *   1 drop      a face gets 0 samples and is counted in status[1] if an index is outside [0, Nv), a coordinate of a corner is not finite, or the
+ *               cross product (v1 - v0) x (v2 - v0) is exactly zero in fp64 (corners widened to fp64, then one subtraction, product, subtraction each).
+ *   2 n         L2 = the largest of the three squared edge lengths, (dx dx + dy dy) + dz dz in fp64 on the widened corners; s2 = fp64(spacing)
+ *               fp64(spacing) (exact).  n = the smallest integer in [1, max_subdiv] with (fp64(n) fp64(n)) s2 >= L2 (n n is exact, one rounding); if
+ *               max_subdiv itself fails the compare, n = max_subdiv and the face is counted as CLAMPED in status[2].  The compare decides: no square
+ *               root is taken.  The face gets n^2 samples, so the sample density differs between faces by what rounding n up to a whole number (and
+ *               the clamp) implies: a CHOICE - a uniform lattice per face instead of an area-weighted draw - that keeps the sampler deterministic.
+ *   3 samples   the n^2 congruent sub-triangles of the uniform subdivision, t in [0, n^2): row r = floor(sqrt(t)) (integer compares settle it),
+ *               c = t - r^2, k = c >> 1.  Even c is upright, odd c inverted; the centroid's integer weights over 3n for (v0, v1, v2) are
+ *                 upright:  3(n - r) - 2,  3(r - k) + 1,  3k + 1            inverted:  3(n - r) - 1,  3(r - k) - 1,  3k + 2
+ *               point = fp32(((w0 v0 + w1 v1) + w2 v2) / fp64(3n)) per axis in fp64, each operation rounded once, one cast.
+ *   4 outputs   rows in face order, t ascending inside a face: points fp32 [., 3], face int32 [.], ids int32 [.] = face_ids[f], or with vertex_ids the id
+ *               of the corner with the largest weight (ties to the lower corner), or 0 with neither (both: PST_EINVAL).
+ *   mesh_sample_count: counts int32 [F] = n^2 or 0; total int64 [1] (cleared by the CALLER) = their sum, by integer atomics; status int32 [4] (cleared by
+ *   the CALLER).  pst_cloud_scan of counts -> prefix int32 [F + 1].  The caller reads `total` and sizes the outputs; mesh_sample_emit refuses
+ *   total > capacity (or > 2^31 - 256: the prefix is int32) with PST_EINVAL before anything is launched, runs one lane per sample, which finds its face
+ *   by binary search in the prefix, and writes nothing but status[0] |= PST_MESH_SAMPLE_TOTAL if prefix[F] != total.  1 <= F <= 2^30.
+ * FIXED-RADIUS NEAREST NEIGHBOUR  targets fp32 [M, 3], queries fp32 [Nq, 3], radius > 0; inv = fp32(1 / radius), r2 = fp32(radius radius) from the host:
+ *   1 cells     the cell of a point is floor(fp32(x inv)) per axis (the voxel contract's rule).  A target with a non-finite coordinate or a cell
+ *               outside (-2^20, 2^20) is left out and counted in status[1].
+ *   2 build     nn_insert: the cell's 3 x 21-bit key into keys uint64 [capacity] (all ones = empty, by the CALLER; capacity a power of two >= 2 M),
+ *               cell_count int32 [capacity] (cleared by the CALLER) += 1 on its slot, point_slot int32 [M] = the slot or -1.  The caller turns
+ *               cell_count into start int32 [capacity] (exclusive prefix sum).  nn_scatter: rows int32 [M]: the rows of slot s at [start[s], start[s] +
+ *               cell_count[s]) in arrival order (fill int32 [capacity], cleared by the CALLER); status[2] = the largest cell_count.
+ *   3 query     one lane per query: every target p in the 27 cells around the query's cell, dx = qx - px, d2 = (dx dx + dy dy) + dz dz in fp32;
+ *               the minimum of (uint64(bits(d2)) << 32) | p: the nearest target, ties to the smaller row, whatever the order inside the lists.
+ *               Accepted iff d2 <= r2: d2 fp32 [Nq], row int32 [Nq]; otherwise row -1 and d2 = +inf.  A query with a non-finite coordinate gets
+ *               row -1 and is counted in status[3].  At most max_cell_points candidates of a cell are visited: the CALLER compares status[2] with it
+ *               after the build and does not launch the query of a fuller cell (a radius too large for the density makes the search quadratic).
+ *               THE SEARCH IS THE 27 CELLS: it equals the search over all targets whenever a pair with d2 <= r2 lies in neighbouring cells.  That
+ *               fails only if the fp32 roundings of inv, of x inv and of qx - px put two points two cells apart whose rounded d2 is still <= r2: a
+ *               pair at a distance within about 2^-23 (|x| / radius + 1) radius of the radius itself.  The scores are counts over millions of points.
+ *   status int32 [4], cleared by the CALLER: [0] = PST_NN_FULL | PST_NN_LISTS, [1] targets left out, [2] largest occupancy, [3] non-finite queries.
+ *   1 <= M, Nq <= 2^30. */
+#define PST_MESH_SAMPLE_MAX_SUBDIV 32768
+#define PST_MESH_SAMPLE_TOTAL 1   /* the prefix handed to mesh_sample_emit does not end in `total` */
+#define PST_NN_FULL 1             /* the table ran full */
+#define PST_NN_LISTS 2            /* start / cell_count / rows are not those of this build */
+int pst_mesh_sample_count(const float* vertices, int64_t Nv, const int32_t* faces, int64_t F, float spacing, int max_subdiv, int32_t* counts, int64_t* total,
+                          int32_t* status, void* stream);
+int pst_mesh_sample_emit(const float* vertices, int64_t Nv, const int32_t* faces, int64_t F, const int32_t* prefix, int64_t total, int64_t capacity,
+                         const int32_t* vertex_ids, const int32_t* face_ids, float* points, int32_t* face, int32_t* ids, int32_t* status, void* stream);
+int pst_nn_insert(const float* targets, int64_t M, float inv, uint64_t* keys, int64_t capacity, int32_t* cell_count, int32_t* point_slot, int32_t* status,
+                  void* stream);
+int pst_nn_scatter(const int32_t* point_slot, int64_t M, const int32_t* start, const int32_t* cell_count, int32_t* fill, int32_t* rows, int32_t* status,
+                   void* stream);
+int pst_nn_query(const float* queries, int64_t Nq, const float* targets, int64_t M, float inv, float r2, const uint64_t* keys, int64_t capacity,
+                 const int32_t* start, const int32_t* cell_count, const int32_t* rows, int max_cell_points, float* d2, int32_t* row, int32_t* status,
+                 void* stream);
+
 /* ---------------------------------------------------------------- panoptic evaluation against ground truth: PQ / SQ / RQ, mIoU (no counterpart in the reference)
  * V predicted maps and V ground-truth maps of the same shapes, flattened and concatenated to pred, gt int32 [N] (1 <= N <= 2^31 - 1, both 16-byte
  * aligned), P predicted and G ground-truth segments (ids unique and > 0 within each list, no crowd regions).  The rules are those of COCO

@@ -1,0 +1,327 @@
+// The two primitives of the 3-D scores (engine/score3d.py; no counterpart in the reference; the contract is the score3d section of
+// include/panst3r_hip.h, restated in tests/nearest_ref.py, [restated, parity unpinned]):
+//   mesh sampler   count  one lane per face: the face's subdivision n (a binary search over [1, max_subdiv] decided by fp64 compares, no sqrt), n^2 into
+//                         counts, dropped and clamped faces counted, the total added up in int64 (one integer atomic per wave)
+//                  scan   pst_cloud_scan of the per-face counts
+//                  emit   one lane per sample: its face by binary search in the prefix, the sub-triangle's integer weights, one fp64 combination
+//   nearest point  insert one lane per target: cell -> key -> slot of the open-addressing table of voxel_table.h, one int32 atomicAdd on the slot's count
+//                  (offsets: a prefix sum of the slot counts, made by the caller)
+//                  scatter the target's row into its cell's list (the position inside the list depends on arrival; nothing that leaves depends on it)
+//                  query  one lane per query: the 27 cells around it, every candidate's fp32 distance, the minimum of (bits(d2) << 32) | row
+// Integer atomics only, no float sum whose order depends on arrival, every probe / candidate / search loop bounded by a number known before the launch,
+// refusals through the status words, every result written with plain vector stores: two calls return identical bytes.  Contraction is off for the
+// whole file: every fp32 and fp64 operation is rounded on its own, in the order written.
+#include "common.h"
+#include "../../include/panst3r_hip.h"
+#include "voxel_table.h"
+
+#pragma clang fp contract(off)
+
+namespace pst {
+
+constexpr int NN_T = 256;
+constexpr int MS_MAX_SUBDIV = PST_MESH_SAMPLE_MAX_SUBDIV;
+static_assert(MS_MAX_SUBDIV == 1 << 15, "n^2 and 3n stay inside int32");
+
+static dim3 nn_grid(int64_t n) { return dim3((unsigned)((n + NN_T - 1) / NN_T)); }
+
+// ---------------------------------------------------------------- mesh surface sampler
+struct MsFace { int ok; double v[3][3]; };
+
+__device__ __forceinline__ MsFace ms_load(const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int f) {
+  MsFace t;
+  t.ok = 1;
+  int idx[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    idx[k] = faces[(int64_t)f * 3 + k];
+    if ((unsigned)idx[k] >= (unsigned)Nv) t.ok = 0;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float x = t.ok ? vertices[(int64_t)idx[k] * 3 + a] : 0.f;
+      if (!(fabsf(x) <= 3.402823466e38f)) t.ok = 0;                 // NaN fails the compare
+      t.v[k][a] = (double)x;
+    }
+  return t;
+}
+
+__device__ __forceinline__ double ms_edge2(const double (&a)[3], const double (&b)[3]) {
+  const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+// the face's sample count n^2 (0 = dropped); clamped = the face wanted more than max_subdiv
+__device__ __forceinline__ int ms_count(const MsFace& t, double s2, int max_subdiv, int& clamped) {
+  clamped = 0;
+  if (!t.ok) return 0;
+  double e1[3], e2[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) { e1[a] = t.v[1][a] - t.v[0][a]; e2[a] = t.v[2][a] - t.v[0][a]; }
+  const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+  if (cx == 0.0 && cy == 0.0 && cz == 0.0) return 0;
+  const double L2 = fmax(fmax(ms_edge2(t.v[1], t.v[0]), ms_edge2(t.v[2], t.v[1])), ms_edge2(t.v[0], t.v[2]));
+  // enough(n) = n n s2 >= L2 is monotone in n: the smallest n of [1, max_subdiv] that is enough, max_subdiv if none is.  At most 16 rounds.
+  int lo = 1, hi = max_subdiv;
+  if (!(((double)hi * (double)hi) * s2 >= L2)) { clamped = 1; return hi * hi; }
+  for (int it = 0; it < 16 && lo < hi; ++it) {
+    const int mid = (lo + hi) >> 1;
+    if (((double)mid * (double)mid) * s2 >= L2) hi = mid; else lo = mid + 1;
+  }
+  return hi * hi;
+}
+
+__global__ __launch_bounds__(NN_T) void mesh_sample_count_kernel(const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int F,
+                                                                 double s2, int max_subdiv, int32_t* __restrict__ counts, int64_t* __restrict__ total,
+                                                                 int32_t* __restrict__ status) {
+  const int f = blockIdx.x * NN_T + threadIdx.x, lane = threadIdx.x & 63;
+  int c = 0, clamped = 0, dropped = 0;
+  if (f < F) {
+    c = ms_count(ms_load(vertices, Nv, faces, f), s2, max_subdiv, clamped);
+    dropped = c == 0;
+    counts[f] = c;
+  }
+  const uint64_t md = __ballot(dropped), mc = __ballot(clamped);
+  int64_t sum = c;                                                  // 64 faces of at most 2^30 samples
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor((long long)sum, o);
+  if (lane == 0) {
+    if (sum) atomicAdd((unsigned long long*)total, (unsigned long long)sum);
+    if (md) atomicAdd(&status[1], (int)__popcll(md));
+    if (mc) atomicAdd(&status[2], (int)__popcll(mc));
+  }
+}
+
+__global__ __launch_bounds__(NN_T) void mesh_sample_emit_kernel(const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int F,
+                                                                const int32_t* __restrict__ prefix, int total, const int32_t* __restrict__ vertex_ids,
+                                                                const int32_t* __restrict__ face_ids, float* __restrict__ points,
+                                                                int32_t* __restrict__ face, int32_t* __restrict__ ids, int32_t* __restrict__ status) {
+  if (prefix[F] != total) {                                         // uniform: the prefix is not the one the caller sized the outputs by
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&status[0], PST_MESH_SAMPLE_TOTAL);
+    return;
+  }
+  const int s = blockIdx.x * NN_T + threadIdx.x;
+  if (s >= total) return;
+  int lo = 0, hi = F - 1;                                           // the last face whose prefix is <= s: it holds sample s (31 rounds at the most)
+  for (int it = 0; it < 32 && lo < hi; ++it) {
+    const int mid = (int)(((int64_t)lo + hi + 1) >> 1);
+    if (prefix[mid] <= s) lo = mid; else hi = mid - 1;
+  }
+  const int f = lo, t = s - prefix[f], cnt = prefix[f + 1] - prefix[f];
+  int n = (int)sqrt((double)cnt);                                   // cnt = n^2 exactly: a first guess, settled by integer compares
+  if ((int64_t)n * n > cnt) --n;
+  if ((int64_t)(n + 1) * (n + 1) <= cnt) ++n;
+  int r = (int)sqrt((double)t);
+  if ((int64_t)r * r > t) --r;
+  if ((int64_t)(r + 1) * (r + 1) <= t) ++r;
+  const int c = t - r * r, k = c >> 1;
+  int w[3];
+  if (c & 1) { w[0] = 3 * (n - r) - 1; w[1] = 3 * (r - k) - 1; w[2] = 3 * k + 2; }
+  else       { w[0] = 3 * (n - r) - 2; w[1] = 3 * (r - k) + 1; w[2] = 3 * k + 1; }
+  const MsFace tri = ms_load(vertices, Nv, faces, f);               // (a face with samples has passed these checks)
+  const double den = (double)(3 * n);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double p = (((double)w[0] * tri.v[0][a] + (double)w[1] * tri.v[1][a]) + (double)w[2] * tri.v[2][a]) / den;
+    points[(int64_t)s * 3 + a] = (float)p;
+  }
+  face[s] = f;
+  int id = 0;
+  if (face_ids) id = face_ids[f];
+  else if (vertex_ids) {
+    const int best = (w[1] > w[0] ? (w[2] > w[1] ? 2 : 1) : (w[2] > w[0] ? 2 : 0));      // the largest weight, ties to the lower corner
+    id = vertex_ids[faces[(int64_t)f * 3 + best]];
+  }
+  ids[s] = id;
+}
+
+// ---------------------------------------------------------------- fixed-radius nearest neighbour
+__device__ __forceinline__ float nn_mulr(float a, float b) { return a * b; }
+__device__ __forceinline__ float nn_addr(float a, float b) { return a + b; }
+__device__ __forceinline__ float nn_subr(float a, float b) { return a - b; }
+
+// the cell of a point by vx_cell's rule (csrc/voxel.hip): floor(x * inv) per axis; finite = every coordinate is, ok = and every cell is inside +-2^20
+__device__ __forceinline__ void nn_cell(const float* __restrict__ p, float inv, float (&x)[3], float (&c)[3], bool& finite, bool& ok) {
+  finite = ok = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    x[a] = p[a];
+    c[a] = floorf(nn_mulr(x[a], inv));
+    finite = finite && (fabsf(x[a]) <= 3.402823466e38f);           // NaN fails the compare
+    ok = ok && (fabsf(c[a]) < (float)VX_LIM);
+  }
+  ok = ok && finite;
+}
+
+__device__ __forceinline__ uint64_t nn_key(int x, int y, int z) {     // only for cells in range: no field wraps
+  return (uint64_t)(x + VX_LIM) | ((uint64_t)(y + VX_LIM) << 21) | ((uint64_t)(z + VX_LIM) << 42);
+}
+
+__global__ __launch_bounds__(NN_T) void nn_insert_kernel(const float* __restrict__ targets, int M, float inv, uint64_t* __restrict__ keys, uint32_t mask,
+                                                         int32_t* __restrict__ cell_count, int32_t* __restrict__ point_slot, int32_t* __restrict__ status) {
+  const int i = blockIdx.x * NN_T + threadIdx.x, lane = threadIdx.x & 63;
+  const bool in = i < M;
+  float x[3], c[3];
+  bool finite = false, ok = false;
+  if (in) nn_cell(targets + (int64_t)i * 3, inv, x, c, finite, ok);
+  const uint64_t dropped = __ballot(in && !ok);
+  if (dropped && lane == (int)__builtin_ctzll(dropped)) atomicAdd(&status[1], (int)__popcll(dropped));
+  if (!in) return;
+  int slot = -1;
+  if (ok) {
+    slot = vx_find_or_claim(keys, mask, nn_key((int)c[0], (int)c[1], (int)c[2]), status);
+    if (slot >= 0) atomicAdd(&cell_count[slot], 1);
+  }
+  point_slot[i] = slot;
+}
+
+// rows[start[slot] + k] = the k-th arrival of the slot's cell; the arrival that fills a list reports its length: status[2] = the largest occupancy
+__global__ __launch_bounds__(NN_T) void nn_scatter_kernel(const int32_t* __restrict__ point_slot, int M, const int32_t* __restrict__ start,
+                                                          const int32_t* __restrict__ cell_count, int32_t* __restrict__ fill, int32_t* __restrict__ rows,
+                                                          int32_t* __restrict__ status) {
+  const int i = blockIdx.x * NN_T + threadIdx.x;
+  if (i >= M) return;
+  const int slot = point_slot[i];
+  if (slot < 0) return;
+  const int k = atomicAdd(&fill[slot], 1), n = cell_count[slot], pos = start[slot] + k;
+  if ((unsigned)k >= (unsigned)n || (unsigned)pos >= (unsigned)M) { atomicOr(&status[0], PST_NN_LISTS); return; }      // not the counts of this insert
+  rows[pos] = i;
+  if (k == n - 1) atomicMax(&status[2], n);
+}
+
+__global__ __launch_bounds__(NN_T) void nn_query_kernel(const float* __restrict__ queries, int Nq, const float* __restrict__ targets, int M, float inv,
+                                                        float r2, const uint64_t* __restrict__ keys, uint32_t mask, const int32_t* __restrict__ start,
+                                                        const int32_t* __restrict__ cell_count, const int32_t* __restrict__ rows, int max_cell_points,
+                                                        float* __restrict__ d2_out, int32_t* __restrict__ row_out, int32_t* __restrict__ status) {
+  const int i = blockIdx.x * NN_T + threadIdx.x, lane = threadIdx.x & 63;
+  const bool in = i < Nq;
+  float q[3], c[3];
+  bool finite = false, ok = false;
+  if (in) nn_cell(queries + (int64_t)i * 3, inv, q, c, finite, ok);
+  const uint64_t bad = __ballot(in && !finite);
+  if (bad && lane == (int)__builtin_ctzll(bad)) atomicAdd(&status[3], (int)__popcll(bad));
+  if (!in) return;
+  uint64_t best = ~0ull;
+  // a finite query whose cell is not within one cell of the range has no target cell among its 27
+  if (finite && fabsf(c[0]) <= (float)VX_LIM && fabsf(c[1]) <= (float)VX_LIM && fabsf(c[2]) <= (float)VX_LIM) {
+    const int cx = (int)c[0], cy = (int)c[1], cz = (int)c[2];
+    for (int nb = 0; nb < 27; ++nb) {
+      const int x = cx + nb % 3 - 1, y = cy + (nb / 3) % 3 - 1, z = cz + nb / 9 - 1;
+      if (x <= -VX_LIM || x >= VX_LIM || y <= -VX_LIM || y >= VX_LIM || z <= -VX_LIM || z >= VX_LIM) continue;      // no such cell: never looked up
+      const uint64_t key = nn_key(x, y, z);
+      uint32_t h = (uint32_t)vx_hash(key) & mask;
+      int slot = -1;
+      uint32_t n = 0;
+      for (; n <= mask; ++n) {                                      // the table is complete (an earlier launch built it): plain loads
+        const uint64_t k = keys[h];
+        if (k == key) { slot = (int)h; break; }
+        if (k == VX_EMPTY) break;
+        h = (h + 1) & mask;
+      }
+      if (n > mask) atomicOr(&status[0], PST_NN_FULL);               // a table without an empty slot: never (capacity >= 2 M)
+      if (slot < 0) continue;
+      const int b = start[slot], cnt = min(cell_count[slot], max_cell_points);      // (the caller refused a fuller cell before this launch)
+      if ((unsigned)b > (unsigned)M || cnt < 0 || cnt > M - b) { atomicOr(&status[0], PST_NN_LISTS); continue; }      // a list that leaves rows[0, M): not this build's
+      for (int j = 0; j < cnt; ++j) {
+        const int p = rows[b + j];
+        if ((unsigned)p >= (unsigned)M) { atomicOr(&status[0], PST_NN_LISTS); continue; }
+        const float dx = nn_subr(q[0], targets[(int64_t)p * 3]), dy = nn_subr(q[1], targets[(int64_t)p * 3 + 1]),
+                    dz = nn_subr(q[2], targets[(int64_t)p * 3 + 2]);
+        const float d2 = nn_addr(nn_addr(nn_mulr(dx, dx), nn_mulr(dy, dy)), nn_mulr(dz, dz));      // >= +0, never NaN: its bits order as an unsigned integer
+        const uint64_t cand = ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)p;
+        best = cand < best ? cand : best;
+      }
+    }
+  }
+  const float d2 = __uint_as_float((uint32_t)(best >> 32));
+  const bool hit = best != ~0ull && d2 <= r2;
+  d2_out[i] = hit ? d2 : __uint_as_float(0x7f800000u);
+  row_out[i] = hit ? (int)(uint32_t)best : -1;
+}
+
+constexpr int64_t NN_MAX_POINTS = 1ll << 30;
+
+}  // namespace pst
+
+extern "C" int pst_mesh_sample_count(const float* vertices, int64_t Nv, const int32_t* faces, int64_t F, float spacing, int max_subdiv, int32_t* counts,
+                                     int64_t* total, int32_t* status, void* stream) {
+  using namespace pst;
+  if (!vertices || !faces || !counts || !total || !status || Nv <= 0 || Nv > 0x7fffffffll || F <= 0 || F > NN_MAX_POINTS || !(spacing > 0.f) ||
+      !(spacing <= 3.402823466e38f) || max_subdiv < 1 || max_subdiv > MS_MAX_SUBDIV) {
+    set_error("mesh_sample_count: bad shape (Nv=%lld, F=%lld: at most 2^30 faces), spacing %g (positive, finite), max_subdiv %d (1 .. %d) or null operand",
+              (long long)Nv, (long long)F, (double)spacing, max_subdiv, MS_MAX_SUBDIV);
+    return PST_EINVAL;
+  }
+  const double s2 = (double)spacing * (double)spacing;              // exact: two 24-bit significands
+  hipLaunchKernelGGL(mesh_sample_count_kernel, nn_grid(F), dim3(NN_T), 0, (hipStream_t)stream, vertices, (int)Nv, faces, (int)F, s2, max_subdiv, counts, total,
+                     status);
+  return check_launch("mesh_sample_count");
+}
+
+extern "C" int pst_mesh_sample_emit(const float* vertices, int64_t Nv, const int32_t* faces, int64_t F, const int32_t* prefix, int64_t total, int64_t capacity,
+                                    const int32_t* vertex_ids, const int32_t* face_ids, float* points, int32_t* face, int32_t* ids, int32_t* status,
+                                    void* stream) {
+  using namespace pst;
+  if (!vertices || !faces || !prefix || !points || !face || !ids || !status || Nv <= 0 || Nv > 0x7fffffffll || F <= 0 || F > NN_MAX_POINTS || total <= 0 ||
+      (vertex_ids && face_ids)) {
+    set_error("mesh_sample_emit: bad shape (Nv=%lld, F=%lld, total=%lld), both kinds of ids or null operand", (long long)Nv, (long long)F, (long long)total);
+    return PST_EINVAL;
+  }
+  if (total > capacity || total > 0x7fffff00ll) {                   // before anything is written
+    set_error("mesh_sample_emit: %lld samples exceed the capacity of %lld (2^31 - 256 at the most): a larger spacing or a smaller max_subdiv gives fewer",
+              (long long)total, (long long)capacity);
+    return PST_EINVAL;
+  }
+  hipLaunchKernelGGL(mesh_sample_emit_kernel, nn_grid(total), dim3(NN_T), 0, (hipStream_t)stream, vertices, (int)Nv, faces, (int)F, prefix, (int)total,
+                     vertex_ids, face_ids, points, face, ids, status);
+  return check_launch("mesh_sample_emit");
+}
+
+static int nn_table_ok(const char* what, int64_t M, int64_t capacity) {
+  using namespace pst;
+  if (M <= 0 || M > NN_MAX_POINTS || capacity < 2 * M || capacity > (1ll << 31) || (capacity & (capacity - 1))) {
+    set_error("%s: bad shape (M=%lld: at most 2^30 targets; capacity=%lld: a power of two >= 2 M)", what, (long long)M, (long long)capacity);
+    return PST_EINVAL;
+  }
+  return 0;
+}
+
+extern "C" int pst_nn_insert(const float* targets, int64_t M, float inv, uint64_t* keys, int64_t capacity, int32_t* cell_count, int32_t* point_slot,
+                             int32_t* status, void* stream) {
+  using namespace pst;
+  if (nn_table_ok("nn_insert", M, capacity)) return PST_EINVAL;
+  if (!targets || !keys || !cell_count || !point_slot || !status || !(inv > 0.f) || !(inv <= 3.402823466e38f)) {
+    set_error("nn_insert: inverse radius %g (positive, finite) or null operand", (double)inv); return PST_EINVAL;
+  }
+  hipLaunchKernelGGL(nn_insert_kernel, nn_grid(M), dim3(NN_T), 0, (hipStream_t)stream, targets, (int)M, inv, keys, (uint32_t)(capacity - 1), cell_count,
+                     point_slot, status);
+  return check_launch("nn_insert");
+}
+
+extern "C" int pst_nn_scatter(const int32_t* point_slot, int64_t M, const int32_t* start, const int32_t* cell_count, int32_t* fill, int32_t* rows,
+                              int32_t* status, void* stream) {
+  using namespace pst;
+  if (!point_slot || !start || !cell_count || !fill || !rows || !status || M <= 0 || M > NN_MAX_POINTS) {
+    set_error("nn_scatter: bad shape (M=%lld) or null operand", (long long)M); return PST_EINVAL;
+  }
+  hipLaunchKernelGGL(nn_scatter_kernel, nn_grid(M), dim3(NN_T), 0, (hipStream_t)stream, point_slot, (int)M, start, cell_count, fill, rows, status);
+  return check_launch("nn_scatter");
+}
+
+extern "C" int pst_nn_query(const float* queries, int64_t Nq, const float* targets, int64_t M, float inv, float r2, const uint64_t* keys, int64_t capacity,
+                            const int32_t* start, const int32_t* cell_count, const int32_t* rows, int max_cell_points, float* d2, int32_t* row,
+                            int32_t* status, void* stream) {
+  using namespace pst;
+  if (nn_table_ok("nn_query", M, capacity)) return PST_EINVAL;
+  if (!queries || !targets || !keys || !start || !cell_count || !rows || !d2 || !row || !status || Nq <= 0 || Nq > NN_MAX_POINTS || !(inv > 0.f) ||
+      !(inv <= 3.402823466e38f) || !(r2 >= 0.f) || !(r2 <= 3.402823466e38f) || max_cell_points < 1) {
+    set_error("nn_query: bad shape (Nq=%lld: at most 2^30 queries), inverse radius %g, squared radius %g (finite), max_cell_points %d (>= 1) or null operand",
+              (long long)Nq, (double)inv, (double)r2, max_cell_points);
+    return PST_EINVAL;
+  }
+  hipLaunchKernelGGL(nn_query_kernel, nn_grid(Nq), dim3(NN_T), 0, (hipStream_t)stream, queries, (int)Nq, targets, (int)M, inv, r2, keys,
+                     (uint32_t)(capacity - 1), start, cell_count, rows, max_cell_points, d2, row, status);
+  return check_launch("nn_query");
+}

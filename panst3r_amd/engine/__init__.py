@@ -11,3 +11,4 @@ from .render import render_cloud, render_cameras, orbit_cameras, CloudRender  # 
 from .evaluate import panoptic_quality  # noqa: F401,E402  (PQ / SQ / RQ and mIoU of panoptic maps against ground truth, per scene or per view; not in the reference)
 from .mesh import render_mesh, ground_truth_maps, mesh_camera_table, load_ply_mesh, panoptic_vertex_ids, MeshRender  # noqa: F401,E402  (ground-truth depth and panoptic maps rasterised from a labelled mesh; reference tools/preprocess_scannetpp.py:395-494 through OpenGL)
 from .surface import panoptic_mesh, PanopticMesh  # noqa: F401,E402  (the pointmap grids triangulated into one labelled surface mesh on the cloud's rows; not in the reference)
+from .score3d import sample_mesh, nearest_points, similarity_from_cameras, score_reconstruction, MeshSamples  # noqa: F401,E402  (a reconstruction scored against a ground-truth mesh in 3-D: F-score, chamfer, a panoptic quality on the surface; not in the reference)

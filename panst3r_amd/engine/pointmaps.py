@@ -38,23 +38,38 @@ def estimate_focal_knowing_depth(pts3d, pp, focal_mode='weiszfeld', min_focal=0.
     return focal.clip(min=min_focal * base, max=max_focal * base)
 
 
+def procrustes_from_moments(sw, sx, sy, syx, sxx=None):
+    """the host step of the registration, float64: sw = sum w, sx = sum w x, sy = sum w y, syx = sum w y x^T -> (R, t) with y ~ R x + t (special
+    Procrustes: the nearest rotation, det +1).  With sxx = sum w |x|^2 also the scale of roma's compute_scaling=True, the D-weighted singular values
+    over the weighted variance of x: -> (R, t, s) with y ~ s R x + t."""
+    xm, ym = sx / sw, sy / sw
+    M = syx - sw * np.outer(ym, xm)                          # sum w (y - ym)(x - xm)^T
+    U, S, Vt = np.linalg.svd(M)
+    D = np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt)) or 1.0])
+    R = U @ D @ Vt
+    if sxx is None:
+        return R, ym - R @ xm
+    s = float((S * np.diag(D)).sum() / (sxx - sw * (xm @ xm)))
+    return R, ym - s * (R @ xm), s
+
+
 def rigid_points_registration(x, y, weights=None, compute_scaling=False):
     """roma.rigid_points_registration restated for batches of point sets: x, y [B, N, 3] (device), weights [B, N] -> (R [B,3,3], t [B,3])
-    with y ~ R x + t (weighted Kabsch; the 16 moments per set are reduced on the device, the 3x3 SVD runs on the host in float64)."""
-    if compute_scaling:
-        raise NotImplementedError('the demo calls it with compute_scaling=False (tools/demo_panst3r.py:265)')
+    with y ~ R x + t (weighted Kabsch; the 16 moments per set are reduced on the device, the 3x3 SVD runs on the host in float64).
+    compute_scaling=True (not used by the demo, tools/demo_panst3r.py:265; engine/score3d.py aligns cameras with it) -> (R, t, scale [B]) with
+    y ~ scale R x + t; the one further moment, sum w |x|^2, is a float64 reduction through torch."""
     B, N = x.shape[0], x.shape[1]
     w = torch.ones(B, N, dtype=torch.float32, device=x.device) if weights is None else weights.float().reshape(B, N).contiguous()
     mom = hip.rigid_moments(x.float().contiguous(), y.float().contiguous(), w, torch.empty(B, 16, dtype=torch.float64, device=x.device), 0.0).cpu().numpy()
-    R, t = np.zeros((B, 3, 3)), np.zeros((B, 3))
+    sxx = (w.double() * x.float().double().pow(2).sum(-1)).sum(-1).cpu().numpy() if compute_scaling else [None] * B
+    R, t, s = np.zeros((B, 3, 3)), np.zeros((B, 3)), np.zeros(B)
     for b in range(B):
-        sw, sx, sy, syx = mom[b, 0], mom[b, 1:4], mom[b, 4:7], mom[b, 7:16].reshape(3, 3)
-        xm, ym = sx / sw, sy / sw
-        M = syx - sw * np.outer(ym, xm)                      # sum w (y - ym)(x - xm)^T
-        U, _, Vt = np.linalg.svd(M)
-        D = np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt)) or 1.0])
-        R[b] = U @ D @ Vt                                     # special Procrustes: nearest rotation, det +1
-        t[b] = ym - R[b] @ xm
+        out = procrustes_from_moments(mom[b, 0], mom[b, 1:4], mom[b, 4:7], mom[b, 7:16].reshape(3, 3), sxx[b])
+        R[b], t[b] = out[0], out[1]
+        if compute_scaling:
+            s[b] = out[2]
+    if compute_scaling:
+        return torch.from_numpy(R).float(), torch.from_numpy(t).float(), torch.from_numpy(s).float()
     return torch.from_numpy(R).float(), torch.from_numpy(t).float()
 
 

@@ -77,6 +77,8 @@ SIGNATURES = {
     'pst_vcc_rank': 'i:pplpppppppppppppp', 'pst_vcc_votes': 'i:pppplppliipplpp', 'pst_vcc_apply': 'i:pppplippiffpppp',
     'pst_surface_rows': 'i:pllpp', 'pst_surface_count': 'i:ppiipfpp', 'pst_surface_emit': 'i:ppiipfpppppp', 'pst_surface_link': 'i:pllpppp',
     'pst_surface_components': 'i:pllppppp', 'pst_surface_keep_count': 'i:pplipp', 'pst_surface_keep_emit': 'i:ppppplippppp',
+    'pst_mesh_sample_count': 'i:plplfipppp', 'pst_mesh_sample_emit': 'i:plplpllppppppp',
+    'pst_nn_insert': 'i:plfplpppp', 'pst_nn_scatter': 'i:plpppppp', 'pst_nn_query': 'i:plplffplpppipppp',
 }
 EXPORTS = list(SIGNATURES)
 
@@ -1601,3 +1603,75 @@ def surface_keep_emit(faces, face_ids, quad, component, ws, min_faces, base, out
     assert base.numel() == (F + SURFACE_WG - 1) // SURFACE_WG + 1
     _call('pst_surface_keep_emit', _ptr(faces), _ptr(face_ids), _ptr(quad), _ptr(component), _ptr(ws['size']), F, int(min_faces), _ptr(base), _ptr(out_faces),
           _ptr(out_face_ids), _ptr(out_quad))
+
+
+# ------------------------------------------------------------------ 3-D scores: mesh surface sampler and fixed-radius nearest neighbour (csrc/nearest.hip; engine/score3d.py holds the public entry points)
+MESH_SAMPLE_MAX_SUBDIV = 1 << 15    # PST_MESH_SAMPLE_MAX_SUBDIV
+MESH_SAMPLE_MAX_TOTAL = 2 ** 31 - 256
+MESH_SAMPLE_TOTAL = 1               # PST_MESH_SAMPLE_TOTAL: the bit of the sampler's status[0]
+NN_FULL, NN_LISTS = 1, 2            # PST_NN_*: the bits of the search's status[0]
+NN_MAX_POINTS = 1 << 30
+
+
+def _mesh_sample_mesh(vertices, faces):
+    _dev(vertices, torch.float32); _dev(faces, torch.int32)
+    assert vertices.is_contiguous() and faces.is_contiguous() and vertices.dim() == 2 and vertices.shape[1] == 3 and faces.dim() == 2 and faces.shape[1] == 3
+    return vertices.shape[0], faces.shape[0]
+
+
+def mesh_sample_count(vertices, faces, spacing, max_subdiv, counts, total, status):
+    """counts int32 [F]; total int64 [1] and status int32 [4] zeroed by the caller (include/panst3r_hip.h)"""
+    Nv, F = _mesh_sample_mesh(vertices, faces)
+    _dev(counts, torch.int32); _dev(total, torch.int64); _dev(status, torch.int32)
+    assert counts.numel() == F and total.numel() == 1 and status.numel() == 4
+    _call('pst_mesh_sample_count', _ptr(vertices), Nv, _ptr(faces), F, float(spacing), int(max_subdiv), _ptr(counts), _ptr(total), _ptr(status))
+
+
+def mesh_sample_emit(vertices, faces, prefix, total, vertex_ids, face_ids, points, face, ids, status):
+    """the outputs' rows are the capacity: a `total` beyond them is refused before the launch"""
+    Nv, F = _mesh_sample_mesh(vertices, faces)
+    _dev(prefix, torch.int32); _dev(points, torch.float32); _dev(face, torch.int32); _dev(ids, torch.int32); _dev(status, torch.int32)
+    capacity = face.numel()
+    assert prefix.numel() == F + 1 and points.is_contiguous() and points.numel() == 3 * capacity and ids.numel() == capacity and status.numel() == 4
+    for t, n in ((vertex_ids, Nv), (face_ids, F)):
+        if t is not None:
+            _dev(t, torch.int32)
+            assert t.is_contiguous() and t.numel() == n
+    _call('pst_mesh_sample_emit', _ptr(vertices), Nv, _ptr(faces), F, _ptr(prefix), int(total), capacity, _ptr(vertex_ids), _ptr(face_ids), _ptr(points),
+          _ptr(face), _ptr(ids), _ptr(status))
+
+
+def nn_workspace(M, device):
+    """the initialised workspaces of one search structure over M targets (include/panst3r_hip.h): dict of device tensors"""
+    cap = voxel_capacity(M)
+    i32 = dict(dtype=torch.int32, device=device)
+    return {'cap': cap, 'keys': torch.full((cap,), -1, dtype=torch.int64, device=device), 'cell_count': torch.zeros(cap, **i32), 'start': None,
+            'fill': torch.zeros(cap, **i32), 'point_slot': torch.empty(M, **i32), 'rows': torch.empty(M, **i32), 'status': torch.zeros(4, **i32)}
+
+
+def _nn_points(points):
+    _dev(points, torch.float32)
+    assert points.is_contiguous() and points.dim() == 2 and points.shape[1] == 3
+    return points.shape[0]
+
+
+def nn_insert(targets, inv, ws):
+    M = _nn_points(targets)
+    assert ws['point_slot'].numel() == M and ws['keys'].numel() == ws['cap'] == ws['cell_count'].numel()
+    _call('pst_nn_insert', _ptr(targets), M, float(inv), _ptr(ws['keys']), ws['cap'], _ptr(ws['cell_count']), _ptr(ws['point_slot']), _ptr(ws['status']))
+
+
+def nn_scatter(ws):
+    """ws['start'] = the exclusive prefix sum of ws['cell_count'] (int32 [cap]), made by the caller"""
+    M = ws['point_slot'].numel()
+    _dev(ws['start'], torch.int32)
+    assert ws['start'].is_contiguous() and ws['start'].numel() == ws['cap'] == ws['fill'].numel() and ws['rows'].numel() == M
+    _call('pst_nn_scatter', _ptr(ws['point_slot']), M, _ptr(ws['start']), _ptr(ws['cell_count']), _ptr(ws['fill']), _ptr(ws['rows']), _ptr(ws['status']))
+
+
+def nn_query(queries, targets, inv, r2, ws, max_cell_points, d2, row):
+    Nq, M = _nn_points(queries), _nn_points(targets)
+    _dev(d2, torch.float32); _dev(row, torch.int32)
+    assert ws['rows'].numel() == M and d2.numel() == Nq and row.numel() == Nq and d2.is_contiguous() and row.is_contiguous()
+    _call('pst_nn_query', _ptr(queries), Nq, _ptr(targets), M, float(inv), float(r2), _ptr(ws['keys']), ws['cap'], _ptr(ws['start']), _ptr(ws['cell_count']),
+          _ptr(ws['rows']), int(max_cell_points), _ptr(d2), _ptr(row), _ptr(ws['status']))

@@ -376,6 +376,7 @@ class PanSt3R(nn.Module):
         Images out of the result: `engine.render_cameras(cloud, cameras)` re-renders the cloud (or the voxels) from the input cameras, and
         `cloud.render(engine.orbit_cameras(...), focal, (H, W))` from any other - depth, panoptic map and colours per pixel (engine/render.py).
         A surface out of the result: `cloud.mesh()` triangulates the pointmap grids into a labelled mesh on the cloud's rows (engine/surface.py).
+        A score of the result in 3-D: `evaluate_3d(cloud, gt_mesh, thresholds=..., spacing=...)` against a ground-truth mesh (engine/score3d.py).
         It only composes the public entry points."""
         from .engine import panoptic_inference_v2, panoptic_inference_v1, panoptic_inference_qubo, panoptic_point_cloud
         from .engine.pointmaps import cameras_from_pointmaps
@@ -411,6 +412,18 @@ class PanSt3R(nn.Module):
         (scope='scene' | 'view', things=).  It only composes."""
         from .engine import panoptic_quality
         return panoptic_quality(pan_preds[0]['pan'], pan_preds[0]['segments_info'], gt_maps, gt_segments, **kw)
+
+    def evaluate_3d(self, cloud_or_voxels_or_mesh, gt_mesh, **kw):
+        """A reconstruction against a ground-truth mesh in 3-D: `engine.score_reconstruction` of a `PanopticCloud`, a `VoxelCloud` or a `PanopticMesh`
+        (precision / recall / F-score at `thresholds=`, accuracy, completeness, chamfer, and with labels the surface panoptic quality `pq3d`).
+        `gt_mesh`: (vertices, faces) or (vertices, faces, vertex_ids, segments) on the device, e.g. from `engine.load_ply_mesh` and
+        `engine.panoptic_vertex_ids`; `transform=engine.similarity_from_cameras(...)` carries the prediction into its frame.  It only composes."""
+        from .engine import score_reconstruction
+        if len(gt_mesh) not in (2, 4):
+            raise ValueError('gt_mesh is (vertices, faces) or (vertices, faces, vertex_ids, segments), got %d entries' % len(gt_mesh))
+        if len(gt_mesh) == 4:
+            kw = dict(kw, gt_vertex_ids=gt_mesh[2], gt_segments=gt_mesh[3])
+        return score_reconstruction(cloud_or_voxels_or_mesh, gt_mesh[0], gt_mesh[1], **kw)
 
     @torch.no_grad()
     def _forward_inference_once(self, imgs, true_shape, classes, num_keyframes=None, use_retrieval=False, max_bs=None,
