@@ -729,6 +729,43 @@ int pst_nn_query(const float* queries, int64_t Nq, const float* targets, int64_t
                  const int32_t* start, const int32_t* cell_count, const int32_t* rows, int max_cell_points, float* d2, int32_t* row, int32_t* status,
                  void* stream);
 
+/* ---------------------------------------------------------------- icp: one fused step of the alignment to the ground truth (no counterpart in the reference)
+ * The hot path of engine/score3d.py's `icp` / `refine_alignment`: the source points are moved by the current transform, each finds its nearest target in
+ * the search structure of the score3d section, and the moments of the matched pairs that `pointmaps.procrustes_from_moments` needs are summed, in one
+ * pass over the sources.  Restated in tests/icp_ref.py [restated, parity unpinned] on the brute-force search of tests/nearest_ref.py; every step is
+ * exact or separately rounded in a fixed order, so the 20 moments, d2, row and the status are held to the restatement bit for bit.  Contraction is
+ * off: every fp32 and fp64 operation is rounded on its own, in the order written.  Additive to ABI 20.
+ *   source fp32 [N, 3]; A = (a00 .. a23) the 3 x 4 fp32 matrix, by value, row-major; targets, inv, keys, capacity, start, cell_count, rows and
+ *   max_cell_points are those of a finished build (nn_insert, the prefix sum, nn_scatter) with cell edge 1 / inv; 0 <= r2 finite.
+ *   1 move      m_r = ((a_r0 x0 + a_r1 x1) + a_r2 x2) + a_r3 in fp32, r = 0, 1, 2.
+ *   2 search    step 3 of the fixed-radius contract with m as the query (the same device function as nn_query): the 27 cells around m's cell, the
+ *               minimum of (uint64(bits(d2)) << 32) | p, ties to the smaller row; accepted iff d2 <= r2.  The search equals the one over all targets
+ *               only for pairs in neighbouring cells, so r2 MUST NOT exceed the square of the cell edge (the CALLER's duty; a smaller r2 is fine: it
+ *               is how the radius shrinks without a rebuild).  A non-finite m is unmatched and counted in status[3].  With d2 fp32 [N] and row int32
+ *               [N] given (both or neither) they are written as nn_query writes them: row -1 and d2 = +inf for an unmatched source.
+ *   3 moments   over the matched sources, with x the ORIGINAL source point (not m) and y = targets[row], both widened to fp64 - a product of two of
+ *               them is exact, only the additions round.  An unmatched source adds nothing.
+ *                 [0] the number matched   [1..3] sum x   [4..6] sum y   [7..15] sum y x^T, row-major [y][x]   [16] sum of (x0 x0 + x1 x1) + x2 x2
+ *                 [17] sum of fp64(d2)     [18], [19] +0.0, reserved
+ *   4 order     block b of PST_ICP_LANES lanes owns the source rows [PST_ICP_CHUNK b, PST_ICP_CHUNK (b + 1)).  Lane l adds its rows PST_ICP_CHUNK b + l +
+ *               PST_ICP_LANES j, j = 0 .. PST_ICP_CHUNK / PST_ICP_LANES - 1 ascending, into accumulators that start at +0.0.  Inside a wave of 64
+ *               lanes six butterfly steps v += v[lane ^ k], k = 32, 16, 8, 4, 2, 1 (fp addition is commutative: all lanes agree); the four waves
+ *               are added as ((w0 + w1) + w2) + w3 -> row b of partials double [ceil(N / PST_ICP_CHUNK), PST_ICP_MOMENTS].  A second launch of one
+ *               block inside the same call adds the rows of partials the same way - lane l takes the rows l, l + PST_ICP_LANES, ... ascending, then
+ *               the same butterfly and the same wave order - into out double [PST_ICP_MOMENTS].  No float atomics, no counter of finished blocks:
+ *               two calls return identical bytes, and d2 / row given or not does not change the moments.
+ *   status int32 [4], cleared by the CALLER, as the search's: [0] = PST_NN_FULL | PST_NN_LISTS, [3] non-finite moved points; [1], [2] untouched.
+ *   Refused with PST_EINVAL before any launch: a null source / targets / table / partials / out / status, exactly one of d2 and row, N < 1 or
+ *   N > 2^30, a table that nn_query would refuse, inv or r2 not finite, max_cell_points < 1.  pst_icp_chunk() returns PST_ICP_CHUNK. */
+#define PST_ICP_CHUNK 4096        /* source rows per block */
+#define PST_ICP_LANES 256         /* lanes per block */
+#define PST_ICP_MOMENTS 20        /* doubles per row of partials and in out */
+int pst_icp_chunk(void);
+int pst_icp_step(const float* source, int64_t N, float a00, float a01, float a02, float a03, float a10, float a11, float a12, float a13, float a20,
+                 float a21, float a22, float a23, const float* targets, int64_t M, float inv, float r2, const uint64_t* keys, int64_t capacity,
+                 const int32_t* start, const int32_t* cell_count, const int32_t* rows, int max_cell_points, float* d2, int32_t* row, double* partials,
+                 double* out, int32_t* status, void* stream);
+
 /* ---------------------------------------------------------------- panoptic evaluation against ground truth: PQ / SQ / RQ, mIoU (no counterpart in the reference)
  * V predicted maps and V ground-truth maps of the same shapes, flattened and concatenated to pred, gt int32 [N] (1 <= N <= 2^31 - 1, both 16-byte
  * aligned), P predicted and G ground-truth segments (ids unique and > 0 within each list, no crowd regions).  The rules are those of COCO

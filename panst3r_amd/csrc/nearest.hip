@@ -8,7 +8,11 @@
 //                  (offsets: a prefix sum of the slot counts, made by the caller)
 //                  scatter the target's row into its cell's list (the position inside the list depends on arrival; nothing that leaves depends on it)
 //                  query  one lane per query: the 27 cells around it, every candidate's fp32 distance, the minimum of (bits(d2) << 32) | row
-// Integer atomics only, no float sum whose order depends on arrival, every probe / candidate / search loop bounded by a number known before the launch,
+//   icp step       step   a block per PST_ICP_CHUNK source rows, 16 rows per lane: the row moved by the 3 x 4 matrix in fp32, the query's search (the same
+//                         __device__ function), the 18 live moments of the matched pairs in fp64 registers; a butterfly per wave, the four waves added
+//                         in order, one row of 20 per block
+//                  reduce one block adds the rows of the blocks the same way
+// Integer atomics only, no float sum whose order depends on arrival (the moments are added in the order the header fixes), every probe / candidate / search loop bounded by a number known before the launch,
 // refusals through the status words, every result written with plain vector stores: two calls return identical bytes.  Contraction is off for the
 // whole file: every fp32 and fp64 operation is rounded on its own, in the order written.
 #include "common.h"
@@ -143,16 +147,21 @@ __device__ __forceinline__ float nn_addr(float a, float b) { return a + b; }
 __device__ __forceinline__ float nn_subr(float a, float b) { return a - b; }
 
 // the cell of a point by vx_cell's rule (csrc/voxel.hip): floor(x * inv) per axis; finite = every coordinate is, ok = and every cell is inside +-2^20
-__device__ __forceinline__ void nn_cell(const float* __restrict__ p, float inv, float (&x)[3], float (&c)[3], bool& finite, bool& ok) {
+__device__ __forceinline__ void nn_cell_of(const float (&x)[3], float inv, float (&c)[3], bool& finite, bool& ok) {
   finite = ok = true;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    x[a] = p[a];
     c[a] = floorf(nn_mulr(x[a], inv));
     finite = finite && (fabsf(x[a]) <= 3.402823466e38f);           // NaN fails the compare
     ok = ok && (fabsf(c[a]) < (float)VX_LIM);
   }
   ok = ok && finite;
+}
+
+__device__ __forceinline__ void nn_cell(const float* __restrict__ p, float inv, float (&x)[3], float (&c)[3], bool& finite, bool& ok) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) x[a] = p[a];
+  nn_cell_of(x, inv, c, finite, ok);
 }
 
 __device__ __forceinline__ uint64_t nn_key(int x, int y, int z) {     // only for cells in range: no field wraps
@@ -191,18 +200,12 @@ __global__ __launch_bounds__(NN_T) void nn_scatter_kernel(const int32_t* __restr
   if (k == n - 1) atomicMax(&status[2], n);
 }
 
-__global__ __launch_bounds__(NN_T) void nn_query_kernel(const float* __restrict__ queries, int Nq, const float* __restrict__ targets, int M, float inv,
-                                                        float r2, const uint64_t* __restrict__ keys, uint32_t mask, const int32_t* __restrict__ start,
-                                                        const int32_t* __restrict__ cell_count, const int32_t* __restrict__ rows, int max_cell_points,
-                                                        float* __restrict__ d2_out, int32_t* __restrict__ row_out, int32_t* __restrict__ status) {
-  const int i = blockIdx.x * NN_T + threadIdx.x, lane = threadIdx.x & 63;
-  const bool in = i < Nq;
-  float q[3], c[3];
-  bool finite = false, ok = false;
-  if (in) nn_cell(queries + (int64_t)i * 3, inv, q, c, finite, ok);
-  const uint64_t bad = __ballot(in && !finite);
-  if (bad && lane == (int)__builtin_ctzll(bad)) atomicAdd(&status[3], (int)__popcll(bad));
-  if (!in) return;
+// step 3 of the fixed-radius contract for one lane, shared by nn_query and icp_step: every candidate of the 27 cells around the cell c of the point q
+// -> the minimum of (bits(d2) << 32) | row, all ones without a candidate.  Nothing here is collective: lanes may call it divergently.
+__device__ __forceinline__ uint64_t nn_search(const float (&q)[3], const float (&c)[3], bool finite, const float* __restrict__ targets, int M,
+                                              const uint64_t* __restrict__ keys, uint32_t mask, const int32_t* __restrict__ start,
+                                              const int32_t* __restrict__ cell_count, const int32_t* __restrict__ rows, int max_cell_points,
+                                              int32_t* __restrict__ status) {
   uint64_t best = ~0ull;
   // a finite query whose cell is not within one cell of the range has no target cell among its 27
   if (finite && fabsf(c[0]) <= (float)VX_LIM && fabsf(c[1]) <= (float)VX_LIM && fabsf(c[2]) <= (float)VX_LIM) {
@@ -235,10 +238,111 @@ __global__ __launch_bounds__(NN_T) void nn_query_kernel(const float* __restrict_
       }
     }
   }
+  return best;
+}
+
+__global__ __launch_bounds__(NN_T) void nn_query_kernel(const float* __restrict__ queries, int Nq, const float* __restrict__ targets, int M, float inv,
+                                                        float r2, const uint64_t* __restrict__ keys, uint32_t mask, const int32_t* __restrict__ start,
+                                                        const int32_t* __restrict__ cell_count, const int32_t* __restrict__ rows, int max_cell_points,
+                                                        float* __restrict__ d2_out, int32_t* __restrict__ row_out, int32_t* __restrict__ status) {
+  const int i = blockIdx.x * NN_T + threadIdx.x, lane = threadIdx.x & 63;
+  const bool in = i < Nq;
+  float q[3], c[3];
+  bool finite = false, ok = false;
+  if (in) nn_cell(queries + (int64_t)i * 3, inv, q, c, finite, ok);
+  const uint64_t bad = __ballot(in && !finite);
+  if (bad && lane == (int)__builtin_ctzll(bad)) atomicAdd(&status[3], (int)__popcll(bad));
+  if (!in) return;
+  const uint64_t best = nn_search(q, c, finite, targets, M, keys, mask, start, cell_count, rows, max_cell_points, status);
   const float d2 = __uint_as_float((uint32_t)(best >> 32));
   const bool hit = best != ~0ull && d2 <= r2;
   d2_out[i] = hit ? d2 : __uint_as_float(0x7f800000u);
   row_out[i] = hit ? (int)(uint32_t)best : -1;
+}
+
+// ---------------------------------------------------------------- one fused ICP step (the icp section of include/panst3r_hip.h)
+constexpr int ICP_ROWS = PST_ICP_CHUNK / NN_T;                       // source rows per lane
+constexpr int ICP_LIVE = 18;                                         // the moments that are sums; [18], [19] are +0.0
+static_assert(NN_T == PST_ICP_LANES && PST_ICP_CHUNK % NN_T == 0 && ICP_LIVE + 2 == PST_ICP_MOMENTS, "the fixed order of the header");
+
+struct IcpMatrix { float a[3][4]; };
+
+// steps 3 to 5 of the fixed order: six butterfly steps inside every wave, then ((w0 + w1) + w2) + w3 -> row[0, 20)
+__device__ __forceinline__ void icp_block_sum(const double (&acc)[ICP_LIVE], double* __restrict__ row) {
+  __shared__ double waves[NN_T / 64][ICP_LIVE];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int s = 0; s < ICP_LIVE; ++s) {
+    double v = acc[s];
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) v += __shfl_xor(v, k);
+    if (lane == 0) waves[wave][s] = v;
+  }
+  __syncthreads();
+  const int s = threadIdx.x;
+  if (s < ICP_LIVE) row[s] = ((waves[0][s] + waves[1][s]) + waves[2][s]) + waves[3][s];
+  else if (s < PST_ICP_MOMENTS) row[s] = 0.0;
+}
+
+__global__ __launch_bounds__(NN_T) void icp_step_kernel(const float* __restrict__ source, int N, IcpMatrix A, const float* __restrict__ targets, int M,
+                                                        float inv, float r2, const uint64_t* __restrict__ keys, uint32_t mask,
+                                                        const int32_t* __restrict__ start, const int32_t* __restrict__ cell_count,
+                                                        const int32_t* __restrict__ rows, int max_cell_points, float* __restrict__ d2_out,
+                                                        int32_t* __restrict__ row_out, double* __restrict__ partials, int32_t* __restrict__ status) {
+  const int first = blockIdx.x * PST_ICP_CHUNK + threadIdx.x;        // N <= 2^30: no row leaves int32
+  double acc[ICP_LIVE];
+#pragma unroll
+  for (int s = 0; s < ICP_LIVE; ++s) acc[s] = 0.0;
+  int bad = 0;
+  for (int j = 0; j < ICP_ROWS; ++j) {                               // (per lane: nothing collective inside)
+    const int i = first + NN_T * j;
+    if (i >= N) break;
+    float x[3], m[3], c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) x[a] = source[(int64_t)i * 3 + a];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+      m[r] = nn_addr(nn_addr(nn_addr(nn_mulr(A.a[r][0], x[0]), nn_mulr(A.a[r][1], x[1])), nn_mulr(A.a[r][2], x[2])), A.a[r][3]);
+    bool finite, ok;
+    nn_cell_of(m, inv, c, finite, ok);
+    bad += !finite;
+    const uint64_t best = nn_search(m, c, finite, targets, M, keys, mask, start, cell_count, rows, max_cell_points, status);
+    const float d2 = __uint_as_float((uint32_t)(best >> 32));
+    const bool hit = best != ~0ull && d2 <= r2;
+    if (d2_out) {
+      d2_out[i] = hit ? d2 : __uint_as_float(0x7f800000u);
+      row_out[i] = hit ? (int)(uint32_t)best : -1;
+    }
+    if (!hit) continue;
+    const int p = (int)(uint32_t)best;                               // (the search took it from rows and checked it against M)
+    double xd[3], yd[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { xd[a] = (double)x[a]; yd[a] = (double)targets[(int64_t)p * 3 + a]; }
+    acc[0] += 1.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { acc[1 + a] += xd[a]; acc[4 + a] += yd[a]; }
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int a = 0; a < 3; ++a) acc[7 + 3 * r + a] += yd[r] * xd[a];      // a product of two widened fp32 values is exact
+    acc[16] += (xd[0] * xd[0] + xd[1] * xd[1]) + xd[2] * xd[2];
+    acc[17] += (double)d2;
+  }
+#pragma unroll
+  for (int k = 32; k > 0; k >>= 1) bad += __shfl_xor(bad, k);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&status[3], bad);
+  icp_block_sum(acc, partials + (int64_t)blockIdx.x * PST_ICP_MOMENTS);
+}
+
+// step 6: one block; lane l adds the rows l, l + 256, ... of the partials in ascending order, then the same butterfly and the same wave order
+__global__ __launch_bounds__(NN_T) void icp_reduce_kernel(const double* __restrict__ partials, int P, double* __restrict__ out) {
+  double acc[ICP_LIVE];
+#pragma unroll
+  for (int s = 0; s < ICP_LIVE; ++s) acc[s] = 0.0;
+  for (int r = threadIdx.x; r < P; r += NN_T)
+#pragma unroll
+    for (int s = 0; s < ICP_LIVE; ++s) acc[s] += partials[(int64_t)r * PST_ICP_MOMENTS + s];
+  icp_block_sum(acc, out);
 }
 
 constexpr int64_t NN_MAX_POINTS = 1ll << 30;
@@ -324,4 +428,27 @@ extern "C" int pst_nn_query(const float* queries, int64_t Nq, const float* targe
   hipLaunchKernelGGL(nn_query_kernel, nn_grid(Nq), dim3(NN_T), 0, (hipStream_t)stream, queries, (int)Nq, targets, (int)M, inv, r2, keys,
                      (uint32_t)(capacity - 1), start, cell_count, rows, max_cell_points, d2, row, status);
   return check_launch("nn_query");
+}
+
+extern "C" int pst_icp_chunk(void) { return PST_ICP_CHUNK; }
+
+extern "C" int pst_icp_step(const float* source, int64_t N, float a00, float a01, float a02, float a03, float a10, float a11, float a12, float a13, float a20,
+                            float a21, float a22, float a23, const float* targets, int64_t M, float inv, float r2, const uint64_t* keys, int64_t capacity,
+                            const int32_t* start, const int32_t* cell_count, const int32_t* rows, int max_cell_points, float* d2, int32_t* row,
+                            double* partials, double* out, int32_t* status, void* stream) {
+  using namespace pst;
+  if (nn_table_ok("icp_step", M, capacity)) return PST_EINVAL;
+  if (!source || !targets || !keys || !start || !cell_count || !rows || !partials || !out || !status || (d2 == nullptr) != (row == nullptr) || N < 1 ||
+      N > NN_MAX_POINTS || !(inv > 0.f) || !(inv <= 3.402823466e38f) || !(r2 >= 0.f) || !(r2 <= 3.402823466e38f) || max_cell_points < 1) {
+    set_error("icp_step: bad shape (N=%lld: 1 .. 2^30 source points), inverse cell edge %g, squared radius %g (finite), max_cell_points %d (>= 1), one of "
+              "d2 / row without the other, or null operand", (long long)N, (double)inv, (double)r2, max_cell_points);
+    return PST_EINVAL;
+  }
+  const IcpMatrix A = {{{a00, a01, a02, a03}, {a10, a11, a12, a13}, {a20, a21, a22, a23}}};
+  const int P = (int)((N + PST_ICP_CHUNK - 1) / PST_ICP_CHUNK);
+  hipLaunchKernelGGL(icp_step_kernel, dim3((unsigned)P), dim3(NN_T), 0, (hipStream_t)stream, source, (int)N, A, targets, (int)M, inv, r2, keys,
+                     (uint32_t)(capacity - 1), start, cell_count, rows, max_cell_points, d2, row, partials, status);
+  if (int rc = check_launch("icp_step")) return rc;
+  hipLaunchKernelGGL(icp_reduce_kernel, dim3(1), dim3(NN_T), 0, (hipStream_t)stream, (const double*)partials, P, out);
+  return check_launch("icp_step (reduce)");
 }

@@ -4,10 +4,11 @@ unit is a piece of ground-truth surface instead of a pixel).  It scores what the
 a `PanopticMesh` or plain points - against the mesh that `load_ply_mesh` / `panoptic_vertex_ids` give.
 
     T = similarity_from_cameras([c['cam2world'] for c in cameras], gt_cams2world)
-    s = score_reconstruction(cloud, gt_vertices, gt_faces, thresholds=(0.05, 0.1), spacing=0.02, transform=T, gt_vertex_ids=ids, gt_segments=segs)
+    s = score_reconstruction(cloud, gt_vertices, gt_faces, thresholds=(0.05, 0.1), spacing=0.02, transform=T, gt_vertex_ids=ids, gt_segments=segs,
+                             refine=True)                  # T refined on the geometry by ICP before anything is scored (stage f11)
 
 POINT TO POINT ONLY: the ground-truth surface is replaced by a deterministic lattice of samples about `spacing` apart and every distance is one between
-two points - no point-to-triangle distance, no BVH, no ICP.  A distance is therefore off by up to about spacing / sqrt(3) against the true surface;
+two points - no point-to-triangle distance, no BVH.  A distance is therefore off by up to about spacing / sqrt(3) against the true surface;
 choose `spacing` well below the smallest threshold.  No counterpart in the reference: *restated, unpinned*.  Two kernels (csrc/nearest.hip; the contract
 is the score3d section of include/panst3r_hip.h, restated in tests/nearest_ref.py and held bit for bit):
   sample_mesh      face f gets n_f^2 samples, the centroids of the n_f^2 congruent sub-triangles of its uniform subdivision, n_f the smallest whole
@@ -16,6 +17,9 @@ is the score3d section of include/panst3r_hip.h, restated in tests/nearest_ref.p
                    is deterministic and needs no random numbers; an area-weighted draw would be uniform in expectation only.
   nearest_points   a hash grid of cell = radius over the targets, the 27 cells around a query, the minimum of (distance bits, row): the nearest target
                    within the radius, ties to the smaller row.
+  icp_step         (stage f11) the sources moved by the current transform, each one's nearest target through the same search, and the float64
+                   moments of the matched pairs in a fixed order, in one pass: the hot path of `icp` / `refine_alignment`, which refine the alignment
+                   that `similarity_from_cameras` can only take from the camera centres.  Restated in tests/icp_ref.py, held bit for bit.
 Everything else composes: the counts are integer compares of the squared distances against float32(tau)^2, the means are float64 reductions of
 sqrt(d2) through torch, the labels go through `panoptic_quality` as one [1, S] map."""
 import math
@@ -242,8 +246,8 @@ def similarity_from_cameras(pred_cams2world, gt_cams2world):
     camera poses are host values here) -> a [4, 4] float64 tensor [[s R, t], [0, 1]] with gt_centre ~ s R pred_centre + t: the scale is folded in.
     Raises ValueError for fewer than 3 cameras, and for centres that do not span a plane - collinear or coincident centres leave the rotation about
     their line free.  The test is a CHOICE: with s1 >= s2 the singular values of the centred centres, s2 > 1e-6 s1 (`PLANE_RANK_TOL`), for both sets;
-    it rejects the degenerate case, it does not promise a well-conditioned one.  The orientations of the cameras are not used.  No refinement (no
-    ICP): the residual of the camera centres is all it minimises."""
+    it rejects the degenerate case, it does not promise a well-conditioned one.  The orientations of the cameras are not used.  The residual of
+    the camera centres is all it minimises: `refine_alignment` (or `score_reconstruction(refine=True)`) refines the result on the geometry."""
     x, y = _centres(pred_cams2world, 'pred_cams2world'), _centres(gt_cams2world, 'gt_cams2world')
     if len(x) != len(y):
         raise ValueError('similarity_from_cameras needs as many ground-truth cameras as predicted ones, got %d and %d' % (len(y), len(x)))
@@ -292,6 +296,133 @@ def _check_transform(transform):
     return T
 
 
+class Alignment:
+    """The result of `icp` / `refine_alignment`: `transform` [4, 4] float64 tensor [[s R, t], [0, 1]] with the scale folded in (as
+    `similarity_from_cameras` gives it), `iterations` (steps run), `converged`, `reason` ('converged', 'iters' or 'degenerate') and `history`, per
+    step a dict of `radius`, `matched` (pairs within it) and `rmse` = sqrt(sum d2 / matched) BEFORE that step's solve (nan without a match)."""
+
+    def __init__(self, transform, iterations, converged, reason, history):
+        self.transform, self.iterations, self.converged, self.reason, self.history = transform, int(iterations), bool(converged), reason, history
+
+    def __repr__(self):
+        last = self.history[-1] if self.history else {}
+        return 'Alignment(%s after %d iterations, %s matched, rmse %s)' % (self.reason, self.iterations, last.get('matched'), last.get('rmse'))
+
+
+def _icp_radius(k, max_dist, min_dist, shrink):
+    """(r_k as float32, its fp32 square, whether the schedule has reached its floor)"""
+    r = np.float32(max_dist if min_dist is None else max(min_dist, max_dist * shrink ** k))
+    return r, r * r, min_dist is None or max_dist * shrink ** k <= min_dist
+
+
+def _corner_shift(box, T0, T1):
+    """the farthest that one of the eight corners moves between two transforms"""
+    a, b = box @ T0[:3, :3].T + T0[:3, 3], box @ T1[:3, :3].T + T1[:3, 3]
+    return float(np.sqrt(((a - b) ** 2).sum(1)).max())
+
+
+def _check_icp(max_dist, init=None, with_scale=True, iters=50, min_dist=None, shrink=0.8, tol=1e-4, every=1, max_cell_points=4096):
+    """the keywords of `icp`, checked -> (max_dist and min_dist as their float32 values, the start as a [4, 4] float64 array, shrink, tol)"""
+    max_dist = _check_length(max_dist, 'max_dist')
+    _check_radius(max_dist, 'max_dist')
+    if min_dist is not None:
+        min_dist = _check_length(min_dist, 'min_dist')
+        if min_dist > max_dist:
+            raise ValueError('min_dist %g lies beyond max_dist %g' % (min_dist, max_dist))
+    if isinstance(shrink, bool) or not isinstance(shrink, (int, float, np.integer, np.floating)) or not 0 < float(shrink) < 1:
+        raise ValueError('shrink must be a number in (0, 1), got %r' % (shrink,))
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (math.isfinite(float(tol)) and float(tol) >= 0):
+        raise ValueError('tol must be a finite number >= 0, got %r' % (tol,))
+    for name, v in (('iters', iters), ('every', every), ('max_cell_points', max_cell_points)):
+        if not _is_int(v) or not 1 <= v <= 2 ** 31 - 1:
+            raise ValueError('%s must be an integer >= 1, got %r' % (name, v))
+    T = np.eye(4) if init is None else _check_transform(init).copy()
+    return max_dist, T, min_dist, float(shrink), float(tol)
+
+
+@torch.no_grad()
+def icp(source, target, *, max_dist, init=None, with_scale=True, iters=50, min_dist=None, shrink=0.8, tol=1e-4, every=1, max_cell_points=4096):
+    """Point-to-point ICP: the similarity (`with_scale=False`: rigid) transform that carries `source` [N, 3] onto `target` [M, 3] (device float
+    tensors), started from `init` ([4, 4], default the identity) -> `Alignment`.  One `NearestIndex` of cell edge `max_dist` over the targets is
+    built once.  Step k moves the sources by float32(T), matches each to its nearest target within r_k = float32(max(min_dist, max_dist shrink^k))
+    (`min_dist=None`: r_k = max_dist throughout; the radius shrinks without a rebuild, the cells stay `max_dist` wide), sums the moments of the
+    matched pairs - all of it ONE fused launch, `hip.icp_step` - and after ONE host sync (the 20 doubles and the status) solves
+    `pointmaps.procrustes_from_moments` for the TOTAL transform from the original sources to their matches, never an increment, so nothing drifts.
+    `every=k` uses the source rows 0, k, 2k, ...  Stops: 'converged' - the radius has reached its floor and the eight corners of the sources' bounding
+    box (one device min / max before the loop; a non-finite source keeps this from ever holding) moved by at most `tol` r_k between two successive
+    T; 'iters' - `iters` steps were run; 'degenerate' - fewer than 3 pairs remain, or with s1 >= s2 the singular values of the centred moment matrix
+    sum (y - ym)(x - xm)^T, s2 <= PLANE_RANK_TOL s1: the matched sources lie on a line, the same CHOICE as in `similarity_from_cameras`; the transform
+    of the step before is returned.  A first step with fewer than 3 pairs raises ValueError.  The schedule, the defaults and the stop rule are
+    CHOICES: a geometric radius schedule sheds outliers as the fit tightens, and a test on the box corners is a length, comparable with the radius,
+    where a test on matrix entries is not.  The moments are summed in a fixed order: two calls return identical bytes.  GPU only: CPU tensors raise."""
+    _check_points(source, 'source')
+    _check_points(target, 'target')
+    max_dist, T, min_dist, shrink, tol = _check_icp(max_dist, init, with_scale, iters, min_dist, shrink, tol, every, max_cell_points)
+    for name, t in (('source', source), ('target', target)):
+        if not t.is_cuda:
+            raise RuntimeError('icp got a %s %s: it runs on the GPU only (no CPU fallback)' % (t.device, name))
+    src = source.float()[::every].contiguous()
+    if src.shape[0] < 3 or target.shape[0] < 3:
+        raise ValueError('icp needs at least 3 source points and 3 targets, got %d (every=%d) and %d' % (src.shape[0], every, target.shape[0]))
+    index = NearestIndex(target, max_dist, max_cell_points=max_cell_points)
+    iws = hip.icp_workspace(src.shape[0], src.device)
+    lo, hi = (v.double().cpu().numpy() for v in torch.aminmax(src, dim=0))
+    box = np.array([[(lo, hi)[(c >> a) & 1][a] for a in range(3)] for c in range(8)])
+    history, reason = [], 'iters'
+    for k in range(int(iters)):
+        r, r2, floor = _icp_radius(k, max_dist, min_dist, shrink)
+        iws['status'].zero_()
+        out = hip.icp_step(src, T[:3].astype(np.float32), index.targets, index.inv, index.r2, float(r2), index.ws, index.max_cell_points, iws)
+        got = torch.cat([out, iws['status'].double()]).cpu().numpy()         # the one host sync of the step
+        mom, bits = got[:20], int(got[20])
+        if bits:
+            raise RuntimeError('icp: the search did not finish (status %d)' % bits)
+        n = int(mom[0])
+        history.append({'radius': float(r), 'matched': n, 'rmse': float(np.sqrt(mom[17] / mom[0])) if n else math.nan})
+        if n < 3:
+            if k == 0:
+                raise ValueError('icp: nothing within max_dist of the initial alignment (%d of %d sources matched within %g)' % (n, src.shape[0], max_dist))
+            reason = 'degenerate'
+            break
+        xm, ym = mom[1:4] / mom[0], mom[4:7] / mom[0]
+        sv = np.linalg.svd(mom[7:16].reshape(3, 3) - mom[0] * np.outer(ym, xm), compute_uv=False)
+        if sv[1] <= PLANE_RANK_TOL * sv[0]:
+            reason = 'degenerate'
+            break
+        new = np.eye(4)
+        if with_scale:
+            R, t, s = procrustes_from_moments(mom[0], mom[1:4], mom[4:7], mom[7:16].reshape(3, 3), mom[16])
+            new[:3, :3], new[:3, 3] = s * R, t
+        else:
+            new[:3, :3], new[:3, 3] = procrustes_from_moments(mom[0], mom[1:4], mom[4:7], mom[7:16].reshape(3, 3))
+        shift, T = _corner_shift(box, T, new), new
+        if floor and shift <= tol * float(r):
+            reason = 'converged'
+            break
+    return Alignment(torch.from_numpy(T), len(history), reason == 'converged', reason, history)
+
+
+@torch.no_grad()
+def refine_alignment(pred, gt_vertices, gt_faces, *, spacing, max_dist, init=None, max_subdiv=1024, **icp_kwargs):
+    """Refine the alignment of a prediction - a `PanopticCloud`, a `VoxelCloud`, a `PanopticMesh` or an [N, 3] device tensor - to the ground-truth mesh
+    on the geometry -> `Alignment` whose `transform` is T_icp @ init, ready for `score_reconstruction(transform=)`.  The prediction is carried by
+    `init` ([4, 4], e.g. `similarity_from_cameras`; default the identity) as `score_reconstruction` carries it - a mesh is moved BEFORE it is
+    sampled at `spacing` - the ground truth is `sample_mesh` at `spacing`, and `icp` runs from the identity on the moved points with
+    `max_dist` and `icp_kwargs`.  The direction is prediction -> ground truth, a CHOICE: a prediction covers part of the scene and the mesh all of
+    it, so the reverse direction would pull the fit towards surface the prediction never saw.  Point to point only.  GPU only."""
+    spacing = _check_length(spacing, 'spacing')
+    T0 = None if init is None else _check_transform(init)
+    if not _is_int(max_subdiv) or not 1 <= max_subdiv <= hip.MESH_SAMPLE_MAX_SUBDIV:
+        raise ValueError('max_subdiv must be an integer in 1 .. %d, got %r' % (hip.MESH_SAMPLE_MAX_SUBDIV, max_subdiv))
+    _check_icp(max_dist, **icp_kwargs)                                        # before the GPU is touched (`init` is this call's own: icp starts from the identity)
+    points, _, _ = _pred_points(pred, spacing, max_subdiv, T0)
+    gt = sample_mesh(gt_vertices, gt_faces, spacing, max_subdiv=max_subdiv)
+    a = icp(points, gt.points, max_dist=max_dist, **icp_kwargs)
+    if T0 is not None:
+        a.transform = torch.from_numpy(a.transform.numpy() @ T0)
+    return a
+
+
 def _direction(d2, row):
     """matched share, mean and median distance (float64 through torch) of one direction; the median is the lower middle element"""
     n = int(d2.numel())
@@ -304,7 +435,7 @@ def _direction(d2, row):
 
 @torch.no_grad()
 def score_reconstruction(pred, gt_vertices, gt_faces, *, thresholds, spacing, max_dist=None, transform=None, gt_vertex_ids=None, gt_segments=None,
-                         things=None, max_subdiv=1024, max_cell_points=4096):
+                         things=None, max_subdiv=1024, max_cell_points=4096, refine=None):
     """Score `pred` - a `PanopticCloud`, a `VoxelCloud` (their `points`), a `PanopticMesh` (sampled with the same `spacing` and its `face_ids`) or an
     [N, 3] device tensor - against the ground-truth mesh (gt_vertices [Nv,3], gt_faces [Nf,3] on the device), sampled by `sample_mesh` at `spacing`.
     `transform`: a [4, 4] matrix applied to the predicted points first (`similarity_from_cameras`), in fp32 on the device; a mesh's vertices are moved
@@ -317,7 +448,11 @@ def score_reconstruction(pred, gt_vertices, gt_faces, *, thresholds, spacing, ma
     match); `chamfer` = accuracy_mean + completeness_mean; n_pred, n_gt, dropped_faces, clamped_faces, thresholds, max_dist, spacing.
     With `gt_vertex_ids` [Nv], `gt_segments` and a labelled `pred`, also `pq3d`: every ground-truth sample takes the panoptic id of its nearest
     predicted point (0 without one within max_dist), and that [1, S] map is scored against the samples' own ids by `panoptic_quality` (`things=`) - PQ
-    / SQ / RQ / mIoU over pieces of ground-truth surface; None otherwise.  Point to point only.  GPU only."""
+    / SQ / RQ / mIoU over pieces of ground-truth surface; None otherwise.  `refine`: True, or a dict of `refine_alignment` keywords - the alignment
+    is refined by ICP on the geometry, starting from `transform`, before anything is scored; its `max_dist` defaults to 4 times the search radius
+    (a CHOICE: wide enough for the error a camera fit leaves, narrow enough for the cells to stay small), its `max_cell_points` to this call's.  The
+    scores are then those of the refined transform and `alignment` holds the `Alignment`.  Without `refine` the dict has no such key and is what it
+    always was.  Point to point only.  GPU only."""
     taus = [_check_length(t, 'a threshold') for t in (thresholds if isinstance(thresholds, (list, tuple, np.ndarray)) else [thresholds])]
     if not taus:
         raise ValueError('score_reconstruction needs at least one threshold')
@@ -329,6 +464,15 @@ def score_reconstruction(pred, gt_vertices, gt_faces, *, thresholds, spacing, ma
     T = None if transform is None else _check_transform(transform)
     if (gt_vertex_ids is None) != (gt_segments is None):
         raise ValueError('gt_vertex_ids and gt_segments go together')
+    if refine is not None and refine is not True and refine is not False and not isinstance(refine, dict):
+        raise ValueError('refine must be True or a dict of refine_alignment keywords, got %r' % (refine,))
+    alignment = None
+    if refine is True or isinstance(refine, dict):
+        kw = {} if refine is True else dict(refine)
+        kw.setdefault('max_dist', 4 * radius)
+        kw.setdefault('max_cell_points', max_cell_points)
+        alignment = refine_alignment(pred, gt_vertices, gt_faces, spacing=spacing, init=T, max_subdiv=max_subdiv, **kw)
+        T = alignment.transform.numpy()
     points, ids, segments = _pred_points(pred, spacing, max_subdiv, T)
     gt = sample_mesh(gt_vertices, gt_faces, spacing, vertex_ids=gt_vertex_ids, max_subdiv=max_subdiv)
     dev = points.device
@@ -355,4 +499,6 @@ def score_reconstruction(pred, gt_vertices, gt_faces, *, thresholds, spacing, ma
             row = comp[1].long()
             taken = torch.where(row >= 0, ids.to(torch.int32)[row.clamp(min=0)], taken)
         out['pq3d'] = panoptic_quality(taken[None, None, :], segments, gt.ids[None, None, :], gt_segments, things=things)
+    if alignment is not None:
+        out['alignment'] = alignment
     return out

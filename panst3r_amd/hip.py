@@ -79,6 +79,7 @@ SIGNATURES = {
     'pst_surface_components': 'i:pllppppp', 'pst_surface_keep_count': 'i:pplipp', 'pst_surface_keep_emit': 'i:ppppplippppp',
     'pst_mesh_sample_count': 'i:plplfipppp', 'pst_mesh_sample_emit': 'i:plplpllppppppp',
     'pst_nn_insert': 'i:plfplpppp', 'pst_nn_scatter': 'i:plpppppp', 'pst_nn_query': 'i:plplffplpppipppp',
+    'pst_icp_chunk': 'i:', 'pst_icp_step': 'i:plffffffffffffplffplpppipppppp',
 }
 EXPORTS = list(SIGNATURES)
 
@@ -1675,3 +1676,37 @@ def nn_query(queries, targets, inv, r2, ws, max_cell_points, d2, row):
     assert ws['rows'].numel() == M and d2.numel() == Nq and row.numel() == Nq and d2.is_contiguous() and row.is_contiguous()
     _call('pst_nn_query', _ptr(queries), Nq, _ptr(targets), M, float(inv), float(r2), _ptr(ws['keys']), ws['cap'], _ptr(ws['start']), _ptr(ws['cell_count']),
           _ptr(ws['rows']), int(max_cell_points), _ptr(d2), _ptr(row), _ptr(ws['status']))
+
+
+# ------------------------------------------------------------------ one fused ICP step (csrc/nearest.hip; engine/score3d.py's icp / refine_alignment)
+ICP_CHUNK, ICP_LANES, ICP_MOMENTS = 4096, 256, 20      # PST_ICP_CHUNK, PST_ICP_LANES, PST_ICP_MOMENTS: the fixed order of the sums (tests/icp_ref.py reads them here)
+
+
+def icp_workspace(N, device):
+    """the workspaces of `icp_step` over N source points: partials double [ceil(N / ICP_CHUNK), 20], out double [20], status int32 [4] (zeroed here;
+    the caller clears it between steps if it reads it per step)"""
+    return {'N': int(N), 'partials': torch.empty((int(N) + ICP_CHUNK - 1) // ICP_CHUNK, ICP_MOMENTS, dtype=torch.float64, device=device),
+            'out': torch.empty(ICP_MOMENTS, dtype=torch.float64, device=device), 'status': torch.zeros(4, dtype=torch.int32, device=device)}
+
+
+def icp_step(source, A, targets, inv, cell_r2, r2, ws, max_cell_points, iws, d2=None, row=None):
+    """one fused ICP step (include/panst3r_hip.h): `source` moved by the 3 x 4 matrix A (12 numbers, rounded to fp32 here), searched in the built
+    structure `ws` of `targets` (cell edge 1 / inv, cell_r2 = its squared edge), accepted within r2 <= cell_r2 -> iws['out'] double [20]; d2 / row
+    [N] are written when given (both or neither).  A larger r2 raises ValueError: the 27 cells would not hold every match."""
+    N, M = _nn_points(source), _nn_points(targets)
+    A = [float(a) for a in (A.reshape(-1).tolist() if hasattr(A, 'reshape') else A)]
+    if len(A) != 12:
+        raise ValueError('icp_step takes a 3 x 4 matrix, got %d numbers' % len(A))
+    if not float(r2) <= float(cell_r2):
+        raise ValueError('icp_step: the squared radius %g exceeds the squared cell edge %g of the search structure' % (r2, cell_r2))
+    if (d2 is None) != (row is None):
+        raise ValueError('icp_step: d2 and row go together')
+    if d2 is not None:
+        _dev(d2, torch.float32); _dev(row, torch.int32)
+        assert d2.numel() == N and row.numel() == N and d2.is_contiguous() and row.is_contiguous()
+    _dev(iws['partials'], torch.float64); _dev(iws['out'], torch.float64); _dev(iws['status'], torch.int32)
+    assert lib().pst_icp_chunk() == ICP_CHUNK and iws['N'] == N and iws['partials'].numel() == (N + ICP_CHUNK - 1) // ICP_CHUNK * ICP_MOMENTS
+    assert ws['rows'].numel() == M and iws['out'].numel() == ICP_MOMENTS and iws['status'].numel() == 4
+    _call('pst_icp_step', _ptr(source), N, *A, _ptr(targets), M, float(inv), float(r2), _ptr(ws['keys']), ws['cap'], _ptr(ws['start']),
+          _ptr(ws['cell_count']), _ptr(ws['rows']), int(max_cell_points), _ptr(d2), _ptr(row), _ptr(iws['partials']), _ptr(iws['out']), _ptr(iws['status']))
+    return iws['out']

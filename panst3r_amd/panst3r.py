@@ -417,7 +417,9 @@ class PanSt3R(nn.Module):
         """A reconstruction against a ground-truth mesh in 3-D: `engine.score_reconstruction` of a `PanopticCloud`, a `VoxelCloud` or a `PanopticMesh`
         (precision / recall / F-score at `thresholds=`, accuracy, completeness, chamfer, and with labels the surface panoptic quality `pq3d`).
         `gt_mesh`: (vertices, faces) or (vertices, faces, vertex_ids, segments) on the device, e.g. from `engine.load_ply_mesh` and
-        `engine.panoptic_vertex_ids`; `transform=engine.similarity_from_cameras(...)` carries the prediction into its frame.  It only composes."""
+        `engine.panoptic_vertex_ids`; `transform=engine.similarity_from_cameras(...)` carries the prediction into its frame, and `refine=True` (or a
+        dict of `engine.refine_alignment` keywords) refines that transform on the geometry by ICP before anything is scored; the result then holds
+        the `Alignment` under 'alignment'.  It only composes."""
         from .engine import score_reconstruction
         if len(gt_mesh) not in (2, 4):
             raise ValueError('gt_mesh is (vertices, faces) or (vertices, faces, vertex_ids, segments), got %d entries' % len(gt_mesh))
