@@ -766,6 +766,75 @@ int pst_icp_step(const float* source, int64_t N, float a00, float a01, float a02
                  const int32_t* start, const int32_t* cell_count, const int32_t* rows, int max_cell_points, float* d2, int32_t* row, double* partials,
                  double* out, int32_t* status, void* stream);
 
+/* ---------------------------------------------------------------- meshdist: the exact distance from a point to a triangle mesh within a radius (no counterpart in the reference)
+ * The primitive of engine/meshdist.py (`mesh_distance`, `score_reconstruction(metric='surface')`): for every query the nearest point of the mesh's
+ * SURFACE within the radius - its squared distance, its face and the point itself - exact against the triangles, where the score3d section measures to
+ * samples of them.  Restated in tests/meshdist_ref.py [restated, parity unpinned]: the closest point as written here, the search by brute force over
+ * all kept faces, the binning on its own.  Every step is exact or separately rounded in a fixed order, so the per-face counts, d2, face and closest are
+ * held to the restatement bit for bit.  Contraction is off: every fp32 and fp64 operation is rounded on its own, in the order written.  Integer
+ * atomics only; every loop is bounded by a number known before the launch.  Additive to ABI 20.
+ *   vertices fp32 [Nv, 3], faces int32 [F, 3], queries fp32 [Nq, 3], radius > 0; inv = fp32(1 / radius), r2 = fp32(radius radius) from the host.
+ *   1 cells     edge `radius`: the cell of a coordinate is floor(fp32(x inv)) (the score3d section's rule), the range (-2^20, 2^20), the keys those of
+ *               the voxel table.
+ *   2 faces     KEPT iff its three indices are in [0, Nv), its nine coordinates are finite and the cross product (v1 - v0) x (v2 - v0) is not exactly
+ *               zero in fp64 (the sampler's rule, step 1 of the score3d section), and its box stays in range.  The box of a face is, per axis,
+ *               [cell(min of the three coordinates) - 1, cell(max) + 1], computed in fp32 (whole numbers: exact): the fp32 bounding box in cells,
+ *               dilated by one cell; it is in range iff its lowest cell > -2^20 and its highest < 2^20 on every axis.  Every other face is DROPPED and
+ *               counted in status[1].
+ *   3 binning   a kept face is listed in every cell of its box: ext0 ext1 ext2 (face, cell) pairs, pair t of the face being the cell lo + (t mod ext0,
+ *               (t / ext0) mod ext1, t / (ext0 ext1)).  A query reads the list of its OWN cell only, so every candidate face is evaluated once.  The
+ *               lists are a superset of what is needed and the result does not depend on them: if |q_a - p_a| <= radius for a point p of the face then
+ *               cell(q_a) is within one of cell(p_a), and cell(p_a) lies between the cells of the face's extremes.  That fails only in the rounding
+ *               case of the score3d section: a pair within about 2^-23 (|x| / radius + 1) radius of the radius itself.  Cells are not pruned against
+ *               the triangle's plane.
+ *   4 build     meshdist_count: counts int32 [F] = the face's number of pairs, 0 for a dropped face, saturated at PST_MESHDIST_FACE_CAP; total int64
+ *               [1] (cleared by the CALLER) = their sum, by integer atomics; the CALLER reads it, refuses what it will not hold and sizes the
+ *               workspaces by it (total <= 2^30).  pst_cloud_scan of counts -> prefix int32 [F + 1].  meshdist_insert: one lane per pair, its face by
+ *               binary search in the prefix, its cell from t; the cell's key into keys uint64 [capacity] (all ones = empty, by the CALLER; capacity a
+ *               power of two >= 2 total), cell_count int32 [capacity] (cleared by the CALLER) += 1 on its slot, pair_slot int32 [total] = the slot.
+ *               The caller turns cell_count into start int32 [capacity] (exclusive prefix sum).  meshdist_scatter: rows int32 [total]: the faces of
+ *               slot s at [start[s], start[s] + cell_count[s]) in arrival order (fill int32 [capacity], cleared by the CALLER); status[2] = the
+ *               longest list.  Insert and scatter write nothing but status[0] |= PST_MESHDIST_TOTAL if prefix[F] != total.
+ *   5 closest   the closest point of triangle (a, b, c) to q, all twelve numbers widened to fp64 once; every line below is fp64, each operation
+ *               rounded once, dot(u, v) = (u0 v0 + u1 v1) + u2 v2, clamp(t) = t > 0 ? min(t, 1) : 0 (so a NaN gives 0):
+ *                 ab = b - a, ac = c - a, ap = q - a, bp = q - b, cp = q - c
+ *                 d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp)
+ *                 vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4
+ *               the first region that holds, in this order (Ericson, Real-Time Collision Detection, 5.1.5):
+ *                 A   d1 <= 0 and d2 <= 0                                  x = a
+ *                 B   d3 >= 0 and d4 <= d3                                 x = b
+ *                 AB  vc <= 0 and d1 >= 0 and d3 <= 0                      t = clamp(d1 / (d1 - d3)),                       x = a + t ab
+ *                 C   d6 >= 0 and d5 <= d6                                 x = c
+ *                 AC  vb <= 0 and d2 >= 0 and d6 <= 0                      t = clamp(d2 / (d2 - d6)),                       x = a + t ac
+ *                 BC  va <= 0 and (d4 - d3) >= 0 and (d5 - d6) >= 0        t = clamp((d4 - d3) / ((d4 - d3) + (d5 - d6))),  x = b + t (c - b)
+ *                 interior  den = 1 / ((va + vb) + vc), v = clamp(vb den), w = clamp(vc den),                               x = (a + v ab) + w ac
+ *               e = q - x, D2 = (e0 e0 + e1 e1) + e2 e2: always the distance to an actual point of the triangle, never NaN; no finite fp32 input
+ *               overflows fp64 here (the largest intermediate is a product of two dots, about 1e155).  fp64 because scans hold sliver faces and
+ *               coordinates metres from the origin; the sampler works in fp64 for the same reason.
+ *   6 query     one lane per query: every face f of the list of the query's cell, d2 = fp32(D2) (one cast), the minimum of (uint64(bits(d2)) << 32) |
+ *               f: the nearest face, ties to the smaller face, whatever the order inside the list.  Accepted iff d2 <= r2: d2 fp32 [Nq], face int32
+ *               [Nq], closest fp32 [Nq, 3] = fp32(x) of the winner, recomputed and cast once (closest may be null: d2 and face do not change);
+ *               otherwise d2 = +inf, face -1 and closest = the query itself.  A query with a non-finite coordinate gets no hit and is counted in
+ *               status[3]; a finite query whose cell is out of range gets no hit.  At most max_cell_faces candidates are visited: the CALLER compares
+ *               status[2] with it after the build and does not launch the query of a longer list.
+ *   status int32 [4], cleared by the CALLER: [0] = PST_MESHDIST_FULL | PST_MESHDIST_LISTS | PST_MESHDIST_TOTAL, [1] dropped faces, [2] the longest
+ *   list, [3] non-finite queries.
+ *   Refused with PST_EINVAL before any launch, every output untouched: a null operand (closest excepted), Nv < 1, F, Nq or total < 1 or > 2^30, a
+ *   capacity that is no power of two or below 2 total, inv or r2 not finite (inv not positive, r2 negative), max_cell_faces < 1. */
+#define PST_MESHDIST_FULL 1       /* the table ran full */
+#define PST_MESHDIST_LISTS 2      /* prefix / start / cell_count / rows are not those of this mesh and this build */
+#define PST_MESHDIST_TOTAL 4      /* the prefix handed to insert / scatter does not end in `total` */
+#define PST_MESHDIST_FACE_CAP 2147483647   /* a face's pair count saturates here */
+int pst_meshdist_count(const float* vertices, int64_t Nv, const int32_t* faces, int64_t F, float inv, int32_t* counts, int64_t* total, int32_t* status,
+                       void* stream);
+int pst_meshdist_insert(const float* vertices, int64_t Nv, const int32_t* faces, int64_t F, float inv, const int32_t* prefix, int64_t total, uint64_t* keys,
+                        int64_t capacity, int32_t* cell_count, int32_t* pair_slot, int32_t* status, void* stream);
+int pst_meshdist_scatter(const int32_t* pair_slot, const int32_t* prefix, int64_t F, int64_t total, const int32_t* start, const int32_t* cell_count,
+                         int32_t* fill, int32_t* rows, int32_t* status, void* stream);
+int pst_meshdist_query(const float* queries, int64_t Nq, const float* vertices, int64_t Nv, const int32_t* faces, int64_t F, float inv, float r2,
+                       const uint64_t* keys, int64_t capacity, const int32_t* start, const int32_t* cell_count, const int32_t* rows, int64_t total,
+                       int max_cell_faces, float* d2, int32_t* face, float* closest, int32_t* status, void* stream);
+
 /* ---------------------------------------------------------------- panoptic evaluation against ground truth: PQ / SQ / RQ, mIoU (no counterpart in the reference)
  * V predicted maps and V ground-truth maps of the same shapes, flattened and concatenated to pred, gt int32 [N] (1 <= N <= 2^31 - 1, both 16-byte
  * aligned), P predicted and G ground-truth segments (ids unique and > 0 within each list, no crowd regions).  The rules are those of COCO

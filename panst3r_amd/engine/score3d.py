@@ -7,9 +7,11 @@ a `PanopticMesh` or plain points - against the mesh that `load_ply_mesh` / `pano
     s = score_reconstruction(cloud, gt_vertices, gt_faces, thresholds=(0.05, 0.1), spacing=0.02, transform=T, gt_vertex_ids=ids, gt_segments=segs,
                              refine=True)                  # T refined on the geometry by ICP before anything is scored (stage f11)
 
-POINT TO POINT ONLY: the ground-truth surface is replaced by a deterministic lattice of samples about `spacing` apart and every distance is one between
-two points - no point-to-triangle distance, no BVH.  A distance is therefore off by up to about spacing / sqrt(3) against the true surface;
-choose `spacing` well below the smallest threshold.  No counterpart in the reference: *restated, unpinned*.  Two kernels (csrc/nearest.hip; the contract
+TWO METRICS.  `metric='points'` (the default): the ground-truth surface is replaced by a deterministic lattice of samples about `spacing` apart and
+every distance is one between two points; a distance is therefore off by up to about spacing / sqrt(3) against the true surface: choose `spacing`
+well below the smallest threshold.  `metric='surface'` (stage f12): the distance from a predicted point is the exact one to the ground truth's
+triangles (`mesh_distance`, engine/meshdist.py), so precision and accuracy no longer depend on `spacing`; the other direction is exact too when the
+prediction is a surface, and stays point to point when it is a cloud.  No BVH.  No counterpart in the reference: *restated, unpinned*.  Two kernels (csrc/nearest.hip; the contract
 is the score3d section of include/panst3r_hip.h, restated in tests/nearest_ref.py and held bit for bit):
   sample_mesh      face f gets n_f^2 samples, the centroids of the n_f^2 congruent sub-triangles of its uniform subdivision, n_f the smallest whole
                    number with n_f spacing >= the face's longest edge (clamped to max_subdiv).  The density differs between faces by what rounding
@@ -433,9 +435,28 @@ def _direction(d2, row):
     return m / n, float(d.sum() / m), float(torch.sort(d).values[(m - 1) // 2]), m
 
 
+def _surface_distances(pred, points, ids, gt, gt_vertices, gt_faces, radius, T, max_cell_points, max_cell_faces, max_pairs):
+    """the two directions of `metric='surface'` -> ((d2, row) predicted -> ground truth, (d2, row) ground truth -> predicted, the ids that `row` of the
+    second indexes, the extra entries of the dict).  `row` is a face where the target is a surface and a point where it is a cloud."""
+    from .meshdist import MeshIndex
+    from .surface import PanopticMesh
+    kw = dict(max_cell_faces=max_cell_faces, max_pairs=max_pairs)
+    to_gt = MeshIndex(gt_vertices, gt_faces, radius, **kw)
+    acc = to_gt.query(points, closest=False)[:2]
+    to_gt.check()
+    if isinstance(pred, PanopticMesh):                                        # a surface: the ground-truth samples against its triangles
+        to_pred = MeshIndex(_moved(pred.vertices, T, 'vertices'), pred.faces, radius, **kw)
+        comp, ids = to_pred.query(gt.points, closest=False)[:2], pred.face_ids
+    else:                                                                     # no surface there: point to point, as under 'points'
+        to_pred = NearestIndex(points, radius, max_cell_points=max_cell_points)
+        comp = to_pred.query(gt.points)
+    to_pred.check()
+    return acc, comp, ids, {'gt_pairs': to_gt.pairs, 'gt_max_cell_faces': to_gt.max_occupancy}
+
+
 @torch.no_grad()
 def score_reconstruction(pred, gt_vertices, gt_faces, *, thresholds, spacing, max_dist=None, transform=None, gt_vertex_ids=None, gt_segments=None,
-                         things=None, max_subdiv=1024, max_cell_points=4096, refine=None):
+                         things=None, max_subdiv=1024, max_cell_points=4096, refine=None, metric='points', max_cell_faces=4096, max_pairs=2 ** 27):
     """Score `pred` - a `PanopticCloud`, a `VoxelCloud` (their `points`), a `PanopticMesh` (sampled with the same `spacing` and its `face_ids`) or an
     [N, 3] device tensor - against the ground-truth mesh (gt_vertices [Nv,3], gt_faces [Nf,3] on the device), sampled by `sample_mesh` at `spacing`.
     `transform`: a [4, 4] matrix applied to the predicted points first (`similarity_from_cameras`), in fp32 on the device; a mesh's vertices are moved
@@ -452,7 +473,17 @@ def score_reconstruction(pred, gt_vertices, gt_faces, *, thresholds, spacing, ma
     is refined by ICP on the geometry, starting from `transform`, before anything is scored; its `max_dist` defaults to 4 times the search radius
     (a CHOICE: wide enough for the error a camera fit leaves, narrow enough for the cells to stay small), its `max_cell_points` to this call's.  The
     scores are then those of the refined transform and `alignment` holds the `Alignment`.  Without `refine` the dict has no such key and is what it
-    always was.  Point to point only.  GPU only."""
+    always was.  `metric`: 'points' - every distance above is one to the nearest SAMPLE or predicted point (`nearest_points`), as it always was - or
+    'surface': predicted -> ground truth is `mesh_distance` to the ground truth's triangles within max_dist (`max_cell_faces`, `max_pairs` are its
+    guards), so `precision`, `pred_within` and `accuracy_*` do not depend on `spacing`; ground truth -> predicted takes the ground-truth samples to
+    the triangles of a `PanopticMesh` (moved by `transform` first; `pq3d` takes the `face_ids` of the nearest face), and for a cloud, a voxel cloud or
+    a tensor - no surface there - it stays `nearest_points`.  The dict holds `metric`, and under 'surface' also `gt_pairs` and `gt_max_cell_faces`
+    (the (face, cell) pairs and the longest cell list of the ground truth's index).  `refine` is point-to-point ICP under both metrics.  GPU only."""
+    if metric not in ('points', 'surface'):
+        raise ValueError("metric must be 'points' or 'surface', got %r" % (metric,))
+    if metric == 'surface':
+        from .meshdist import _check_limits
+        _check_limits(max_cell_faces, max_pairs)                                  # before the GPU is touched
     taus = [_check_length(t, 'a threshold') for t in (thresholds if isinstance(thresholds, (list, tuple, np.ndarray)) else [thresholds])]
     if not taus:
         raise ValueError('score_reconstruction needs at least one threshold')
@@ -476,12 +507,17 @@ def score_reconstruction(pred, gt_vertices, gt_faces, *, thresholds, spacing, ma
     points, ids, segments = _pred_points(pred, spacing, max_subdiv, T)
     gt = sample_mesh(gt_vertices, gt_faces, spacing, vertex_ids=gt_vertex_ids, max_subdiv=max_subdiv)
     dev = points.device
-    to_gt, to_pred = NearestIndex(gt.points, radius, max_cell_points=max_cell_points), NearestIndex(points, radius, max_cell_points=max_cell_points)
-    acc, comp = to_gt.query(points), to_pred.query(gt.points)
-    to_gt.check(); to_pred.check()
+    surface = {}
+    if metric == 'surface':
+        acc, comp, ids, surface = _surface_distances(pred, points, ids, gt, gt_vertices, gt_faces, radius, T, max_cell_points, max_cell_faces, max_pairs)
+    else:
+        to_gt, to_pred = NearestIndex(gt.points, radius, max_cell_points=max_cell_points), NearestIndex(points, radius, max_cell_points=max_cell_points)
+        acc, comp = to_gt.query(points), to_pred.query(gt.points)
+        to_gt.check(); to_pred.check()
     n_pred, n_gt = int(points.shape[0]), len(gt)
     out = {'thresholds': taus, 'max_dist': radius, 'spacing': spacing, 'n_pred': n_pred, 'n_gt': n_gt, 'dropped_faces': gt.dropped_faces,
-           'clamped_faces': gt.clamped_faces, 'precision': [], 'recall': [], 'fscore': [], 'pred_within': [], 'gt_within': []}
+           'clamped_faces': gt.clamped_faces, 'precision': [], 'recall': [], 'fscore': [], 'pred_within': [], 'gt_within': [], 'metric': metric}
+    out.update(surface)
     t2 = torch.tensor([float(np.float32(t) * np.float32(t)) for t in taus], dtype=torch.float32, device=dev)
     within = torch.stack([(acc[0][None, :] <= t2[:, None]).sum(1), (comp[0][None, :] <= t2[:, None]).sum(1)]).tolist()
     for a, c in zip(*within):
@@ -495,7 +531,7 @@ def score_reconstruction(pred, gt_vertices, gt_faces, *, thresholds, spacing, ma
     if gt_vertex_ids is not None and ids is not None and segments is not None and n_gt:
         from .evaluate import panoptic_quality
         taken = torch.zeros(n_gt, dtype=torch.int32, device=dev)
-        if n_pred:
+        if ids.numel():
             row = comp[1].long()
             taken = torch.where(row >= 0, ids.to(torch.int32)[row.clamp(min=0)], taken)
         out['pq3d'] = panoptic_quality(taken[None, None, :], segments, gt.ids[None, None, :], gt_segments, things=things)

@@ -80,6 +80,8 @@ SIGNATURES = {
     'pst_mesh_sample_count': 'i:plplfipppp', 'pst_mesh_sample_emit': 'i:plplpllppppppp',
     'pst_nn_insert': 'i:plfplpppp', 'pst_nn_scatter': 'i:plpppppp', 'pst_nn_query': 'i:plplffplpppipppp',
     'pst_icp_chunk': 'i:', 'pst_icp_step': 'i:plffffffffffffplffplpppipppppp',
+    'pst_meshdist_count': 'i:plplfpppp', 'pst_meshdist_insert': 'i:plplfplplpppp', 'pst_meshdist_scatter': 'i:ppllpppppp',
+    'pst_meshdist_query': 'i:plplplffplppplippppp',
 }
 EXPORTS = list(SIGNATURES)
 
@@ -1710,3 +1712,55 @@ def icp_step(source, A, targets, inv, cell_r2, r2, ws, max_cell_points, iws, d2=
     _call('pst_icp_step', _ptr(source), N, *A, _ptr(targets), M, float(inv), float(r2), _ptr(ws['keys']), ws['cap'], _ptr(ws['start']),
           _ptr(ws['cell_count']), _ptr(ws['rows']), int(max_cell_points), _ptr(d2), _ptr(row), _ptr(iws['partials']), _ptr(iws['out']), _ptr(iws['status']))
     return iws['out']
+
+
+# ------------------------------------------------------------------ the exact distance to a triangle mesh within a radius (csrc/meshdist.hip; engine/meshdist.py holds the public entry points)
+MESHDIST_FULL, MESHDIST_LISTS, MESHDIST_TOTAL = 1, 2, 4      # PST_MESHDIST_*: the bits of status[0]
+MESHDIST_FACE_CAP = 2 ** 31 - 1                              # PST_MESHDIST_FACE_CAP
+MESHDIST_MAX = 1 << 30                                       # queries, faces and pairs of one call
+
+
+def meshdist_count(vertices, faces, inv, counts, total, status):
+    """counts int32 [F]; total int64 [1] and status int32 [4] zeroed by the caller (include/panst3r_hip.h)"""
+    Nv, F = _mesh_sample_mesh(vertices, faces)
+    _dev(counts, torch.int32); _dev(total, torch.int64); _dev(status, torch.int32)
+    assert counts.numel() == F and total.numel() == 1 and status.numel() == 4
+    _call('pst_meshdist_count', _ptr(vertices), Nv, _ptr(faces), F, float(inv), _ptr(counts), _ptr(total), _ptr(status))
+
+
+def meshdist_workspace(P, device):
+    """the initialised workspaces of one index of P (face, cell) pairs (include/panst3r_hip.h): dict of device tensors"""
+    cap = voxel_capacity(P)
+    i32 = dict(dtype=torch.int32, device=device)
+    return {'P': int(P), 'cap': cap, 'keys': torch.full((cap,), -1, dtype=torch.int64, device=device), 'cell_count': torch.zeros(cap, **i32), 'start': None,
+            'fill': torch.zeros(cap, **i32), 'pair_slot': torch.empty(P, **i32), 'rows': torch.empty(P, **i32)}
+
+
+def meshdist_insert(vertices, faces, inv, prefix, ws, status):
+    """the workspaces' rows are `total`: a prefix that ends elsewhere sets MESHDIST_TOTAL and nothing is written"""
+    Nv, F = _mesh_sample_mesh(vertices, faces)
+    _dev(prefix, torch.int32); _dev(status, torch.int32)
+    assert prefix.numel() == F + 1 and status.numel() == 4 and ws['pair_slot'].numel() == ws['P'] and ws['keys'].numel() == ws['cap'] == ws['cell_count'].numel()
+    _call('pst_meshdist_insert', _ptr(vertices), Nv, _ptr(faces), F, float(inv), _ptr(prefix), ws['P'], _ptr(ws['keys']), ws['cap'], _ptr(ws['cell_count']),
+          _ptr(ws['pair_slot']), _ptr(status))
+
+
+def meshdist_scatter(prefix, ws, status):
+    """ws['start'] = the exclusive prefix sum of ws['cell_count'] (int32 [cap]), made by the caller"""
+    _dev(prefix, torch.int32); _dev(ws['start'], torch.int32); _dev(status, torch.int32)
+    assert ws['start'].is_contiguous() and ws['start'].numel() == ws['cap'] == ws['fill'].numel() and ws['rows'].numel() == ws['P'] and status.numel() == 4
+    _call('pst_meshdist_scatter', _ptr(ws['pair_slot']), _ptr(prefix), prefix.numel() - 1, ws['P'], _ptr(ws['start']), _ptr(ws['cell_count']), _ptr(ws['fill']),
+          _ptr(ws['rows']), _ptr(status))
+
+
+def meshdist_query(queries, vertices, faces, inv, r2, ws, max_cell_faces, d2, face, closest, status):
+    """d2 fp32 [Nq], face int32 [Nq], closest fp32 [Nq, 3] or None"""
+    Nq = _nn_points(queries)
+    Nv, F = _mesh_sample_mesh(vertices, faces)
+    _dev(d2, torch.float32); _dev(face, torch.int32); _dev(status, torch.int32)
+    assert d2.numel() == Nq and face.numel() == Nq and d2.is_contiguous() and face.is_contiguous() and status.numel() == 4 and ws['rows'].numel() == ws['P']
+    if closest is not None:
+        _dev(closest, torch.float32)
+        assert closest.is_contiguous() and closest.numel() == 3 * Nq
+    _call('pst_meshdist_query', _ptr(queries), Nq, _ptr(vertices), Nv, _ptr(faces), F, float(inv), float(r2), _ptr(ws['keys']), ws['cap'], _ptr(ws['start']),
+          _ptr(ws['cell_count']), _ptr(ws['rows']), ws['P'], int(max_cell_faces), _ptr(d2), _ptr(face), _ptr(closest), _ptr(status))
