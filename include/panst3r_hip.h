@@ -697,8 +697,8 @@ int pst_surface_keep_emit(const int32_t* faces, const int32_t* face_ids, const i
  *   total > capacity (or > 2^31 - 256: the prefix is int32) with PST_EINVAL before anything is launched, runs one lane per sample, which finds its face
  *   by binary search in the prefix, and writes nothing but status[0] |= PST_MESH_SAMPLE_TOTAL if prefix[F] != total.  1 <= F <= 2^30.
  * FIXED-RADIUS NEAREST NEIGHBOUR  targets fp32 [M, 3], queries fp32 [Nq, 3], radius > 0; inv = fp32(1 / radius), r2 = fp32(radius radius) from the host:
- *   1 cells     the cell of a point is floor(fp32(x inv)) per axis (the voxel contract's rule).  A target with a non-finite coordinate or a cell
- *               outside (-2^20, 2^20) is left out and counted in status[1].
+ *   1 cells     the cell of a point is floor(fp32(x inv)) per axis (the voxel contract's rule: vx_cell_of of csrc/voxel_table.h for every stage).
+ *               A target with a non-finite coordinate or a cell outside (-2^20, 2^20) is left out and counted in status[1].
  *   2 build     nn_insert: the cell's 3 x 21-bit key into keys uint64 [capacity] (all ones = empty, by the CALLER; capacity a power of two >= 2 M),
  *               cell_count int32 [capacity] (cleared by the CALLER) += 1 on its slot, point_slot int32 [M] = the slot or -1.  The caller turns
  *               cell_count into start int32 [capacity] (exclusive prefix sum).  nn_scatter: rows int32 [M]: the rows of slot s at [start[s], start[s] +

@@ -22,6 +22,8 @@ int check_launch(const char* what);
 // (a second thread may not launch before the first one has finished setting the attributes).  `seen` = the call site's static bitmask.
 void once_per_device(unsigned long long& seen, void (*run)());
 
+constexpr float PST_FMAX = 3.402823466e38f;       // FLT_MAX.  finite: fabsf(x) <= PST_FMAX, never the negated compare, so that a NaN fails it
+
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 
 // round-to-nearest-even fp32 -> bf16 (NaN kept quiet)

@@ -1,8 +1,8 @@
 // 3-D connected components of the voxel cloud and the despeckling of its labels (no counterpart in the reference; restated in tests/vcc_ref.py,
 // [restated, parity unpinned]).  On the voxels that csrc/voxel.hip left on the device:
 //   cells     the integer cell of every voxel's first point (step 1 of the voxel contract), written while the fusion's workspace is alive
-//   build     cell key (3 x 21 bits, the hash of voxel.hip) -> voxel row in an open-addressing table of its own (capacity >= 2 Mv): keys are unique, so a
-//             compare-and-swap claim plus a plain store of the row; parent[v] = v (void: -1)
+//   build     cell key -> voxel row in an open-addressing table of its own (capacity >= 2 Mv; the key, the hash and both probes are voxel_table.h):
+//             keys are unique, so a compare-and-swap claim plus a plain store of the row; parent[v] = v (void: -1)
 //   link      one voxel per lane looks up the lexicographically positive half of its neighbourhood (3, 9 or 13 cells) and unites itself with every
 //             neighbour of its own id in parent[]: find with path halving, hook the larger root under the smaller with atomicMin, go on from the value
 //             the atomic returned when another thread got there first.  Parent values only decrease and parent[x] <= x, so every loop ends, no thread
@@ -29,28 +29,14 @@ __device__ __forceinline__ float cc_mulr(float a, float b) { return a * b; }
 __device__ __forceinline__ float cc_addr(float a, float b) { return a + b; }
 
 constexpr int CC_T = 256, CC_PT = 4, CC_WG = CC_T * CC_PT;         // count / rank: 1024 rows per workgroup, as pst_cloud_scan's other callers
-constexpr int CC_FULL = PST_VCC_FULL, CC_DUP = PST_VCC_DUPLICATE, CC_RANGE = PST_VCC_RANGE, CC_LOOP = PST_VCC_LOOP;
+constexpr int CC_DUP = PST_VCC_DUPLICATE, CC_RANGE = PST_VCC_RANGE, CC_LOOP = PST_VCC_LOOP;
 constexpr int CC_MAX_COLORS = 4096;
 
-__device__ __forceinline__ bool cc_in_range(int x, int y, int z) {
-  return x > -VX_LIM && x < VX_LIM && y > -VX_LIM && y < VX_LIM && z > -VX_LIM && z < VX_LIM;
-}
-__device__ __forceinline__ uint64_t cc_key(int x, int y, int z) {     // only for cells in range: no field wraps
-  return (uint64_t)(x + VX_LIM) | ((uint64_t)(y + VX_LIM) << 21) | ((uint64_t)(z + VX_LIM) << 42);
-}
-
-// the row stored for `key`, -1 if the cell is empty.  The table is complete (an earlier launch built it): plain loads.
+// the row stored for `key`, -1 if the cell is empty
 __device__ __forceinline__ int cc_lookup(const uint64_t* __restrict__ keys, const int32_t* __restrict__ rows, uint32_t mask, uint64_t key,
                                          int32_t* __restrict__ status) {
-  uint32_t h = (uint32_t)vx_hash(key) & mask;
-  for (uint32_t n = 0; n <= mask; ++n) {
-    const uint64_t k = keys[h];
-    if (k == key) return rows[h];
-    if (k == VX_EMPTY) return -1;
-    h = (h + 1) & mask;
-  }
-  atomicOr(status, CC_FULL);                                        // a table without an empty slot: never (capacity >= 2 Mv)
-  return -1;
+  const int slot = vx_find(keys, mask, key, status);
+  return slot >= 0 ? rows[slot] : -1;
 }
 
 // offset k in [0, 27) of the 3 x 3 x 3 neighbourhood -> (dx, dy, dz) and the number of axes that differ; k > 13 is the lexicographically positive half
@@ -64,8 +50,12 @@ __global__ __launch_bounds__(CC_T) void vcc_cells_kernel(const float* __restrict
   const int r = blockIdx.x * CC_T + threadIdx.x;
   if (r >= *mv_ptr) return;
   const float* p = points + (int64_t)first_row[r] * 3;
+  const float x[3] = {p[0], p[1], p[2]};
+  float c[3];
+  bool finite, ok;
+  vx_cell_of(x, inv, c, finite, ok);                                // ok: the fusion kept the point
 #pragma unroll
-  for (int a = 0; a < 3; ++a) cells[(int64_t)r * 3 + a] = (int)floorf(cc_mulr(p[a], inv));       // |c| < 2^20: the fusion kept the point
+  for (int a = 0; a < 3; ++a) cells[(int64_t)r * 3 + a] = (int)c[a];
 }
 
 __global__ __launch_bounds__(CC_T) void vcc_build_kernel(const int32_t* __restrict__ cells, const int32_t* __restrict__ pan, int Mv, uint64_t* __restrict__ keys,
@@ -74,17 +64,12 @@ __global__ __launch_bounds__(CC_T) void vcc_build_kernel(const int32_t* __restri
   if (v >= Mv) return;
   parent[v] = pan[v] > 0 ? v : -1;
   const int x = cells[(int64_t)v * 3], y = cells[(int64_t)v * 3 + 1], z = cells[(int64_t)v * 3 + 2];
-  if (!cc_in_range(x, y, z)) { atomicOr(status, CC_RANGE); return; }
-  const uint64_t key = cc_key(x, y, z);
-  uint32_t h = (uint32_t)vx_hash(key) & mask;
-  for (uint32_t n = 0; n <= mask; ++n) {
-    uint64_t k = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == VX_EMPTY) k = atomicCAS((unsigned long long*)&keys[h], (unsigned long long)VX_EMPTY, (unsigned long long)key);
-    if (k == VX_EMPTY) { rows[h] = v; return; }                     // claimed: the only writer of this slot's row
-    if (k == key) { atomicOr(status, CC_DUP); return; }             // two voxels in one cell: not a voxel cloud
-    h = (h + 1) & mask;
-  }
-  atomicOr(status, CC_FULL);
+  if (!vx_in_range(x, y, z)) { atomicOr(status, CC_RANGE); return; }
+  bool claimed;
+  const int slot = vx_find_or_claim(keys, mask, vx_key(x, y, z), status, &claimed);
+  if (slot < 0) return;                                             // (a full table: reported by the probe)
+  if (claimed) rows[slot] = v;                                      // the only writer of this slot's row
+  else atomicOr(status, CC_DUP);                                    // two voxels in one cell: not a voxel cloud
 }
 
 __global__ __launch_bounds__(CC_T) void vcc_link_kernel(const int32_t* __restrict__ cells, const int32_t* __restrict__ pan, int Mv, const uint64_t* __restrict__ keys,
@@ -95,12 +80,12 @@ __global__ __launch_bounds__(CC_T) void vcc_link_kernel(const int32_t* __restric
   const int id = pan[v];
   if (id <= 0) return;
   const int x = cells[(int64_t)v * 3], y = cells[(int64_t)v * 3 + 1], z = cells[(int64_t)v * 3 + 2];
-  if (!cc_in_range(x, y, z)) return;                                // (reported by build)
+  if (!vx_in_range(x, y, z)) return;                                // (reported by build)
   for (int k = 14; k < 27; ++k) {
     int dx, dy, dz;
     if (cc_offset(k, dx, dy, dz) > max_axes) continue;
-    if (!cc_in_range(x + dx, y + dy, z + dz)) continue;             // no such cell: never looked up
-    const int n = cc_lookup(keys, rows, mask, cc_key(x + dx, y + dy, z + dz), status);
+    if (!vx_in_range(x + dx, y + dy, z + dz)) continue;             // no such cell: never looked up
+    const int n = cc_lookup(keys, rows, mask, vx_key(x + dx, y + dy, z + dz), status);
     if (n >= 0 && pan[n] == id) cc_unite(parent, v, n, Mv, status);
   }
 }
@@ -237,13 +222,13 @@ __global__ __launch_bounds__(CC_T) void vcc_votes_kernel(const int32_t* __restri
   const int r = root[v];
   if (r < 0 || size[r] >= min_voxels) return;                       // void, or a component that stays
   const int x = cells[(int64_t)v * 3], y = cells[(int64_t)v * 3 + 1], z = cells[(int64_t)v * 3 + 2];
-  if (!cc_in_range(x, y, z)) return;
+  if (!vx_in_range(x, y, z)) return;
   for (int k = 0; k < 27; ++k) {
     int dx, dy, dz;
     const int axes = cc_offset(k, dx, dy, dz);
     if (axes == 0 || axes > max_axes) continue;
-    if (!cc_in_range(x + dx, y + dy, z + dz)) continue;
-    const int n = cc_lookup(keys, rows, mask, cc_key(x + dx, y + dy, z + dz), status);
+    if (!vx_in_range(x + dx, y + dy, z + dz)) continue;
+    const int n = cc_lookup(keys, rows, mask, vx_key(x + dx, y + dy, z + dz), status);
     if (n < 0) continue;
     const int id = pan[n], rn = root[n];
     if (id <= 0 || rn < 0 || size[rn] < min_voxels) continue;       // void and small neighbours do not vote
@@ -280,7 +265,6 @@ __global__ __launch_bounds__(CC_T) void vcc_apply_kernel(const int32_t* __restri
   }
 }
 
-static bool cc_cap_ok(int64_t n, int64_t cap) { return cap >= 2 * n && cap <= (1ll << 31) && (cap & (cap - 1)) == 0; }
 static bool cc_pow2(int64_t cap) { return cap >= 2 && cap <= (1ll << 31) && (cap & (cap - 1)) == 0; }
 static int cc_axes(int connectivity) { return connectivity == 6 ? 1 : connectivity == 18 ? 2 : connectivity == 26 ? 3 : 0; }
 static dim3 cc_grid(int64_t n) { return dim3((unsigned)((n + CC_T - 1) / CC_T)); }
@@ -301,7 +285,7 @@ extern "C" int pst_vcc_build(const int32_t* cells, const int32_t* pan, int64_t M
                              int32_t* status, void* stream) {
   using namespace pst;
   if (!cells || !pan || !keys || !rows || !parent || !status) { set_error("vcc_build: null operand"); return PST_EINVAL; }
-  if (Mv <= 0 || Mv > CC_MAX_ROWS || !cc_cap_ok(Mv, capacity)) {
+  if (Mv <= 0 || Mv > CC_MAX_ROWS || !vx_cap_ok(Mv, capacity)) {
     set_error("vcc_build: bad shape (Mv=%lld, capacity=%lld: a power of two >= 2 Mv)", (long long)Mv, (long long)capacity); return PST_EINVAL;
   }
   hipLaunchKernelGGL(vcc_build_kernel, cc_grid(Mv), dim3(CC_T), 0, (hipStream_t)stream, cells, pan, (int)Mv, keys, rows, (uint32_t)(capacity - 1), parent, status);
@@ -312,7 +296,7 @@ extern "C" int pst_vcc_link(const int32_t* cells, const int32_t* pan, int64_t Mv
                             int32_t* parent, int32_t* status, void* stream) {
   using namespace pst;
   if (!cells || !pan || !keys || !rows || !parent || !status) { set_error("vcc_link: null operand"); return PST_EINVAL; }
-  if (Mv <= 0 || Mv > CC_MAX_ROWS || !cc_cap_ok(Mv, capacity) || !cc_axes(connectivity)) {
+  if (Mv <= 0 || Mv > CC_MAX_ROWS || !vx_cap_ok(Mv, capacity) || !cc_axes(connectivity)) {
     set_error("vcc_link: bad shape (Mv=%lld, capacity=%lld) or connectivity %d (6, 18 or 26)", (long long)Mv, (long long)capacity, connectivity); return PST_EINVAL;
   }
   hipLaunchKernelGGL(vcc_link_kernel, cc_grid(Mv), dim3(CC_T), 0, (hipStream_t)stream, cells, pan, (int)Mv, keys, rows, (uint32_t)(capacity - 1),
@@ -361,7 +345,7 @@ extern "C" int pst_vcc_votes(const int32_t* cells, const int32_t* pan, const int
                              int64_t pair_capacity, int32_t* status, void* stream) {
   using namespace pst;
   if (!cells || !pan || !root || !size || !keys || !rows || !pair_keys || !pair_cnt || !status) { set_error("vcc_votes: null operand"); return PST_EINVAL; }
-  if (Mv <= 0 || Mv > CC_MAX_ROWS || !cc_cap_ok(Mv, capacity) || !cc_pow2(pair_capacity) || !cc_axes(connectivity) || min_voxels < 1) {
+  if (Mv <= 0 || Mv > CC_MAX_ROWS || !vx_cap_ok(Mv, capacity) || !cc_pow2(pair_capacity) || !cc_axes(connectivity) || min_voxels < 1) {
     set_error("vcc_votes: bad shape (Mv=%lld, capacity=%lld, pair_capacity=%lld), connectivity %d or min_voxels %d", (long long)Mv, (long long)capacity,
               (long long)pair_capacity, connectivity, min_voxels);
     return PST_EINVAL;

@@ -34,7 +34,6 @@ __device__ __forceinline__ float ms_divr(float a, float b) { return (float)((dou
 constexpr int MS_T = 256;
 constexpr unsigned long long MS_EMPTY = ~0ull;
 constexpr float MS_LIM = 16384.f;                                  // |u|, |v| <= 2^14: |X|, |Y| <= 2^22, every edge value below 2^47
-constexpr float MS_FMAX = 3.402823466e38f;
 constexpr int MS_CAM = 16;                                         // floats per camera: rows of [R^T | -R^T t], then fx, fy, cx, cy
 constexpr int MS_BIG_BLOCKS = 2048;                                // the wave path's fixed grid: 8 192 waves stride the list
 
@@ -55,7 +54,7 @@ __device__ __forceinline__ bool ms_vertex(const float* __restrict__ c, const flo
   for (int a = 0; a < 3; ++a)
     pc[a] = ms_addr(ms_addr(ms_addr(ms_mulr(c[4 * a + 0], x), ms_mulr(c[4 * a + 1], y)), ms_mulr(c[4 * a + 2], z)), c[4 * a + 3]);
   zc = pc[2];
-  if (!(fabsf(pc[0]) <= MS_FMAX && fabsf(pc[1]) <= MS_FMAX && fabsf(zc) <= MS_FMAX) || !(zc >= near)) return false;      // a NaN fails every compare
+  if (!(fabsf(pc[0]) <= PST_FMAX && fabsf(pc[1]) <= PST_FMAX && fabsf(zc) <= PST_FMAX) || !(zc >= near)) return false;      // a NaN fails every compare
   const float u = ms_addr(ms_divr(ms_mulr(c[12], pc[0]), zc), c[14]), v = ms_addr(ms_divr(ms_mulr(c[13], pc[1]), zc), c[15]);
   if (!(fabsf(u) <= MS_LIM && fabsf(v) <= MS_LIM)) return false;
   X = (int)rintf(u * 256.f);                                        // the product is exact; rintf rounds half to even
@@ -251,7 +250,7 @@ extern "C" int pst_mesh_raster(const float* vertices, int64_t Nv, const int32_t*
               (long long)Nv, (long long)Nf, ncams, H, W, (long long)big_capacity);
     return PST_EINVAL;
   }
-  if (!(near_z > 0.f) || !(far_z > near_z) || !(far_z <= MS_FMAX)) { set_error("mesh_raster: needs 0 < near < far, finite; got %g, %g", (double)near_z, (double)far_z); return PST_EINVAL; }
+  if (!(near_z > 0.f) || !(far_z > near_z) || !(far_z <= PST_FMAX)) { set_error("mesh_raster: needs 0 < near < far, finite; got %g, %g", (double)near_z, (double)far_z); return PST_EINVAL; }
   if (!vertices || !faces || !cams || !zbuf || !big_count || (big_capacity > 0 && !big)) { set_error("mesh_raster: null operand"); return PST_EINVAL; }
   const dim3 grid((unsigned)((Nf + MS_T - 1) / MS_T), (unsigned)ncams);
   hipStream_t st = (hipStream_t)stream;

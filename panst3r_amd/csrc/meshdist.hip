@@ -4,17 +4,20 @@
 //            counts, dropped faces counted, the total added up in int64 (one integer atomic per wave)
 //   scan     pst_cloud_scan of the per-face counts
 //   insert   one lane per (face, cell) pair: its face by binary search in the prefix, its cell from the pair's local index -> key -> slot of the
-//            open-addressing table of voxel_table.h, one int32 atomicAdd on the slot's count
+//            open-addressing table, one int32 atomicAdd on the slot's count
 //            (offsets: a prefix sum of the slot counts, made by the caller)
 //   scatter  the pair's face into its cell's list (the position inside the list depends on arrival; nothing that leaves depends on it)
 //   query    one lane per query: the list of the query's OWN cell, every candidate's closest point in fp64 (Ericson's region sequence), the minimum of
 //            (bits(float32 d2) << 32) | face, the winner's closest point once more for the output
+// Which faces are kept and the search in the prefix are mesh_face.h, shared with the surface sampler of csrc/nearest.hip; the cell of a query, the
+// key, the table's probes and the per-cell lists are voxel_table.h, shared by every hash-grid stage.
 // Integer atomics only, every probe / candidate / search loop bounded by a number known before the launch, refusals through the status words, every
 // result written with plain vector stores: two calls return identical bytes.  Contraction is off for the whole file: every fp32 and fp64 operation is
 // rounded on its own, in the order written.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
 #include "voxel_table.h"
+#include "mesh_face.h"
 
 #pragma clang fp contract(off)
 
@@ -26,45 +29,9 @@ constexpr int64_t MD_FACE_CAP = PST_MESHDIST_FACE_CAP;               // a face's
 
 static dim3 md_grid(int64_t n) { return dim3((unsigned)((n + MD_T - 1) / MD_T)); }
 
-__device__ __forceinline__ uint64_t md_key(int x, int y, int z) {     // only for cells in range: no field wraps
-  return (uint64_t)(x + VX_LIM) | ((uint64_t)(y + VX_LIM) << 21) | ((uint64_t)(z + VX_LIM) << 42);
-}
-
-// ---------------------------------------------------------------- a face: kept or dropped, its corners, its cell box
-struct MdFace { int ok; float v[3][3]; };
-
-// the sampler's rule (ms_load of csrc/nearest.hip): three indices inside the vertices, nine finite coordinates
-__device__ __forceinline__ MdFace md_load(const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int f) {
-  MdFace t;
-  t.ok = 1;
-  int idx[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    idx[k] = faces[(int64_t)f * 3 + k];
-    if ((unsigned)idx[k] >= (unsigned)Nv) t.ok = 0;
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float x = t.ok ? vertices[(int64_t)idx[k] * 3 + a] : 0.f;
-      if (!(fabsf(x) <= 3.402823466e38f)) t.ok = 0;                 // NaN fails the compare
-      t.v[k][a] = x;
-    }
-  return t;
-}
-
-// ... and a cross product of the edges that is not exactly zero in fp64 (ms_count's rule)
-__device__ __forceinline__ bool md_has_area(const MdFace& t) {
-  double e1[3], e2[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { e1[a] = (double)t.v[1][a] - (double)t.v[0][a]; e2[a] = (double)t.v[2][a] - (double)t.v[0][a]; }
-  const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-  return !(cx == 0.0 && cy == 0.0 && cz == 0.0);
-}
-
+// ---------------------------------------------------------------- the cell box of a face, its pairs
 // the cell box [lo, lo + ext) of a loaded face: cell(min corner) - 1 .. cell(max corner) + 1 per axis; false if a cell of it leaves (-2^20, 2^20)
-__device__ __forceinline__ bool md_box(const MdFace& t, float inv, int (&lo)[3], int (&ext)[3]) {
+__device__ __forceinline__ bool md_box(const MeshFace& t, float inv, int (&lo)[3], int (&ext)[3]) {
   bool in = true;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -80,8 +47,8 @@ __device__ __forceinline__ bool md_box(const MdFace& t, float inv, int (&lo)[3],
 // the number of (face, cell) pairs of face f, 0 = dropped, saturated at MD_FACE_CAP
 __device__ __forceinline__ int64_t md_pairs(const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int f, float inv, int (&lo)[3],
                                             int (&ext)[3]) {
-  const MdFace t = md_load(vertices, Nv, faces, f);
-  if (!t.ok || !md_has_area(t) || !md_box(t, inv, lo, ext)) return 0;
+  const MeshFace t = mf_load(vertices, Nv, faces, f);
+  if (!t.ok || !mf_has_area(t) || !md_box(t, inv, lo, ext)) return 0;
   const int64_t n = (int64_t)ext[0] * ext[1] * ext[2];                // three factors below 2^21
   return n < MD_FACE_CAP ? n : MD_FACE_CAP;
 }
@@ -107,16 +74,6 @@ __global__ __launch_bounds__(MD_T) void meshdist_count_kernel(const float* __res
   }
 }
 
-// the last face whose prefix is <= p: it holds pair p (31 rounds at the most)
-__device__ __forceinline__ int md_face_of(const int32_t* __restrict__ prefix, int F, int p) {
-  int lo = 0, hi = F - 1;
-  for (int it = 0; it < 32 && lo < hi; ++it) {
-    const int mid = (int)(((int64_t)lo + hi + 1) >> 1);
-    if (prefix[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(MD_T) void meshdist_insert_kernel(const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int F, float inv,
                                                                const int32_t* __restrict__ prefix, int P, uint64_t* __restrict__ keys, uint32_t mask,
                                                                int32_t* __restrict__ cell_count, int32_t* __restrict__ pair_slot,
@@ -127,19 +84,19 @@ __global__ __launch_bounds__(MD_T) void meshdist_insert_kernel(const float* __re
   }
   const int p = blockIdx.x * MD_T + threadIdx.x;
   if (p >= P) return;
-  const int f = md_face_of(prefix, F, p), t = p - prefix[f], cnt = prefix[f + 1] - prefix[f];
+  const int f = mf_prefix_owner(prefix, F, p), t = p - prefix[f], cnt = prefix[f + 1] - prefix[f];
   int lo[3], ext[3];
   int slot = -1;
   if (md_pairs(vertices, Nv, faces, f, inv, lo, ext) != (int64_t)cnt || t < 0 || t >= cnt) atomicOr(&status[0], PST_MESHDIST_LISTS);      // not this mesh's prefix
   else {
     const int x = lo[0] + t % ext[0], y = lo[1] + (t / ext[0]) % ext[1], z = lo[2] + t / (ext[0] * ext[1]);      // ext0 ext1 <= cnt: inside int32
-    slot = vx_find_or_claim(keys, mask, md_key(x, y, z), status);
+    slot = vx_find_or_claim(keys, mask, vx_key(x, y, z), status);
     if (slot >= 0) atomicAdd(&cell_count[slot], 1);
   }
   pair_slot[p] = slot;
 }
 
-// rows[start[slot] + k] = the face of the k-th arrival of the slot's cell; the arrival that fills a list reports its length: status[2] = the longest list
+// the pair's face into its cell's list; status[2] = the longest list
 __global__ __launch_bounds__(MD_T) void meshdist_scatter_kernel(const int32_t* __restrict__ pair_slot, const int32_t* __restrict__ prefix, int F, int P,
                                                                 const int32_t* __restrict__ start, const int32_t* __restrict__ cell_count,
                                                                 int32_t* __restrict__ fill, int32_t* __restrict__ rows, int32_t* __restrict__ status) {
@@ -151,10 +108,7 @@ __global__ __launch_bounds__(MD_T) void meshdist_scatter_kernel(const int32_t* _
   if (p >= P) return;
   const int slot = pair_slot[p];
   if (slot < 0) return;
-  const int k = atomicAdd(&fill[slot], 1), n = cell_count[slot], pos = start[slot] + k;
-  if ((unsigned)k >= (unsigned)n || (unsigned)pos >= (unsigned)P) { atomicOr(&status[0], PST_MESHDIST_LISTS); return; }      // not the counts of this insert
-  rows[pos] = md_face_of(prefix, F, p);
-  if (k == n - 1) atomicMax(&status[2], n);
+  vx_list_place(slot, start, cell_count, fill, P, rows, status, [&] { return mf_prefix_owner(prefix, F, p); });
 }
 
 // ---------------------------------------------------------------- the closest point of a triangle, in fp64, in the order the header writes out
@@ -198,7 +152,7 @@ __device__ __forceinline__ double md_closest(const double (&a)[3], const double 
   return (dx * dx + dy * dy) + dz * dz;
 }
 
-__device__ __forceinline__ double md_face_distance(const MdFace& t, const double (&q)[3], double (&cp)[3]) {
+__device__ __forceinline__ double md_face_distance(const MeshFace& t, const double (&q)[3], double (&cp)[3]) {
   double a[3], b[3], c[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) { a[k] = (double)t.v[0][k]; b[k] = (double)t.v[1][k]; c[k] = (double)t.v[2][k]; }
@@ -217,13 +171,8 @@ __global__ __launch_bounds__(MD_T) void meshdist_query_kernel(const float* __res
   bool finite = true, ok = true;
   if (in) {
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      x[a] = queries[(int64_t)i * 3 + a];
-      c[a] = floorf(x[a] * inv);                                     // nn_cell_of's rule
-      finite = finite && (fabsf(x[a]) <= 3.402823466e38f);           // NaN fails the compare
-      ok = ok && (fabsf(c[a]) < (float)VX_LIM);
-    }
-    ok = ok && finite;
+    for (int a = 0; a < 3; ++a) x[a] = queries[(int64_t)i * 3 + a];
+    vx_cell_of(x, inv, c, finite, ok);
   }
   const uint64_t bad = __ballot(in && !finite);
   if (bad && lane == (int)__builtin_ctzll(bad)) atomicAdd(&status[3], (int)__popcll(bad));
@@ -231,32 +180,19 @@ __global__ __launch_bounds__(MD_T) void meshdist_query_kernel(const float* __res
   const double q[3] = {(double)x[0], (double)x[1], (double)x[2]};
   uint64_t best = ~0ull;
   if (ok) {                                                          // a query outside the range has no cell of a kept face
-    const uint64_t key = md_key((int)c[0], (int)c[1], (int)c[2]);
-    uint32_t h = (uint32_t)vx_hash(key) & mask;
-    int slot = -1;
-    uint32_t n = 0;
-    for (; n <= mask; ++n) {                                         // the table is complete (an earlier launch built it): plain loads
-      const uint64_t k = keys[h];
-      if (k == key) { slot = (int)h; break; }
-      if (k == VX_EMPTY) break;
-      h = (h + 1) & mask;
-    }
-    if (n > mask) atomicOr(&status[0], PST_MESHDIST_FULL);           // a table without an empty slot: never (capacity >= 2 P)
-    if (slot >= 0) {
-      const int b = start[slot], cnt = min(cell_count[slot], max_cell_faces);      // (the caller refused a longer list before this launch)
-      if ((unsigned)b > (unsigned)P || cnt < 0 || cnt > P - b) atomicOr(&status[0], PST_MESHDIST_LISTS);      // a list that leaves rows[0, P): not this build's
-      else
-        for (int j = 0; j < cnt; ++j) {
-          const int f = rows[b + j];
-          if ((unsigned)f >= (unsigned)F) { atomicOr(&status[0], PST_MESHDIST_LISTS); continue; }
-          const MdFace t = md_load(vertices, Nv, faces, f);
-          if (!t.ok) { atomicOr(&status[0], PST_MESHDIST_LISTS); continue; }       // a listed face was kept by the build
-          double cp[3];
-          const float d2 = (float)md_face_distance(t, q, cp);       // >= +0, never NaN: its bits order as an unsigned integer
-          const uint64_t cand = ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)f;
-          best = cand < best ? cand : best;
-        }
-    }
+    const int slot = vx_find(keys, mask, vx_key((int)c[0], (int)c[1], (int)c[2]), status);
+    int b, cnt;
+    if (slot >= 0 && vx_list_range(slot, start, cell_count, P, max_cell_faces, status, b, cnt))
+      for (int j = 0; j < cnt; ++j) {
+        const int f = rows[b + j];
+        if ((unsigned)f >= (unsigned)F) { atomicOr(&status[0], PST_MESHDIST_LISTS); continue; }
+        const MeshFace t = mf_load(vertices, Nv, faces, f);
+        if (!t.ok) { atomicOr(&status[0], PST_MESHDIST_LISTS); continue; }       // a listed face was kept by the build
+        double cp[3];
+        const float d2 = (float)md_face_distance(t, q, cp);       // >= +0, never NaN: its bits order as an unsigned integer
+        const uint64_t cand = ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)f;
+        best = cand < best ? cand : best;
+      }
   }
   const float d2 = __uint_as_float((uint32_t)(best >> 32));
   const bool hit = best != ~0ull && d2 <= r2;
@@ -266,7 +202,7 @@ __global__ __launch_bounds__(MD_T) void meshdist_query_kernel(const float* __res
     float out[3] = {x[0], x[1], x[2]};                               // without a hit: the query itself
     if (hit) {
       double cp[3];
-      md_face_distance(md_load(vertices, Nv, faces, (int)(uint32_t)best), q, cp);
+      md_face_distance(mf_load(vertices, Nv, faces, (int)(uint32_t)best), q, cp);
 #pragma unroll
       for (int a = 0; a < 3; ++a) out[a] = (float)cp[a];
     }
@@ -276,17 +212,9 @@ __global__ __launch_bounds__(MD_T) void meshdist_query_kernel(const float* __res
 }
 
 static int md_mesh_ok(const char* what, const void* vertices, const void* faces, int64_t Nv, int64_t F, float inv) {
-  if (!vertices || !faces || Nv <= 0 || Nv > 0x7fffffffll || F <= 0 || F > MD_MAX || !(inv > 0.f) || !(inv <= 3.402823466e38f)) {
+  if (!vertices || !faces || Nv <= 0 || Nv > 0x7fffffffll || F <= 0 || F > MD_MAX || !(inv > 0.f) || !(inv <= PST_FMAX)) {
     set_error("%s: bad shape (Nv=%lld, F=%lld: 1 .. 2^30 faces), inverse radius %g (positive, finite) or null mesh", what, (long long)Nv, (long long)F,
               (double)inv);
-    return PST_EINVAL;
-  }
-  return 0;
-}
-
-static int md_table_ok(const char* what, int64_t P, int64_t capacity) {
-  if (P <= 0 || P > MD_MAX || capacity < 2 * P || capacity > (1ll << 31) || (capacity & (capacity - 1))) {
-    set_error("%s: bad shape (total=%lld: 1 .. 2^30 pairs; capacity=%lld: a power of two >= 2 total)", what, (long long)P, (long long)capacity);
     return PST_EINVAL;
   }
   return 0;
@@ -306,7 +234,7 @@ extern "C" int pst_meshdist_count(const float* vertices, int64_t Nv, const int32
 extern "C" int pst_meshdist_insert(const float* vertices, int64_t Nv, const int32_t* faces, int64_t F, float inv, const int32_t* prefix, int64_t total,
                                    uint64_t* keys, int64_t capacity, int32_t* cell_count, int32_t* pair_slot, int32_t* status, void* stream) {
   using namespace pst;
-  if (md_mesh_ok("meshdist_insert", vertices, faces, Nv, F, inv) || md_table_ok("meshdist_insert", total, capacity)) return PST_EINVAL;
+  if (md_mesh_ok("meshdist_insert", vertices, faces, Nv, F, inv) || vx_table_ok("meshdist_insert", total, MD_MAX, capacity, "total", "1 .. 2^30 pairs")) return PST_EINVAL;
   if (!prefix || !keys || !cell_count || !pair_slot || !status) { set_error("meshdist_insert: null operand"); return PST_EINVAL; }
   hipLaunchKernelGGL(meshdist_insert_kernel, md_grid(total), dim3(MD_T), 0, (hipStream_t)stream, vertices, (int)Nv, faces, (int)F, inv, prefix, (int)total,
                      keys, (uint32_t)(capacity - 1), cell_count, pair_slot, status);
@@ -328,9 +256,9 @@ extern "C" int pst_meshdist_query(const float* queries, int64_t Nq, const float*
                                   const uint64_t* keys, int64_t capacity, const int32_t* start, const int32_t* cell_count, const int32_t* rows,
                                   int64_t total, int max_cell_faces, float* d2, int32_t* face, float* closest, int32_t* status, void* stream) {
   using namespace pst;
-  if (md_mesh_ok("meshdist_query", vertices, faces, Nv, F, inv) || md_table_ok("meshdist_query", total, capacity)) return PST_EINVAL;
+  if (md_mesh_ok("meshdist_query", vertices, faces, Nv, F, inv) || vx_table_ok("meshdist_query", total, MD_MAX, capacity, "total", "1 .. 2^30 pairs")) return PST_EINVAL;
   if (!queries || !keys || !start || !cell_count || !rows || !d2 || !face || !status || Nq <= 0 || Nq > MD_MAX || !(r2 >= 0.f) ||
-      !(r2 <= 3.402823466e38f) || max_cell_faces < 1) {
+      !(r2 <= PST_FMAX) || max_cell_faces < 1) {
     set_error("meshdist_query: bad shape (Nq=%lld: 1 .. 2^30 queries), squared radius %g (finite), max_cell_faces %d (>= 1) or null operand",
               (long long)Nq, (double)r2, max_cell_faces);
     return PST_EINVAL;

@@ -4,7 +4,9 @@
 //                         counts, dropped and clamped faces counted, the total added up in int64 (one integer atomic per wave)
 //                  scan   pst_cloud_scan of the per-face counts
 //                  emit   one lane per sample: its face by binary search in the prefix, the sub-triangle's integer weights, one fp64 combination
-//   nearest point  insert one lane per target: cell -> key -> slot of the open-addressing table of voxel_table.h, one int32 atomicAdd on the slot's count
+//                  (which faces are kept, and the search in the prefix: mesh_face.h, shared with csrc/meshdist.hip)
+//   nearest point  insert one lane per target: cell -> key -> slot of the open-addressing table, one int32 atomicAdd on the slot's count
+//                  (the cell rule, the key, the table's probes and the per-cell lists: voxel_table.h, shared by every hash-grid stage)
 //                  (offsets: a prefix sum of the slot counts, made by the caller)
 //                  scatter the target's row into its cell's list (the position inside the list depends on arrival; nothing that leaves depends on it)
 //                  query  one lane per query: the 27 cells around it, every candidate's fp32 distance, the minimum of (bits(d2) << 32) | row
@@ -18,6 +20,7 @@
 #include "common.h"
 #include "../../include/panst3r_hip.h"
 #include "voxel_table.h"
+#include "mesh_face.h"
 
 #pragma clang fp contract(off)
 
@@ -30,43 +33,21 @@ static_assert(MS_MAX_SUBDIV == 1 << 15, "n^2 and 3n stay inside int32");
 static dim3 nn_grid(int64_t n) { return dim3((unsigned)((n + NN_T - 1) / NN_T)); }
 
 // ---------------------------------------------------------------- mesh surface sampler
-struct MsFace { int ok; double v[3][3]; };
-
-__device__ __forceinline__ MsFace ms_load(const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int f) {
-  MsFace t;
-  t.ok = 1;
-  int idx[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    idx[k] = faces[(int64_t)f * 3 + k];
-    if ((unsigned)idx[k] >= (unsigned)Nv) t.ok = 0;
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float x = t.ok ? vertices[(int64_t)idx[k] * 3 + a] : 0.f;
-      if (!(fabsf(x) <= 3.402823466e38f)) t.ok = 0;                 // NaN fails the compare
-      t.v[k][a] = (double)x;
-    }
-  return t;
-}
-
 __device__ __forceinline__ double ms_edge2(const double (&a)[3], const double (&b)[3]) {
   const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
   return (dx * dx + dy * dy) + dz * dz;
 }
 
 // the face's sample count n^2 (0 = dropped); clamped = the face wanted more than max_subdiv
-__device__ __forceinline__ int ms_count(const MsFace& t, double s2, int max_subdiv, int& clamped) {
+__device__ __forceinline__ int ms_count(const MeshFace& t, double s2, int max_subdiv, int& clamped) {
   clamped = 0;
-  if (!t.ok) return 0;
-  double e1[3], e2[3];
+  if (!t.ok || !mf_has_area(t)) return 0;
+  double v[3][3];                                                   // (widening a float is exact: the same values as the loader's)
 #pragma unroll
-  for (int a = 0; a < 3; ++a) { e1[a] = t.v[1][a] - t.v[0][a]; e2[a] = t.v[2][a] - t.v[0][a]; }
-  const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-  if (cx == 0.0 && cy == 0.0 && cz == 0.0) return 0;
-  const double L2 = fmax(fmax(ms_edge2(t.v[1], t.v[0]), ms_edge2(t.v[2], t.v[1])), ms_edge2(t.v[0], t.v[2]));
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) v[k][a] = (double)t.v[k][a];
+  const double L2 = fmax(fmax(ms_edge2(v[1], v[0]), ms_edge2(v[2], v[1])), ms_edge2(v[0], v[2]));
   // enough(n) = n n s2 >= L2 is monotone in n: the smallest n of [1, max_subdiv] that is enough, max_subdiv if none is.  At most 16 rounds.
   int lo = 1, hi = max_subdiv;
   if (!(((double)hi * (double)hi) * s2 >= L2)) { clamped = 1; return hi * hi; }
@@ -83,7 +64,7 @@ __global__ __launch_bounds__(NN_T) void mesh_sample_count_kernel(const float* __
   const int f = blockIdx.x * NN_T + threadIdx.x, lane = threadIdx.x & 63;
   int c = 0, clamped = 0, dropped = 0;
   if (f < F) {
-    c = ms_count(ms_load(vertices, Nv, faces, f), s2, max_subdiv, clamped);
+    c = ms_count(mf_load(vertices, Nv, faces, f), s2, max_subdiv, clamped);
     dropped = c == 0;
     counts[f] = c;
   }
@@ -108,12 +89,7 @@ __global__ __launch_bounds__(NN_T) void mesh_sample_emit_kernel(const float* __r
   }
   const int s = blockIdx.x * NN_T + threadIdx.x;
   if (s >= total) return;
-  int lo = 0, hi = F - 1;                                           // the last face whose prefix is <= s: it holds sample s (31 rounds at the most)
-  for (int it = 0; it < 32 && lo < hi; ++it) {
-    const int mid = (int)(((int64_t)lo + hi + 1) >> 1);
-    if (prefix[mid] <= s) lo = mid; else hi = mid - 1;
-  }
-  const int f = lo, t = s - prefix[f], cnt = prefix[f + 1] - prefix[f];
+  const int f = mf_prefix_owner(prefix, F, s), t = s - prefix[f], cnt = prefix[f + 1] - prefix[f];
   int n = (int)sqrt((double)cnt);                                   // cnt = n^2 exactly: a first guess, settled by integer compares
   if ((int64_t)n * n > cnt) --n;
   if ((int64_t)(n + 1) * (n + 1) <= cnt) ++n;
@@ -124,11 +100,11 @@ __global__ __launch_bounds__(NN_T) void mesh_sample_emit_kernel(const float* __r
   int w[3];
   if (c & 1) { w[0] = 3 * (n - r) - 1; w[1] = 3 * (r - k) - 1; w[2] = 3 * k + 2; }
   else       { w[0] = 3 * (n - r) - 2; w[1] = 3 * (r - k) + 1; w[2] = 3 * k + 1; }
-  const MsFace tri = ms_load(vertices, Nv, faces, f);               // (a face with samples has passed these checks)
+  const MeshFace tri = mf_load(vertices, Nv, faces, f);             // (a face with samples has passed these checks)
   const double den = (double)(3 * n);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const double p = (((double)w[0] * tri.v[0][a] + (double)w[1] * tri.v[1][a]) + (double)w[2] * tri.v[2][a]) / den;
+    const double p = (((double)w[0] * (double)tri.v[0][a] + (double)w[1] * (double)tri.v[1][a]) + (double)w[2] * (double)tri.v[2][a]) / den;
     points[(int64_t)s * 3 + a] = (float)p;
   }
   face[s] = f;
@@ -146,26 +122,10 @@ __device__ __forceinline__ float nn_mulr(float a, float b) { return a * b; }
 __device__ __forceinline__ float nn_addr(float a, float b) { return a + b; }
 __device__ __forceinline__ float nn_subr(float a, float b) { return a - b; }
 
-// the cell of a point by vx_cell's rule (csrc/voxel.hip): floor(x * inv) per axis; finite = every coordinate is, ok = and every cell is inside +-2^20
-__device__ __forceinline__ void nn_cell_of(const float (&x)[3], float inv, float (&c)[3], bool& finite, bool& ok) {
-  finite = ok = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    c[a] = floorf(nn_mulr(x[a], inv));
-    finite = finite && (fabsf(x[a]) <= 3.402823466e38f);           // NaN fails the compare
-    ok = ok && (fabsf(c[a]) < (float)VX_LIM);
-  }
-  ok = ok && finite;
-}
-
 __device__ __forceinline__ void nn_cell(const float* __restrict__ p, float inv, float (&x)[3], float (&c)[3], bool& finite, bool& ok) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) x[a] = p[a];
-  nn_cell_of(x, inv, c, finite, ok);
-}
-
-__device__ __forceinline__ uint64_t nn_key(int x, int y, int z) {     // only for cells in range: no field wraps
-  return (uint64_t)(x + VX_LIM) | ((uint64_t)(y + VX_LIM) << 21) | ((uint64_t)(z + VX_LIM) << 42);
+  vx_cell_of(x, inv, c, finite, ok);
 }
 
 __global__ __launch_bounds__(NN_T) void nn_insert_kernel(const float* __restrict__ targets, int M, float inv, uint64_t* __restrict__ keys, uint32_t mask,
@@ -180,13 +140,13 @@ __global__ __launch_bounds__(NN_T) void nn_insert_kernel(const float* __restrict
   if (!in) return;
   int slot = -1;
   if (ok) {
-    slot = vx_find_or_claim(keys, mask, nn_key((int)c[0], (int)c[1], (int)c[2]), status);
+    slot = vx_find_or_claim(keys, mask, vx_key((int)c[0], (int)c[1], (int)c[2]), status);
     if (slot >= 0) atomicAdd(&cell_count[slot], 1);
   }
   point_slot[i] = slot;
 }
 
-// rows[start[slot] + k] = the k-th arrival of the slot's cell; the arrival that fills a list reports its length: status[2] = the largest occupancy
+// the target's row into its cell's list; status[2] = the largest occupancy
 __global__ __launch_bounds__(NN_T) void nn_scatter_kernel(const int32_t* __restrict__ point_slot, int M, const int32_t* __restrict__ start,
                                                           const int32_t* __restrict__ cell_count, int32_t* __restrict__ fill, int32_t* __restrict__ rows,
                                                           int32_t* __restrict__ status) {
@@ -194,10 +154,7 @@ __global__ __launch_bounds__(NN_T) void nn_scatter_kernel(const int32_t* __restr
   if (i >= M) return;
   const int slot = point_slot[i];
   if (slot < 0) return;
-  const int k = atomicAdd(&fill[slot], 1), n = cell_count[slot], pos = start[slot] + k;
-  if ((unsigned)k >= (unsigned)n || (unsigned)pos >= (unsigned)M) { atomicOr(&status[0], PST_NN_LISTS); return; }      // not the counts of this insert
-  rows[pos] = i;
-  if (k == n - 1) atomicMax(&status[2], n);
+  vx_list_place(slot, start, cell_count, fill, M, rows, status, [&] { return i; });
 }
 
 // step 3 of the fixed-radius contract for one lane, shared by nn_query and icp_step: every candidate of the 27 cells around the cell c of the point q
@@ -212,21 +169,10 @@ __device__ __forceinline__ uint64_t nn_search(const float (&q)[3], const float (
     const int cx = (int)c[0], cy = (int)c[1], cz = (int)c[2];
     for (int nb = 0; nb < 27; ++nb) {
       const int x = cx + nb % 3 - 1, y = cy + (nb / 3) % 3 - 1, z = cz + nb / 9 - 1;
-      if (x <= -VX_LIM || x >= VX_LIM || y <= -VX_LIM || y >= VX_LIM || z <= -VX_LIM || z >= VX_LIM) continue;      // no such cell: never looked up
-      const uint64_t key = nn_key(x, y, z);
-      uint32_t h = (uint32_t)vx_hash(key) & mask;
-      int slot = -1;
-      uint32_t n = 0;
-      for (; n <= mask; ++n) {                                      // the table is complete (an earlier launch built it): plain loads
-        const uint64_t k = keys[h];
-        if (k == key) { slot = (int)h; break; }
-        if (k == VX_EMPTY) break;
-        h = (h + 1) & mask;
-      }
-      if (n > mask) atomicOr(&status[0], PST_NN_FULL);               // a table without an empty slot: never (capacity >= 2 M)
-      if (slot < 0) continue;
-      const int b = start[slot], cnt = min(cell_count[slot], max_cell_points);      // (the caller refused a fuller cell before this launch)
-      if ((unsigned)b > (unsigned)M || cnt < 0 || cnt > M - b) { atomicOr(&status[0], PST_NN_LISTS); continue; }      // a list that leaves rows[0, M): not this build's
+      if (!vx_in_range(x, y, z)) continue;                          // no such cell: never looked up
+      const int slot = vx_find(keys, mask, vx_key(x, y, z), status);
+      int b, cnt;
+      if (slot < 0 || !vx_list_range(slot, start, cell_count, M, max_cell_points, status, b, cnt)) continue;
       for (int j = 0; j < cnt; ++j) {
         const int p = rows[b + j];
         if ((unsigned)p >= (unsigned)M) { atomicOr(&status[0], PST_NN_LISTS); continue; }
@@ -304,7 +250,7 @@ __global__ __launch_bounds__(NN_T) void icp_step_kernel(const float* __restrict_
     for (int r = 0; r < 3; ++r)
       m[r] = nn_addr(nn_addr(nn_addr(nn_mulr(A.a[r][0], x[0]), nn_mulr(A.a[r][1], x[1])), nn_mulr(A.a[r][2], x[2])), A.a[r][3]);
     bool finite, ok;
-    nn_cell_of(m, inv, c, finite, ok);
+    vx_cell_of(m, inv, c, finite, ok);
     bad += !finite;
     const uint64_t best = nn_search(m, c, finite, targets, M, keys, mask, start, cell_count, rows, max_cell_points, status);
     const float d2 = __uint_as_float((uint32_t)(best >> 32));
@@ -353,7 +299,7 @@ extern "C" int pst_mesh_sample_count(const float* vertices, int64_t Nv, const in
                                      int64_t* total, int32_t* status, void* stream) {
   using namespace pst;
   if (!vertices || !faces || !counts || !total || !status || Nv <= 0 || Nv > 0x7fffffffll || F <= 0 || F > NN_MAX_POINTS || !(spacing > 0.f) ||
-      !(spacing <= 3.402823466e38f) || max_subdiv < 1 || max_subdiv > MS_MAX_SUBDIV) {
+      !(spacing <= PST_FMAX) || max_subdiv < 1 || max_subdiv > MS_MAX_SUBDIV) {
     set_error("mesh_sample_count: bad shape (Nv=%lld, F=%lld: at most 2^30 faces), spacing %g (positive, finite), max_subdiv %d (1 .. %d) or null operand",
               (long long)Nv, (long long)F, (double)spacing, max_subdiv, MS_MAX_SUBDIV);
     return PST_EINVAL;
@@ -383,20 +329,11 @@ extern "C" int pst_mesh_sample_emit(const float* vertices, int64_t Nv, const int
   return check_launch("mesh_sample_emit");
 }
 
-static int nn_table_ok(const char* what, int64_t M, int64_t capacity) {
-  using namespace pst;
-  if (M <= 0 || M > NN_MAX_POINTS || capacity < 2 * M || capacity > (1ll << 31) || (capacity & (capacity - 1))) {
-    set_error("%s: bad shape (M=%lld: at most 2^30 targets; capacity=%lld: a power of two >= 2 M)", what, (long long)M, (long long)capacity);
-    return PST_EINVAL;
-  }
-  return 0;
-}
-
 extern "C" int pst_nn_insert(const float* targets, int64_t M, float inv, uint64_t* keys, int64_t capacity, int32_t* cell_count, int32_t* point_slot,
                              int32_t* status, void* stream) {
   using namespace pst;
-  if (nn_table_ok("nn_insert", M, capacity)) return PST_EINVAL;
-  if (!targets || !keys || !cell_count || !point_slot || !status || !(inv > 0.f) || !(inv <= 3.402823466e38f)) {
+  if (vx_table_ok("nn_insert", M, NN_MAX_POINTS, capacity, "M", "at most 2^30 targets")) return PST_EINVAL;
+  if (!targets || !keys || !cell_count || !point_slot || !status || !(inv > 0.f) || !(inv <= PST_FMAX)) {
     set_error("nn_insert: inverse radius %g (positive, finite) or null operand", (double)inv); return PST_EINVAL;
   }
   hipLaunchKernelGGL(nn_insert_kernel, nn_grid(M), dim3(NN_T), 0, (hipStream_t)stream, targets, (int)M, inv, keys, (uint32_t)(capacity - 1), cell_count,
@@ -418,9 +355,9 @@ extern "C" int pst_nn_query(const float* queries, int64_t Nq, const float* targe
                             const int32_t* start, const int32_t* cell_count, const int32_t* rows, int max_cell_points, float* d2, int32_t* row,
                             int32_t* status, void* stream) {
   using namespace pst;
-  if (nn_table_ok("nn_query", M, capacity)) return PST_EINVAL;
+  if (vx_table_ok("nn_query", M, NN_MAX_POINTS, capacity, "M", "at most 2^30 targets")) return PST_EINVAL;
   if (!queries || !targets || !keys || !start || !cell_count || !rows || !d2 || !row || !status || Nq <= 0 || Nq > NN_MAX_POINTS || !(inv > 0.f) ||
-      !(inv <= 3.402823466e38f) || !(r2 >= 0.f) || !(r2 <= 3.402823466e38f) || max_cell_points < 1) {
+      !(inv <= PST_FMAX) || !(r2 >= 0.f) || !(r2 <= PST_FMAX) || max_cell_points < 1) {
     set_error("nn_query: bad shape (Nq=%lld: at most 2^30 queries), inverse radius %g, squared radius %g (finite), max_cell_points %d (>= 1) or null operand",
               (long long)Nq, (double)inv, (double)r2, max_cell_points);
     return PST_EINVAL;
@@ -437,9 +374,9 @@ extern "C" int pst_icp_step(const float* source, int64_t N, float a00, float a01
                             const int32_t* start, const int32_t* cell_count, const int32_t* rows, int max_cell_points, float* d2, int32_t* row,
                             double* partials, double* out, int32_t* status, void* stream) {
   using namespace pst;
-  if (nn_table_ok("icp_step", M, capacity)) return PST_EINVAL;
+  if (vx_table_ok("icp_step", M, NN_MAX_POINTS, capacity, "M", "at most 2^30 targets")) return PST_EINVAL;
   if (!source || !targets || !keys || !start || !cell_count || !rows || !partials || !out || !status || (d2 == nullptr) != (row == nullptr) || N < 1 ||
-      N > NN_MAX_POINTS || !(inv > 0.f) || !(inv <= 3.402823466e38f) || !(r2 >= 0.f) || !(r2 <= 3.402823466e38f) || max_cell_points < 1) {
+      N > NN_MAX_POINTS || !(inv > 0.f) || !(inv <= PST_FMAX) || !(r2 >= 0.f) || !(r2 <= PST_FMAX) || max_cell_points < 1) {
     set_error("icp_step: bad shape (N=%lld: 1 .. 2^30 source points), inverse cell edge %g, squared radius %g (finite), max_cell_points %d (>= 1), one of "
               "d2 / row without the other, or null operand", (long long)N, (double)inv, (double)r2, max_cell_points);
     return PST_EINVAL;

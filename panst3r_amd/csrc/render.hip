@@ -34,7 +34,6 @@ __device__ __forceinline__ float rd_divr(float a, float b) { return (float)((dou
 constexpr int RD_T = 256;
 constexpr unsigned long long RD_EMPTY = ~0ull;                     // no key is all ones: bits(zc) = 0xFFFFFFFF is a NaN, and a NaN is culled
 constexpr float RD_LIM = 1048576.f;                                // |u|, |v| <= 2^20
-constexpr float RD_FMAX = 3.402823466e38f;
 constexpr int RD_CAM = 16;                                         // floats per camera: rows of [R^T | -R^T t], then f, cx, cy, near
 
 template <bool PRECHECK>
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(RD_T) void render_splat_kernel(const float* __restr
     pc[a] = rd_addr(rd_addr(rd_addr(rd_mulr(c[4 * a + 0], x), rd_mulr(c[4 * a + 1], y)), rd_mulr(c[4 * a + 2], z)), c[4 * a + 3]);
   const float f = c[12], cx = c[13], cy = c[14], near = c[15];
   const float zc = pc[2];
-  if (!(fabsf(pc[0]) <= RD_FMAX && fabsf(pc[1]) <= RD_FMAX && fabsf(zc) <= RD_FMAX) || !(zc >= near)) return;      // a NaN fails every compare
+  if (!(fabsf(pc[0]) <= PST_FMAX && fabsf(pc[1]) <= PST_FMAX && fabsf(zc) <= PST_FMAX) || !(zc >= near)) return;      // a NaN fails every compare
   const float u = rd_addr(rd_divr(rd_mulr(f, pc[0]), zc), cx), v = rd_addr(rd_divr(rd_mulr(f, pc[1]), zc), cy);
   if (!(fabsf(u) <= RD_LIM && fabsf(v) <= RD_LIM)) return;
   const int px = (int)floorf(u), py = (int)floorf(v);
@@ -100,7 +99,7 @@ extern "C" int pst_render_splat(const float* points, int64_t M, const float* cam
     set_error("render_splat: bad shape (M=%lld in [1, 2^32 - 1], %d cameras in [1, 65535], %d x %d pixels, cameras x pixels < 2^31)", (long long)M, ncams, H, W);
     return PST_EINVAL;
   }
-  if (radius < 0 || radius > PST_RENDER_MAX_RADIUS || max_radius < 0 || max_radius > PST_RENDER_MAX_RADIUS || !(half_size >= 0.f) || !(half_size <= RD_FMAX)) {
+  if (radius < 0 || radius > PST_RENDER_MAX_RADIUS || max_radius < 0 || max_radius > PST_RENDER_MAX_RADIUS || !(half_size >= 0.f) || !(half_size <= PST_FMAX)) {
     set_error("render_splat: radius=%d / max_radius=%d outside [0, %d] or half_size=%g not a finite number >= 0", radius, max_radius, PST_RENDER_MAX_RADIUS,
               (double)half_size);
     return PST_EINVAL;

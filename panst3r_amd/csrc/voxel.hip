@@ -1,8 +1,8 @@
 // Voxel fusion of the panoptic point cloud with multi-view label votes (no counterpart in the reference, whose viewer shows the raw concatenation;
 // restated in tests/voxel_ref.py, [restated, parity unpinned]).  One pass over the cloud that csrc/cloud.hip left on the device:
 //   insert      every point's cell -> a 64-bit key (3 x 21 bits) in an open-addressing table (linear probing, slots claimed by 64-bit compare-and-swap,
-//               every probe loop bounded by the capacity); atomicMin of the point's row into the slot: the voxel's FIRST row.  A point left out
-//               (non-finite, or a cell outside +-2^20) gets slot -1 and is counted.
+//               every probe loop bounded by the capacity; the cell rule, the key and the table are voxel_table.h); atomicMin of the point's row into
+//               the slot: the voxel's FIRST row.  A point left out (non-finite, or a cell outside +-2^20) gets slot -1 and is counted.
 //   count/rank  a point is its voxel's first one iff first[slot] == its row: counted per 1024 points, turned into output ranks by pst_cloud_scan, so
 //               the voxels come out in the order of their first rows without a sort.
 //   accumulate  per point, into arrays indexed by the voxel's rank: count, three sums of the 16-bit in-cell offsets, three colour sums - 64-bit
@@ -30,20 +30,12 @@ constexpr int VX_MAX_COLORS = 4096;
 
 // cell (as floats, exact integers) and in-cell offset q = floor((t - c) * 65536) in [0, 65536] of a point; false = the point is left out
 __device__ __forceinline__ bool vx_cell(const float* __restrict__ p, float inv, float (&c)[3], int (&q)[3]) {
-  bool ok = true;
+  const float x[3] = {p[0], p[1], p[2]};
+  bool finite, ok;
+  vx_cell_of(x, inv, c, finite, ok);
 #pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float x = p[a];
-    const float t = vx_mulr(x, inv);
-    c[a] = floorf(t);
-    ok = ok && (fabsf(x) <= 3.402823466e38f) && (fabsf(c[a]) < (float)VX_LIM);          // NaN fails both compares
-    q[a] = (int)floorf(vx_mulr(vx_subr(t, c[a]), 65536.f));
-  }
+  for (int a = 0; a < 3; ++a) q[a] = (int)floorf(vx_mulr(vx_subr(vx_mulr(x[a], inv), c[a]), 65536.f));      // t = x * inv: the product vx_cell_of floors
   return ok;
-}
-
-__device__ __forceinline__ uint64_t vx_key(const float (&c)[3]) {
-  return (uint64_t)((int)c[0] + VX_LIM) | ((uint64_t)((int)c[1] + VX_LIM) << 21) | ((uint64_t)((int)c[2] + VX_LIM) << 42);
 }
 
 template <bool MERGE>
@@ -54,7 +46,7 @@ __global__ __launch_bounds__(VX_T) void voxel_insert_kernel(const float* __restr
   float c[3]; int q[3];
   bool ok = false;
   if (in) ok = vx_cell(points + (int64_t)i * 3, inv, c, q);
-  const uint64_t key = ok ? vx_key(c) : VX_EMPTY;
+  const uint64_t key = ok ? vx_key((int)c[0], (int)c[1], (int)c[2]) : VX_EMPTY;
   const uint64_t dropped = __ballot(in && !ok);
   if (dropped && lane == (int)__builtin_ctzll(dropped)) atomicAdd(&status[1], (int)__popcll(dropped));
   int slot = -1;
@@ -204,7 +196,7 @@ __global__ __launch_bounds__(VX_T) void voxel_vote_kernel(const uint64_t* __rest
                                                           unsigned long long* __restrict__ best) {
   for (int64_t s = (int64_t)blockIdx.x * VX_T + threadIdx.x; s < cap; s += (int64_t)gridDim.x * VX_T) {
     const uint64_t k = pkeys[s];
-    if (k == VX_EMPTY) continue;
+    if (k == VX_EMPTY) continue;                                     // (a pass over every slot, not a probe: those are voxel_table.h's)
     atomicMax(&best[k >> 32], ((unsigned long long)(uint32_t)pcnt[s] << 32) | (0xFFFFFFFFu - (uint32_t)k));
   }
 }
@@ -237,8 +229,6 @@ __global__ __launch_bounds__(VX_T) void voxel_emit_kernel(const float* __restric
   out_votes[r] = b ? (int)(b >> 32) : n;                            // only void votes: all of them
   out_first[r] = index[i];
 }
-
-static bool vx_cap_ok(int64_t M, int64_t cap) { return cap >= 2 * M && cap <= (1ll << 31) && (cap & (cap - 1)) == 0; }
 
 }  // namespace pst
 

@@ -16,21 +16,7 @@ import math
 import torch
 
 from .. import hip
-from .score3d import _check_points, _check_radius, _is_int
-
-
-def _check_mesh(vertices, faces):
-    for name, t in (('vertices', vertices), ('faces', faces)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError('%s must be a torch tensor, got %s' % (name, type(t).__name__))
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.dtype.is_floating_point:
-        raise ValueError('vertices must be a floating-point [Nv, 3] tensor, got %s %s' % (vertices.dtype, tuple(vertices.shape)))
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
-        raise ValueError('faces must be an int32 / int64 [Nf, 3] tensor, got %s %s' % (faces.dtype, tuple(faces.shape)))
-    Nv, Nf = int(vertices.shape[0]), int(faces.shape[0])
-    if not (Nv <= 2 ** 31 - 1 and Nf <= hip.MESHDIST_MAX):
-        raise ValueError('a mesh to search has at most 2^31 - 1 vertices and 2^30 faces, got %d and %d' % (Nv, Nf))
-    return Nv, Nf
+from .score3d import _build_lists, _check_mesh, _check_points, _check_radius, _gpu_only, _int32_faces, _is_int, _search_status
 
 
 def _check_limits(max_cell_faces, max_pairs):
@@ -48,21 +34,16 @@ class MeshIndex:
     (d2, face, None) with `closest=False`; `check()` reads the status words after the queries and raises if a kernel gave up."""
 
     def __init__(self, vertices, faces, radius, *, max_cell_faces=4096, max_pairs=2 ** 27):
-        Nv, self.F = _check_mesh(vertices, faces)
+        Nv, self.F = _check_mesh(vertices, faces, 'search', hip.MESHDIST_MAX)
         self.radius, self.inv, self.r2 = _check_radius(radius)
         self.max_cell_faces, self.max_pairs = _check_limits(max_cell_faces, max_pairs)
-        for name, t in (('vertices', vertices), ('faces', faces)):
-            if not t.is_cuda:
-                raise RuntimeError('mesh_distance got %s %s: it runs on the GPU only (no CPU fallback)' % (t.device, name))
+        _gpu_only('mesh_distance', vertices=vertices, faces=faces)
         dev = self.device = vertices.device
         self.dropped_faces, self.pairs, self.max_occupancy, self.bad_queries, self.ws = self.F, 0, 0, 0, None
         if self.F == 0 or Nv == 0:
             return
         i32 = dict(dtype=torch.int32, device=dev)
-        self.vertices = vertices.float().contiguous()
-        if faces.dtype == torch.int64:                                            # an index that does not fit int32 is outside the vertices: keep it so
-            faces = torch.where((faces < 0) | (faces >= Nv), torch.full_like(faces, -1), faces)
-        self.faces = faces.to(torch.int32).contiguous()
+        self.vertices, self.faces = vertices.float().contiguous(), _int32_faces(faces, Nv)
         self.counts, total, self.status = torch.empty(self.F, **i32), torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(4, **i32)
         hip.meshdist_count(self.vertices, self.faces, self.inv, self.counts, total, self.status)
         self.pairs, _, self.dropped_faces, _, _ = torch.cat([total, self.status.to(torch.int64)]).tolist()      # the host sync of the pair total
@@ -76,22 +57,15 @@ class MeshIndex:
         hip.cloud_scan(self.counts, self.prefix)
         ws = self.ws = hip.meshdist_workspace(self.pairs, dev)
         hip.meshdist_insert(self.vertices, self.faces, self.inv, self.prefix, ws, self.status)
-        csum = torch.cumsum(ws['cell_count'], 0, dtype=torch.int32)               # plumbing: the offsets of the per-cell lists
-        ws['start'] = csum - ws['cell_count']
-        hip.meshdist_scatter(self.prefix, ws, self.status)
-        bits, _, self.max_occupancy, _ = self.status.tolist()                     # the host sync of the build
-        if bits:
-            raise RuntimeError('mesh_distance: the build did not finish (status %d): the cell table ran full or its lists are inconsistent' % bits)
-        if self.max_occupancy > self.max_cell_faces:
-            raise ValueError('mesh_distance: the radius %g is too large for this mesh: one cell of that edge lists %d of the %d faces, above '
-                             'max_cell_faces = %d (every query in it would visit them all; a smaller radius makes shorter lists)'
-                             % (self.radius, self.max_occupancy, self.F, self.max_cell_faces))
+        _, self.max_occupancy = _build_lists(
+            'mesh_distance', ws, lambda: hip.meshdist_scatter(self.prefix, ws, self.status), self.status, 'the radius %g is too large for this mesh: one cell '
+            'of that edge lists %d of the %d faces, above max_cell_faces = %d (every query in it would visit them all; a smaller radius makes shorter lists)',
+            self.radius, self.F, self.max_cell_faces)
 
     @torch.no_grad()
     def query(self, points, closest=True):
         Nq = _check_points(points, 'points')
-        if not points.is_cuda:
-            raise RuntimeError('mesh_distance got %s points: it runs on the GPU only (no CPU fallback)' % points.device)
+        _gpu_only('mesh_distance', points=points)
         q = points.float().contiguous()
         d2 = torch.full((Nq,), math.inf, dtype=torch.float32, device=self.device)
         face = torch.full((Nq,), -1, dtype=torch.int32, device=self.device)
@@ -103,9 +77,7 @@ class MeshIndex:
     def check(self):
         """after the queries (a host sync): the status bits, and the number of non-finite queries so far"""
         if self.ws is not None:
-            bits, _, _, self.bad_queries = self.status.tolist()
-            if bits:
-                raise RuntimeError('mesh_distance: the search did not finish (status %d)' % bits)
+            self.bad_queries = _search_status('mesh_distance', self.status)
         return self.bad_queries
 
 
@@ -123,12 +95,10 @@ def mesh_distance(points, vertices, faces, radius, *, max_cell_faces=4096, max_p
     Three host syncs: the pair total, the build's status with the longest list, and the query's status, which raises RuntimeError if a kernel gave
     up.  GPU only: CPU tensors raise."""
     Nq = _check_points(points, 'points')
-    _, Nf = _check_mesh(vertices, faces)
+    _, Nf = _check_mesh(vertices, faces, 'search', hip.MESHDIST_MAX)
     _check_radius(radius)
     _check_limits(max_cell_faces, max_pairs)
-    for name, t in (('points', points), ('vertices', vertices), ('faces', faces)):
-        if not t.is_cuda:
-            raise RuntimeError('mesh_distance got %s %s: it runs on the GPU only (no CPU fallback)' % (t.device, name))
+    _gpu_only('mesh_distance', points=points, vertices=vertices, faces=faces)
     if Nq == 0 or Nf == 0 or vertices.shape[0] == 0:                              # nothing to search: no build, no launch
         dev = points.device
         return (torch.full((Nq,), math.inf, dtype=torch.float32, device=dev), torch.full((Nq,), -1, dtype=torch.int32, device=dev),

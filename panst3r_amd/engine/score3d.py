@@ -82,8 +82,17 @@ def _check_points(t, name):
     return int(t.shape[0])
 
 
-def _check_sample_mesh(vertices, faces, vertex_ids, face_ids, max_subdiv):
-    for name, t in (('vertices', vertices), ('faces', faces), ('vertex_ids', vertex_ids), ('face_ids', face_ids)):
+def _gpu_only(who, what='%(device)s %(name)s', **tensors):
+    """`who` has no CPU path: a given tensor that is not on the GPU raises; `what` = how the caller's message names it"""
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise RuntimeError('%s got %s: it runs on the GPU only (no CPU fallback)' % (who, what % dict(device=t.device, name=name)))
+
+
+def _check_mesh(vertices, faces, use, max_faces, **ids):
+    """the mesh of `sample_mesh` (use = 'sample') and of `mesh_distance` ('search'), of at most max_faces = 2^30 faces -> (Nv, Nf); `ids`: further
+    tensors or None"""
+    for name, t in dict(vertices=vertices, faces=faces, **ids).items():
         if t is not None and not isinstance(t, torch.Tensor):
             raise ValueError('%s must be a torch tensor, got %s' % (name, type(t).__name__))
     if vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.dtype.is_floating_point:
@@ -91,8 +100,43 @@ def _check_sample_mesh(vertices, faces, vertex_ids, face_ids, max_subdiv):
     if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64):
         raise ValueError('faces must be an int32 / int64 [Nf, 3] tensor, got %s %s' % (faces.dtype, tuple(faces.shape)))
     Nv, Nf = int(vertices.shape[0]), int(faces.shape[0])
-    if not (Nv <= 2 ** 31 - 1 and Nf <= hip.NN_MAX_POINTS):
-        raise ValueError('a mesh to sample has at most 2^31 - 1 vertices and 2^30 faces, got %d and %d' % (Nv, Nf))
+    if not (Nv <= 2 ** 31 - 1 and Nf <= max_faces):
+        raise ValueError('a mesh to %s has at most 2^31 - 1 vertices and 2^30 faces, got %d and %d' % (use, Nv, Nf))
+    return Nv, Nf
+
+
+def _int32_faces(faces, Nv):
+    """contiguous int32 faces; an int64 index that does not fit int32 is outside the vertices: -1 keeps it so"""
+    if faces.dtype == torch.int64:
+        faces = torch.where((faces < 0) | (faces >= Nv), torch.full_like(faces, -1), faces)
+    return faces.to(torch.int32).contiguous()
+
+
+def _build_lists(who, ws, scatter, status, too_long, radius, n, limit):
+    """The tail of a hash-grid build, after the insert has counted the cells: the offsets of the per-cell lists, the scatter (`scatter()` launches
+    it), the host sync of the build and its two refusals -> (status[1], the longest list).  `too_long` is the text after '`who`: ', formatted with
+    (radius, the longest list, n, limit)."""
+    csum = torch.cumsum(ws['cell_count'], 0, dtype=torch.int32)               # plumbing: the offsets of the per-cell lists
+    ws['start'] = csum - ws['cell_count']
+    scatter()
+    bits, left_out, longest, _ = status.tolist()                              # the host sync of the build
+    if bits:
+        raise RuntimeError('%s: the build did not finish (status %d): the cell table ran full or its lists are inconsistent' % (who, bits))
+    if longest > limit:
+        raise ValueError('%s: ' % who + too_long % (radius, longest, n, limit))
+    return left_out, longest
+
+
+def _search_status(who, status):
+    """after the queries (a host sync): raises if a kernel gave up -> the number of non-finite queries so far"""
+    bits, _, _, bad = status.tolist()
+    if bits:
+        raise RuntimeError('%s: the search did not finish (status %d)' % (who, bits))
+    return bad
+
+
+def _check_sample_mesh(vertices, faces, vertex_ids, face_ids, max_subdiv):
+    Nv, Nf = _check_mesh(vertices, faces, 'sample', hip.NN_MAX_POINTS, vertex_ids=vertex_ids, face_ids=face_ids)
     if vertex_ids is not None and face_ids is not None:
         raise ValueError('give vertex_ids or face_ids, not both')
     for name, t, n in (('vertex_ids', vertex_ids, Nv), ('face_ids', face_ids, Nf)):
@@ -118,9 +162,7 @@ def sample_mesh(vertices, faces, spacing, *, vertex_ids=None, face_ids=None, max
         capacity = hip.MESH_SAMPLE_MAX_TOTAL
     if not _is_int(capacity) or not 0 <= capacity <= hip.MESH_SAMPLE_MAX_TOTAL:
         raise ValueError('capacity must be an integer in 0 .. 2^31 - 256, got %r' % (capacity,))
-    for t in (vertices, faces, vertex_ids, face_ids):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError('sample_mesh got a %s tensor: it runs on the GPU only (no CPU fallback)' % t.device)
+    _gpu_only('sample_mesh', 'a %(device)s tensor', vertices=vertices, faces=faces, vertex_ids=vertex_ids, face_ids=face_ids)
     dev = vertices.device
     i32 = dict(dtype=torch.int32, device=dev)
 
@@ -130,10 +172,7 @@ def sample_mesh(vertices, faces, spacing, *, vertex_ids=None, face_ids=None, max
         return MeshSamples(points, face, ids, dropped, clamped)
     if Nf == 0 or Nv == 0:
         return result(0, Nf, 0)
-    verts = vertices.float().contiguous()
-    if faces.dtype == torch.int64:                                            # an index that does not fit int32 is outside the vertices: keep it so
-        faces = torch.where((faces < 0) | (faces >= Nv), torch.full_like(faces, -1), faces)
-    faces = faces.to(torch.int32).contiguous()
+    verts, faces = vertices.float().contiguous(), _int32_faces(faces, Nv)
     vid = None if vertex_ids is None else vertex_ids.to(torch.int32).contiguous()
     fid = None if face_ids is None else face_ids.to(torch.int32).contiguous()
     counts, prefix = torch.empty(Nf, **i32), torch.empty(Nf + 1, **i32)
@@ -164,29 +203,21 @@ class NearestIndex:
         if not _is_int(max_cell_points) or not 1 <= max_cell_points <= 2 ** 31 - 1:
             raise ValueError('max_cell_points must be an integer >= 1, got %r' % (max_cell_points,))
         self.max_cell_points = int(max_cell_points)
-        if not targets.is_cuda:
-            raise RuntimeError('nearest_points got %s targets: it runs on the GPU only (no CPU fallback)' % targets.device)
+        _gpu_only('nearest_points', targets=targets)
         self.device, self.dropped, self.max_occupancy, self.bad_queries = targets.device, 0, 0, 0
         if self.M == 0:
             return
         self.targets = targets.float().contiguous()
         ws = self.ws = hip.nn_workspace(self.M, self.device)
         hip.nn_insert(self.targets, self.inv, ws)
-        csum = torch.cumsum(ws['cell_count'], 0, dtype=torch.int32)           # plumbing: the offsets of the per-cell lists
-        ws['start'] = csum - ws['cell_count']
-        hip.nn_scatter(ws)
-        bits, self.dropped, self.max_occupancy, _ = ws['status'].tolist()    # the host sync of the build
-        if bits:
-            raise RuntimeError('nearest_points: the build did not finish (status %d): the cell table ran full or its lists are inconsistent' % bits)
-        if self.max_occupancy > self.max_cell_points:
-            raise ValueError('nearest_points: the radius %g is too large for this density: one cell of that edge holds %d of the %d targets, above '
-                             'max_cell_points = %d (every query next to it would visit them all)' % (self.radius, self.max_occupancy, self.M, self.max_cell_points))
+        self.dropped, self.max_occupancy = _build_lists(
+            'nearest_points', ws, lambda: hip.nn_scatter(ws), ws['status'], 'the radius %g is too large for this density: one cell of that edge holds %d '
+            'of the %d targets, above max_cell_points = %d (every query next to it would visit them all)', self.radius, self.M, self.max_cell_points)
 
     @torch.no_grad()
     def query(self, queries):
         Nq = _check_points(queries, 'queries')
-        if not queries.is_cuda:
-            raise RuntimeError('nearest_points got %s queries: it runs on the GPU only (no CPU fallback)' % queries.device)
+        _gpu_only('nearest_points', queries=queries)
         d2 = torch.full((Nq,), math.inf, dtype=torch.float32, device=self.device)
         row = torch.full((Nq,), -1, dtype=torch.int32, device=self.device)
         if Nq and self.M:
@@ -196,9 +227,7 @@ class NearestIndex:
     def check(self):
         """after the queries (a host sync): the status bits, and the number of non-finite queries so far"""
         if self.M:
-            bits, _, _, self.bad_queries = self.ws['status'].tolist()
-            if bits:
-                raise RuntimeError('nearest_points: the search did not finish (status %d)' % bits)
+            self.bad_queries = _search_status('nearest_points', self.ws['status'])
         return self.bad_queries
 
 
@@ -216,9 +245,7 @@ def nearest_points(queries, targets, radius, *, max_cell_points=4096):
     _check_radius(radius)
     if not _is_int(max_cell_points) or not 1 <= max_cell_points <= 2 ** 31 - 1:
         raise ValueError('max_cell_points must be an integer >= 1, got %r' % (max_cell_points,))
-    for name, t in (('queries', queries), ('targets', targets)):
-        if not t.is_cuda:
-            raise RuntimeError('nearest_points got %s %s: it runs on the GPU only (no CPU fallback)' % (t.device, name))
+    _gpu_only('nearest_points', queries=queries, targets=targets)
     if Nq == 0 or targets.shape[0] == 0:                                      # nothing to search: no build, no launch
         dev = queries.device
         return torch.full((Nq,), math.inf, dtype=torch.float32, device=dev), torch.full((Nq,), -1, dtype=torch.int32, device=dev)
@@ -265,8 +292,7 @@ def similarity_from_cameras(pred_cams2world, gt_cams2world):
 
 def _moved(points, T, what):
     """fp32 points on the device, carried by the [4, 4] matrix T (or as they are)"""
-    if not points.is_cuda:
-        raise RuntimeError('score_reconstruction got %s %s: it runs on the GPU only (no CPU fallback)' % (points.device, what))
+    _gpu_only('score_reconstruction', **{what: points})
     points = points.float()
     if T is not None:
         A = torch.from_numpy(T).to(device=points.device, dtype=torch.float32)
@@ -360,9 +386,7 @@ def icp(source, target, *, max_dist, init=None, with_scale=True, iters=50, min_d
     _check_points(source, 'source')
     _check_points(target, 'target')
     max_dist, T, min_dist, shrink, tol = _check_icp(max_dist, init, with_scale, iters, min_dist, shrink, tol, every, max_cell_points)
-    for name, t in (('source', source), ('target', target)):
-        if not t.is_cuda:
-            raise RuntimeError('icp got a %s %s: it runs on the GPU only (no CPU fallback)' % (t.device, name))
+    _gpu_only('icp', 'a %(device)s %(name)s', source=source, target=target)
     src = source.float()[::every].contiguous()
     if src.shape[0] < 3 or target.shape[0] < 3:
         raise ValueError('icp needs at least 3 source points and 3 targets, got %d (every=%d) and %d' % (src.shape[0], every, target.shape[0]))

@@ -1644,12 +1644,17 @@ def mesh_sample_emit(vertices, faces, prefix, total, vertex_ids, face_ids, point
           _ptr(face), _ptr(ids), _ptr(status))
 
 
-def nn_workspace(M, device):
-    """the initialised workspaces of one search structure over M targets (include/panst3r_hip.h): dict of device tensors"""
-    cap = voxel_capacity(M)
+def _lists_workspace(n, device, slot_name):
+    """the initialised cell table and per-cell lists of n entries (csrc/voxel_table.h): dict of device tensors; `start` is made by the caller"""
+    cap = voxel_capacity(n)
     i32 = dict(dtype=torch.int32, device=device)
     return {'cap': cap, 'keys': torch.full((cap,), -1, dtype=torch.int64, device=device), 'cell_count': torch.zeros(cap, **i32), 'start': None,
-            'fill': torch.zeros(cap, **i32), 'point_slot': torch.empty(M, **i32), 'rows': torch.empty(M, **i32), 'status': torch.zeros(4, **i32)}
+            'fill': torch.zeros(cap, **i32), slot_name: torch.empty(n, **i32), 'rows': torch.empty(n, **i32)}
+
+
+def nn_workspace(M, device):
+    """the initialised workspaces of one search structure over M targets (include/panst3r_hip.h): dict of device tensors"""
+    return dict(_lists_workspace(M, device, 'point_slot'), status=torch.zeros(4, dtype=torch.int32, device=device))
 
 
 def _nn_points(points):
@@ -1730,10 +1735,7 @@ def meshdist_count(vertices, faces, inv, counts, total, status):
 
 def meshdist_workspace(P, device):
     """the initialised workspaces of one index of P (face, cell) pairs (include/panst3r_hip.h): dict of device tensors"""
-    cap = voxel_capacity(P)
-    i32 = dict(dtype=torch.int32, device=device)
-    return {'P': int(P), 'cap': cap, 'keys': torch.full((cap,), -1, dtype=torch.int64, device=device), 'cell_count': torch.zeros(cap, **i32), 'start': None,
-            'fill': torch.zeros(cap, **i32), 'pair_slot': torch.empty(P, **i32), 'rows': torch.empty(P, **i32)}
+    return dict(_lists_workspace(P, device, 'pair_slot'), P=int(P))
 
 
 def meshdist_insert(vertices, faces, inv, prefix, ws, status):

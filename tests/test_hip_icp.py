@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import grid_lists as G
 import icp_ref as I
 import mesh_ref as M
 import nearest_ref as N
@@ -190,6 +191,35 @@ def test_every_refusal_of_the_launcher_leaves_the_outputs_untouched():
         hip.icp_step(x, A, index.targets, index.inv, index.r2, float(R2), ws, 4096, iws, d2, None)
     with pytest.raises(ValueError, match='3 x 4'):
         hip.icp_step(x, np.eye(4), index.targets, index.inv, index.r2, float(R2), ws, 4096, iws)
+
+
+def test_the_step_refuses_a_list_that_leaves_the_rows_and_a_row_past_the_targets():
+    """the search of the step is the query's: the same tampered lists (tests/grid_lists.py), refused through the STEP's status words"""
+    touched, untouched = G.check_lattice()
+    X, T = G.lattice()
+    x, t = G.padded(X), G.padded(T)
+    _, inv, r2 = (float(v) for v in N.radius_numbers(G.CELL))
+    still = np.eye(3, 4, dtype=F)                                                # moves nothing: x 1 + y 0 + z 0 + 0 is x
+    good = G.nn_build(t)
+
+    def step(ws):
+        iws = hip.icp_workspace(len(X), DEV)
+        d2, row = torch.full((len(X),), -7.0, device=DEV), torch.full((len(X),), -7, dtype=torch.int32, device=DEV)
+        hip.icp_step(x, still, t, inv, r2, r2, ws, 4096, iws, d2, row)
+        assert ws['status'].tolist() == [0, 0, 0, 0]                             # the index's own status words are not the step's
+        return iws, d2, row
+    want = I.step(X, still, T, G.CELL, F(r2))
+    assert (want['moved'] == X).all() and want['out'][0] == len(X)
+    iws, d2, row = step(G.fresh(good))                                           # (d) the untampered workspace through the same helpers
+    assert iws['status'].tolist() == [0, 0, 0, 0] and same(iws['out'], want['out']) and same(d2, want['d2']) and same(row, want['row'])
+    slot, M = int(good['point_slot'][0]), len(T)
+    for tamper in (lambda ws: G.move_list_out(ws, slot, M), lambda ws: G.first_entry_past_the_end(ws, slot, M)):      # (a), (b)
+        ws = G.fresh(good)
+        tamper(ws)
+        bad, bd2, brow = step(ws)
+        assert bad['status'].tolist() == [G.LISTS, 0, 0, 0]
+        assert (bits(bd2)[untouched] == bits(d2)[untouched]).all() and (bits(brow)[untouched] == bits(row)[untouched]).all()
+        assert bool(((brow >= -1) & (brow < M)).all()) and (bits(brow)[touched] != bits(row)[touched]).any()      # a target was lost, none past the end was taken
 
 
 # ---------------------------------------------------------------- the loop

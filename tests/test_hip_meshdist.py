@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import grid_lists as G
 import mesh_ref as M
 import meshdist_ref as MD
 import nearest_ref as N
@@ -362,6 +363,61 @@ def test_a_mesh_of_dropped_faces_alone_builds_nothing():
     index = MeshIndex(V, dev(np.array([[0, 1, 2], [0, 1, 7]])), RADIUS)
     d2, face, closest = index.query(V)
     assert index.dropped_faces == 2 and index.pairs == 0 and index.ws is None and (face == -1).all() and torch.isinf(d2).all() and index.check() == 0
+
+
+# ---------------------------------------------------------------- lists that are not the build's (the guards of csrc/voxel_table.h)
+@functools.lru_cache(maxsize=None)
+def two_faces():
+    """two triangles under the lattice of queries of tests/grid_lists.py whose cell boxes both hold the cell (0, 0, 0), that of query 0"""
+    V = np.array([[0.05, 0.05, 0.1], [0.45, 0.05, 0.1], [0.05, 0.45, 0.1], [0.3, 0.3, 0.3], [0.7, 0.3, 0.3], [0.3, 0.7, 0.3]], dtype=F)
+    return V, np.array([[0, 1, 2], [3, 4, 5]], dtype=np.int32)
+
+
+def check_two_faces():
+    """-> (the pair of face 0 in the cell of query 0, the queries of that cell, the others, the restated result)"""
+    Q, _ = G.lattice()
+    V, Fc = two_faces()
+    b, cq = MD.binning(V, Fc, G.CELL), N.cells(Q, G.CELL)[0].astype(int)
+    lo, ext = b['lo'].astype(int), b['ext'].astype(int)
+    assert b['kept'].all() and (cq[0] == 0).all() and ((lo <= 0) & (lo + ext > 0)).all()        # both faces are listed in the cell (0, 0, 0)
+    touched = (cq == 0).all(1)
+    want = MD.mesh_distance(Q, V, Fc, G.CELL)
+    assert touched.sum() >= 4 and (want['face'][touched] >= 0).all() and (want['face'][~touched] >= 0).sum() > 50 and (want['face'][~touched] < 0).sum() > 50
+    assert (np.nonzero(~touched)[0] >= 256).any()
+    return int(-lo[0, 0] + ext[0, 0] * (-lo[0, 1] + ext[0, 1] * -lo[0, 2])), touched, ~touched, want
+
+
+def test_the_query_refuses_a_list_that_leaves_the_rows_and_a_face_past_the_mesh():
+    pair, touched, untouched, want = check_two_faces()
+    v, f, q = G.padded(two_faces()[0]), G.padded(two_faces()[1]), G.padded(G.lattice()[0])
+    _, inv, r2 = (float(x) for x in N.radius_numbers(G.CELL))
+    good = G.mesh_build(v, f)
+    assert good['status'].tolist() == [0, 0, 2, 0] and good['P'] == MD.binning(*two_faces(), G.CELL)['total']
+
+    def query(ws):
+        out = torch.full((len(q),), -7.0, device=DEV), torch.full((len(q),), -7, dtype=torch.int32, device=DEV), torch.full((len(q), 3), -7.0, device=DEV)
+        hip.meshdist_query(q, v, f, inv, r2, ws, 4096, *out, ws['status'])
+        return out, ws['status'].tolist()
+    got, status = query(G.fresh(good))                                           # (d) the untampered workspace through the same helpers
+    assert status == [0, 0, 0, 0]
+    assert_result(got, want)
+    slot = int(good['pair_slot'][pair])
+    assert sorted(G.lists_of(good)[slot]) == [0, 1]
+    for case, tamper in (('a', lambda ws: G.move_list_out(ws, slot, good['P'])), ('b', lambda ws: G.first_entry_past_the_end(ws, slot, len(f)))):
+        ws = G.fresh(good)
+        tamper(ws)
+        bad, status = query(ws)
+        assert status == [G.LISTS, 0, 0, 0]
+        assert all((bits(a)[untouched] == bits(b)[untouched]).all() for a, b in zip(bad, got))
+        assert bool(((bad[1] >= -1) & (bad[1] < len(f))).all())                  # a face of the mesh or none
+        assert case == 'b' or bool((bad[1][torch.from_numpy(touched).to(DEV)] == -1).all())      # (a): the refused list is not read at all
+
+
+def test_the_scatter_refuses_a_count_that_is_not_the_inserts():
+    pair = check_two_faces()[0]
+    v, f = G.padded(two_faces()[0]), G.padded(two_faces()[1])
+    good = G.mesh_build(v, f)
+    G.assert_a_short_count_is_refused(good, lambda tamper: G.mesh_build(v, f, tamper), lambda ws: int(ws['pair_slot'][pair]), good['P'])
 
 
 # ---------------------------------------------------------------- the composition

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import grid_lists as G
 import mesh_ref as M
 import nearest_ref as N
 from panst3r_amd import hip
@@ -325,6 +326,40 @@ def test_a_full_cell_runs_and_a_fuller_one_is_refused_before_the_query(monkeypat
     monkeypatch.setattr(hip, 'nn_query', lambda *a, **k: pytest.fail('the query was launched'))
     with pytest.raises(ValueError, match='too large for this density'):
         nearest_points(dev(Q), dev(T), RADIUS, max_cell_points=K - 1)
+
+
+# ---------------------------------------------------------------- lists that are not the build's (the guards of csrc/voxel_table.h)
+def lattice_query(q, t, ws):
+    d2, row = torch.full((len(q),), -7.0, device=DEV), torch.full((len(q),), -7, dtype=torch.int32, device=DEV)
+    hip.nn_query(q, t, float(N.radius_numbers(G.CELL)[1]), float(N.radius_numbers(G.CELL)[2]), ws, 4096, d2, row)
+    return d2, row, ws['status'].tolist()
+
+
+def test_the_query_refuses_a_list_that_leaves_the_rows_and_a_row_past_the_targets():
+    touched, untouched = G.check_lattice()
+    Q, T = G.lattice()
+    q, t = G.padded(Q), G.padded(T)
+    good = G.nn_build(t)
+    assert good['status'].tolist() == [0, 0, 8, 0]
+    want = N.nearest(Q, T, G.CELL)
+    d2, row, status = lattice_query(q, t, G.fresh(good))                         # (d) the untampered workspace through the same helpers
+    assert status == [0, 0, 0, 0] and (row.cpu().numpy() == want['row']).all() and (bits(d2) == bits(want['d2'])).all()
+    slot, M = int(good['point_slot'][0]), len(T)
+    for tamper in (lambda ws: G.move_list_out(ws, slot, M), lambda ws: G.first_entry_past_the_end(ws, slot, M)):      # (a), (b)
+        ws = G.fresh(good)
+        tamper(ws)
+        bd2, brow, status = lattice_query(q, t, ws)
+        assert status == [G.LISTS, 0, 0, 0]
+        assert (bits(bd2)[untouched] == bits(d2)[untouched]).all() and (bits(brow)[untouched] == bits(row)[untouched]).all()
+        assert bool(((brow >= -1) & (brow < M)).all()) and (bits(brow)[touched] != bits(row)[touched]).any()      # a target was lost, none past the end was taken
+    assert (good['status'] == torch.tensor([0, 0, 8, 0], device=DEV)).all() and (bits(lattice_query(q, t, G.fresh(good))[0]) == bits(d2)).all()
+
+
+def test_the_scatter_refuses_a_count_that_is_not_the_inserts():
+    G.check_lattice()
+    t = G.padded(G.lattice()[1])
+    good = G.nn_build(t)
+    G.assert_a_short_count_is_refused(good, lambda tamper: G.nn_build(t, tamper), lambda ws: int(ws['point_slot'][0]), len(t))
 
 
 # ---------------------------------------------------------------- the composition
