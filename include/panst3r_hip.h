@@ -835,6 +835,56 @@ int pst_meshdist_query(const float* queries, int64_t Nq, const float* vertices, 
                        const uint64_t* keys, int64_t capacity, const int32_t* start, const int32_t* cell_count, const int32_t* rows, int64_t total,
                        int max_cell_faces, float* d2, int32_t* face, float* closest, int32_t* status, void* stream);
 
+/* ---------------------------------------------------------------- icp-plane: one fused point-to-plane step against the triangles (no counterpart in the reference)
+ * The hot path of engine/meshdist.py's `icp_to_mesh` / `refine_alignment(target='surface')`: the source points are moved by the current transform, each
+ * finds its nearest face in the search structure of the meshdist section, and the normal equations of the LINEARISED POINT-TO-PLANE objective - the
+ * squared distance of the moved point to the plane of its face, under a small similarity about a centre c0 - are summed, in one pass over the sources.
+ * `pointmaps.plane_step_from_moments` solves them on the host.  Restated in tests/icp_plane_ref.py [restated, parity unpinned] on the brute-force
+ * search of tests/meshdist_ref.py and the fixed-order sum of tests/icp_ref.py; every step is separately rounded in a fixed order, so the 40 moments,
+ * the partials, d2, face and the status are held to the restatement bit for bit.  Contraction is off: every fp32 and fp64 operation is rounded on its
+ * own, in the order written.  Additive to ABI 20.
+ *   source fp32 [N, 3]; A = (a00 .. a23) the 3 x 4 fp32 matrix, by value, row-major; c0 = (c0x, c0y, c0z) fp32, by value, finite: the centre the
+ *   increment turns and scales about, in the frame of the MOVED points; vertices, faces, inv, keys, capacity, start, cell_count, rows, total and
+ *   max_cell_faces are those of a finished build of the meshdist section (count, scan, insert, the prefix sum, scatter) with cell edge 1 / inv;
+ *   0 <= r2 finite.
+ *   1 move      step 1 of the icp section: m_r = ((a_r0 x0 + a_r1 x1) + a_r2 x2) + a_r3 in fp32.
+ *   2 search    step 6 of the meshdist section with m as the query (the same device function as meshdist_query): the list of m's own cell, every
+ *               face's fp64 D2 cast to fp32 once, the minimum of (uint64(bits(d2)) << 32) | face, ties to the smaller face; accepted iff d2 <= r2.
+ *               The lists hold every face within one cell edge, so r2 MUST NOT exceed the square of the cell edge (the CALLER's duty, as in
+ *               icp_step; a smaller r2 is how the radius shrinks without a rebuild).  A non-finite m is unmatched and counted in status[3]; a
+ *               finite m whose cell is out of range is unmatched.  A listed face that is out of range or was not kept sets PST_MESHDIST_LISTS.  With
+ *               d2 fp32 [N] and face int32 [N] given (both or neither) they are written as meshdist_query writes them: face -1 and d2 = +inf
+ *               for an unmatched source.
+ *   3 terms     of a matched source, all fp64, a, b, c (the corners of its face), m and c0 widened once; every operation rounded once, in this
+ *               order; dot(u, v) = (u0 v0 + u1 v1) + u2 v2 as in the meshdist section:
+ *                 e1 = b - a, e2 = c - a
+ *                 N = (e1_1 e2_2 - e1_2 e2_1, e1_2 e2_0 - e1_0 e2_2, e1_0 e2_1 - e1_1 e2_0)     the face's UNNORMALISED normal (the kept-face test's)
+ *                 w = 1 / ((N0 N0 + N1 N1) + N2 N2)                                             a kept face has N != 0; no square root anywhere
+ *                 p = m - c0, u = m - a
+ *                 rN = dot(N, u)               |N| times the signed distance to the face's PLANE: the in-plane offset of an edge or corner hit is
+ *                                              ignored, which is the point of the objective
+ *                 J = (p1 N2 - p2 N1, p2 N0 - p0 N2, p0 N1 - p1 N0, N0, N1, N2, dot(N, p))      = (p x N, N, N . p): the derivative of rN under
+ *                                              m -> c0 + (1 + sigma) R(omega) (m - c0) + tau at (omega, tau, sigma) = 0
+ *                 g_i = w J_i
+ *               moments, an unmatched source adds nothing:
+ *                 [0] the number matched       [1..28] sum of g_i J_j for i <= j, row-major (i = 0: j = 0 .. 6, then i = 1: j = 1 .. 6, ...)
+ *                 [29..35] sum of g_i rN       [36] sum of (w rN) rN, the squared distance to the plane
+ *                 [37] sum of fp64(d2), the squared distance to the triangle                    [38], [39] +0.0, reserved
+ *               Unlike the icp section's, these products round: each is one multiplication of the two factors named, then one addition into the sum.
+ *   4 order     step 4 of the icp section, verbatim, with PST_ICP_CHUNK and PST_ICP_LANES (csrc/icp_sum.h is the one text of both): partials double
+ *               [ceil(N / PST_ICP_CHUNK), PST_ICP_PLANE_MOMENTS], out double [PST_ICP_PLANE_MOMENTS].  One kernel and the one-block reducer.  No
+ *               float atomics: two calls return identical bytes, and d2 / face given or not does not change the moments.
+ *   status int32 [4], cleared by the CALLER, as the meshdist query's: [0] = PST_MESHDIST_FULL | PST_MESHDIST_LISTS, [3] non-finite moved points; [1],
+ *   [2] untouched.
+ *   Refused with PST_EINVAL before any launch, every output untouched: a null source / mesh / table / partials / out / status, exactly one of d2 and
+ *   face, N < 1 or N > 2^30, a mesh, a table or limits that pst_meshdist_query would refuse, inv, r2 or c0 not finite.
+ *   (The entry point is pst_plane_icp_step: the names pst_icp_* and pst_meshdist_* are closed sets.) */
+#define PST_ICP_PLANE_MOMENTS 40  /* doubles per row of partials and in out */
+int pst_plane_icp_step(const float* source, int64_t N, float a00, float a01, float a02, float a03, float a10, float a11, float a12, float a13, float a20,
+                       float a21, float a22, float a23, float c0x, float c0y, float c0z, const float* vertices, int64_t Nv, const int32_t* faces, int64_t F,
+                       float inv, float r2, const uint64_t* keys, int64_t capacity, const int32_t* start, const int32_t* cell_count, const int32_t* rows,
+                       int64_t total, int max_cell_faces, float* d2, int32_t* face, double* partials, double* out, int32_t* status, void* stream);
+
 /* ---------------------------------------------------------------- panoptic evaluation against ground truth: PQ / SQ / RQ, mIoU (no counterpart in the reference)
  * V predicted maps and V ground-truth maps of the same shapes, flattened and concatenated to pred, gt int32 [N] (1 <= N <= 2^31 - 1, both 16-byte
  * aligned), P predicted and G ground-truth segments (ids unique and > 0 within each list, no crowd regions).  The rules are those of COCO

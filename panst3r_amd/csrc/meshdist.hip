@@ -9,15 +9,20 @@
 //   scatter  the pair's face into its cell's list (the position inside the list depends on arrival; nothing that leaves depends on it)
 //   query    one lane per query: the list of the query's OWN cell, every candidate's closest point in fp64 (Ericson's region sequence), the minimum of
 //            (bits(float32 d2) << 32) | face, the winner's closest point once more for the output
+//   plane    one fused point-to-plane ICP step (the icp-plane section of the header, restated in tests/icp_plane_ref.py): a block per PST_ICP_CHUNK
+//            source rows, 16 rows per lane: the row moved by the 3 x 4 matrix in fp32, the query's list walk (the same __device__ function), then the
+//            winner's plane terms once - the unnormalised normal, its weight 1 / |N|^2, the seven derivatives - and the 38 live moments of the
+//            normal equations in fp64 registers; the fixed order of the sums and the reducer are icp_sum.h, shared with icp_step of csrc/nearest.hip
 // Which faces are kept and the search in the prefix are mesh_face.h, shared with the surface sampler of csrc/nearest.hip; the cell of a query, the
 // key, the table's probes and the per-cell lists are voxel_table.h, shared by every hash-grid stage.
 // Integer atomics only, every probe / candidate / search loop bounded by a number known before the launch, refusals through the status words, every
-// result written with plain vector stores: two calls return identical bytes.  Contraction is off for the whole file: every fp32 and fp64 operation is
+// result written with plain vector stores, no float atomics: two calls return identical bytes.  Contraction is off for the whole file: every fp32 and fp64 operation is
 // rounded on its own, in the order written.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
 #include "voxel_table.h"
 #include "mesh_face.h"
+#include "icp_sum.h"
 
 #pragma clang fp contract(off)
 
@@ -159,6 +164,31 @@ __device__ __forceinline__ double md_face_distance(const MeshFace& t, const doub
   return md_closest(a, b, c, q, cp);
 }
 
+// step 6 of the contract for one lane, shared by meshdist_query and icp_plane_step: every face of the list of the cell c of the point q (ok = q is
+// finite and c in range) -> the minimum of (bits(fp32 D2) << 32) | face, all ones without a candidate.  Nothing here is collective: lanes may
+// call it divergently.
+__device__ __forceinline__ uint64_t md_search(const double (&q)[3], const float (&c)[3], bool ok, const float* __restrict__ vertices, int Nv,
+                                              const int32_t* __restrict__ faces, int F, const uint64_t* __restrict__ keys, uint32_t mask,
+                                              const int32_t* __restrict__ start, const int32_t* __restrict__ cell_count, const int32_t* __restrict__ rows,
+                                              int P, int max_cell_faces, int32_t* __restrict__ status) {
+  uint64_t best = ~0ull;
+  if (!ok) return best;                                              // a query outside the range has no cell of a kept face
+  const int slot = vx_find(keys, mask, vx_key((int)c[0], (int)c[1], (int)c[2]), status);
+  int b, cnt;
+  if (slot >= 0 && vx_list_range(slot, start, cell_count, P, max_cell_faces, status, b, cnt))
+    for (int j = 0; j < cnt; ++j) {
+      const int f = rows[b + j];
+      if ((unsigned)f >= (unsigned)F) { atomicOr(&status[0], PST_MESHDIST_LISTS); continue; }
+      const MeshFace t = mf_load(vertices, Nv, faces, f);
+      if (!t.ok) { atomicOr(&status[0], PST_MESHDIST_LISTS); continue; }       // a listed face was kept by the build
+      double cp[3];
+      const float d2 = (float)md_face_distance(t, q, cp);         // >= +0, never NaN: its bits order as an unsigned integer
+      const uint64_t cand = ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)f;
+      best = cand < best ? cand : best;
+    }
+  return best;
+}
+
 __global__ __launch_bounds__(MD_T) void meshdist_query_kernel(const float* __restrict__ queries, int Nq, const float* __restrict__ vertices, int Nv,
                                                               const int32_t* __restrict__ faces, int F, float inv, float r2,
                                                               const uint64_t* __restrict__ keys, uint32_t mask, const int32_t* __restrict__ start,
@@ -178,22 +208,7 @@ __global__ __launch_bounds__(MD_T) void meshdist_query_kernel(const float* __res
   if (bad && lane == (int)__builtin_ctzll(bad)) atomicAdd(&status[3], (int)__popcll(bad));
   if (!in) return;
   const double q[3] = {(double)x[0], (double)x[1], (double)x[2]};
-  uint64_t best = ~0ull;
-  if (ok) {                                                          // a query outside the range has no cell of a kept face
-    const int slot = vx_find(keys, mask, vx_key((int)c[0], (int)c[1], (int)c[2]), status);
-    int b, cnt;
-    if (slot >= 0 && vx_list_range(slot, start, cell_count, P, max_cell_faces, status, b, cnt))
-      for (int j = 0; j < cnt; ++j) {
-        const int f = rows[b + j];
-        if ((unsigned)f >= (unsigned)F) { atomicOr(&status[0], PST_MESHDIST_LISTS); continue; }
-        const MeshFace t = mf_load(vertices, Nv, faces, f);
-        if (!t.ok) { atomicOr(&status[0], PST_MESHDIST_LISTS); continue; }       // a listed face was kept by the build
-        double cp[3];
-        const float d2 = (float)md_face_distance(t, q, cp);       // >= +0, never NaN: its bits order as an unsigned integer
-        const uint64_t cand = ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)f;
-        best = cand < best ? cand : best;
-      }
-  }
+  const uint64_t best = md_search(q, c, ok, vertices, Nv, faces, F, keys, mask, start, cell_count, rows, P, max_cell_faces, status);
   const float d2 = __uint_as_float((uint32_t)(best >> 32));
   const bool hit = best != ~0ull && d2 <= r2;
   d2_out[i] = hit ? d2 : __uint_as_float(0x7f800000u);
@@ -209,6 +224,82 @@ __global__ __launch_bounds__(MD_T) void meshdist_query_kernel(const float* __res
 #pragma unroll
     for (int a = 0; a < 3; ++a) closest[(int64_t)i * 3 + a] = out[a];
   }
+}
+
+// ---------------------------------------------------------------- one fused point-to-plane ICP step (the icp-plane section of include/panst3r_hip.h)
+constexpr int PL_LIVE = 38;                                          // the moments that are sums; [38], [39] are +0.0
+static_assert(MD_T == ICP_T && PL_LIVE + 2 == PST_ICP_PLANE_MOMENTS, "the fixed order of the header (icp_sum.h)");
+
+struct PlaneCentre { float c[3]; };
+
+// step 3 of the section: the terms of one matched source into the lane's accumulators.  a, b, c the winner's corners, m the moved point, c0 the
+// centre, all widened once; every product and sum below is rounded on its own, in the order written.
+__device__ __forceinline__ void pl_accumulate(const MeshFace& t, const float (&mf)[3], const PlaneCentre& C, float d2, double (&acc)[PL_LIVE]) {
+  double e1[3], e2[3], p[3], u[3], J[7];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double a = (double)t.v[0][k], m = (double)mf[k];
+    e1[k] = (double)t.v[1][k] - a;
+    e2[k] = (double)t.v[2][k] - a;
+    p[k] = m - (double)C.c[k];
+    u[k] = m - a;
+  }
+  const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};      // as mf_has_area writes them
+  const double w = 1.0 / ((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);                                                      // a kept face: n != 0
+  const double rN = md_dot(n, u);
+  J[0] = p[1] * n[2] - p[2] * n[1];
+  J[1] = p[2] * n[0] - p[0] * n[2];
+  J[2] = p[0] * n[1] - p[1] * n[0];
+  J[3] = n[0]; J[4] = n[1]; J[5] = n[2];
+  J[6] = md_dot(n, p);
+  acc[0] += 1.0;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const double g = w * J[i];
+#pragma unroll
+    for (int j = i; j < 7; ++j) acc[1 + 7 * i - i * (i - 1) / 2 + (j - i)] += g * J[j];      // the upper triangle, row-major: [1, 29)
+    acc[29 + i] += g * rN;
+  }
+  acc[36] += (w * rN) * rN;
+  acc[37] += (double)d2;
+}
+
+__global__ __launch_bounds__(MD_T) void icp_plane_step_kernel(const float* __restrict__ source, int N, IcpMatrix A, PlaneCentre C,
+                                                              const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int F,
+                                                              float inv, float r2, const uint64_t* __restrict__ keys, uint32_t mask,
+                                                              const int32_t* __restrict__ start, const int32_t* __restrict__ cell_count,
+                                                              const int32_t* __restrict__ rows, int P, int max_cell_faces, float* __restrict__ d2_out,
+                                                              int32_t* __restrict__ face_out, double* __restrict__ partials, int32_t* __restrict__ status) {
+  const int first = blockIdx.x * PST_ICP_CHUNK + threadIdx.x;        // N <= 2^30: no row leaves int32
+  double acc[PL_LIVE];
+#pragma unroll
+  for (int s = 0; s < PL_LIVE; ++s) acc[s] = 0.0;
+  int bad = 0;
+  for (int j = 0; j < ICP_ROWS; ++j) {                               // (per lane: nothing collective inside)
+    const int i = first + MD_T * j;
+    if (i >= N) break;
+    float x[3], m[3], c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) x[a] = source[(int64_t)i * 3 + a];
+    icp_move(A, x, m);
+    bool finite, ok;
+    vx_cell_of(m, inv, c, finite, ok);
+    bad += !finite;
+    const double q[3] = {(double)m[0], (double)m[1], (double)m[2]};
+    const uint64_t best = md_search(q, c, ok, vertices, Nv, faces, F, keys, mask, start, cell_count, rows, P, max_cell_faces, status);
+    const float d2 = __uint_as_float((uint32_t)(best >> 32));
+    const bool hit = best != ~0ull && d2 <= r2;
+    if (d2_out) {
+      d2_out[i] = hit ? d2 : __uint_as_float(0x7f800000u);
+      face_out[i] = hit ? (int)(uint32_t)best : -1;
+    }
+    if (!hit) continue;
+    pl_accumulate(mf_load(vertices, Nv, faces, (int)(uint32_t)best), m, C, d2, acc);      // (the walk took the face from rows and checked it)
+  }
+#pragma unroll
+  for (int k = 32; k > 0; k >>= 1) bad += __shfl_xor(bad, k);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&status[3], bad);
+  icp_block_sum<PL_LIVE, PST_ICP_PLANE_MOMENTS>(acc, partials + (int64_t)blockIdx.x * PST_ICP_PLANE_MOMENTS);
 }
 
 static int md_mesh_ok(const char* what, const void* vertices, const void* faces, int64_t Nv, int64_t F, float inv) {
@@ -266,4 +357,27 @@ extern "C" int pst_meshdist_query(const float* queries, int64_t Nq, const float*
   hipLaunchKernelGGL(meshdist_query_kernel, md_grid(Nq), dim3(MD_T), 0, (hipStream_t)stream, queries, (int)Nq, vertices, (int)Nv, faces, (int)F, inv, r2, keys,
                      (uint32_t)(capacity - 1), start, cell_count, rows, (int)total, max_cell_faces, d2, face, closest, status);
   return check_launch("meshdist_query");
+}
+
+extern "C" int pst_plane_icp_step(const float* source, int64_t N, float a00, float a01, float a02, float a03, float a10, float a11, float a12, float a13,
+                                  float a20, float a21, float a22, float a23, float c0x, float c0y, float c0z, const float* vertices, int64_t Nv,
+                                  const int32_t* faces, int64_t F, float inv, float r2, const uint64_t* keys, int64_t capacity, const int32_t* start,
+                                  const int32_t* cell_count, const int32_t* rows, int64_t total, int max_cell_faces, float* d2, int32_t* face,
+                                  double* partials, double* out, int32_t* status, void* stream) {
+  using namespace pst;
+  if (md_mesh_ok("plane_icp_step", vertices, faces, Nv, F, inv) || vx_table_ok("plane_icp_step", total, MD_MAX, capacity, "total", "1 .. 2^30 pairs")) return PST_EINVAL;
+  if (!source || !keys || !start || !cell_count || !rows || !partials || !out || !status || (d2 == nullptr) != (face == nullptr) || N < 1 || N > MD_MAX ||
+      !(r2 >= 0.f) || !(r2 <= PST_FMAX) || !(fabsf(c0x) <= PST_FMAX) || !(fabsf(c0y) <= PST_FMAX) || !(fabsf(c0z) <= PST_FMAX) || max_cell_faces < 1) {
+    set_error("plane_icp_step: bad shape (N=%lld: 1 .. 2^30 source points), squared radius %g (finite), centre (%g, %g, %g) (finite), max_cell_faces %d "
+              "(>= 1), one of d2 / face without the other, or null operand", (long long)N, (double)r2, (double)c0x, (double)c0y, (double)c0z, max_cell_faces);
+    return PST_EINVAL;
+  }
+  const IcpMatrix A = {{{a00, a01, a02, a03}, {a10, a11, a12, a13}, {a20, a21, a22, a23}}};
+  const PlaneCentre C = {{c0x, c0y, c0z}};
+  const int P = (int)((N + PST_ICP_CHUNK - 1) / PST_ICP_CHUNK);
+  hipLaunchKernelGGL(icp_plane_step_kernel, dim3((unsigned)P), dim3(MD_T), 0, (hipStream_t)stream, source, (int)N, A, C, vertices, (int)Nv, faces, (int)F, inv,
+                     r2, keys, (uint32_t)(capacity - 1), start, cell_count, rows, (int)total, max_cell_faces, d2, face, partials, status);
+  if (int rc = check_launch("plane_icp_step")) return rc;
+  hipLaunchKernelGGL((icp_reduce_kernel<PL_LIVE, PST_ICP_PLANE_MOMENTS>), dim3(1), dim3(MD_T), 0, (hipStream_t)stream, (const double*)partials, P, out);
+  return check_launch("plane_icp_step (reduce)");
 }

@@ -14,6 +14,7 @@
 //                         __device__ function), the 18 live moments of the matched pairs in fp64 registers; a butterfly per wave, the four waves added
 //                         in order, one row of 20 per block
 //                  reduce one block adds the rows of the blocks the same way
+//                  (the move and the fixed order of the sums: icp_sum.h, shared with the point-to-plane step of csrc/meshdist.hip)
 // Integer atomics only, no float sum whose order depends on arrival (the moments are added in the order the header fixes), every probe / candidate / search loop bounded by a number known before the launch,
 // refusals through the status words, every result written with plain vector stores: two calls return identical bytes.  Contraction is off for the
 // whole file: every fp32 and fp64 operation is rounded on its own, in the order written.
@@ -21,6 +22,7 @@
 #include "../../include/panst3r_hip.h"
 #include "voxel_table.h"
 #include "mesh_face.h"
+#include "icp_sum.h"
 
 #pragma clang fp contract(off)
 
@@ -207,28 +209,8 @@ __global__ __launch_bounds__(NN_T) void nn_query_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------- one fused ICP step (the icp section of include/panst3r_hip.h)
-constexpr int ICP_ROWS = PST_ICP_CHUNK / NN_T;                       // source rows per lane
 constexpr int ICP_LIVE = 18;                                         // the moments that are sums; [18], [19] are +0.0
-static_assert(NN_T == PST_ICP_LANES && PST_ICP_CHUNK % NN_T == 0 && ICP_LIVE + 2 == PST_ICP_MOMENTS, "the fixed order of the header");
-
-struct IcpMatrix { float a[3][4]; };
-
-// steps 3 to 5 of the fixed order: six butterfly steps inside every wave, then ((w0 + w1) + w2) + w3 -> row[0, 20)
-__device__ __forceinline__ void icp_block_sum(const double (&acc)[ICP_LIVE], double* __restrict__ row) {
-  __shared__ double waves[NN_T / 64][ICP_LIVE];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < ICP_LIVE; ++s) {
-    double v = acc[s];
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) v += __shfl_xor(v, k);
-    if (lane == 0) waves[wave][s] = v;
-  }
-  __syncthreads();
-  const int s = threadIdx.x;
-  if (s < ICP_LIVE) row[s] = ((waves[0][s] + waves[1][s]) + waves[2][s]) + waves[3][s];
-  else if (s < PST_ICP_MOMENTS) row[s] = 0.0;
-}
+static_assert(NN_T == ICP_T && ICP_LIVE + 2 == PST_ICP_MOMENTS, "the fixed order of the header (icp_sum.h: the move, the block sum and the reducer)");
 
 __global__ __launch_bounds__(NN_T) void icp_step_kernel(const float* __restrict__ source, int N, IcpMatrix A, const float* __restrict__ targets, int M,
                                                         float inv, float r2, const uint64_t* __restrict__ keys, uint32_t mask,
@@ -246,9 +228,7 @@ __global__ __launch_bounds__(NN_T) void icp_step_kernel(const float* __restrict_
     float x[3], m[3], c[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) x[a] = source[(int64_t)i * 3 + a];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      m[r] = nn_addr(nn_addr(nn_addr(nn_mulr(A.a[r][0], x[0]), nn_mulr(A.a[r][1], x[1])), nn_mulr(A.a[r][2], x[2])), A.a[r][3]);
+    icp_move(A, x, m);
     bool finite, ok;
     vx_cell_of(m, inv, c, finite, ok);
     bad += !finite;
@@ -277,18 +257,7 @@ __global__ __launch_bounds__(NN_T) void icp_step_kernel(const float* __restrict_
 #pragma unroll
   for (int k = 32; k > 0; k >>= 1) bad += __shfl_xor(bad, k);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&status[3], bad);
-  icp_block_sum(acc, partials + (int64_t)blockIdx.x * PST_ICP_MOMENTS);
-}
-
-// step 6: one block; lane l adds the rows l, l + 256, ... of the partials in ascending order, then the same butterfly and the same wave order
-__global__ __launch_bounds__(NN_T) void icp_reduce_kernel(const double* __restrict__ partials, int P, double* __restrict__ out) {
-  double acc[ICP_LIVE];
-#pragma unroll
-  for (int s = 0; s < ICP_LIVE; ++s) acc[s] = 0.0;
-  for (int r = threadIdx.x; r < P; r += NN_T)
-#pragma unroll
-    for (int s = 0; s < ICP_LIVE; ++s) acc[s] += partials[(int64_t)r * PST_ICP_MOMENTS + s];
-  icp_block_sum(acc, out);
+  icp_block_sum<ICP_LIVE, PST_ICP_MOMENTS>(acc, partials + (int64_t)blockIdx.x * PST_ICP_MOMENTS);
 }
 
 constexpr int64_t NN_MAX_POINTS = 1ll << 30;
@@ -386,6 +355,6 @@ extern "C" int pst_icp_step(const float* source, int64_t N, float a00, float a01
   hipLaunchKernelGGL(icp_step_kernel, dim3((unsigned)P), dim3(NN_T), 0, (hipStream_t)stream, source, (int)N, A, targets, (int)M, inv, r2, keys,
                      (uint32_t)(capacity - 1), start, cell_count, rows, max_cell_points, d2, row, partials, status);
   if (int rc = check_launch("icp_step")) return rc;
-  hipLaunchKernelGGL(icp_reduce_kernel, dim3(1), dim3(NN_T), 0, (hipStream_t)stream, (const double*)partials, P, out);
+  hipLaunchKernelGGL((icp_reduce_kernel<ICP_LIVE, PST_ICP_MOMENTS>), dim3(1), dim3(NN_T), 0, (hipStream_t)stream, (const double*)partials, P, out);
   return check_launch("icp_step (reduce)");
 }

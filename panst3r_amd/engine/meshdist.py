@@ -10,13 +10,23 @@ include/panst3r_hip.h, restated in tests/meshdist_ref.py and held bit for bit):
                              cell) pair, the voxel stages' hash table, integer atomics only.
   query                      the list of the query's own cell, every candidate's closest point in fp64 (Ericson's region sequence, a fixed order of
                              operations), the minimum of (distance bits, face): the nearest face within the radius, ties to the smaller face.
-The search is exact against the triangles; no BVH, no pruning of cells against a triangle's plane, no signed distance, no normals."""
+The search is exact against the triangles; no BVH, no pruning of cells against a triangle's plane, no signed distance.
+
+`icp_to_mesh` (stage f13) aligns points to the mesh by POINT-TO-PLANE ICP on the same lists: one more kernel, icp_plane_step (the icp-plane section
+of the header, restated in tests/icp_plane_ref.py and held bit for bit) - the sources moved by the current transform, the query's list walk, the
+winner's unnormalised face normal and the fp64 normal equations of the linearised plane distances in f11's fixed order - and the 7 x 7 host solve
+`pointmaps.plane_step_from_moments`.  The normals are the ground truth's faces'; the sources need none.
+
+    a = icp_to_mesh(points, gt_vertices, gt_faces, max_dist=0.3)       # or refine_alignment(..., target='surface')"""
 import math
 
+import numpy as np
 import torch
 
 from .. import hip
-from .score3d import _build_lists, _check_mesh, _check_points, _check_radius, _gpu_only, _int32_faces, _is_int, _search_status
+from .pointmaps import plane_step_from_moments
+from .score3d import (Alignment, _build_lists, _check_icp, _check_mesh, _check_points, _check_radius, _corner_shift, _gpu_only, _icp_radius, _int32_faces,
+                      _is_int, _search_status)
 
 
 def _check_limits(max_cell_faces, max_pairs):
@@ -107,3 +117,72 @@ def mesh_distance(points, vertices, faces, radius, *, max_cell_faces=4096, max_p
     out = index.query(points)
     index.check()
     return out
+
+
+@torch.no_grad()
+def icp_to_mesh(source, vertices, faces, *, max_dist, init=None, with_scale=True, iters=50, min_dist=None, shrink=0.8, tol=1e-4, every=1,
+                max_cell_faces=4096, max_pairs=2 ** 27):
+    """Point-to-plane ICP against the triangles: the similarity (`with_scale=False`: rigid) transform that carries `source` [N, 3] onto the surface of
+    the mesh (vertices [Nv, 3] float, faces [Nf, 3] int32 / int64, device tensors), started from `init` ([4, 4], default the identity) ->
+    `Alignment`.  One `MeshIndex` of cell edge `max_dist` is built once.  Step k moves the sources by float32(T), matches each to its nearest face
+    within r_k (the schedule of `icp`: float32(max(min_dist, max_dist shrink^k)), `min_dist=None`: max_dist throughout; the radius shrinks without a
+    rebuild), and sums the normal equations of the squared distances to the PLANES of the matched faces, linearised in a small rotation, shift and
+    scale about c0 - all of it ONE fused launch, `hip.icp_plane_step` - and after ONE host sync (the 40 doubles and the status)
+    `pointmaps.plane_step_from_moments` solves the 7 x 7 (rigid: 6 x 6) system for an INCREMENT, T <- increment @ T in float64: increments
+    compose here, where `icp` solves for the total transform at every step - the plane objective is not a Procrustes problem and has no closed
+    form for the total; each increment is a similarity by construction (Rodrigues' formula), so the product is one.  c0 = float32 of T applied to
+    the centre of the sources' bounding box; the columns of the system are scaled by half the box's diagonal times cbrt(|det T[:3, :3]|).  A point on
+    a wall may slide along it at no cost, which is the point: `icp` pins every source to its nearest sample and creeps (docs/experiments.md 6r).
+    `every=k` uses the source rows 0, k, 2k, ...  Stops: 'converged' - the radius has reached its floor and the eight corners of the sources' box
+    moved by at most `tol` r_k in this step; 'iters'; 'degenerate' - fewer matched sources than unknowns (7, rigid 6), or the matched planes do not
+    fix the motion (`plane_step_from_moments` returns None: a single plane, parallel planes, a corridor) - the transform of the step before is
+    returned, at step 0 that is `init`.  A first step without a single match raises ValueError, as does a non-finite source.  `history` holds per
+    step `radius`, `matched`, `rmse` (to the triangles) and `plane_rmse` (to the planes of the matched faces), before that step's solve.
+    `max_cell_faces` and `max_pairs` guard the index as in `mesh_distance`.  The moments are summed in a fixed order: two calls return identical
+    bytes.  No source normals, no robust weights.  GPU only: CPU tensors raise."""
+    _check_points(source, 'source')
+    _check_mesh(vertices, faces, 'search', hip.MESHDIST_MAX)
+    max_dist, T, min_dist, shrink, tol = _check_icp(max_dist, init, with_scale, iters, min_dist, shrink, tol, every)
+    _check_limits(max_cell_faces, max_pairs)
+    _gpu_only('icp_to_mesh', 'a %(device)s %(name)s', source=source, vertices=vertices, faces=faces)
+    src = source.float()[::every].contiguous()
+    unknowns = 7 if with_scale else 6
+    if src.shape[0] < unknowns:
+        raise ValueError('icp_to_mesh needs at least %d source points, got %d (every=%d)' % (unknowns, src.shape[0], every))
+    lo, hi = (v.double().cpu().numpy() for v in torch.aminmax(src, dim=0))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError('icp_to_mesh: a source point is not finite')
+    box = np.array([[(lo, hi)[(c >> a) & 1][a] for a in range(3)] for c in range(8)])
+    centre, half = 0.5 * (lo + hi), 0.5 * float(np.sqrt(((hi - lo) ** 2).sum()))
+    index = MeshIndex(vertices, faces, max_dist, max_cell_faces=max_cell_faces, max_pairs=max_pairs)
+    iws = hip.icp_plane_workspace(src.shape[0], src.device)
+    history, reason = [], 'iters'
+    for k in range(int(iters)):
+        r, r2, floor = _icp_radius(k, max_dist, min_dist, shrink)
+        c0 = (T[:3, :3] @ centre + T[:3, 3]).astype(np.float32)
+        length = half * float(np.cbrt(abs(np.linalg.det(T[:3, :3]))))
+        if index.ws is None:                                                      # no face was kept: nothing can match
+            mom, bits = np.zeros(hip.ICP_PLANE_MOMENTS), 0
+        else:
+            iws['status'].zero_()
+            out = hip.icp_plane_step(src, T[:3].astype(np.float32), c0, index.vertices, index.faces, index.inv, index.r2, float(r2), index.ws,
+                                     index.max_cell_faces, iws)
+            got = torch.cat([out, iws['status'].double()]).cpu().numpy()         # the one host sync of the step
+            mom, bits = got[:hip.ICP_PLANE_MOMENTS], int(got[hip.ICP_PLANE_MOMENTS])
+        if bits:
+            raise RuntimeError('icp_to_mesh: the search did not finish (status %d)' % bits)
+        n = int(mom[0])
+        history.append({'radius': float(r), 'matched': n, 'rmse': float(np.sqrt(mom[37] / mom[0])) if n else math.nan,
+                        'plane_rmse': float(np.sqrt(mom[36] / mom[0])) if n else math.nan})
+        if n == 0 and k == 0:
+            raise ValueError('icp_to_mesh: nothing within max_dist of the initial alignment (none of %d sources matched within %g)' % (src.shape[0], max_dist))
+        inc = plane_step_from_moments(mom, c0.astype(np.float64), length, with_scale) if n >= unknowns else None
+        if inc is None:
+            reason = 'degenerate'
+            break
+        new = inc @ T
+        shift, T = _corner_shift(box, T, new), new
+        if floor and shift <= tol * float(r):
+            reason = 'converged'
+            break
+    return Alignment(torch.from_numpy(T), len(history), reason == 'converged', reason, history)

@@ -53,6 +53,44 @@ def procrustes_from_moments(sw, sx, sy, syx, sxx=None):
     return R, ym - s * (R @ xm), s
 
 
+PLANE_SYSTEM_TOL = 1e-6     # plane_step_from_moments: the planes fix the motion iff the smallest eigenvalue of the scaled system exceeds this share of the largest
+
+
+def plane_step_from_moments(mom, centre, length, with_scale=True):
+    """the host step of the point-to-plane ICP, float64: `mom` = the 40 moments of `hip.icp_plane_step` (the icp-plane section of
+    include/panst3r_hip.h: [1..28] the upper triangle of sum w J J^T, [29..35] sum w J rN, J = (p x N, N, N . p) about `centre`) -> the [4, 4]
+    increment x -> c + (1 + sigma) R(omega) (x - c) + tau that minimises the linearised squared plane distances, or None if the planes do not fix
+    the motion.  (omega, tau, sigma) solve (sum w J J^T) x = -sum w J rN; `with_scale=False` solves the leading 6 x 6 and sigma = 0.  The rotation
+    and scale columns are scaled by 1 / `length` first (a length of the sources, e.g. half their box's diagonal), so that every column is a
+    length and the system's eigenvalues compare; None iff the smallest is <= PLANE_SYSTEM_TOL times the largest - a single plane, parallel planes or a
+    corridor, where the sources may slide or turn freely.  The tolerance is a CHOICE, as PLANE_RANK_TOL is: it rejects the degenerate case, it does
+    not promise a well-conditioned one (a room's ratio is about 7e-3, a single plane's below 1e-16: docs/experiments.md 6r).  R is Rodrigues'
+    formula of omega, so the increment is a similarity by construction whatever the size of the step."""
+    mom, c = np.asarray(mom, dtype=np.float64), np.asarray(centre, dtype=np.float64)
+    n = 7 if with_scale else 6
+    A = np.zeros((7, 7))
+    A[np.triu_indices(7)] = mom[1:29]
+    A = A + np.triu(A, 1).T
+    d = np.ones(7)
+    d[[0, 1, 2, 6]] = 1.0 / float(length)
+    As, bs = (A * np.outer(d, d))[:n, :n], (mom[29:36] * d)[:n]
+    if not (np.isfinite(As).all() and np.isfinite(bs).all()):
+        return None
+    ev = np.linalg.eigvalsh(As)
+    if not (ev[-1] > 0 and ev[0] > PLANE_SYSTEM_TOL * ev[-1]):
+        return None
+    x = np.zeros(7)
+    x[:n] = d[:n] * np.linalg.solve(As, -bs)
+    omega, tau, sigma = x[:3], x[3:6], x[6]
+    theta = float(np.sqrt(omega @ omega))
+    K = np.array([[0.0, -omega[2], omega[1]], [omega[2], 0.0, -omega[0]], [-omega[1], omega[0], 0.0]])
+    R = np.eye(3) if theta == 0 else np.eye(3) + (np.sin(theta) / theta) * K + ((1.0 - np.cos(theta)) / (theta * theta)) * (K @ K)
+    M = (1.0 + sigma) * R
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = M, (c - M @ c) + tau
+    return T
+
+
 def rigid_points_registration(x, y, weights=None, compute_scaling=False):
     """roma.rigid_points_registration restated for batches of point sets: x, y [B, N, 3] (device), weights [B, N] -> (R [B,3,3], t [B,3])
     with y ~ R x + t (weighted Kabsch; the 16 moments per set are reduced on the device, the 3x3 SVD runs on the host in float64).

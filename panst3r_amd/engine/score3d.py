@@ -429,17 +429,36 @@ def icp(source, target, *, max_dist, init=None, with_scale=True, iters=50, min_d
 
 
 @torch.no_grad()
-def refine_alignment(pred, gt_vertices, gt_faces, *, spacing, max_dist, init=None, max_subdiv=1024, **icp_kwargs):
+def refine_alignment(pred, gt_vertices, gt_faces, *, spacing, max_dist, init=None, max_subdiv=1024, target='samples', **icp_kwargs):
     """Refine the alignment of a prediction - a `PanopticCloud`, a `VoxelCloud`, a `PanopticMesh` or an [N, 3] device tensor - to the ground-truth mesh
     on the geometry -> `Alignment` whose `transform` is T_icp @ init, ready for `score_reconstruction(transform=)`.  The prediction is carried by
     `init` ([4, 4], e.g. `similarity_from_cameras`; default the identity) as `score_reconstruction` carries it - a mesh is moved BEFORE it is
     sampled at `spacing` - the ground truth is `sample_mesh` at `spacing`, and `icp` runs from the identity on the moved points with
     `max_dist` and `icp_kwargs`.  The direction is prediction -> ground truth, a CHOICE: a prediction covers part of the scene and the mesh all of
-    it, so the reverse direction would pull the fit towards surface the prediction never saw.  Point to point only.  GPU only."""
+    it, so the reverse direction would pull the fit towards surface the prediction never saw.  `target='samples'` (the default, what it always
+    was): point-to-point `icp` against the samples.  `target='surface'` (stage f13): point-to-plane `icp_to_mesh` (engine/meshdist.py) of the same
+    points against the ground truth's TRIANGLES - `gt_vertices` / `gt_faces` as they are; `spacing` then only samples a `PanopticMesh` prediction,
+    and `icp_kwargs` are `icp_to_mesh`'s (`max_cell_faces`, `max_pairs` instead of `max_cell_points`).  On scenes made of large planes the
+    point-to-point fit resists sliding along every wall and creeps; the plane fit does not (docs/experiments.md 6r).  GPU only."""
     spacing = _check_length(spacing, 'spacing')
     T0 = None if init is None else _check_transform(init)
     if not _is_int(max_subdiv) or not 1 <= max_subdiv <= hip.MESH_SAMPLE_MAX_SUBDIV:
         raise ValueError('max_subdiv must be an integer in 1 .. %d, got %r' % (hip.MESH_SAMPLE_MAX_SUBDIV, max_subdiv))
+    if target not in ('samples', 'surface'):
+        raise ValueError("target must be 'samples' or 'surface', got %r" % (target,))
+    if target == 'surface':
+        from .meshdist import _check_limits, icp_to_mesh
+        kw = dict(icp_kwargs)
+        _check_limits(kw.pop('max_cell_faces', 4096), kw.pop('max_pairs', 2 ** 27))      # before the GPU is touched, as below
+        if 'max_cell_points' in kw:
+            raise ValueError("refine_alignment(target='surface') takes max_cell_faces and max_pairs, not max_cell_points")
+        _check_icp(max_dist, **kw)
+        _check_mesh(gt_vertices, gt_faces, 'search', hip.MESHDIST_MAX)
+        points, _, _ = _pred_points(pred, spacing, max_subdiv, T0)
+        a = icp_to_mesh(points, gt_vertices, gt_faces, max_dist=max_dist, **icp_kwargs)
+        if T0 is not None:
+            a.transform = torch.from_numpy(a.transform.numpy() @ T0)
+        return a
     _check_icp(max_dist, **icp_kwargs)                                        # before the GPU is touched (`init` is this call's own: icp starts from the identity)
     points, _, _ = _pred_points(pred, spacing, max_subdiv, T0)
     gt = sample_mesh(gt_vertices, gt_faces, spacing, max_subdiv=max_subdiv)
@@ -502,7 +521,10 @@ def score_reconstruction(pred, gt_vertices, gt_faces, *, thresholds, spacing, ma
     guards), so `precision`, `pred_within` and `accuracy_*` do not depend on `spacing`; ground truth -> predicted takes the ground-truth samples to
     the triangles of a `PanopticMesh` (moved by `transform` first; `pq3d` takes the `face_ids` of the nearest face), and for a cloud, a voxel cloud or
     a tensor - no surface there - it stays `nearest_points`.  The dict holds `metric`, and under 'surface' also `gt_pairs` and `gt_max_cell_faces`
-    (the (face, cell) pairs and the longest cell list of the ground truth's index).  `refine` is point-to-point ICP under both metrics.  GPU only."""
+    (the (face, cell) pairs and the longest cell list of the ground truth's index).  `refine=True` is point-to-point ICP against the samples under
+    both metrics, as it always was; `refine={'target': 'surface'}` opts into the point-to-plane ICP against the ground truth's triangles
+    (`icp_to_mesh`, stage f13; its `max_cell_faces` and `max_pairs` default to this call's), so that `metric='surface'` measures under an alignment
+    fitted to the same triangles.  GPU only."""
     if metric not in ('points', 'surface'):
         raise ValueError("metric must be 'points' or 'surface', got %r" % (metric,))
     if metric == 'surface':
@@ -525,7 +547,11 @@ def score_reconstruction(pred, gt_vertices, gt_faces, *, thresholds, spacing, ma
     if refine is True or isinstance(refine, dict):
         kw = {} if refine is True else dict(refine)
         kw.setdefault('max_dist', 4 * radius)
-        kw.setdefault('max_cell_points', max_cell_points)
+        if kw.get('target', 'samples') == 'surface':                          # the opt-in of f13: point to plane against the triangles
+            kw.setdefault('max_cell_faces', max_cell_faces)
+            kw.setdefault('max_pairs', max_pairs)
+        else:
+            kw.setdefault('max_cell_points', max_cell_points)
         alignment = refine_alignment(pred, gt_vertices, gt_faces, spacing=spacing, init=T, max_subdiv=max_subdiv, **kw)
         T = alignment.transform.numpy()
     points, ids, segments = _pred_points(pred, spacing, max_subdiv, T)

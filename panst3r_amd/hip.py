@@ -82,6 +82,7 @@ SIGNATURES = {
     'pst_icp_chunk': 'i:', 'pst_icp_step': 'i:plffffffffffffplffplpppipppppp',
     'pst_meshdist_count': 'i:plplfpppp', 'pst_meshdist_insert': 'i:plplfplplpppp', 'pst_meshdist_scatter': 'i:ppllpppppp',
     'pst_meshdist_query': 'i:plplplffplppplippppp',
+    'pst_plane_icp_step': 'i:plfffffffffffffffplplffplppplipppppp',
 }
 EXPORTS = list(SIGNATURES)
 
@@ -1766,3 +1767,41 @@ def meshdist_query(queries, vertices, faces, inv, r2, ws, max_cell_faces, d2, fa
         assert closest.is_contiguous() and closest.numel() == 3 * Nq
     _call('pst_meshdist_query', _ptr(queries), Nq, _ptr(vertices), Nv, _ptr(faces), F, float(inv), float(r2), _ptr(ws['keys']), ws['cap'], _ptr(ws['start']),
           _ptr(ws['cell_count']), _ptr(ws['rows']), ws['P'], int(max_cell_faces), _ptr(d2), _ptr(face), _ptr(closest), _ptr(status))
+
+
+# ------------------------------------------------------------------ one fused point-to-plane ICP step against the triangles (csrc/meshdist.hip; engine/meshdist.py's icp_to_mesh)
+ICP_PLANE_MOMENTS = 40      # PST_ICP_PLANE_MOMENTS: doubles per row of partials and in out (the order of the sums is ICP_CHUNK / ICP_LANES, as icp_step's)
+
+
+def icp_plane_workspace(N, device):
+    """the workspaces of `icp_plane_step` over N source points: partials double [ceil(N / ICP_CHUNK), 40], out double [40], status int32 [4] (zeroed
+    here; the caller clears it between steps if it reads it per step)"""
+    return {'N': int(N), 'partials': torch.empty((int(N) + ICP_CHUNK - 1) // ICP_CHUNK, ICP_PLANE_MOMENTS, dtype=torch.float64, device=device),
+            'out': torch.empty(ICP_PLANE_MOMENTS, dtype=torch.float64, device=device), 'status': torch.zeros(4, dtype=torch.int32, device=device)}
+
+
+def icp_plane_step(source, A, c0, vertices, faces, inv, cell_r2, r2, ws, max_cell_faces, iws, d2=None, face=None):
+    """one fused point-to-plane step (include/panst3r_hip.h): `source` moved by the 3 x 4 matrix A (12 numbers, rounded to fp32 here), searched in the
+    built lists `ws` of the mesh (cell edge 1 / inv, cell_r2 = its squared edge), accepted within r2 <= cell_r2, the normal equations about the centre
+    c0 (3 numbers) -> iws['out'] double [40]; d2 / face [N] are written when given (both or neither).  A larger r2 raises ValueError: the lists
+    would not hold every match."""
+    N = _nn_points(source)
+    Nv, F = _mesh_sample_mesh(vertices, faces)
+    A = [float(a) for a in (A.reshape(-1).tolist() if hasattr(A, 'reshape') else A)]
+    c0 = [float(c) for c in (c0.reshape(-1).tolist() if hasattr(c0, 'reshape') else c0)]
+    if len(A) != 12 or len(c0) != 3:
+        raise ValueError('icp_plane_step takes a 3 x 4 matrix and a centre of 3 numbers, got %d and %d numbers' % (len(A), len(c0)))
+    if not float(r2) <= float(cell_r2):
+        raise ValueError('icp_plane_step: the squared radius %g exceeds the squared cell edge %g of the search structure' % (r2, cell_r2))
+    if (d2 is None) != (face is None):
+        raise ValueError('icp_plane_step: d2 and face go together')
+    if d2 is not None:
+        _dev(d2, torch.float32); _dev(face, torch.int32)
+        assert d2.numel() == N and face.numel() == N and d2.is_contiguous() and face.is_contiguous()
+    _dev(iws['partials'], torch.float64); _dev(iws['out'], torch.float64); _dev(iws['status'], torch.int32)
+    assert iws['N'] == N and iws['partials'].numel() == (N + ICP_CHUNK - 1) // ICP_CHUNK * ICP_PLANE_MOMENTS and iws['partials'].is_contiguous()
+    assert ws['rows'].numel() == ws['P'] and iws['out'].numel() == ICP_PLANE_MOMENTS and iws['status'].numel() == 4
+    _call('pst_plane_icp_step', _ptr(source), N, *A, *c0, _ptr(vertices), Nv, _ptr(faces), F, float(inv), float(r2), _ptr(ws['keys']), ws['cap'],
+          _ptr(ws['start']), _ptr(ws['cell_count']), _ptr(ws['rows']), ws['P'], int(max_cell_faces), _ptr(d2), _ptr(face), _ptr(iws['partials']),
+          _ptr(iws['out']), _ptr(iws['status']))
+    return iws['out']

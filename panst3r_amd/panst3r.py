@@ -419,7 +419,8 @@ class PanSt3R(nn.Module):
         `gt_mesh`: (vertices, faces) or (vertices, faces, vertex_ids, segments) on the device, e.g. from `engine.load_ply_mesh` and
         `engine.panoptic_vertex_ids`; `transform=engine.similarity_from_cameras(...)` carries the prediction into its frame, and `refine=True` (or a
         dict of `engine.refine_alignment` keywords) refines that transform on the geometry by ICP before anything is scored; the result then holds
-        the `Alignment` under 'alignment'.  `metric='surface'` measures the predicted points against the ground truth's triangles themselves
+        the `Alignment` under 'alignment' (`refine={'target': 'surface'}`: point-to-plane ICP against the triangles, `engine.icp_to_mesh`; the default
+        stays point to point against samples).  `metric='surface'` measures the predicted points against the ground truth's triangles themselves
         (`engine.mesh_distance`) instead of samples of them, so precision and accuracy do not depend on `spacing`.  It only composes."""
         from .engine import score_reconstruction
         if len(gt_mesh) not in (2, 4):
