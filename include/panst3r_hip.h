@@ -439,7 +439,11 @@ int pst_retrieval_scores(const int32_t* q_off, const int32_t* q_word, const uint
  *                         pointer to M (base + n), max_points >= M sizes the grid.  Workspaces, all ZEROED by the caller: hist int32
  *                         [nseg, 3, 2, 256] (16-byte aligned; left zeroed), prefix uint32 / rank int32 [nseg, 3, 2], nan_cnt int32 [nseg, 3].
  *                         -> count int32 [nseg] (kept points of the segment), median fp32 [nseg, 3]: the middle element for an odd count,
- *                         (a + b) * 0.5f of the two middle ones for an even count (np.median of float32), NaN for an axis with a NaN or a count of 0. */
+ *                         (a + b) * 0.5f of the two middle ones for an even count (np.median of float32), NaN for an axis with a NaN or a count of 0.
+ *                         The order is total: -inf < ... < -0.0 < +0.0 < ... < +inf (the two zeros are told apart, so the middle two of
+ *                         {-0, -0, +0, +0} are -0 and +0 and their median is +0).  The sum and the product are plain fp32 operations, rounded
+ *                         on their own: subnormal operands and results are kept (nothing is flushed), a sum beyond FLT_MAX is inf and stays inf,
+ *                         -inf + inf is NaN.  Ties need no rule: equal keys are equal values. */
 typedef struct pst_cloud_view {
   const float* conf;          /* [npix] */
   const float* pts3d;         /* [npix, 3] */

@@ -23,8 +23,13 @@ def blend(rgb, pan_vis, opacity):
 
 
 def median_two_stat(x):
-    """the kernel's form of np.median for float32: the middle order statistic (odd), (a + b) * 0.5f of the two middle ones (even)"""
-    s = np.sort(np.asarray(x, dtype=F))
+    """the kernel's form of np.median for float32: the middle order statistic (odd), (a + b) * 0.5f of the two middle ones (even).  The order is the
+    total one of include/panst3r_hip.h: -0.0 below +0.0 (np.sort leaves equal zeros where it finds them).  NaN for an axis that holds a NaN, as
+    np.median, and for no values at all.  The sum and the product are plain float32 operations: subnormals are kept, an overflowing sum is inf."""
+    x = np.asarray(x, dtype=F).reshape(-1)
+    if len(x) == 0 or np.isnan(x).any():
+        return F(np.nan)
+    s = x[np.lexsort((~np.signbit(x), x))]
     n = len(s)
     return s[n // 2] if n % 2 else F(F(s[n // 2 - 1] + s[n // 2]) * F(0.5))
 
