@@ -12,15 +12,11 @@
 // No float atomics, every result written with plain vector stores.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
+#include "wave_ops.h"            // rn_mul, rn_add, wg_rank, wave_scan, last_le
 
 #pragma clang fp contract(off)
 
 namespace pst {
-
-// separately rounded product and sum: written in this file, under the pragma above, so that no multiply-add can be formed from them (the HIP
-// header's __fmul_rn / __fadd_rn are plain operators compiled under the default contraction and DO fuse after inlining)
-__device__ __forceinline__ float mulr(float a, float b) { return a * b; }
-__device__ __forceinline__ float addr(float a, float b) { return a + b; }
 
 constexpr int CL_T = 256, CL_PT = 4, CL_WG = CL_T * CL_PT;        // threads, points per thread, points per workgroup
 constexpr int CL_MAX_COLORS = 4096;                               // colour table rows that fit in LDS next to the staging buffer (48 + 12 KiB)
@@ -30,12 +26,7 @@ constexpr int MD_ROW = 3 * 2 * 256;                               // counters pe
 
 // the view that owns workgroup wg: the last one whose first workgroup is <= wg (uniform: scalar loads)
 __device__ __forceinline__ int view_of(const pst_cloud_view* __restrict__ views, int nviews, int wg) {
-  int lo = 0, hi = nviews - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (views[mid].first_wg <= wg) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  return last_le(nviews, wg, [&](int v) { return views[v].first_wg; });
 }
 
 // bit k = point i0 + k exists and conf >= thr (a NaN confidence is dropped, as `conf >= thr` drops it in numpy)
@@ -52,29 +43,14 @@ __device__ __forceinline__ int keep_mask(const float* __restrict__ conf, int npi
   return m;
 }
 
-// kept points of the lower lanes of this wave (each lane owns 4 consecutive points: four ballots), and the wave's total
-__device__ __forceinline__ int lane_prefix(int m, int& total) {
-  int pre = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < CL_PT; ++k) {
-    const uint64_t b = __ballot((m >> k) & 1);
-    pre += __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0));
-    total += __popcll(b);
-  }
-  return pre;
-}
-
 __global__ __launch_bounds__(CL_T) void cloud_count_kernel(const pst_cloud_view* __restrict__ views, int nviews, float thr, int32_t* __restrict__ counts) {
   __shared__ int wtot[CL_T / 64];
   const int wg = blockIdx.x;
   const pst_cloud_view& v = views[view_of(views, nviews, wg)];
   const int i0 = (wg - v.first_wg) * CL_WG + threadIdx.x * CL_PT;
   int total;
-  lane_prefix(keep_mask(v.conf, v.npix, i0, thr), total);
-  if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = total;
-  __syncthreads();
-  if (threadIdx.x == 0) counts[wg] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+  wg_rank<CL_T, CL_PT>(keep_mask(v.conf, v.npix, i0, thr), wtot, total);
+  if (threadIdx.x == 0) counts[wg] = total;
 }
 
 // base[i] = counts[0] + ... + counts[i - 1], base[n] = M.  One workgroup of 1024 threads, 1024 counts per round with a running carry.
@@ -87,12 +63,7 @@ __global__ __launch_bounds__(1024) void cloud_scan_kernel(const int32_t* __restr
   for (int r0 = 0; r0 < n; r0 += 1024) {
     const int i = r0 + tid;
     const int c = i < n ? counts[i] : 0;
-    int s = c;                                   // inclusive scan inside the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(s, o);
-      if (lane >= o) s += t;
-    }
+    const int s = wave_scan(c, lane);
     if (lane == 63) wsum[wave] = s;
     __syncthreads();
     int wbase = 0, tot = 0;
@@ -144,10 +115,7 @@ __global__ __launch_bounds__(CL_T) void cloud_compact_kernel(const pst_cloud_vie
   const int i0 = (wg - v.first_wg) * CL_WG + tid * CL_PT;
   const int m = keep_mask(v.conf, npix, i0, thr);
   int total;
-  int slot = lane_prefix(m, total);
-  if ((tid & 63) == 0) wtot[tid >> 6] = total;
-  __syncthreads();                                                 // also: the colour table is in LDS
-  for (int w = 0; w < (tid >> 6); ++w) slot += wtot[w];
+  const int slot = wg_rank<CL_T, CL_PT>(m, wtot, total);           // its barrier also publishes the colour table in LDS
 
   float R[12];
 #pragma unroll
@@ -171,8 +139,8 @@ __global__ __launch_bounds__(CL_T) void cloud_compact_kernel(const pst_cloud_vie
       const float x = p[0], y = p[1], z = p[2];
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        const float a = addr(mulr(R[4 * r], x), mulr(R[4 * r + 1], y));
-        val[k][r] = __float_as_uint(addr(addr(a, mulr(R[4 * r + 2], z)), R[4 * r + 3]));
+        const float a = rn_add(rn_mul(R[4 * r], x), rn_mul(R[4 * r + 1], y));
+        val[k][r] = __float_as_uint(rn_add(rn_add(a, rn_mul(R[4 * r + 2], z)), R[4 * r + 3]));
       }
     }
   stage_out<3>(stage, val, m, slot, cnt, (uint32_t*)(points_local + b0 * 3));
@@ -187,10 +155,10 @@ __global__ __launch_bounds__(CL_T) void cloud_compact_kernel(const pst_cloud_vie
       const bool known = p > 0 && p < ncolors;                    // void (0) and ids outside the table are black; the table is never indexed with them
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const float g = addr(mulr(v.img[(int64_t)c * npix + i0 + k], 0.5f), 0.5f);
+        const float g = rn_add(rn_mul(v.img[(int64_t)c * npix + i0 + k], 0.5f), 0.5f);
         const float pv = known ? ctab[p * 3 + c] : 0.f;
         val[k][c] = __float_as_uint(g);
-        cval[k][c] = __float_as_uint(addr(mulr(w1, g), mulr(w2, pv)));
+        cval[k][c] = __float_as_uint(rn_add(rn_mul(w1, g), rn_mul(w2, pv)));
       }
     }
   stage_out<3>(stage, val, m, slot, cnt, (uint32_t*)(rgb + b0 * 3));
@@ -305,7 +273,7 @@ __global__ __launch_bounds__(64) void median_narrow_kernel(int32_t* __restrict__
   if (pass == 3 && lane == 0) {
     const int cnt = count[sa / 3];
     const float a = __uint_as_float(funkey(key[0])), b = __uint_as_float(funkey(key[1]));
-    float med = (cnt & 1) ? a : mulr(addr(a, b), 0.5f);
+    float med = (cnt & 1) ? a : rn_mul(rn_add(a, b), 0.5f);
     if (nan_cnt[sa] > 0 || cnt == 0) med = __uint_as_float(0x7fc00000u);
     median[sa] = med;
   }

@@ -18,6 +18,7 @@ namespace pst {
 
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+static inline dim3 blocks_for(int64_t n, int T) { return dim3((unsigned)((n + T - 1) / T)); }      // a 1-D grid of T-thread workgroups over n items
 // Function attributes (MaxDynamicSharedMemorySize) are PER DEVICE: `run` executes once per (call site, current device), under a lock
 // (a second thread may not launch before the first one has finished setting the attributes).  `seen` = the call site's static bitmask.
 void once_per_device(unsigned long long& seen, void (*run)());

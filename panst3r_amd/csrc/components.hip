@@ -18,15 +18,12 @@
 // Integer atomics only, every probe / find / union loop bounded (an overflow sets a bit of status[0] and ends the loop), plain vector stores for results.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
-#include "voxel_table.h"
+#include "voxel_table.h"         // and through it wave_ops.h: rn_mul / rn_add, wg_rank, wave_scan, vx_run, wave_count_add
 #include "union_find.h"          // cc_load, cc_find, cc_unite
 
 #pragma clang fp contract(off)
 
 namespace pst {
-
-__device__ __forceinline__ float cc_mulr(float a, float b) { return a * b; }
-__device__ __forceinline__ float cc_addr(float a, float b) { return a + b; }
 
 constexpr int CC_T = 256, CC_PT = 4, CC_WG = CC_T * CC_PT;         // count / rank: 1024 rows per workgroup, as pst_cloud_scan's other callers
 constexpr int CC_DUP = PST_VCC_DUPLICATE, CC_RANGE = PST_VCC_RANGE, CC_LOOP = PST_VCC_LOOP;
@@ -90,17 +87,6 @@ __global__ __launch_bounds__(CC_T) void vcc_link_kernel(const int32_t* __restric
   }
 }
 
-// reduction of v over the lanes [head, lane] of a run (segmented inclusive scan): the run's last lane holds the run's total
-template <typename T, typename Op>
-__device__ __forceinline__ T cc_seg_scan(T v, int lane, int head, Op op) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T t = __shfl_up(v, o);
-    if (lane - o >= head) v = op(v, t);
-  }
-  return v;
-}
-
 template <bool MERGE>
 __global__ __launch_bounds__(CC_T) void vcc_flatten_kernel(const int32_t* __restrict__ parent, const int32_t* __restrict__ count, const int32_t* __restrict__ cells,
                                                            int Mv, int32_t* __restrict__ root, int32_t* __restrict__ size, unsigned long long* __restrict__ points,
@@ -129,11 +115,11 @@ __global__ __launch_bounds__(CC_T) void vcc_flatten_kernel(const int32_t* __rest
     const auto add = [](auto p, auto q) { return p + q; };
     const auto mn = [](int p, int q) { return min(p, q); };
     const auto mx = [](int p, int q) { return max(p, q); };
-    n = cc_seg_scan(n, lane, head, add);
-    pts = cc_seg_scan(pts, lane, head, add);
+    n = wave_scan(n, lane, head, add);
+    pts = wave_scan(pts, lane, head, add);
     int l[3], h[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { l[a] = cc_seg_scan(c[a], lane, head, mn); h[a] = cc_seg_scan(c[a], lane, head, mx); }
+    for (int a = 0; a < 3; ++a) { l[a] = wave_scan(c[a], lane, head, mn); h[a] = wave_scan(c[a], lane, head, mx); }
     if (r >= 0 && lane == tail) {
       atomicAdd(&size[r], n);
       atomicAdd(&points[r], (unsigned long long)pts);
@@ -157,25 +143,11 @@ __device__ __forceinline__ int cc_root_mask(const int32_t* __restrict__ root, in
   return m;
 }
 
-__device__ __forceinline__ int cc_lane_prefix(int m, int& total) {
-  int pre = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < CC_PT; ++k) {
-    const uint64_t b = __ballot((m >> k) & 1);
-    pre += __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0));
-    total += __popcll(b);
-  }
-  return pre;
-}
-
 __global__ __launch_bounds__(CC_T) void vcc_count_kernel(const int32_t* __restrict__ root, int Mv, int32_t* __restrict__ counts) {
   __shared__ int wtot[CC_T / 64];
   int total;
-  cc_lane_prefix(cc_root_mask(root, Mv, blockIdx.x * CC_WG + threadIdx.x * CC_PT), total);
-  if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = total;
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+  wg_rank<CC_T, CC_PT>(cc_root_mask(root, Mv, blockIdx.x * CC_WG + threadIdx.x * CC_PT), wtot, total);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 // rank of every root = workgroup base + wave base + lane prefix (ranks follow the rows) -> rank_of[row] and the component's row of the table
@@ -188,11 +160,7 @@ __global__ __launch_bounds__(CC_T) void vcc_rank_kernel(const int32_t* __restric
   const int tid = threadIdx.x, i0 = blockIdx.x * CC_WG + tid * CC_PT;
   const int m = cc_root_mask(root, Mv, i0);
   int total;
-  int r = cc_lane_prefix(m, total);
-  if ((tid & 63) == 0) wtot[tid >> 6] = total;
-  __syncthreads();
-  for (int w = 0; w < (tid >> 6); ++w) r += wtot[w];
-  r += base[blockIdx.x];
+  int r = base[blockIdx.x] + wg_rank<CC_T, CC_PT>(m, wtot, total);
 #pragma unroll
   for (int k = 0; k < CC_PT; ++k)
     if ((m >> k) & 1) {
@@ -241,7 +209,7 @@ __global__ __launch_bounds__(CC_T) void vcc_apply_kernel(const int32_t* __restri
                                                          const unsigned long long* __restrict__ best, int Mv, int min_voxels, const float* __restrict__ rgb,
                                                          const float* __restrict__ colors, int ncolors, float w1, float w2, int32_t* __restrict__ out_pan,
                                                          float* __restrict__ out_colors, int32_t* __restrict__ status) {
-  const int v = blockIdx.x * CC_T + threadIdx.x, lane = threadIdx.x & 63;
+  const int v = blockIdx.x * CC_T + threadIdx.x;
   int id = 0;
   bool small = false;
   if (v < Mv) {
@@ -255,19 +223,15 @@ __global__ __launch_bounds__(CC_T) void vcc_apply_kernel(const int32_t* __restri
     const bool known = id > 0 && id < ncolors;
 #pragma unroll
     for (int a = 0; a < 3; ++a)
-      out_colors[(int64_t)v * 3 + a] = cc_addr(cc_mulr(w1, rgb[(int64_t)v * 3 + a]), cc_mulr(w2, known ? colors[id * 3 + a] : 0.f));
+      out_colors[(int64_t)v * 3 + a] = rn_add(rn_mul(w1, rgb[(int64_t)v * 3 + a]), rn_mul(w2, known ? colors[id * 3 + a] : 0.f));
     out_pan[v] = id;
   }
-  const uint64_t moved = __ballot(small && id > 0), gone = __ballot(small && id == 0);
-  if (lane == 0) {
-    if (moved) atomicAdd(&status[1], (int)__popcll(moved));
-    if (gone) atomicAdd(&status[2], (int)__popcll(gone));
-  }
+  wave_count_add(small && id > 0, &status[1]);                      // moved
+  wave_count_add(small && id == 0, &status[2]);                     // gone
 }
 
 static bool cc_pow2(int64_t cap) { return cap >= 2 && cap <= (1ll << 31) && (cap & (cap - 1)) == 0; }
 static int cc_axes(int connectivity) { return connectivity == 6 ? 1 : connectivity == 18 ? 2 : connectivity == 26 ? 3 : 0; }
-static dim3 cc_grid(int64_t n) { return dim3((unsigned)((n + CC_T - 1) / CC_T)); }
 constexpr int64_t CC_MAX_ROWS = 0x3fffffffLL;
 
 }  // namespace pst
@@ -277,7 +241,7 @@ extern "C" int pst_vcc_cells(const float* points, const int32_t* first_row, cons
   if (!points || !first_row || !mv_ptr || !cells || max_voxels <= 0 || max_voxels > CC_MAX_ROWS || !(inv > 0.f)) {
     set_error("vcc_cells: bad shape (max_voxels=%lld), inverse voxel size or null operand", (long long)max_voxels); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(vcc_cells_kernel, cc_grid(max_voxels), dim3(CC_T), 0, (hipStream_t)stream, points, first_row, mv_ptr, inv, cells);
+  hipLaunchKernelGGL(vcc_cells_kernel, blocks_for(max_voxels, CC_T), dim3(CC_T), 0, (hipStream_t)stream, points, first_row, mv_ptr, inv, cells);
   return check_launch("vcc_cells");
 }
 
@@ -288,7 +252,7 @@ extern "C" int pst_vcc_build(const int32_t* cells, const int32_t* pan, int64_t M
   if (Mv <= 0 || Mv > CC_MAX_ROWS || !vx_cap_ok(Mv, capacity)) {
     set_error("vcc_build: bad shape (Mv=%lld, capacity=%lld: a power of two >= 2 Mv)", (long long)Mv, (long long)capacity); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(vcc_build_kernel, cc_grid(Mv), dim3(CC_T), 0, (hipStream_t)stream, cells, pan, (int)Mv, keys, rows, (uint32_t)(capacity - 1), parent, status);
+  hipLaunchKernelGGL(vcc_build_kernel, blocks_for(Mv, CC_T), dim3(CC_T), 0, (hipStream_t)stream, cells, pan, (int)Mv, keys, rows, (uint32_t)(capacity - 1), parent, status);
   return check_launch("vcc_build");
 }
 
@@ -299,7 +263,7 @@ extern "C" int pst_vcc_link(const int32_t* cells, const int32_t* pan, int64_t Mv
   if (Mv <= 0 || Mv > CC_MAX_ROWS || !vx_cap_ok(Mv, capacity) || !cc_axes(connectivity)) {
     set_error("vcc_link: bad shape (Mv=%lld, capacity=%lld) or connectivity %d (6, 18 or 26)", (long long)Mv, (long long)capacity, connectivity); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(vcc_link_kernel, cc_grid(Mv), dim3(CC_T), 0, (hipStream_t)stream, cells, pan, (int)Mv, keys, rows, (uint32_t)(capacity - 1),
+  hipLaunchKernelGGL(vcc_link_kernel, blocks_for(Mv, CC_T), dim3(CC_T), 0, (hipStream_t)stream, cells, pan, (int)Mv, keys, rows, (uint32_t)(capacity - 1),
                      cc_axes(connectivity), parent, status);
   return check_launch("vcc_link");
 }
@@ -310,9 +274,9 @@ extern "C" int pst_vcc_flatten(const int32_t* parent, const int32_t* count, cons
   if (!parent || !count || !cells || !root || !size || !points || !cell_lo || !cell_hi || !status || Mv <= 0 || Mv > CC_MAX_ROWS) {
     set_error("vcc_flatten: bad shape (Mv=%lld) or null operand", (long long)Mv); return PST_EINVAL;
   }
-  if (merge) hipLaunchKernelGGL(vcc_flatten_kernel<true>, cc_grid(Mv), dim3(CC_T), 0, (hipStream_t)stream, parent, count, cells, (int)Mv, root, size,
+  if (merge) hipLaunchKernelGGL(vcc_flatten_kernel<true>, blocks_for(Mv, CC_T), dim3(CC_T), 0, (hipStream_t)stream, parent, count, cells, (int)Mv, root, size,
                                 (unsigned long long*)points, cell_lo, cell_hi, status);
-  else hipLaunchKernelGGL(vcc_flatten_kernel<false>, cc_grid(Mv), dim3(CC_T), 0, (hipStream_t)stream, parent, count, cells, (int)Mv, root, size,
+  else hipLaunchKernelGGL(vcc_flatten_kernel<false>, blocks_for(Mv, CC_T), dim3(CC_T), 0, (hipStream_t)stream, parent, count, cells, (int)Mv, root, size,
                           (unsigned long long*)points, cell_lo, cell_hi, status);
   return check_launch("vcc_flatten");
 }
@@ -320,7 +284,7 @@ extern "C" int pst_vcc_flatten(const int32_t* parent, const int32_t* count, cons
 extern "C" int pst_vcc_count(const int32_t* root, int64_t Mv, int32_t* counts, void* stream) {
   using namespace pst;
   if (!root || !counts || Mv <= 0 || Mv > CC_MAX_ROWS) { set_error("vcc_count: bad shape / null operand"); return PST_EINVAL; }
-  hipLaunchKernelGGL(vcc_count_kernel, dim3((unsigned)((Mv + CC_WG - 1) / CC_WG)), dim3(CC_T), 0, (hipStream_t)stream, root, (int)Mv, counts);
+  hipLaunchKernelGGL(vcc_count_kernel, blocks_for(Mv, CC_WG), dim3(CC_T), 0, (hipStream_t)stream, root, (int)Mv, counts);
   return check_launch("vcc_count");
 }
 
@@ -332,11 +296,11 @@ extern "C" int pst_vcc_rank(const int32_t* root, const int32_t* pan, int64_t Mv,
       Mv <= 0 || Mv > CC_MAX_ROWS) {
     set_error("vcc_rank: bad shape / null operand"); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(vcc_rank_kernel, dim3((unsigned)((Mv + CC_WG - 1) / CC_WG)), dim3(CC_T), 0, (hipStream_t)stream, root, pan, (int)Mv, base, size, points, cell_lo,
+  hipLaunchKernelGGL(vcc_rank_kernel, blocks_for(Mv, CC_WG), dim3(CC_T), 0, (hipStream_t)stream, root, pan, (int)Mv, base, size, points, cell_lo,
                      cell_hi, rank_of, t_root, t_pan, t_size, t_points, t_lo, t_hi);
   const int rc = check_launch("vcc_rank");
   if (rc) return rc;
-  hipLaunchKernelGGL(vcc_component_kernel, cc_grid(Mv), dim3(CC_T), 0, (hipStream_t)stream, root, rank_of, (int)Mv, component);
+  hipLaunchKernelGGL(vcc_component_kernel, blocks_for(Mv, CC_T), dim3(CC_T), 0, (hipStream_t)stream, root, rank_of, (int)Mv, component);
   return check_launch("vcc_rank (component)");
 }
 
@@ -350,7 +314,7 @@ extern "C" int pst_vcc_votes(const int32_t* cells, const int32_t* pan, const int
               (long long)pair_capacity, connectivity, min_voxels);
     return PST_EINVAL;
   }
-  hipLaunchKernelGGL(vcc_votes_kernel, cc_grid(Mv), dim3(CC_T), 0, (hipStream_t)stream, cells, pan, root, size, (int)Mv, keys, rows, (uint32_t)(capacity - 1),
+  hipLaunchKernelGGL(vcc_votes_kernel, blocks_for(Mv, CC_T), dim3(CC_T), 0, (hipStream_t)stream, cells, pan, root, size, (int)Mv, keys, rows, (uint32_t)(capacity - 1),
                      cc_axes(connectivity), min_voxels, pair_keys, pair_cnt, (uint32_t)(pair_capacity - 1), status);
   return check_launch("vcc_votes");
 }
@@ -362,7 +326,7 @@ extern "C" int pst_vcc_apply(const int32_t* pan, const int32_t* root, const int3
   if (Mv <= 0 || Mv > CC_MAX_ROWS || min_voxels < 1 || ncolors < 1 || ncolors > CC_MAX_COLORS) {
     set_error("vcc_apply: bad shape (Mv=%lld, ncolors=%d) or min_voxels %d", (long long)Mv, ncolors, min_voxels); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(vcc_apply_kernel, cc_grid(Mv), dim3(CC_T), 0, (hipStream_t)stream, pan, root, size, (const unsigned long long*)best, (int)Mv, min_voxels, rgb,
+  hipLaunchKernelGGL(vcc_apply_kernel, blocks_for(Mv, CC_T), dim3(CC_T), 0, (hipStream_t)stream, pan, root, size, (const unsigned long long*)best, (int)Mv, min_voxels, rgb,
                      colors, ncolors, w1, w2, out_pan, out_colors, status);
   return check_launch("vcc_apply");
 }

@@ -11,10 +11,11 @@
 // The contract (include/panst3r_hip.h) is integer arithmetic plus one fp64 division: contraction is off for the whole file, no float atomics, every
 // result but `counts` is written with plain vector stores by one thread - two calls return identical bytes.
 // `merge`: segmentation maps are piecewise constant, and same-address atomics serialise.  A lane loads four pixels; a lane whose four keys agree joins
-// the run of adjacent such lanes with that key, and the run's first lane adds 4 x the run's length (ballot, as voxel.hip's vx_run); any other lane adds
+// the run of adjacent such lanes with that key, and the run's first lane adds 4 x the run's length (ballot, as wave_ops.h's vx_run); any other lane adds
 // its own in-lane runs.  A wave inside one (p, g) region issues ONE atomic.  Same results.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
+#include "wave_ops.h"            // last_le, id_row
 
 #pragma clang fp contract(off)
 
@@ -25,18 +26,7 @@ constexpr uint32_t EV_NONE = 0xffffffffu;                          // no key: a 
 
 // the slab that owns pixel i: the last one whose offset is <= i (uniform per workgroup: scalar loads)
 __device__ __forceinline__ int ev_slab_of(const int64_t* __restrict__ off, int S, int64_t i) {
-  int lo = 0, hi = S - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ int ev_row(int id, const int32_t* __restrict__ tab, int ntab, int n) {
-  if (id <= 0 || id >= ntab) return n;
-  const int r = tab[id];
-  return (r >= 0 && r < n) ? r : n;
+  return last_le(S, i, [&](int s) { return off[s]; });
 }
 
 template <bool MERGE>
@@ -61,7 +51,7 @@ __global__ __launch_bounds__(EV_T) void pq_count_kernel(const int32_t* __restric
   for (int k = 0; k < EV_PT; ++k) {
     const int64_t i = i0 + k;
     while (s + 1 < S && i >= slab_off[s + 1]) ++s;
-    const uint32_t p = (uint32_t)ev_row(a[k], id2row_p, ntab_p, P), g = (uint32_t)ev_row(b[k], id2row_g, ntab_g, G);
+    const uint32_t p = (uint32_t)id_row(a[k], id2row_p, ntab_p, P, P), g = (uint32_t)id_row(b[k], id2row_g, ntab_g, G, G);      // none: the void row / column
     key[k] = i < N ? ((uint32_t)s * (uint32_t)(P + 1) + p) * (uint32_t)(G + 1) + g : EV_NONE;
   }
   if constexpr (MERGE) {
@@ -171,7 +161,7 @@ extern "C" int pst_pq_count(const int32_t* pred, const int32_t* gt, int64_t N, c
     set_error("pq_count: bad shape (N=%lld, slabs=%d, P=%d, G=%d, ntab=%d / %d)", (long long)N, nslabs, P, G, ntab_p, ntab_g); return PST_EINVAL;
   }
   if ((((uintptr_t)pred) | ((uintptr_t)gt)) & 15) { set_error("pq_count: the maps must be 16-byte aligned"); return PST_EINVAL; }
-  const dim3 grid((unsigned)((N + EV_WG - 1) / EV_WG));
+  const dim3 grid = blocks_for(N, EV_WG);
   if (merge) hipLaunchKernelGGL(pq_count_kernel<true>, grid, dim3(EV_T), 0, (hipStream_t)stream, pred, gt, N, slab_off, nslabs, id2row_p, ntab_p, id2row_g, ntab_g,
                                 P, G, counts);
   else hipLaunchKernelGGL(pq_count_kernel<false>, grid, dim3(EV_T), 0, (hipStream_t)stream, pred, gt, N, slab_off, nslabs, id2row_p, ntab_p, id2row_g, ntab_g, P, G,
@@ -186,12 +176,12 @@ extern "C" int pst_pq_match(const int32_t* counts, int nslabs, int P, int G, con
   if ((P > 0 && (!cat_p || !pred_area || !pred_state)) || (G > 0 && (!cat_g || !gt_area || !match || !iou))) { set_error("pq_match: null operand"); return PST_EINVAL; }
   const int64_t rows = (int64_t)nslabs * P, cols = (int64_t)nslabs * G;
   hipStream_t st = (hipStream_t)stream;
-  if (P > 0) hipLaunchKernelGGL(pq_pred_area_kernel, dim3((unsigned)((rows + EV_T / 64 - 1) / (EV_T / 64))), dim3(EV_T), 0, st, counts, rows, P, G, pred_area);
+  if (P > 0) hipLaunchKernelGGL(pq_pred_area_kernel, blocks_for(rows, EV_T / 64), dim3(EV_T), 0, st, counts, rows, P, G, pred_area);
   if (G > 0) {
-    const dim3 grid((unsigned)((cols + EV_T - 1) / EV_T));
+    const dim3 grid = blocks_for(cols, EV_T);
     hipLaunchKernelGGL(pq_gt_area_kernel, grid, dim3(EV_T), 0, st, counts, cols, P, G, gt_area);
     hipLaunchKernelGGL(pq_match_kernel, grid, dim3(EV_T), 0, st, counts, cols, P, G, cat_p, cat_g, pred_area, gt_area, match, iou);
   }
-  if (P > 0) hipLaunchKernelGGL(pq_state_kernel, dim3((unsigned)((rows + EV_T - 1) / EV_T)), dim3(EV_T), 0, st, counts, rows, P, G, pred_area, match, pred_state);
+  if (P > 0) hipLaunchKernelGGL(pq_state_kernel, blocks_for(rows, EV_T), dim3(EV_T), 0, st, counts, rows, P, G, pred_area, match, pred_state);
   return check_launch("pq_match");
 }

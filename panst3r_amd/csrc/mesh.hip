@@ -22,14 +22,11 @@
 // `precheck`: as render.hip's - a relaxed load of the cell first, the atomic only for a key below what the load saw.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
+#include "wave_ops.h"            // rn_mul, rn_add, rn_div, vx_run, id_row
 
 #pragma clang fp contract(off)
 
 namespace pst {
-
-__device__ __forceinline__ float ms_mulr(float a, float b) { return a * b; }
-__device__ __forceinline__ float ms_addr(float a, float b) { return a + b; }
-__device__ __forceinline__ float ms_divr(float a, float b) { return (float)((double)a / (double)b); }     // render.hip's rd_divr: fp64, rounded once
 
 constexpr int MS_T = 256;
 constexpr unsigned long long MS_EMPTY = ~0ull;
@@ -52,10 +49,10 @@ __device__ __forceinline__ bool ms_vertex(const float* __restrict__ c, const flo
   float pc[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a)
-    pc[a] = ms_addr(ms_addr(ms_addr(ms_mulr(c[4 * a + 0], x), ms_mulr(c[4 * a + 1], y)), ms_mulr(c[4 * a + 2], z)), c[4 * a + 3]);
+    pc[a] = rn_add(rn_add(rn_add(rn_mul(c[4 * a + 0], x), rn_mul(c[4 * a + 1], y)), rn_mul(c[4 * a + 2], z)), c[4 * a + 3]);
   zc = pc[2];
   if (!(fabsf(pc[0]) <= PST_FMAX && fabsf(pc[1]) <= PST_FMAX && fabsf(zc) <= PST_FMAX) || !(zc >= near)) return false;      // a NaN fails every compare
-  const float u = ms_addr(ms_divr(ms_mulr(c[12], pc[0]), zc), c[14]), v = ms_addr(ms_divr(ms_mulr(c[13], pc[1]), zc), c[15]);
+  const float u = rn_add(rn_div(rn_mul(c[12], pc[0]), zc), c[14]), v = rn_add(rn_div(rn_mul(c[13], pc[1]), zc), c[15]);
   if (!(fabsf(u) <= MS_LIM && fabsf(v) <= MS_LIM)) return false;
   X = (int)rintf(u * 256.f);                                        // the product is exact; rintf rounds half to even
   Y = (int)rintf(v * 256.f);
@@ -200,29 +197,20 @@ __global__ __launch_bounds__(MS_T) void mesh_resolve_kernel(const unsigned long 
 
 constexpr uint32_t MS_NONE = 0xffffffffu;
 
-__device__ __forceinline__ int ms_row(int id, const int32_t* __restrict__ tab, int ntab, int S) {      // evaluate.hip's ev_row: -1 = not listed
-  if (id <= 0 || id >= ntab) return -1;
-  const int r = tab[id];
-  return (r >= 0 && r < S) ? r : -1;
-}
-
 // counts[b, row] += 1 per pixel of a listed id.  Maps are piecewise constant and same-address atomics serialise: a run of adjacent lanes with one key
-// adds its length with one atomic from its first lane (evaluate.hip's merge).  Every lane takes part in the shuffle and the ballot.
+// adds its length with one atomic from its first lane (evaluate.hip's merge).  Every lane takes part in vx_run.
 __global__ __launch_bounds__(MS_T) void mesh_area_count_kernel(const int32_t* __restrict__ pan, int64_t npix, int64_t hw, const int32_t* __restrict__ id2row, int ntab,
                                                                int S, int32_t* __restrict__ counts) {
   const int lane = threadIdx.x & 63;
   const int64_t p = (int64_t)blockIdx.x * MS_T + threadIdx.x;
   uint32_t key = MS_NONE;
   if (p < npix) {
-    const int r = ms_row(pan[p], id2row, ntab, S);
+    const int r = id_row(pan[p], id2row, ntab, S, -1);                 // -1 = not listed
     if (r >= 0) key = (uint32_t)((p / hw) * S + r);                 // B S <= 2^31 - 1
   }
-  const uint32_t prev = __shfl_up(key, 1);
-  const uint64_t heads = __ballot(lane == 0 || prev != key);
-  if (((heads >> lane) & 1) && key != MS_NONE) {
-    const uint64_t above = lane == 63 ? 0ull : heads >> (lane + 1);
-    atomicAdd(&counts[key], above ? 1 + (int)__builtin_ctzll(above) : 64 - lane);
-  }
+  int head, tail;
+  vx_run(key, lane, head, tail);
+  if (lane == head && key != MS_NONE) atomicAdd(&counts[key], tail - head + 1);
 }
 
 __global__ __launch_bounds__(MS_T) void mesh_area_apply_kernel(const int32_t* __restrict__ pan, int64_t npix, int64_t hw, const int32_t* __restrict__ id2row, int ntab,
@@ -230,7 +218,7 @@ __global__ __launch_bounds__(MS_T) void mesh_area_apply_kernel(const int32_t* __
   const int64_t p = (int64_t)blockIdx.x * MS_T + threadIdx.x;
   if (p >= npix) return;
   const int id = pan[p];
-  const int r = ms_row(id, id2row, ntab, S);
+  const int r = id_row(id, id2row, ntab, S, -1);
   out[p] = (r >= 0 && counts[(p / hw) * S + r] >= min_area) ? id : 0;
 }
 
@@ -252,7 +240,7 @@ extern "C" int pst_mesh_raster(const float* vertices, int64_t Nv, const int32_t*
   }
   if (!(near_z > 0.f) || !(far_z > near_z) || !(far_z <= PST_FMAX)) { set_error("mesh_raster: needs 0 < near < far, finite; got %g, %g", (double)near_z, (double)far_z); return PST_EINVAL; }
   if (!vertices || !faces || !cams || !zbuf || !big_count || (big_capacity > 0 && !big)) { set_error("mesh_raster: null operand"); return PST_EINVAL; }
-  const dim3 grid((unsigned)((Nf + MS_T - 1) / MS_T), (unsigned)ncams);
+  const dim3 grid(blocks_for(Nf, MS_T).x, (unsigned)ncams);
   hipStream_t st = (hipStream_t)stream;
   unsigned long long *zb = (unsigned long long*)zbuf, *bg = (unsigned long long*)big, *bc = (unsigned long long*)big_count;
   if (precheck) hipLaunchKernelGGL(mesh_raster_kernel<true>, grid, dim3(MS_T), 0, st, vertices, Nv, faces, Nf, cams, H, W, near_z, far_z, zb, bg, bc, big_capacity);
@@ -278,7 +266,7 @@ extern "C" int pst_mesh_resolve(const uint64_t* zbuf, int ncams, int H, int W, c
   if (vertex_ids && face_ids) { set_error("mesh_resolve: vertex_ids and face_ids are exclusive"); return PST_EINVAL; }
   if (!zbuf || !vertices || !faces || !cams || !face || !depth || !pan) { set_error("mesh_resolve: null operand"); return PST_EINVAL; }
   const int64_t npix = (int64_t)ncams * H * W;
-  hipLaunchKernelGGL(mesh_resolve_kernel, dim3((unsigned)((npix + MS_T - 1) / MS_T)), dim3(MS_T), 0, (hipStream_t)stream, (const unsigned long long*)zbuf, npix, H, W,
+  hipLaunchKernelGGL(mesh_resolve_kernel, blocks_for(npix, MS_T), dim3(MS_T), 0, (hipStream_t)stream, (const unsigned long long*)zbuf, npix, H, W,
                      vertices, Nv, faces, Nf, cams, near_z, vertex_ids, face_ids, face, depth, pan);
   return check_launch("mesh_resolve");
 }
@@ -297,7 +285,7 @@ extern "C" int pst_mesh_area_count(const int32_t* pan, int ncams, int64_t hw, co
   using namespace pst;
   if (!ms_area_ok("mesh_area_count", pan, ncams, hw, id2row, ntab, S, counts)) return PST_EINVAL;
   const int64_t npix = ncams * hw;
-  hipLaunchKernelGGL(mesh_area_count_kernel, dim3((unsigned)((npix + MS_T - 1) / MS_T)), dim3(MS_T), 0, (hipStream_t)stream, pan, npix, hw, id2row, ntab, S, counts);
+  hipLaunchKernelGGL(mesh_area_count_kernel, blocks_for(npix, MS_T), dim3(MS_T), 0, (hipStream_t)stream, pan, npix, hw, id2row, ntab, S, counts);
   return check_launch("mesh_area_count");
 }
 
@@ -307,7 +295,7 @@ extern "C" int pst_mesh_area_apply(const int32_t* pan, int ncams, int64_t hw, co
   if (!ms_area_ok("mesh_area_apply", pan, ncams, hw, id2row, ntab, S, counts)) return PST_EINVAL;
   if (!out) { set_error("mesh_area_apply: null operand"); return PST_EINVAL; }
   const int64_t npix = ncams * hw;
-  hipLaunchKernelGGL(mesh_area_apply_kernel, dim3((unsigned)((npix + MS_T - 1) / MS_T)), dim3(MS_T), 0, (hipStream_t)stream, pan, npix, hw, id2row, ntab, S, counts,
+  hipLaunchKernelGGL(mesh_area_apply_kernel, blocks_for(npix, MS_T), dim3(MS_T), 0, (hipStream_t)stream, pan, npix, hw, id2row, ntab, S, counts,
                      min_area, out);
   return check_launch("mesh_area_apply");
 }

@@ -20,7 +20,7 @@
 // rounded on its own, in the order written.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
-#include "voxel_table.h"
+#include "voxel_table.h"         // and through it wave_ops.h: wave_count_add, wave_sum
 #include "mesh_face.h"
 #include "icp_sum.h"
 
@@ -31,8 +31,6 @@ namespace pst {
 constexpr int MD_T = 256;
 constexpr int64_t MD_MAX = 1ll << 30;                                // queries, faces and pairs of one call
 constexpr int64_t MD_FACE_CAP = PST_MESHDIST_FACE_CAP;               // a face's count saturates here: one such face is beyond every legal total
-
-static dim3 md_grid(int64_t n) { return dim3((unsigned)((n + MD_T - 1) / MD_T)); }
 
 // ---------------------------------------------------------------- the cell box of a face, its pairs
 // the cell box [lo, lo + ext) of a loaded face: cell(min corner) - 1 .. cell(max corner) + 1 per axis; false if a cell of it leaves (-2^20, 2^20)
@@ -60,7 +58,7 @@ __device__ __forceinline__ int64_t md_pairs(const float* __restrict__ vertices, 
 
 __global__ __launch_bounds__(MD_T) void meshdist_count_kernel(const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int F, float inv,
                                                               int32_t* __restrict__ counts, int64_t* __restrict__ total, int32_t* __restrict__ status) {
-  const int f = blockIdx.x * MD_T + threadIdx.x, lane = threadIdx.x & 63;
+  const int f = blockIdx.x * MD_T + threadIdx.x;
   int64_t c = 0;
   int dropped = 0;
   if (f < F) {
@@ -69,14 +67,9 @@ __global__ __launch_bounds__(MD_T) void meshdist_count_kernel(const float* __res
     dropped = c == 0;
     counts[f] = (int)c;
   }
-  const uint64_t md = __ballot(dropped);
-  int64_t sum = c;                                                  // 64 faces of at most 2^31 - 1 pairs
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor((long long)sum, o);
-  if (lane == 0) {
-    if (sum) atomicAdd((unsigned long long*)total, (unsigned long long)sum);
-    if (md) atomicAdd(&status[1], (int)__popcll(md));
-  }
+  const long long sum = wave_sum(c);                                 // 64 faces of at most 2^31 - 1 pairs
+  if ((threadIdx.x & 63) == 0 && sum) atomicAdd((unsigned long long*)total, (unsigned long long)sum);
+  wave_count_add(dropped, &status[1]);
 }
 
 __global__ __launch_bounds__(MD_T) void meshdist_insert_kernel(const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int F, float inv,
@@ -195,7 +188,7 @@ __global__ __launch_bounds__(MD_T) void meshdist_query_kernel(const float* __res
                                                               const int32_t* __restrict__ cell_count, const int32_t* __restrict__ rows, int P,
                                                               int max_cell_faces, float* __restrict__ d2_out, int32_t* __restrict__ face_out,
                                                               float* __restrict__ closest, int32_t* __restrict__ status) {
-  const int i = blockIdx.x * MD_T + threadIdx.x, lane = threadIdx.x & 63;
+  const int i = blockIdx.x * MD_T + threadIdx.x;
   const bool in = i < Nq;
   float x[3] = {0.f, 0.f, 0.f}, c[3];
   bool finite = true, ok = true;
@@ -204,8 +197,7 @@ __global__ __launch_bounds__(MD_T) void meshdist_query_kernel(const float* __res
     for (int a = 0; a < 3; ++a) x[a] = queries[(int64_t)i * 3 + a];
     vx_cell_of(x, inv, c, finite, ok);
   }
-  const uint64_t bad = __ballot(in && !finite);
-  if (bad && lane == (int)__builtin_ctzll(bad)) atomicAdd(&status[3], (int)__popcll(bad));
+  wave_count_add(in && !finite, &status[3]);
   if (!in) return;
   const double q[3] = {(double)x[0], (double)x[1], (double)x[2]};
   const uint64_t best = md_search(q, c, ok, vertices, Nv, faces, F, keys, mask, start, cell_count, rows, P, max_cell_faces, status);
@@ -318,7 +310,7 @@ extern "C" int pst_meshdist_count(const float* vertices, int64_t Nv, const int32
   using namespace pst;
   if (md_mesh_ok("meshdist_count", vertices, faces, Nv, F, inv)) return PST_EINVAL;
   if (!counts || !total || !status) { set_error("meshdist_count: null operand"); return PST_EINVAL; }
-  hipLaunchKernelGGL(meshdist_count_kernel, md_grid(F), dim3(MD_T), 0, (hipStream_t)stream, vertices, (int)Nv, faces, (int)F, inv, counts, total, status);
+  hipLaunchKernelGGL(meshdist_count_kernel, blocks_for(F, MD_T), dim3(MD_T), 0, (hipStream_t)stream, vertices, (int)Nv, faces, (int)F, inv, counts, total, status);
   return check_launch("meshdist_count");
 }
 
@@ -327,7 +319,7 @@ extern "C" int pst_meshdist_insert(const float* vertices, int64_t Nv, const int3
   using namespace pst;
   if (md_mesh_ok("meshdist_insert", vertices, faces, Nv, F, inv) || vx_table_ok("meshdist_insert", total, MD_MAX, capacity, "total", "1 .. 2^30 pairs")) return PST_EINVAL;
   if (!prefix || !keys || !cell_count || !pair_slot || !status) { set_error("meshdist_insert: null operand"); return PST_EINVAL; }
-  hipLaunchKernelGGL(meshdist_insert_kernel, md_grid(total), dim3(MD_T), 0, (hipStream_t)stream, vertices, (int)Nv, faces, (int)F, inv, prefix, (int)total,
+  hipLaunchKernelGGL(meshdist_insert_kernel, blocks_for(total, MD_T), dim3(MD_T), 0, (hipStream_t)stream, vertices, (int)Nv, faces, (int)F, inv, prefix, (int)total,
                      keys, (uint32_t)(capacity - 1), cell_count, pair_slot, status);
   return check_launch("meshdist_insert");
 }
@@ -338,7 +330,7 @@ extern "C" int pst_meshdist_scatter(const int32_t* pair_slot, const int32_t* pre
   if (!pair_slot || !prefix || !start || !cell_count || !fill || !rows || !status || F <= 0 || F > MD_MAX || total <= 0 || total > MD_MAX) {
     set_error("meshdist_scatter: bad shape (F=%lld, total=%lld: 1 .. 2^30) or null operand", (long long)F, (long long)total); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(meshdist_scatter_kernel, md_grid(total), dim3(MD_T), 0, (hipStream_t)stream, pair_slot, prefix, (int)F, (int)total, start, cell_count,
+  hipLaunchKernelGGL(meshdist_scatter_kernel, blocks_for(total, MD_T), dim3(MD_T), 0, (hipStream_t)stream, pair_slot, prefix, (int)F, (int)total, start, cell_count,
                      fill, rows, status);
   return check_launch("meshdist_scatter");
 }
@@ -354,7 +346,7 @@ extern "C" int pst_meshdist_query(const float* queries, int64_t Nq, const float*
               (long long)Nq, (double)r2, max_cell_faces);
     return PST_EINVAL;
   }
-  hipLaunchKernelGGL(meshdist_query_kernel, md_grid(Nq), dim3(MD_T), 0, (hipStream_t)stream, queries, (int)Nq, vertices, (int)Nv, faces, (int)F, inv, r2, keys,
+  hipLaunchKernelGGL(meshdist_query_kernel, blocks_for(Nq, MD_T), dim3(MD_T), 0, (hipStream_t)stream, queries, (int)Nq, vertices, (int)Nv, faces, (int)F, inv, r2, keys,
                      (uint32_t)(capacity - 1), start, cell_count, rows, (int)total, max_cell_faces, d2, face, closest, status);
   return check_launch("meshdist_query");
 }

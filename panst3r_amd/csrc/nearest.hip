@@ -20,7 +20,7 @@
 // whole file: every fp32 and fp64 operation is rounded on its own, in the order written.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
-#include "voxel_table.h"
+#include "voxel_table.h"         // and through it wave_ops.h: rn_mul / rn_add / rn_sub, wave_count_add, wave_sum
 #include "mesh_face.h"
 #include "icp_sum.h"
 
@@ -31,8 +31,6 @@ namespace pst {
 constexpr int NN_T = 256;
 constexpr int MS_MAX_SUBDIV = PST_MESH_SAMPLE_MAX_SUBDIV;
 static_assert(MS_MAX_SUBDIV == 1 << 15, "n^2 and 3n stay inside int32");
-
-static dim3 nn_grid(int64_t n) { return dim3((unsigned)((n + NN_T - 1) / NN_T)); }
 
 // ---------------------------------------------------------------- mesh surface sampler
 __device__ __forceinline__ double ms_edge2(const double (&a)[3], const double (&b)[3]) {
@@ -63,22 +61,17 @@ __device__ __forceinline__ int ms_count(const MeshFace& t, double s2, int max_su
 __global__ __launch_bounds__(NN_T) void mesh_sample_count_kernel(const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int F,
                                                                  double s2, int max_subdiv, int32_t* __restrict__ counts, int64_t* __restrict__ total,
                                                                  int32_t* __restrict__ status) {
-  const int f = blockIdx.x * NN_T + threadIdx.x, lane = threadIdx.x & 63;
+  const int f = blockIdx.x * NN_T + threadIdx.x;
   int c = 0, clamped = 0, dropped = 0;
   if (f < F) {
     c = ms_count(mf_load(vertices, Nv, faces, f), s2, max_subdiv, clamped);
     dropped = c == 0;
     counts[f] = c;
   }
-  const uint64_t md = __ballot(dropped), mc = __ballot(clamped);
-  int64_t sum = c;                                                  // 64 faces of at most 2^30 samples
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor((long long)sum, o);
-  if (lane == 0) {
-    if (sum) atomicAdd((unsigned long long*)total, (unsigned long long)sum);
-    if (md) atomicAdd(&status[1], (int)__popcll(md));
-    if (mc) atomicAdd(&status[2], (int)__popcll(mc));
-  }
+  const long long sum = wave_sum(c);                                 // 64 faces of at most 2^30 samples
+  if ((threadIdx.x & 63) == 0 && sum) atomicAdd((unsigned long long*)total, (unsigned long long)sum);
+  wave_count_add(dropped, &status[1]);
+  wave_count_add(clamped, &status[2]);
 }
 
 __global__ __launch_bounds__(NN_T) void mesh_sample_emit_kernel(const float* __restrict__ vertices, int Nv, const int32_t* __restrict__ faces, int F,
@@ -120,10 +113,6 @@ __global__ __launch_bounds__(NN_T) void mesh_sample_emit_kernel(const float* __r
 }
 
 // ---------------------------------------------------------------- fixed-radius nearest neighbour
-__device__ __forceinline__ float nn_mulr(float a, float b) { return a * b; }
-__device__ __forceinline__ float nn_addr(float a, float b) { return a + b; }
-__device__ __forceinline__ float nn_subr(float a, float b) { return a - b; }
-
 __device__ __forceinline__ void nn_cell(const float* __restrict__ p, float inv, float (&x)[3], float (&c)[3], bool& finite, bool& ok) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) x[a] = p[a];
@@ -132,13 +121,12 @@ __device__ __forceinline__ void nn_cell(const float* __restrict__ p, float inv, 
 
 __global__ __launch_bounds__(NN_T) void nn_insert_kernel(const float* __restrict__ targets, int M, float inv, uint64_t* __restrict__ keys, uint32_t mask,
                                                          int32_t* __restrict__ cell_count, int32_t* __restrict__ point_slot, int32_t* __restrict__ status) {
-  const int i = blockIdx.x * NN_T + threadIdx.x, lane = threadIdx.x & 63;
+  const int i = blockIdx.x * NN_T + threadIdx.x;
   const bool in = i < M;
   float x[3], c[3];
   bool finite = false, ok = false;
   if (in) nn_cell(targets + (int64_t)i * 3, inv, x, c, finite, ok);
-  const uint64_t dropped = __ballot(in && !ok);
-  if (dropped && lane == (int)__builtin_ctzll(dropped)) atomicAdd(&status[1], (int)__popcll(dropped));
+  wave_count_add(in && !ok, &status[1]);
   if (!in) return;
   int slot = -1;
   if (ok) {
@@ -178,9 +166,9 @@ __device__ __forceinline__ uint64_t nn_search(const float (&q)[3], const float (
       for (int j = 0; j < cnt; ++j) {
         const int p = rows[b + j];
         if ((unsigned)p >= (unsigned)M) { atomicOr(&status[0], PST_NN_LISTS); continue; }
-        const float dx = nn_subr(q[0], targets[(int64_t)p * 3]), dy = nn_subr(q[1], targets[(int64_t)p * 3 + 1]),
-                    dz = nn_subr(q[2], targets[(int64_t)p * 3 + 2]);
-        const float d2 = nn_addr(nn_addr(nn_mulr(dx, dx), nn_mulr(dy, dy)), nn_mulr(dz, dz));      // >= +0, never NaN: its bits order as an unsigned integer
+        const float dx = rn_sub(q[0], targets[(int64_t)p * 3]), dy = rn_sub(q[1], targets[(int64_t)p * 3 + 1]),
+                    dz = rn_sub(q[2], targets[(int64_t)p * 3 + 2]);
+        const float d2 = rn_add(rn_add(rn_mul(dx, dx), rn_mul(dy, dy)), rn_mul(dz, dz));      // >= +0, never NaN: its bits order as an unsigned integer
         const uint64_t cand = ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)p;
         best = cand < best ? cand : best;
       }
@@ -193,13 +181,12 @@ __global__ __launch_bounds__(NN_T) void nn_query_kernel(const float* __restrict_
                                                         float r2, const uint64_t* __restrict__ keys, uint32_t mask, const int32_t* __restrict__ start,
                                                         const int32_t* __restrict__ cell_count, const int32_t* __restrict__ rows, int max_cell_points,
                                                         float* __restrict__ d2_out, int32_t* __restrict__ row_out, int32_t* __restrict__ status) {
-  const int i = blockIdx.x * NN_T + threadIdx.x, lane = threadIdx.x & 63;
+  const int i = blockIdx.x * NN_T + threadIdx.x;
   const bool in = i < Nq;
   float q[3], c[3];
   bool finite = false, ok = false;
   if (in) nn_cell(queries + (int64_t)i * 3, inv, q, c, finite, ok);
-  const uint64_t bad = __ballot(in && !finite);
-  if (bad && lane == (int)__builtin_ctzll(bad)) atomicAdd(&status[3], (int)__popcll(bad));
+  wave_count_add(in && !finite, &status[3]);
   if (!in) return;
   const uint64_t best = nn_search(q, c, finite, targets, M, keys, mask, start, cell_count, rows, max_cell_points, status);
   const float d2 = __uint_as_float((uint32_t)(best >> 32));
@@ -274,7 +261,7 @@ extern "C" int pst_mesh_sample_count(const float* vertices, int64_t Nv, const in
     return PST_EINVAL;
   }
   const double s2 = (double)spacing * (double)spacing;              // exact: two 24-bit significands
-  hipLaunchKernelGGL(mesh_sample_count_kernel, nn_grid(F), dim3(NN_T), 0, (hipStream_t)stream, vertices, (int)Nv, faces, (int)F, s2, max_subdiv, counts, total,
+  hipLaunchKernelGGL(mesh_sample_count_kernel, blocks_for(F, NN_T), dim3(NN_T), 0, (hipStream_t)stream, vertices, (int)Nv, faces, (int)F, s2, max_subdiv, counts, total,
                      status);
   return check_launch("mesh_sample_count");
 }
@@ -293,7 +280,7 @@ extern "C" int pst_mesh_sample_emit(const float* vertices, int64_t Nv, const int
               (long long)total, (long long)capacity);
     return PST_EINVAL;
   }
-  hipLaunchKernelGGL(mesh_sample_emit_kernel, nn_grid(total), dim3(NN_T), 0, (hipStream_t)stream, vertices, (int)Nv, faces, (int)F, prefix, (int)total,
+  hipLaunchKernelGGL(mesh_sample_emit_kernel, blocks_for(total, NN_T), dim3(NN_T), 0, (hipStream_t)stream, vertices, (int)Nv, faces, (int)F, prefix, (int)total,
                      vertex_ids, face_ids, points, face, ids, status);
   return check_launch("mesh_sample_emit");
 }
@@ -305,7 +292,7 @@ extern "C" int pst_nn_insert(const float* targets, int64_t M, float inv, uint64_
   if (!targets || !keys || !cell_count || !point_slot || !status || !(inv > 0.f) || !(inv <= PST_FMAX)) {
     set_error("nn_insert: inverse radius %g (positive, finite) or null operand", (double)inv); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(nn_insert_kernel, nn_grid(M), dim3(NN_T), 0, (hipStream_t)stream, targets, (int)M, inv, keys, (uint32_t)(capacity - 1), cell_count,
+  hipLaunchKernelGGL(nn_insert_kernel, blocks_for(M, NN_T), dim3(NN_T), 0, (hipStream_t)stream, targets, (int)M, inv, keys, (uint32_t)(capacity - 1), cell_count,
                      point_slot, status);
   return check_launch("nn_insert");
 }
@@ -316,7 +303,7 @@ extern "C" int pst_nn_scatter(const int32_t* point_slot, int64_t M, const int32_
   if (!point_slot || !start || !cell_count || !fill || !rows || !status || M <= 0 || M > NN_MAX_POINTS) {
     set_error("nn_scatter: bad shape (M=%lld) or null operand", (long long)M); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(nn_scatter_kernel, nn_grid(M), dim3(NN_T), 0, (hipStream_t)stream, point_slot, (int)M, start, cell_count, fill, rows, status);
+  hipLaunchKernelGGL(nn_scatter_kernel, blocks_for(M, NN_T), dim3(NN_T), 0, (hipStream_t)stream, point_slot, (int)M, start, cell_count, fill, rows, status);
   return check_launch("nn_scatter");
 }
 
@@ -331,7 +318,7 @@ extern "C" int pst_nn_query(const float* queries, int64_t Nq, const float* targe
               (long long)Nq, (double)inv, (double)r2, max_cell_points);
     return PST_EINVAL;
   }
-  hipLaunchKernelGGL(nn_query_kernel, nn_grid(Nq), dim3(NN_T), 0, (hipStream_t)stream, queries, (int)Nq, targets, (int)M, inv, r2, keys,
+  hipLaunchKernelGGL(nn_query_kernel, blocks_for(Nq, NN_T), dim3(NN_T), 0, (hipStream_t)stream, queries, (int)Nq, targets, (int)M, inv, r2, keys,
                      (uint32_t)(capacity - 1), start, cell_count, rows, max_cell_points, d2, row, status);
   return check_launch("nn_query");
 }

@@ -6,7 +6,7 @@
 //            orders as an unsigned integer: the smallest key is the nearest point, equal depths go to the smallest row.
 //   resolve  one thread per pixel: the winner's row and depth out of the key, pan / rgb / colors gathered from that row, plain vector stores.
 // The arithmetic is part of the contract (include/panst3r_hip.h): contraction is off for the whole file, every fp32 product and sum is rounded on
-// its own, and the perspective quotient is taken in fp64 and rounded once (rd_divr).  INTEGER atomics only: the buffer's final state is the minimum
+// its own, and the perspective quotient is taken in fp64 and rounded once (rn_div of wave_ops.h).  INTEGER atomics only: the buffer's final state is the minimum
 // over a fixed set of keys, whatever the schedule - two calls return identical bytes.
 // `precheck`: the buffer has far fewer cells than the cloud has points (9.8 M points on 0.2 M pixels at the benchmark's scene size), so most
 // candidates lose.  A relaxed device-scope load of the cell first, and the atomic only for a key that is smaller than what the load saw, trades
@@ -17,19 +17,11 @@
 // coalesced read of the buffer plus scattered 28-byte gathers and 44 bytes of stores per pixel: bound by the gathers' latency, small next to splat.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
+#include "wave_ops.h"            // rn_mul, rn_add, rn_div
 
 #pragma clang fp contract(off)
 
 namespace pst {
-
-// separately rounded operations (see csrc/cloud.hip: written under the pragma above so that no multiply-add is formed from them)
-__device__ __forceinline__ float rd_mulr(float a, float b) { return a * b; }
-__device__ __forceinline__ float rd_addr(float a, float b) { return a + b; }
-// the contract's quotient: fp64 division rounded once to fp32.  (For two fp32 operands that IS the correctly rounded fp32 quotient - 53 >= 2 x 24 + 2
-// bits make the double rounding innocuous - and numpy's float32 division gives the same.  hipcc does narrow it: the gfx950 code holds, per quotient,
-// v_div_scale_f32 x2 / v_rcp_f32 / five fma / v_div_fmas_f32 / v_div_fixup_f32, the IEEE expansion, with fp32 denormals on (float_denorm_mode_32 = 3)
-// and no fast-math flag in the build - the same value by either route, which is why the contract can name the fp64 form.)
-__device__ __forceinline__ float rd_divr(float a, float b) { return (float)((double)a / (double)b); }
 
 constexpr int RD_T = 256;
 constexpr unsigned long long RD_EMPTY = ~0ull;                     // no key is all ones: bits(zc) = 0xFFFFFFFF is a NaN, and a NaN is culled
@@ -46,15 +38,15 @@ __global__ __launch_bounds__(RD_T) void render_splat_kernel(const float* __restr
   float pc[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a)
-    pc[a] = rd_addr(rd_addr(rd_addr(rd_mulr(c[4 * a + 0], x), rd_mulr(c[4 * a + 1], y)), rd_mulr(c[4 * a + 2], z)), c[4 * a + 3]);
+    pc[a] = rn_add(rn_add(rn_add(rn_mul(c[4 * a + 0], x), rn_mul(c[4 * a + 1], y)), rn_mul(c[4 * a + 2], z)), c[4 * a + 3]);
   const float f = c[12], cx = c[13], cy = c[14], near = c[15];
   const float zc = pc[2];
   if (!(fabsf(pc[0]) <= PST_FMAX && fabsf(pc[1]) <= PST_FMAX && fabsf(zc) <= PST_FMAX) || !(zc >= near)) return;      // a NaN fails every compare
-  const float u = rd_addr(rd_divr(rd_mulr(f, pc[0]), zc), cx), v = rd_addr(rd_divr(rd_mulr(f, pc[1]), zc), cy);
+  const float u = rn_add(rn_div(rn_mul(f, pc[0]), zc), cx), v = rn_add(rn_div(rn_mul(f, pc[1]), zc), cy);
   if (!(fabsf(u) <= RD_LIM && fabsf(v) <= RD_LIM)) return;
   const int px = (int)floorf(u), py = (int)floorf(v);
   // r = min(max_radius, max(radius, floor(f half_size / zc))): the quotient is >= 0 (or +inf), clamped as a float before it becomes an int
-  const int rs = (int)fminf(floorf(rd_divr(rd_mulr(f, half_size), zc)), (float)max_radius);
+  const int rs = (int)fminf(floorf(rn_div(rn_mul(f, half_size), zc)), (float)max_radius);
   const int r = min(max_radius, max(radius, rs));
   const int x0 = max(px - r, 0), x1 = min(px + r, W - 1), y0 = max(py - r, 0), y1 = min(py + r, H - 1);                // |px|, |py| <= 2^20: no overflow
   if (x0 > x1 || y0 > y1) return;
@@ -105,7 +97,7 @@ extern "C" int pst_render_splat(const float* points, int64_t M, const float* cam
     return PST_EINVAL;
   }
   if (!points || !cams || !zbuf) { set_error("render_splat: null operand"); return PST_EINVAL; }
-  const dim3 grid((unsigned)((M + RD_T - 1) / RD_T), (unsigned)ncams);
+  const dim3 grid(blocks_for(M, RD_T).x, (unsigned)ncams);
   if (precheck) hipLaunchKernelGGL(render_splat_kernel<true>, grid, dim3(RD_T), 0, (hipStream_t)stream, points, M, cams, H, W, half_size, radius, max_radius,
                                    (unsigned long long*)zbuf);
   else hipLaunchKernelGGL(render_splat_kernel<false>, grid, dim3(RD_T), 0, (hipStream_t)stream, points, M, cams, H, W, half_size, radius, max_radius,
@@ -120,7 +112,7 @@ extern "C" int pst_render_resolve(const uint64_t* zbuf, int64_t npix, int64_t M,
     set_error("render_resolve: bad shape (%lld pixels in [1, 2^31 - 1], M=%lld in [1, 2^32 - 1])", (long long)npix, (long long)M); return PST_EINVAL;
   }
   if (!zbuf || !rgb || !colors || !pan || !index || !depth || !out_pan || !out_rgb || !out_colors) { set_error("render_resolve: null operand"); return PST_EINVAL; }
-  hipLaunchKernelGGL(render_resolve_kernel, dim3((unsigned)((npix + RD_T - 1) / RD_T)), dim3(RD_T), 0, (hipStream_t)stream, (const unsigned long long*)zbuf, npix, M,
+  hipLaunchKernelGGL(render_resolve_kernel, blocks_for(npix, RD_T), dim3(RD_T), 0, (hipStream_t)stream, (const unsigned long long*)zbuf, npix, M,
                      rgb, colors, pan, index, depth, out_pan, out_rgb, out_colors);
   return check_launch("render_resolve");
 }

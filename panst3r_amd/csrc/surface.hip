@@ -18,6 +18,7 @@
 #include "common.h"
 #include "../../include/panst3r_hip.h"
 #include "union_find.h"
+#include "wave_ops.h"            // rn_mul, rn_sub, wg_rank, last_le
 
 #pragma clang fp contract(off)
 
@@ -26,17 +27,9 @@ namespace pst {
 constexpr int SF_T = PST_SURFACE_WG;                               // threads = quads (or faces) per workgroup
 static_assert(SF_T == 256, "four waves per workgroup");
 
-__device__ __forceinline__ float sf_mulr(float a, float b) { return a * b; }
-__device__ __forceinline__ float sf_subr(float a, float b) { return a - b; }
-
 // the view that owns quad workgroup wg: the last one whose first workgroup is <= wg (a view without quads owns none).  dims int32 [V, 4] = H, W, first_wg, 0
 __device__ __forceinline__ int sf_view_of(const int32_t* __restrict__ dims, int nviews, int wg) {
-  int lo = 0, hi = nviews - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (dims[mid * 4 + 2] <= wg) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  return last_le(nviews, wg, [&](int v) { return dims[v * 4 + 2]; });
 }
 
 template <typename T>
@@ -60,7 +53,7 @@ __device__ __forceinline__ SfTri sf_triangle(int code, const int (&r)[4], const 
   }
   const bool pos = zz[0] > 0.f && zz[1] > 0.f && zz[2] > 0.f;      // no NaN beyond this point
   const float zmin = fminf(fminf(zz[0], zz[1]), zz[2]), zmax = fmaxf(fmaxf(zz[0], zz[1]), zz[2]);
-  t.keep = pos && zmax <= sf_mulr(zmin, k);
+  t.keep = pos && zmax <= rn_mul(zmin, k);
   return t;
 }
 
@@ -89,7 +82,7 @@ __device__ __forceinline__ SfQuad sf_quad(const pst_cloud_view* __restrict__ vie
     if (r[c] >= 0) { z[c] = loc[(int64_t)px[c] * 3 + 2]; ++n; }
   }
   if (n == 4) {
-    const bool bc = fabsf(sf_subr(z[1], z[2])) < fabsf(sf_subr(z[0], z[3]));      // a tie or a NaN: diagonal a-d
+    const bool bc = fabsf(rn_sub(z[1], z[2])) < fabsf(rn_sub(z[0], z[3]));      // a tie or a NaN: diagonal a-d
     q.t[0] = sf_triangle(bc ? SF_ACB : SF_ACD, r, z, k);
     q.t[1] = sf_triangle(bc ? SF_BCD : SF_ADB, r, z, k);
   } else if (n == 3) {
@@ -97,23 +90,6 @@ __device__ __forceinline__ SfQuad sf_quad(const pst_cloud_view* __restrict__ vie
     q.t[0] = sf_triangle(code, r, z, k);
   }
   return q;
-}
-
-__device__ __forceinline__ int sf_below(uint64_t b) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0)); }
-
-// slot of this lane's first item inside the workgroup when it holds n0 + n1 items (each 0 or 1), and the workgroup's total (valid after the barrier inside)
-__device__ __forceinline__ int sf_slot(int n0, int n1, int* wtot, int& total) {
-  const uint64_t m0 = __ballot(n0), m1 = __ballot(n1);
-  int slot = sf_below(m0) + sf_below(m1);
-  if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = __popcll(m0) + __popcll(m1);
-  __syncthreads();
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < SF_T / 64; ++w) {
-    if (w < (int)(threadIdx.x >> 6)) slot += wtot[w];
-    total += wtot[w];
-  }
-  return slot;
 }
 
 __global__ __launch_bounds__(SF_T) void surface_fill_kernel(int32_t* __restrict__ row, int64_t n) {
@@ -133,7 +109,7 @@ __global__ __launch_bounds__(SF_T) void surface_count_kernel(const pst_cloud_vie
   __shared__ int wtot[SF_T / 64];
   const SfQuad q = sf_quad(views, dims, nviews, blockIdx.x, threadIdx.x, row, k);
   int total;
-  sf_slot(q.t[0].keep, q.t[1].keep, wtot, total);
+  wg_rank<SF_T, 2>(q.t[0].keep | q.t[1].keep << 1, wtot, total);   // two items per lane: T0, then T1
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
@@ -148,7 +124,7 @@ __global__ __launch_bounds__(SF_T) void surface_emit_kernel(const pst_cloud_view
   if (base[blockIdx.x + 1] == (int)b0) return;                      // uniform: nothing to write
   const SfQuad q = sf_quad(views, dims, nviews, blockIdx.x, threadIdx.x, row, k);
   int total;
-  int64_t s = b0 + sf_slot(q.t[0].keep, q.t[1].keep, wtot, total);
+  int64_t s = b0 + wg_rank<SF_T, 2>(q.t[0].keep | q.t[1].keep << 1, wtot, total);
 #pragma unroll
   for (int j = 0; j < 2; ++j)
     if (q.t[j].keep) {
@@ -200,7 +176,7 @@ __global__ __launch_bounds__(SF_T) void surface_keep_count_kernel(const int32_t*
                                                                   int32_t* __restrict__ counts) {
   __shared__ int wtot[SF_T / 64];
   int total;
-  sf_slot(sf_survives(component, size, F, min_faces, blockIdx.x * SF_T + threadIdx.x), 0, wtot, total);
+  wg_rank<SF_T, 1>(sf_survives(component, size, F, min_faces, blockIdx.x * SF_T + threadIdx.x), wtot, total);
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
@@ -212,7 +188,7 @@ __global__ __launch_bounds__(SF_T) void surface_keep_emit_kernel(const int32_t* 
   const int f = blockIdx.x * SF_T + threadIdx.x;
   const int keep = sf_survives(component, size, F, min_faces, f);
   int total;
-  const int64_t s = (int64_t)base[blockIdx.x] + sf_slot(keep, 0, wtot, total);
+  const int64_t s = (int64_t)base[blockIdx.x] + wg_rank<SF_T, 1>(keep, wtot, total);
   if (!keep) return;
 #pragma unroll
   for (int j = 0; j < 3; ++j) out_faces[s * 3 + j] = faces[(int64_t)f * 3 + j];
@@ -221,7 +197,6 @@ __global__ __launch_bounds__(SF_T) void surface_keep_emit_kernel(const int32_t* 
 }
 
 constexpr int64_t SF_MAX_PIXELS = 1ll << 30, SF_MAX_FACES = 0x7fffff00ll;       // (a grid of 256-thread workgroups over F faces stays inside int32)
-static dim3 sf_grid(int64_t n) { return dim3((unsigned)((n + SF_T - 1) / SF_T)); }
 static bool sf_faces_ok(int64_t F, int64_t M) { return F > 0 && F <= SF_MAX_FACES && M > 0 && M <= SF_MAX_PIXELS; }
 
 }  // namespace pst
@@ -231,10 +206,10 @@ extern "C" int pst_surface_rows(const int64_t* index, int64_t M, int64_t N, int3
   if (!row || N <= 0 || N > SF_MAX_PIXELS || M < 0 || M > N || (M > 0 && !index)) {
     set_error("surface_rows: bad shape (M=%lld, N=%lld: at most 2^30 pixels) or null operand", (long long)M, (long long)N); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(surface_fill_kernel, sf_grid(N), dim3(SF_T), 0, (hipStream_t)stream, row, N);
+  hipLaunchKernelGGL(surface_fill_kernel, blocks_for(N, SF_T), dim3(SF_T), 0, (hipStream_t)stream, row, N);
   const int rc = check_launch("surface_rows (fill)");
   if (rc || M == 0) return rc;
-  hipLaunchKernelGGL(surface_rows_kernel, sf_grid(M), dim3(SF_T), 0, (hipStream_t)stream, index, (int)M, N, row);
+  hipLaunchKernelGGL(surface_rows_kernel, blocks_for(M, SF_T), dim3(SF_T), 0, (hipStream_t)stream, index, (int)M, N, row);
   return check_launch("surface_rows");
 }
 
@@ -269,10 +244,10 @@ extern "C" int pst_surface_link(const int32_t* faces, int64_t F, int64_t M, int3
   if (!faces || !parent || !size || !status || !sf_faces_ok(F, M)) {
     set_error("surface_link: bad shape (F=%lld, M=%lld) or null operand", (long long)F, (long long)M); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(surface_parent_kernel, sf_grid(M), dim3(SF_T), 0, (hipStream_t)stream, parent, size, (int)M);
+  hipLaunchKernelGGL(surface_parent_kernel, blocks_for(M, SF_T), dim3(SF_T), 0, (hipStream_t)stream, parent, size, (int)M);
   const int rc = check_launch("surface_link (parent)");
   if (rc) return rc;
-  hipLaunchKernelGGL(surface_link_kernel, sf_grid(F), dim3(SF_T), 0, (hipStream_t)stream, faces, (int)F, (int)M, parent, status);
+  hipLaunchKernelGGL(surface_link_kernel, blocks_for(F, SF_T), dim3(SF_T), 0, (hipStream_t)stream, faces, (int)F, (int)M, parent, status);
   return check_launch("surface_link");
 }
 
@@ -282,7 +257,7 @@ extern "C" int pst_surface_components(const int32_t* faces, int64_t F, int64_t M
   if (!faces || !parent || !component || !size || !status || !sf_faces_ok(F, M)) {
     set_error("surface_components: bad shape (F=%lld, M=%lld) or null operand", (long long)F, (long long)M); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(surface_root_kernel, sf_grid(F), dim3(SF_T), 0, (hipStream_t)stream, faces, (int)F, (int)M, parent, component, size, status);
+  hipLaunchKernelGGL(surface_root_kernel, blocks_for(F, SF_T), dim3(SF_T), 0, (hipStream_t)stream, faces, (int)F, (int)M, parent, component, size, status);
   return check_launch("surface_components");
 }
 
@@ -291,7 +266,7 @@ extern "C" int pst_surface_keep_count(const int32_t* component, const int32_t* s
   if (!component || !size || !counts || F <= 0 || F > SF_MAX_FACES || min_faces < 1) {
     set_error("surface_keep_count: bad shape (F=%lld), min_faces %d or null operand", (long long)F, min_faces); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(surface_keep_count_kernel, sf_grid(F), dim3(SF_T), 0, (hipStream_t)stream, component, size, (int)F, min_faces, counts);
+  hipLaunchKernelGGL(surface_keep_count_kernel, blocks_for(F, SF_T), dim3(SF_T), 0, (hipStream_t)stream, component, size, (int)F, min_faces, counts);
   return check_launch("surface_keep_count");
 }
 
@@ -302,7 +277,7 @@ extern "C" int pst_surface_keep_emit(const int32_t* faces, const int32_t* face_i
       min_faces < 1) {
     set_error("surface_keep_emit: bad shape (F=%lld), min_faces %d or null operand", (long long)F, min_faces); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(surface_keep_emit_kernel, sf_grid(F), dim3(SF_T), 0, (hipStream_t)stream, faces, face_ids, quad, component, size, (int)F, min_faces, base,
+  hipLaunchKernelGGL(surface_keep_emit_kernel, blocks_for(F, SF_T), dim3(SF_T), 0, (hipStream_t)stream, faces, face_ids, quad, component, size, (int)F, min_faces, base,
                      out_faces, out_face_ids, out_quad);
   return check_launch("surface_keep_emit");
 }

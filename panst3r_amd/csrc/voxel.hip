@@ -15,15 +15,11 @@
 // atomics - the run's first lane inserts, its last lane adds the run's sums (a wave-wide prefix sum, differenced at the run's ends).  Same results.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
-#include "voxel_table.h"
+#include "voxel_table.h"         // and through it wave_ops.h: rn_mul / rn_add / rn_sub, wg_rank, wave_scan, vx_run, wave_count_add
 
 #pragma clang fp contract(off)
 
 namespace pst {
-
-__device__ __forceinline__ float vx_mulr(float a, float b) { return a * b; }
-__device__ __forceinline__ float vx_addr(float a, float b) { return a + b; }
-__device__ __forceinline__ float vx_subr(float a, float b) { return a - b; }
 
 constexpr int VX_T = 256, VX_PT = 4, VX_WG = VX_T * VX_PT;         // count / rank: the 1024-point workgroups of pst_cloud_scan's callers
 constexpr int VX_MAX_COLORS = 4096;
@@ -34,7 +30,7 @@ __device__ __forceinline__ bool vx_cell(const float* __restrict__ p, float inv, 
   bool finite, ok;
   vx_cell_of(x, inv, c, finite, ok);
 #pragma unroll
-  for (int a = 0; a < 3; ++a) q[a] = (int)floorf(vx_mulr(vx_subr(vx_mulr(x[a], inv), c[a]), 65536.f));      // t = x * inv: the product vx_cell_of floors
+  for (int a = 0; a < 3; ++a) q[a] = (int)floorf(rn_mul(rn_sub(rn_mul(x[a], inv), c[a]), 65536.f));      // t = x * inv: the product vx_cell_of floors
   return ok;
 }
 
@@ -47,8 +43,7 @@ __global__ __launch_bounds__(VX_T) void voxel_insert_kernel(const float* __restr
   bool ok = false;
   if (in) ok = vx_cell(points + (int64_t)i * 3, inv, c, q);
   const uint64_t key = ok ? vx_key((int)c[0], (int)c[1], (int)c[2]) : VX_EMPTY;
-  const uint64_t dropped = __ballot(in && !ok);
-  if (dropped && lane == (int)__builtin_ctzll(dropped)) atomicAdd(&status[1], (int)__popcll(dropped));
+  wave_count_add(in && !ok, &status[1]);
   int slot = -1;
   if constexpr (MERGE) {
     int head, tail;
@@ -77,26 +72,12 @@ __device__ __forceinline__ int vx_first_mask(const int32_t* __restrict__ point_s
   return m;
 }
 
-__device__ __forceinline__ int vx_lane_prefix(int m, int& total) {
-  int pre = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < VX_PT; ++k) {
-    const uint64_t b = __ballot((m >> k) & 1);
-    pre += __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0));
-    total += __popcll(b);
-  }
-  return pre;
-}
-
 __global__ __launch_bounds__(VX_T) void voxel_count_kernel(const int32_t* __restrict__ point_slot, const int32_t* __restrict__ first, int M,
                                                            int32_t* __restrict__ counts) {
   __shared__ int wtot[VX_T / 64];
   int total;
-  vx_lane_prefix(vx_first_mask(point_slot, first, M, blockIdx.x * VX_WG + threadIdx.x * VX_PT), total);
-  if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = total;
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+  wg_rank<VX_T, VX_PT>(vx_first_mask(point_slot, first, M, blockIdx.x * VX_WG + threadIdx.x * VX_PT), wtot, total);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 // rank of every first point = workgroup base + wave base + lane prefix (stable: ranks follow the rows) -> slot_rank[slot], first_row[rank]
@@ -106,11 +87,7 @@ __global__ __launch_bounds__(VX_T) void voxel_rank_kernel(const int32_t* __restr
   const int tid = threadIdx.x, i0 = blockIdx.x * VX_WG + tid * VX_PT;
   const int m = vx_first_mask(point_slot, first, M, i0);
   int total;
-  int r = vx_lane_prefix(m, total);
-  if ((tid & 63) == 0) wtot[tid >> 6] = total;
-  __syncthreads();
-  for (int w = 0; w < (tid >> 6); ++w) r += wtot[w];
-  r += base[blockIdx.x];
+  int r = base[blockIdx.x] + wg_rank<VX_T, VX_PT>(m, wtot, total);
 #pragma unroll
   for (int k = 0; k < VX_PT; ++k)
     if ((m >> k) & 1) {
@@ -120,15 +97,6 @@ __global__ __launch_bounds__(VX_T) void voxel_rank_kernel(const int32_t* __restr
     }
 }
 
-__device__ __forceinline__ uint32_t vx_scan(uint32_t v, int lane) {   // inclusive prefix sum over the wave
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
 __device__ __forceinline__ void vx_vote(uint64_t* __restrict__ pkeys, int32_t* __restrict__ pcnt, uint32_t mask, uint64_t pkey, int n,
                                         int32_t* __restrict__ status) {
   const int s = vx_find_or_claim(pkeys, mask, pkey, status);
@@ -136,7 +104,7 @@ __device__ __forceinline__ void vx_vote(uint64_t* __restrict__ pkeys, int32_t* _
 }
 
 // uchar of a colour channel: floor(clamp(x, 0, 1) * 255 + 0.5) in fp32, a NaN counts as 0
-__device__ __forceinline__ uint32_t vx_u8(float x) { return (uint32_t)floorf(vx_addr(vx_mulr(fminf(fmaxf(x, 0.f), 1.f), 255.f), 0.5f)); }
+__device__ __forceinline__ uint32_t vx_u8(float x) { return (uint32_t)floorf(rn_add(rn_mul(fminf(fmaxf(x, 0.f), 1.f), 255.f), 0.5f)); }
 
 template <bool MERGE>
 __global__ __launch_bounds__(VX_T) void voxel_accumulate_kernel(const float* __restrict__ points, const float* __restrict__ rgb, const int32_t* __restrict__ pan,
@@ -170,7 +138,7 @@ __global__ __launch_bounds__(VX_T) void voxel_accumulate_kernel(const float* __r
     const int src = max(head - 1, 0);
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-      const uint32_t s = vx_scan(v[k], lane);
+      const uint32_t s = wave_scan(v[k], lane);
       const uint32_t b = __shfl(s, src);
       v[k] = s - (head > 0 ? b : 0u);
     }
@@ -223,7 +191,7 @@ __global__ __launch_bounds__(VX_T) void voxel_emit_kernel(const float* __restric
     out_points[(int64_t)r * 3 + a] = (float)(((double)c[a] + off) * voxel_size);
     const float g = (float)(((double)sums[(int64_t)r * 6 + 3 + a] / dn) / 255.0);
     out_rgb[(int64_t)r * 3 + a] = g;
-    out_colors[(int64_t)r * 3 + a] = vx_addr(vx_mulr(w1, g), vx_mulr(w2, known ? colors[id * 3 + a] : 0.f));
+    out_colors[(int64_t)r * 3 + a] = rn_add(rn_mul(w1, g), rn_mul(w2, known ? colors[id * 3 + a] : 0.f));
   }
   out_pan[r] = id;
   out_votes[r] = b ? (int)(b >> 32) : n;                            // only void votes: all of them
@@ -239,7 +207,7 @@ extern "C" int pst_voxel_insert(const float* points, int64_t M, float inv, uint6
   if (M <= 0 || M > 0x3fffffffLL || !vx_cap_ok(M, cap) || !(inv > 0.f)) {
     set_error("voxel_insert: bad shape (M=%lld, capacity=%lld: a power of two >= 2 M) or inverse voxel size", (long long)M, (long long)cap); return PST_EINVAL;
   }
-  const dim3 grid((unsigned)((M + VX_T - 1) / VX_T));
+  const dim3 grid = blocks_for(M, VX_T);
   if (merge) hipLaunchKernelGGL(voxel_insert_kernel<true>, grid, dim3(VX_T), 0, (hipStream_t)stream, points, (int)M, inv, keys, (uint32_t)(cap - 1), first, point_slot, status);
   else hipLaunchKernelGGL(voxel_insert_kernel<false>, grid, dim3(VX_T), 0, (hipStream_t)stream, points, (int)M, inv, keys, (uint32_t)(cap - 1), first, point_slot, status);
   return check_launch("voxel_insert");
@@ -248,7 +216,7 @@ extern "C" int pst_voxel_insert(const float* points, int64_t M, float inv, uint6
 extern "C" int pst_voxel_count(const int32_t* point_slot, const int32_t* first, int64_t M, int32_t* counts, void* stream) {
   using namespace pst;
   if (!point_slot || !first || !counts || M <= 0 || M > 0x3fffffffLL) { set_error("voxel_count: bad shape / null operand"); return PST_EINVAL; }
-  hipLaunchKernelGGL(voxel_count_kernel, dim3((unsigned)((M + VX_WG - 1) / VX_WG)), dim3(VX_T), 0, (hipStream_t)stream, point_slot, first, (int)M, counts);
+  hipLaunchKernelGGL(voxel_count_kernel, blocks_for(M, VX_WG), dim3(VX_T), 0, (hipStream_t)stream, point_slot, first, (int)M, counts);
   return check_launch("voxel_count");
 }
 
@@ -256,7 +224,7 @@ extern "C" int pst_voxel_rank(const int32_t* point_slot, const int32_t* first, i
                               void* stream) {
   using namespace pst;
   if (!point_slot || !first || !base || !slot_rank || !first_row || M <= 0 || M > 0x3fffffffLL) { set_error("voxel_rank: bad shape / null operand"); return PST_EINVAL; }
-  hipLaunchKernelGGL(voxel_rank_kernel, dim3((unsigned)((M + VX_WG - 1) / VX_WG)), dim3(VX_T), 0, (hipStream_t)stream, point_slot, first, (int)M, base, slot_rank,
+  hipLaunchKernelGGL(voxel_rank_kernel, blocks_for(M, VX_WG), dim3(VX_T), 0, (hipStream_t)stream, point_slot, first, (int)M, base, slot_rank,
                      first_row);
   return check_launch("voxel_rank");
 }
@@ -271,7 +239,7 @@ extern "C" int pst_voxel_accumulate(const float* points, const float* rgb, const
   if (M <= 0 || M > 0x3fffffffLL || !vx_cap_ok(M, cap) || ntab < 1) {
     set_error("voxel_accumulate: bad shape (M=%lld, capacity=%lld, ntab=%d)", (long long)M, (long long)cap, ntab); return PST_EINVAL;
   }
-  const dim3 grid((unsigned)((M + VX_T - 1) / VX_T));
+  const dim3 grid = blocks_for(M, VX_T);
   if (merge) hipLaunchKernelGGL(voxel_accumulate_kernel<true>, grid, dim3(VX_T), 0, (hipStream_t)stream, points, rgb, pan, (int)M, inv, point_slot, slot_rank, id2row,
                                 ntab, cnt, (unsigned long long*)sums, pair_keys, pair_cnt, (uint32_t)(cap - 1), point_voxel, status);
   else hipLaunchKernelGGL(voxel_accumulate_kernel<false>, grid, dim3(VX_T), 0, (hipStream_t)stream, points, rgb, pan, (int)M, inv, point_slot, slot_rank, id2row,
@@ -300,7 +268,7 @@ extern "C" int pst_voxel_emit(const float* points, const int64_t* index, const i
   if (max_voxels <= 0 || max_voxels > 0x3fffffffLL || ncolors < 1 || ncolors > VX_MAX_COLORS || !(voxel_size > 0.0)) {
     set_error("voxel_emit: bad shape (max_voxels=%lld, ncolors=%d) or voxel size", (long long)max_voxels, ncolors); return PST_EINVAL;
   }
-  hipLaunchKernelGGL(voxel_emit_kernel, dim3((unsigned)((max_voxels + VX_T - 1) / VX_T)), dim3(VX_T), 0, (hipStream_t)stream, points, index, first_row, mv_ptr, inv,
+  hipLaunchKernelGGL(voxel_emit_kernel, blocks_for(max_voxels, VX_T), dim3(VX_T), 0, (hipStream_t)stream, points, index, first_row, mv_ptr, inv,
                      voxel_size, cnt, (const unsigned long long*)sums, (const unsigned long long*)best, colors, ncolors, w1, w2, out_points, out_rgb, out_pan,
                      out_colors, out_votes, out_first);
   return check_launch("voxel_emit");

@@ -1,11 +1,13 @@
 // The cell grid of the hash-grid stages (csrc/voxel.hip, csrc/components.hip, csrc/nearest.hip, csrc/meshdist.hip), written once: the cell of a
 // point, the 3 x 21-bit cell key and its range test, the hash, the open-addressing table (the bounded claiming probe of a build, the read-only
-// probe of a finished table), the per-cell lists (filled by arrival, guarded before they are read), the runs of equal keys inside a wave and the
-// launchers' capacity check.  Integer code, and one fp32 multiply in vx_cell_of, which sets `fp contract(off)` for itself: whoever includes this
-// header, and with whatever flags, the product is rounded on its own before the floor.
+// probe of a finished table), the per-cell lists (filled by arrival, guarded before they are read) and the launchers' capacity check.  (The runs
+// of equal keys inside a wave, vx_run, are in wave_ops.h, which this header includes for its users.)  Integer code, and one fp32 multiply in
+// vx_cell_of, which sets `fp contract(off)` for itself: whoever includes this header, and with whatever flags, the product is rounded on its own
+// before the floor.
 #pragma once
 #include "common.h"
 #include "../../include/panst3r_hip.h"
+#include "wave_ops.h"
 
 namespace pst {
 
@@ -38,15 +40,6 @@ __device__ __forceinline__ void vx_cell_of(const float (&x)[3], float inv, float
 __device__ __forceinline__ uint64_t vx_hash(uint64_t k) {
   k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
   return k;
-}
-
-// lanes [head, tail] = the run of adjacent lanes that hold this lane's key.  Every lane of the wave must call it.
-__device__ __forceinline__ void vx_run(uint64_t key, int lane, int& head, int& tail) {
-  const uint64_t prev = __shfl_up((unsigned long long)key, 1);
-  const uint64_t heads = __ballot(lane == 0 || prev != key);
-  head = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
-  const uint64_t above = lane == 63 ? 0ull : heads >> (lane + 1);
-  tail = above ? lane + __builtin_ctzll(above) : 63;
 }
 
 // the slot of `key` while the table is being built: claimed if it is not in the table yet (*claimed, where given, tells which).

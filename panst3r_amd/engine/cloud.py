@@ -202,8 +202,7 @@ class _Source:
         dev, N, S = self.device, self.N, len(self.segments_info)
         thr = float(min_conf_thr)
         w1, w2 = float(np.float32(1.0 - float(opacity))), float(np.float32(float(opacity)))
-        counts = torch.empty(self.nwg, dtype=torch.int32, device=dev)
-        base = torch.empty(self.nwg + 1, dtype=torch.int32, device=dev)
+        _, counts, base = hip.scan_buffers(dev, nwg=self.nwg)
         f3 = lambda: torch.empty(N, 3, dtype=torch.float32, device=dev)
         points, local, rgb, col = f3(), f3(), f3(), f3()
         pan = torch.empty(N, dtype=torch.int32, device=dev)
@@ -220,16 +219,19 @@ class _Source:
             res = torch.cat([res, count, median.view(torch.int32).reshape(-1)])
         res = res.cpu().numpy()                                                  # the only host sync: M and the segment table
         M = int(res[0])
-        segments = []
-        if S:
-            med = res[1 + S:].view(np.float32).reshape(S, 3)
-            for r, s in enumerate(self.segments_info):
-                if res[1 + r] > 0:
-                    segments.append({'id': s['id'], 'query_id': s.get('query_id'), 'category_id': s.get('category_id'), 'count': int(res[1 + r]),
-                                     'median': med[r].copy()})
+        segments = decode_segments(res, self.segments_info, 1)
         points, local = points[:M], local[:M]
         return PanopticCloud(local if self.local_pointmaps else points, local, rgb[:M], pan[:M], col[:M], index[:M], list(self.view_offsets), segments,
                              self.cameras, thr, float(opacity), source=self)
+
+
+def decode_segments(res, infos, at):
+    """the segment table of a result buffer on the host, int32 [.., count[S] from `at`, median[S, 3] as bits] -> the `segments` list: one entry per
+    segment of `infos` with a kept point"""
+    S = len(infos)
+    med = res[at + S:].view(np.float32).reshape(S, 3)
+    return [{'id': s['id'], 'query_id': s.get('query_id'), 'category_id': s.get('category_id'), 'count': int(res[at + r]), 'median': med[r].copy()}
+            for r, s in enumerate(infos) if res[at + r] > 0]
 
 
 @torch.no_grad()

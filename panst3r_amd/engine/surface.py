@@ -110,9 +110,7 @@ class PanopticMesh:
         if F == 0:
             return self._with_faces(self.faces, self.face_ids, self.quad)
         component, ws = self._label()
-        n = (F + hip.SURFACE_WG - 1) // hip.SURFACE_WG
-        counts = torch.empty(n, dtype=torch.int32, device=dev)
-        base = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        n, counts, base = hip.scan_buffers(dev, F, hip.SURFACE_WG)
         faces, face_ids, quad = torch.empty(F, 3, dtype=torch.int32, device=dev), torch.empty(F, dtype=torch.int32, device=dev), torch.empty(F, dtype=torch.int64, device=dev)
         hip.surface_keep_count(component, ws, min_faces, counts)
         hip.cloud_scan(counts, base)
@@ -173,7 +171,7 @@ def panoptic_mesh(cloud, *, max_depth_ratio=0.1):
     if M == 0 or nwg == 0:
         return result(torch.empty(0, 3, **i32), torch.empty(0, **i32), torch.empty(0, dtype=torch.int64, device=dev))
     row = torch.empty(N, **i32)
-    counts, base = torch.empty(nwg, **i32), torch.empty(nwg + 1, **i32)
+    _, counts, base = hip.scan_buffers(dev, nwg=nwg)
     cap = 2 * hip.SURFACE_WG * nwg                                               # two faces per quad, whole workgroups
     faces, face_ids, quad = torch.empty(cap, 3, **i32), torch.empty(cap, **i32), torch.empty(cap, dtype=torch.int64, device=dev)
     hip.surface_rows(cloud.index.contiguous(), N, row)

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from .. import hip
-from .cloud import default_colors, ply_colors_u8
+from .cloud import decode_segments, default_colors, ply_colors_u8
 
 
 class VoxelCloud:
@@ -172,8 +172,7 @@ def voxelize_cloud(cloud, voxel_size, *, colors=None, opacity=None):
     id2row = torch.from_numpy(row).to(dev)
     points, rgb, pan, index = cloud.points.float().contiguous(), cloud.rgb.float().contiguous(), cloud.pan.to(torch.int32).contiguous(), cloud.index.contiguous()
     ws = hip.voxel_workspace(M, dev)
-    nwg = (M + hip.CLOUD_WG - 1) // hip.CLOUD_WG
-    counts, base = torch.empty(nwg, **i32), torch.empty(nwg + 1, **i32)
+    nwg, counts, base = hip.scan_buffers(dev, M)
     point_voxel = torch.empty(M, **i32)
     out_points, out_rgb, out_colors = f3(M), f3(M), f3(M)
     out_pan, out_votes, out_first = torch.empty(M, **i32), torch.empty(M, **i32), torch.empty(M, dtype=torch.int64, device=dev)
@@ -197,12 +196,7 @@ def voxelize_cloud(cloud, voxel_size, *, colors=None, opacity=None):
     res = res.cpu().numpy()                                                  # the only host sync: Mv, the status words, the segment table
     check_status(res[1])
     Mv, dropped = int(res[0]), int(res[2])
-    segments = []
-    if S:
-        med = res[3 + S:].view(np.float32).reshape(S, 3)
-        for r, s in enumerate(infos):
-            if res[3 + r] > 0:
-                segments.append({'id': s['id'], 'query_id': s.get('query_id'), 'category_id': s.get('category_id'), 'count': int(res[3 + r]), 'median': med[r].copy()})
+    segments = decode_segments(res, infos, 3)
     return VoxelCloud(out_points[:Mv], out_rgb[:Mv], out_pan[:Mv], out_colors[:Mv], ws['cnt'][:Mv], out_votes[:Mv], out_first[:Mv], point_voxel, segments,
                       dropped=dropped, cells=cells[:Mv], color_table=ctab, **common)
 
@@ -247,8 +241,7 @@ def _label(cells, pan, count, connectivity, pairs=0):
     dev, Mv = pan.device, pan.numel()
     i32 = dict(dtype=torch.int32, device=dev)
     ws = hip.vcc_workspace(Mv, dev, pairs)
-    nwg = (Mv + hip.CLOUD_WG - 1) // hip.CLOUD_WG
-    counts, base = torch.empty(nwg, **i32), torch.empty(nwg + 1, **i32)
+    nwg, counts, base = hip.scan_buffers(dev, Mv)
     component = torch.empty(Mv, **i32)
     table = {'root': torch.empty(Mv, **i32), 'pan': torch.empty(Mv, **i32), 'size': torch.empty(Mv, **i32), 'points': torch.empty(Mv, dtype=torch.int64, device=dev),
              'cell_lo': torch.empty(Mv, 3, **i32), 'cell_hi': torch.empty(Mv, 3, **i32)}

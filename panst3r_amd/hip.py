@@ -1183,6 +1183,12 @@ def cloud_scan(counts, base):
     _call('pst_cloud_scan', _ptr(counts), counts.numel(), _ptr(base))
 
 
+def scan_buffers(device, n=None, wg=CLOUD_WG, *, nwg=None):
+    """counts [nwg], base [nwg + 1] of one count / cloud_scan / emit compaction over n items in workgroups of wg, or over nwg given -> (nwg, counts, base)"""
+    nwg = (n + wg - 1) // wg if nwg is None else nwg
+    return nwg, torch.empty(nwg, dtype=torch.int32, device=device), torch.empty(nwg + 1, dtype=torch.int32, device=device)
+
+
 def cloud_compact(table, nviews, nwg, thr, base, colors, w1, w2, points, points_local, rgb, pan, colors_out, index):
     _dev(table, torch.uint8); _dev(base, torch.int32); _dev(colors, torch.float32); _dev(pan, torch.int32); _dev(index, torch.int64)
     n = pan.numel()

@@ -1,6 +1,8 @@
 """Shared by tests/test_hip_geom_stages.py (GPU) and tests/test_geom_stage_checks.py (CPU): the cases and the numpy references that hold the kernels of
 csrc/cloud.hip (count, scan, compact, segment median) and csrc/voxel.hip (with the table of csrc/voxel_table.h) to their contract stage by stage, at the
-value classes and alignments where such kernels go wrong.  Nothing here imports the code under test.
+value classes and alignments where such kernels go wrong, and the two other users of the workgroup rank of csrc/wave_ops.h - the component ranks of
+csrc/components.hip (four rows per lane) and the face compaction of csrc/surface.hip (one face per lane) - at the wave and workgroup edges of that rank.
+Nothing here imports the code under test.
 
 The references are the restatements the end-to-end tests already use (cloud_ref.cloud, cloud_ref.median_two_stat, voxel_ref.voxelize) plus `scan_ref`.
 Every comparison is bit for bit; where the reference is NaN the result must be NaN (sign and payload of a NaN are not part of the contract).
@@ -552,3 +554,96 @@ def cloud_wg_counts(case):
             m = c >= F(case['thr'])
         out += [int(m[i:i + WG].sum()) for i in range(0, len(c), WG)]
     return np.asarray(out, dtype=np.int32)
+
+
+# ------------------------------------------------------------------------------------------------------- the workgroup rank: components and surface keep
+RANK_PATTERNS = ('none', 'all', 'wave_last', 'wg_first', 'alternating', 'random', 'wg_blocks')
+VCC_MV = [1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2049]            # rows; a workgroup ranks 1024 rows, four per lane
+VCC_PT = 4
+KEEP_F = [1, 63, 64, 65, 255, 256, 257, 513]                                # faces; a workgroup ranks 256 faces, one per lane
+KEEP_WG, KEEP_PT = 256, 1
+KEEP_MIN_FACES = 3
+RANK_EDGES = ('empty_wave', 'full_wave', 'lane0_only', 'lane63_only', 'full_wg_next_to_empty', 'last_wg_one_row')
+
+
+def rank_pattern(name, n, wg, pt):
+    """bool [n]: which rows hold an item.  A lane owns pt consecutive rows, a wave 64 pt, a workgroup wg.
+    none / all; wave_last: the last row of every wave (lane 63 alone); wg_first: the first row of every workgroup (lane 0 alone, three waves without an
+    item); alternating; random: seeded, half of the rows; wg_blocks: every row of the even workgroups, none of the odd ones"""
+    i = np.arange(n)
+    if name == 'random':
+        return np.random.Generator(np.random.PCG64(7000 + n)).uniform(size=n) < 0.5
+    return {'none': i < 0, 'all': i >= 0, 'wave_last': i % (64 * pt) == 64 * pt - 1, 'wg_first': i % wg == 0, 'alternating': i % 2 == 0,
+            'wg_blocks': (i // wg) % 2 == 0}[name]
+
+
+def rank_edges(mask, wg, pt):
+    """the names of RANK_EDGES that a pattern over len(mask) rows holds"""
+    n, W = len(mask), 64 * pt
+    m = np.zeros((n + wg - 1) // wg * wg, dtype=bool)
+    m[:n] = mask
+    exists = np.arange(len(m)) < n
+    waves, lanes = m.reshape(-1, W), m.reshape(-1, 64, pt).any(axis=2)
+    whole = exists.reshape(-1, W).all(axis=1)
+    per_wg = m.reshape(-1, wg).sum(axis=1)
+    out = set()
+    if (~waves.any(axis=1) & whole).any():
+        out.add('empty_wave')
+    if waves.all(axis=1).any():
+        out.add('full_wave')
+    one = waves.sum(axis=1) == 1
+    if (one & lanes[:, 0]).any():
+        out.add('lane0_only')
+    if (one & lanes[:, 63]).any():
+        out.add('lane63_only')
+    if ((per_wg[:-1] == wg) & (per_wg[1:] == 0) & exists.reshape(-1, wg)[1:].any(axis=1)).any():
+        out.add('full_wg_next_to_empty')
+    if n % wg == 1 and n > wg and mask[-1]:
+        out.add('last_wg_one_row')
+    return out
+
+
+def wg_counts(mask, wg):
+    return np.asarray([int(mask[i:i + wg].sum()) for i in range(0, len(mask), wg)], dtype=np.int32)
+
+
+def vcc_rank_case(Mv, pattern):
+    """the inputs of vcc_count / vcc_rank written by hand and what they must give.  root[v] = v for a root, else the nearest lower root, -1 where there is
+    none; size, points (beyond 32 bits), lo, hi and pan identify their row.
+    -> dict(root, pan, size, points, lo, hi; want: counts, base, C, roots, component, table{root, pan, size, points, cell_lo, cell_hi})"""
+    is_root = rank_pattern(pattern, Mv, WG, VCC_PT)
+    v = np.arange(Mv, dtype=np.int64)
+    root = np.maximum.accumulate(np.where(is_root, v, -1)).astype(np.int32)
+    pan = (v % 97 + 1).astype(np.int32)
+    size = (3 * v + 1).astype(np.int32)
+    points = (v << 33) + 5
+    lo = np.stack([-v, v + 1, 2 * v], axis=1).astype(np.int32)
+    hi = np.stack([v + 7, -3 * v, 5 * v], axis=1).astype(np.int32)
+    roots = np.nonzero(is_root)[0]
+    rank_of = np.full(Mv, -1, dtype=np.int32)
+    rank_of[roots] = np.arange(len(roots), dtype=np.int32)
+    counts = wg_counts(is_root, WG)
+    want = dict(counts=counts, base=scan_ref(counts), C=len(roots), roots=roots, rank_of=rank_of,
+                component=np.where(root >= 0, rank_of[np.maximum(root, 0)], -1).astype(np.int32),
+                table={'root': roots.astype(np.int32), 'pan': pan[roots], 'size': size[roots], 'points': points[roots], 'cell_lo': lo[roots], 'cell_hi': hi[roots]})
+    return dict(is_root=is_root, root=root, pan=pan, size=size, points=points, lo=lo, hi=hi, want=want)
+
+
+def keep_case(F_, pattern):
+    """the inputs of surface_keep_count / surface_keep_emit written by hand.  M = the vertex rows of the workspace, a multiple of 4; size[r] cycles through
+    0, min_faces - 1, min_faces and 50 faces.  A face that survives points to a row of exactly min_faces or of 50 faces, one that does not to a row of
+    min_faces - 1 or of no faces, or carries component -1.  faces, face_ids and quad identify their face.
+    -> dict(M, component, size, faces, face_ids, quad, min_faces; want: survives, counts, base, kept, faces, face_ids, quad)"""
+    survives = rank_pattern(pattern, F_, KEEP_WG, KEEP_PT)
+    f = np.arange(F_, dtype=np.int64)
+    M = 4 * ((F_ + 3) // 4)
+    size = np.asarray([0, KEEP_MIN_FACES - 1, KEEP_MIN_FACES, 50], dtype=np.int32)[np.arange(M) % 4]
+    klass = np.where(survives, 2 + f % 2, f % 3 - 1)                       # of a face that goes: -1 = no component, 0 = a row of none, 1 = of min_faces - 1
+    component = np.where(klass < 0, -1, 4 * ((7 * f) % (M // 4)) + klass).astype(np.int32)
+    faces = np.stack([3 * f, 3 * f + 1, 3 * f + 2], axis=1).astype(np.int32)
+    face_ids = (f % 11).astype(np.int32)
+    quad = (f << 33) + 9
+    keep = (component >= 0) & (size[np.maximum(component, 0)] >= KEEP_MIN_FACES)
+    counts = wg_counts(keep, KEEP_WG)
+    want = dict(survives=keep, counts=counts, base=scan_ref(counts), kept=int(keep.sum()), faces=faces[keep], face_ids=face_ids[keep], quad=quad[keep])
+    return dict(M=M, component=component, size=size, faces=faces, face_ids=face_ids, quad=quad, min_faces=KEEP_MIN_FACES, pattern=survives, want=want)

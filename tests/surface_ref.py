@@ -222,6 +222,23 @@ def grid_scene(h, w, seed=1):
     return _views_to_scene([z], [np.full((h, w), 5.0, dtype=F)], [np.ones((h, w), dtype=np.int32)], [np.eye(4, dtype=F)], 1)
 
 
+STRIP_SHAPE, STRIP_DROP = (2, 258), (0, 0, 1, 1, 0, 1, 1, 0)
+
+
+def strip_scene():
+    """one 2 x 258 view: 257 quads in raster order, so the quad kernels' 256-quad workgroups are one full workgroup and one that holds a single quad.
+    The top row is kept; bottom pixel x is dropped where STRIP_DROP[x mod 8] is set, so quad x has 4 - drop[x] - drop[x + 1] corners and yields
+    2, 1, 0, 1, 1, 0, 1, 2 faces for x mod 8 = 0 .. 7: before and after every multiple of 8 - the 64-lane edges, and 256 from below - stand quads with
+    0, 1 and 2 faces.  The depth stays inside the cut, the ids change every 16 pixels."""
+    H, W = STRIP_SHAPE
+    x = np.arange(W)
+    z = np.broadcast_to((1.0 + 0.001 * (x % 7)).astype(F), (H, W)).copy()
+    conf = np.full((H, W), 5.0, dtype=F)
+    conf[1, np.asarray(STRIP_DROP, dtype=bool)[x % 8]] = 0.0
+    pan = np.broadcast_to(1 + x // 16, (H, W)).astype(np.int32)
+    return _views_to_scene([z], [conf], [pan], [np.eye(4, dtype=F)], 17)
+
+
 def of_scene(sc, thr, max_depth_ratio=0.1, force_diagonal=None):
     """(cloud, mesh) of a scene tuple by the two restatements"""
     x_out, imgs, pan, info, cams = sc[:5]

@@ -5,7 +5,9 @@ Median: the numpy emulation of the four radix passes equals cloud_ref.median_two
 mistakes - a key that only flips the sign bit, one prefix shared by both ranks, the upper rank for both, >= for > in the bin walk - differs on the
 cases listed in CAUGHT and on no other: the value classes tell the mistakes apart before a GPU sees them.  Hash: the restatement finds cells and
 (rank, id) pairs with a chosen home slot.  Voxel: every case's built-for property, asserted on voxel_ref.voxelize alone.  Scan and cloud: the sizes,
-counts, thresholds and conf offsets of the GPU module really contain the edges they name."""
+counts, thresholds and conf offsets of the GPU module really contain the edges they name.  Rank: the sizes and patterns of the component-rank and
+surface-keep cases hold every edge of the workgroup rank (a wave without an item, a full wave, an item in lane 0 or lane 63 alone, a full workgroup next
+to an empty one, a last workgroup of one row), and the hand-written inputs are what the cases say they are."""
 import numpy as np
 import pytest
 
@@ -187,3 +189,67 @@ def test_cloud_conf_offsets_cover_every_alignment():
         for n, o in zip(G.CLOUD_NPIX, off):
             seen.setdefault(n, set()).add(o * 4 % 16)
     assert all(s == {0, 4, 8, 12} for s in seen.values()), seen
+
+
+# ------------------------------------------------------------------------------------------------------- the workgroup rank: components and surface keep
+RANK_FAMILIES = {'vcc': (G.VCC_MV, G.WG, G.VCC_PT), 'keep': (G.KEEP_F, G.KEEP_WG, G.KEEP_PT)}
+
+
+@pytest.mark.parametrize('family', list(RANK_FAMILIES))
+def test_rank_patterns_hold_every_edge_of_the_workgroup_rank(family):
+    sizes, wg, pt = RANK_FAMILIES[family]
+    W = 64 * pt
+    assert {1, W - 1, W, W + 1, wg - 1, wg, wg + 1, 2 * wg + 1} <= set(sizes) and wg == 4 * W
+    assert set(G.RANK_PATTERNS) >= {'none', 'all', 'wave_last', 'wg_first', 'alternating', 'random'}
+    big = max(sizes)
+    edges = {p: G.rank_edges(G.rank_pattern(p, big, wg, pt), wg, pt) for p in G.RANK_PATTERNS}
+    assert 'empty_wave' in edges['none'] and 'empty_wave' in edges['wg_first']
+    assert 'full_wave' in edges['all'] and 'last_wg_one_row' in edges['all']
+    assert 'lane0_only' in edges['wg_first'] and 'lane63_only' in edges['wave_last']
+    assert 'full_wg_next_to_empty' in edges['wg_blocks'] and 'last_wg_one_row' in edges['wg_blocks']
+    assert set().union(*edges.values()) == set(G.RANK_EDGES)
+    assert G.rank_edges(G.rank_pattern('all', wg + 1, wg, pt), wg, pt) >= {'full_wave', 'last_wg_one_row'}
+    for n in sizes:
+        m = {p: G.rank_pattern(p, n, wg, pt) for p in G.RANK_PATTERNS}
+        assert all(v.dtype == bool and v.shape == (n,) for v in m.values())
+        assert not m['none'].any() and m['all'].all() and m['alternating'].sum() == (n + 1) // 2
+        assert m['wave_last'].sum() == n // W and m['wg_first'].sum() == (n + wg - 1) // wg
+        if n >= 63:
+            assert 0 < m['random'].sum() < n
+    lane = (np.nonzero(G.rank_pattern('wave_last', big, wg, pt))[0] // pt) % 64
+    assert (lane == 63).all() and len(lane) >= 2
+
+
+@pytest.mark.parametrize('Mv', G.VCC_MV)
+def test_vcc_rank_cases_are_what_they_say(Mv):
+    for p in G.RANK_PATTERNS:
+        c = G.vcc_rank_case(Mv, p)
+        w, root, v = c['want'], c['root'], np.arange(Mv)
+        assert np.array_equal(root == v, c['is_root']) and (root <= v).all() and (root >= -1).all()
+        for i in range(Mv):                                                   # the nearest lower root, by hand
+            below = np.nonzero(c['is_root'][:i + 1])[0]
+            assert root[i] == (below[-1] if len(below) else -1)
+        assert w['C'] == c['is_root'].sum() == w['counts'].sum() == w['base'][-1] and len(w['counts']) == (Mv + G.WG - 1) // G.WG
+        assert np.array_equal(w['table']['root'], np.nonzero(c['is_root'])[0]) and (np.diff(w['table']['root']) > 0).all()
+        assert ((w['component'] == -1) == (root < 0)).all() and (w['component'][root >= 0] == w['rank_of'][root[root >= 0]]).all()
+        # every value identifies its row: a table row taken from a neighbouring voxel shows
+        assert len(set(c['size'].tolist())) == Mv and len(set(c['points'].tolist())) == Mv and (c['points'] >= 5).all() and (Mv < 2 or c['points'].max() > 2 ** 32)
+        assert len(np.unique(c['lo'], axis=0)) == Mv and len(np.unique(c['hi'], axis=0)) == Mv
+        assert c['root'].dtype == c['pan'].dtype == c['size'].dtype == c['lo'].dtype == np.int32 and c['points'].dtype == np.int64
+
+
+@pytest.mark.parametrize('F_', G.KEEP_F)
+def test_keep_cases_are_what_they_say(F_):
+    seen = set()
+    for p in G.RANK_PATTERNS:
+        c = G.keep_case(F_, p)
+        w, comp, size = c['want'], c['component'], c['size']
+        assert np.array_equal(w['survives'], c['pattern']), p               # the hand-written inputs realise the pattern
+        assert c['M'] >= F_ and c['M'] % 4 == 0 and len(size) == c['M'] and comp.min() >= -1 and comp.max() < c['M']
+        assert w['kept'] == c['pattern'].sum() == w['base'][-1] and len(w['counts']) == (F_ + G.KEEP_WG - 1) // G.KEEP_WG
+        of = np.where(comp >= 0, size[np.maximum(comp, 0)], -1)
+        seen |= set(of.tolist())
+        assert set(of[c['pattern']].tolist()) <= {c['min_faces'], 50} and set(of[~c['pattern']].tolist()) <= {-1, 0, c['min_faces'] - 1}
+        assert np.array_equal(w['faces'][:, 0] // 3, np.nonzero(c['pattern'])[0]) and np.array_equal(w['quad'] >> 33, np.nonzero(c['pattern'])[0])
+    if F_ >= 63:
+        assert seen == {-1, 0, c['min_faces'] - 1, c['min_faces'], 50}        # no component, sizes 0, min_faces - 1, min_faces and beyond

@@ -1,4 +1,5 @@
-"""Stage-level parity of csrc/cloud.hip and csrc/voxel.hip (with the table of csrc/voxel_table.h): every wrapper of panst3r_amd.hip called by hand
+"""Stage-level parity of csrc/cloud.hip and csrc/voxel.hip (with the table of csrc/voxel_table.h), and of the two other users of the workgroup rank of
+csrc/wave_ops.h (the component ranks of csrc/components.hip, the face compaction of csrc/surface.hip): every wrapper of panst3r_amd.hip called by hand
 and compared BIT FOR BIT with the numpy restatement of the same stage (tests/geom_stage_cases.py: scan_ref, cloud_ref.median_two_stat, cloud_ref.cloud,
 voxel_ref.voxelize), at the value classes and alignments the end-to-end scenes of test_hip_cloud.py / test_hip_voxel.py never reach.  No tolerance and no
 cap; where the reference is NaN the result must be NaN.  tests/test_geom_stage_checks.py asserts without a GPU that every case holds what it was built
@@ -14,6 +15,10 @@ for and that the median cases catch four planted mistakes.
   voxel    insert, count, scan, rank, accumulate, vote, emit by hand, with and without the wave-level merge: cell faces on both sides of zero and the
            last cells in range, a table at load factor 1 / 2 whose probe chains wrap from the last slot to slot 0 (cells and pairs), runs across the
            wave, workgroup and rank-group edges, vote ties, void-only voxels, offset sums beyond 2^32, colour clamps and NaN
+  vcc rank vcc_count, scan, vcc_rank on a hand-written root[]: 1 .. 2049 rows around the 64-lane, 256-row wave and 1024-row workgroup edges; no root, all
+           roots, roots in lane 63 / lane 0 alone, alternating, random, a full workgroup next to an empty one; rows >= C of the table keep a canary
+  keep     surface_keep_count, scan, surface_keep_emit on a hand-written component[] / size[]: 1 .. 513 faces around the 64 and 256 edges, the same
+           patterns, component -1, sizes 0, min_faces - 1, min_faces; outputs beyond `kept` keep a canary
 
 Every index a kernel reads stays inside a tensor of the test; the only refusals exercised are the launchers' own, made on the host before any launch."""
 import functools
@@ -283,3 +288,60 @@ def test_voxel_stages(name, merge):
     assert status[1] == ref['dropped'] == case['dropped']
     for k in G.VOXEL_FIELDS:
         _assert_same(got[k], ref[k], '%s of %s (merge=%d)' % (k, name, merge))
+
+
+# ------------------------------------------------------------------------------------------------------- the workgroup rank: components and surface keep
+@pytest.mark.parametrize('Mv', G.VCC_MV)
+def test_vcc_count_and_rank(Mv):
+    hip = _hip()
+    for pattern in G.RANK_PATTERNS:
+        c = G.vcc_rank_case(Mv, pattern)
+        w = c['want']
+        ws = hip.vcc_workspace(Mv, DEV)
+        for k in ('root', 'size', 'points', 'lo', 'hi'):
+            ws[k].copy_(_dev(c[k]))
+        ws['rank_of'].fill_(CANARY_I)
+        nwg = (Mv + hip.CLOUD_WG - 1) // hip.CLOUD_WG
+        counts, base, component = _filled((nwg,), torch.int32), _filled((nwg + 1,), torch.int32), _filled((Mv,), torch.int32)
+        table = {k: _filled((Mv, 3) if k.startswith('cell') else (Mv,), torch.int64 if k == 'points' else torch.int32) for k in w['table']}
+        hip.vcc_count(ws, counts)
+        hip.cloud_scan(counts, base)
+        hip.vcc_rank(_dev(c['pan']), ws, base, component, table)
+        torch.cuda.synchronize()
+        what = ' (Mv = %d, %s)' % (Mv, pattern)
+        _assert_same(counts, w['counts'], 'counts' + what)
+        _assert_same(base, w['base'], 'base' + what)
+        rank_of = ws['rank_of'].cpu().numpy()
+        _assert_same(rank_of[w['roots']], w['rank_of'][w['roots']], 'rank_of at the roots' + what)
+        assert (rank_of[~c['is_root']] == CANARY_I).all(), 'rank_of was written at a row that is no root' + what
+        _assert_same(component, w['component'], 'component' + what)
+        for k, t in table.items():
+            _assert_same(t[:w['C']], w['table'][k], k + what)
+            assert _untouched(t[w['C']:]), k + ': rows past C were written' + what
+        assert int(ws['status'][0]) == 0
+
+
+@pytest.mark.parametrize('F_', G.KEEP_F)
+def test_surface_keep_count_and_emit(F_):
+    hip = _hip()
+    for pattern in G.RANK_PATTERNS:
+        c = G.keep_case(F_, pattern)
+        w = c['want']
+        ws = hip.surface_workspace(c['M'], DEV)
+        ws['size'].copy_(_dev(c['size']))
+        ws['parent'].fill_(CANARY_I)                                         # not read by the two kernels
+        component = _dev(c['component'])
+        nwg = (F_ + hip.SURFACE_WG - 1) // hip.SURFACE_WG
+        counts, base = _filled((nwg,), torch.int32), _filled((nwg + 1,), torch.int32)
+        out = {'faces': _filled((F_, 3), torch.int32), 'face_ids': _filled((F_,), torch.int32), 'quad': _filled((F_,), torch.int64)}
+        hip.surface_keep_count(component, ws, c['min_faces'], counts)
+        hip.cloud_scan(counts, base)
+        hip.surface_keep_emit(_dev(c['faces']), _dev(c['face_ids']), _dev(c['quad']), component, ws, c['min_faces'], base, out['faces'], out['face_ids'], out['quad'])
+        torch.cuda.synchronize()
+        what = ' (F = %d, %s)' % (F_, pattern)
+        _assert_same(counts, w['counts'], 'counts' + what)
+        _assert_same(base, w['base'], 'base' + what)
+        for k, t in out.items():
+            _assert_same(t[:w['kept']], w[k], k + what)
+            assert _untouched(t[w['kept']:]), k + ': rows past kept were written' + what
+        assert int(ws['status'][0]) == 0 and _untouched(ws['parent'])

@@ -1,6 +1,7 @@
 """The surface mesh of the pointmap grids on the GPU (csrc/surface.hip, panst3r_amd/engine/surface.py) against the numpy restatement of
 tests/surface_ref.py: faces, face ids, quads and F BIT FOR BIT - integer work and fp32 compares leave no tolerance to choose - then the islands, and the
-hand-over to the mesh rasteriser, the PLY reader and the evaluation.
+hand-over to the mesh rasteriser, the PLY reader and the evaluation.  A strip of 257 quads (surface_ref.strip_scene) holds the two-items-per-lane rank of
+surface_count / surface_emit at its wave and workgroup edges: quads with 0, 1 and 2 faces on both sides of every 64-quad edge, a last workgroup of one quad.
 
 Conditions, not measurements: before the GPU is compared, `check_conditions` asserts ON THE RESTATEMENT that the generated scene (surface_ref.scene)
 holds what it was built for - quads with 4, 3 (each pattern), 2 and 0 corners, both diagonals and an exact tie, a quad whose T0 is cut while T1
@@ -102,6 +103,38 @@ def check_plane():
     H, W = PLANE_SHAPE
     assert len(m['faces']) == 2 * (H - 1) * (W - 1)
     assert 0 < splat_hits < mesh_hits == H * W                                 # the splat leaves holes, the surface none
+
+
+# ---------------------------------------------------------------- the strip of 257 quads
+@functools.lru_cache(maxsize=None)
+def strip_reference():
+    return S.of_scene(S.strip_scene(), S.THR)
+
+
+def check_strip():
+    """per quad the number of faces, on the restatement: 0, 1 and 2 on both sides of the wave edges 64, 128, 192 and below the workgroup edge 256; the
+    one quad of the second workgroup yields two faces, whose slots are the first workgroup's total and the one after"""
+    H, W = S.STRIP_SHAPE
+    assert H == 2 and (H - 1) * (W - 1) == 257
+    cloud, m = strip_reference()
+    y = m['keep'].sum(axis=1)
+    assert len(y) == 257 and y.sum() == len(m['faces']) and (m['corners'] >= 2).all() and np.array_equal(y, np.maximum(m['corners'] - 2, 0))
+    for e in (64, 128, 192, 256):
+        assert set(y[e - 3:e]) == {0, 1, 2}, (e, y[e - 3:e])
+        assert set(y[e:e + 3]) == ({0, 1, 2} if e < 256 else {2}), (e, y[e:e + 3])
+    for w in range(4):                                                         # no wave of the first workgroup is empty or full: every wave base counts
+        assert 0 < y[64 * w:64 * w + 64].sum() < 128
+    assert m['quad'][-2:].tolist() == [256, 256] and len(set(cloud['pan'][m['faces']].reshape(-1))) > 10
+
+
+def test_the_two_item_rank_at_the_wave_and_workgroup_edges():
+    check_strip()
+    cloud = build_cloud(S.strip_scene(), S.THR)
+    want_cloud, want = strip_reference()
+    assert np.array_equal(cloud.index.cpu().numpy(), want_cloud['index'])
+    mesh = cloud.mesh()
+    assert_same(mesh, want)
+    assert_same(cloud.mesh(), want)                                            # a second call: the same bytes
 
 
 # ---------------------------------------------------------------- the GPU side

@@ -159,3 +159,4 @@ def test_the_scene_meets_the_conditions_the_gpu_tests_rely_on():
     import test_hip_surface as T
     T.check_conditions()
     T.check_plane()
+    T.check_strip()
