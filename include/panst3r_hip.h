@@ -585,6 +585,40 @@ int pst_render_splat(const float* points, int64_t M, const float* cams, int ncam
 int pst_render_resolve(const uint64_t* zbuf, int64_t npix, int64_t M, const float* rgb, const float* colors, const int32_t* pan, int64_t* index, float* depth,
                        int32_t* out_pan, float* out_rgb, float* out_colors, void* stream);
 
+/* ---------------------------------------------------------------- cross-view depth consistency of the pointmaps (ABI 20, additive; no counterpart in the reference)
+ * Every pixel of every view projected into every OTHER view and compared with the depth that view measured there -> per pixel of the concatenated
+ * scene (N pixels, view v owns [offset_v, offset_v + H_v W_v)) the number of views that agree with it, the number it violates and the number of
+ * agreeing views that give it the same panoptic id; restated in tests/consistency_ref.py [restated, parity unpinned], held to it bit for bit.  No
+ * atomics; every fp32 product, sum and difference is rounded on its own, in the order written (contraction off); every test is a negated compare, so
+ * a NaN fails it.  The scene is the cloud's table of pst_cloud_view (conf, pts3d, pts3d_local, pan - which may be NULL: every id void -, offset, npix,
+ * first_wg and c2w are read, img is not: a view owns ceil(npix / 1024) consecutive workgroups from first_wg, nwg = their sum) next to two plain
+ * tables: cams float [V, 16] per view W00 W01 W02 s0 W10 W11 W12 s1 W20 W21 W22 s2 f cx cy near, the render section's step 1 of the view's OWN
+ * camera, and dims int32 [V, 2] = (H, W) with H W = npix (a view whose H W exceeds its npix is the target of nothing).
+ *   world    the pixel's world point P: pts3d; with local != 0 pts3d_local moved by c2w, x' = ((R00 x + R01 y) + R02 z) + t0 ..., as cloud_compact's
+ *            points_local.
+ *   camera   pc = W2C P of a view: xc = ((W00 X + W01 Y) + W02 Z) + s0, likewise yc, zc (the render section's step 1).
+ *   depth    pst_consist_depth, depth fp32 [N]: zc of the pixel's point in its OWN camera if conf >= thr, xc, yc and zc are finite and zc >= near;
+ *            else 0 = "this view measured nothing here" (near > 0, so a measured depth is never 0).
+ *   count    pst_consist_count, agree / violate / same_label int32 [N] (same_label may be NULL: no panoptic id is read).  A pixel whose own depth is 0
+ *            gets zeros.  Any other, for every view j but its own, in this order:
+ *              1  pc = W2C_j P; left out if xc, yc or zc is not finite or !(zc >= near_j)
+ *              2  u = (f xc) / zc + cx, v = (f yc) / zc + cy, the quotient fp32(fp64(f xc) / fp64(zc)) as the render section's; left out unless
+ *                 |u| <= 2^20 and |v| <= 2^20
+ *              3  px = floor(u + 0.5f), py = floor(v + 0.5f): THE NEAREST PIXEL CENTRE.  The pointmaps put pixel x at u = x exactly
+ *                 (estimate_focal_knowing_depth subtracts pp from integer pixel coordinates); the render section's floor(u), whose pixel j covers
+ *                 [j, j + 1), would send half of a view's own points to their left neighbour.  Outside [0, W_j) x [0, H_j): unseen by j.
+ *              4  d = depth[offset_j + py W_j + px]; d == 0: unseen by j
+ *              5  tol = rel_tol d.  AGREE if |zc - d| <= tol (a tie agrees); else VIOLATE if d - zc > tol: the point lies in front of what j measured
+ *                 along that ray, in space j sees through; else the point is occluded in j and counts for nothing.
+ *              6  same_label is incremented on an agreeing pair whose source id pan > 0 equals pan_j[py W_j + px].
+ *            No read falls outside a view's planes: the index is formed only after the in-image test.
+ * Refused with PST_EINVAL before any launch: nviews outside [1, 65535], N outside [1, 2^31 - 1], nwg outside [1, N], rel_tol not a number in [0, 1),
+ * a null views / cams / dims / depth / agree / violate.  Nothing can fail on the device: there is no status word.  No bilinear sampling of the
+ * target's depth, no weighting by normal or grazing angle, no frustum pre-cull. */
+int pst_consist_depth(const pst_cloud_view* views, const float* cams, int nviews, int nwg, int64_t N, float thr, int local, float* depth, void* stream);
+int pst_consist_count(const pst_cloud_view* views, const float* cams, const int32_t* dims, int nviews, int nwg, int64_t N, float rel_tol, int local,
+                      const float* depth, int32_t* agree, int32_t* violate, int32_t* same_label, void* stream);
+
 /* ---------------------------------------------------------------- z-buffered triangle rasterisation of a labelled mesh: ground-truth depth and panoptic maps
  * A mesh (vertices fp32 [Nv, 3] in the world frame, faces int32 [Nf, 3], one panoptic id per vertex or per face) seen from B pinhole cameras at one shape
  * (H, W) -> per pixel the nearest face's depth, index and id, and after a per-view minimum-area filter the ground-truth maps pst_pq_count scores

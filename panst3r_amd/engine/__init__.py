@@ -8,6 +8,7 @@ from .retrieval import PanSt3RRetriever  # noqa: F401,E402  (keyframe selection 
 from .cloud import panoptic_point_cloud, PanopticCloud, default_colors, camera_frusta  # noqa: F401,E402  (the scene's labelled point cloud, demo :279-300, :622-687)
 from .voxels import voxelize_cloud, VoxelCloud, VoxelComponents, voxel_components, clean_voxel_labels  # noqa: F401,E402  (voxel fusion of the cloud with multi-view label votes; not in the reference)
 from .render import render_cloud, render_cameras, orbit_cameras, CloudRender  # noqa: F401,E402  (the cloud seen from any camera: depth, panoptic map, colours; not in the reference)
+from .consistency import view_consistency, ViewConsistency  # noqa: F401,E402  (f14: every pixel checked against every other view's depth - agreeing views, views that see through it, agreeing labels - and the floater filter PanopticCloud.filter_consistent; not in the reference)
 from .evaluate import panoptic_quality  # noqa: F401,E402  (PQ / SQ / RQ and mIoU of panoptic maps against ground truth, per scene or per view; not in the reference)
 from .mesh import render_mesh, ground_truth_maps, mesh_camera_table, load_ply_mesh, panoptic_vertex_ids, MeshRender  # noqa: F401,E402  (ground-truth depth and panoptic maps rasterised from a labelled mesh; reference tools/preprocess_scannetpp.py:395-494 through OpenGL)
 from .surface import panoptic_mesh, PanopticMesh  # noqa: F401,E402  (the pointmap grids triangulated into one labelled surface mesh on the cloud's rows; not in the reference)

@@ -10,6 +10,7 @@ held to that restatement bit for bit.
 Differences from the demo, on purpose: the colour table is an input (the demo draws random pastel colours from an unseeded generator,
 :137-174); the default is `default_colors`, deterministic and keyed by segment id.  Void (id 0) and ids outside the table are black.
 """
+import copy
 import math
 
 import numpy as np
@@ -117,6 +118,22 @@ class PanopticCloud:
         from .surface import panoptic_mesh
         return panoptic_mesh(self, **kw)
 
+    def consistency(self, **kw):
+        """engine.consistency.view_consistency of this cloud's own source - its views, cameras, confidence threshold and `local_pointmaps` - with the
+        panoptic maps (labels=False: without them); `rel_tol`, `pp`, `near` as there -> `ViewConsistency` over the pixels of the scene"""
+        if self._source is None:
+            raise RuntimeError('this cloud does not hold its device inputs (it was moved to the CPU or built by hand)')
+        return self._source.consistency(self.min_conf_thr, **kw)
+
+    def filter_consistent(self, min_views=1, max_violations=0, **kw):
+        """A new cloud without the pixels that other views contradict: kept are the pixels that at least `min_views` other views agree with and at
+        most `max_violations` other views see through (`ViewConsistency.keep`; `rel_tol`, `pp`, `near` go to `consistency`).  The result is built
+        from a new source whose confidence planes are copies in which a dropped pixel is NaN - the value every stage's `conf >= thr` drops - so
+        `rethreshold`, `recolor`, `voxelize`, `mesh`, `render`, the segment medians and `write_ply` work on it unchanged and stay filtered."""
+        if self._source is None:
+            raise RuntimeError('this cloud does not hold its device inputs (it was moved to the CPU or built by hand)')
+        return self._source.filtered(self.min_conf_thr, min_views, max_violations, **kw).assemble(self.min_conf_thr, self.opacity)
+
     def cpu(self):
         f = lambda t: t.cpu()
         return PanopticCloud(f(self.points), f(self.points_local), f(self.rgb), f(self.pan), f(self.colors), f(self.index), list(self.view_offsets),
@@ -163,6 +180,7 @@ class _Source:
         self.device = views[0][0].device
         c34 = [np.asarray(torch.as_tensor(c).detach().cpu().numpy(), dtype=np.float32)[:3, :4] for c in cams2world]
         self.views = views                                                     # keeps the tensors the table points into alive
+        self.c34, self.cams2world, self.focals = c34, list(cams2world), focals  # (the consistency stage builds its own tables from them)
         self.table, self.nwg, self.N = hip.cloud_view_table(views, c34, self.device)
         self.view_offsets = [0] + list(np.cumsum([h * w for h, w in self.shapes]).tolist())
         self.segments_info = [dict(s) for s in segments_info]
@@ -195,6 +213,26 @@ class _Source:
         if ids and max(ids) >= c.shape[0]:
             raise ValueError('segments_info id %d does not fit the colour table of %d rows' % (max(ids), c.shape[0]))
         self.colors = c.to(self.device).contiguous()
+
+    def consistency(self, min_conf_thr, *, rel_tol=0.03, pp=None, near=1e-3, labels=True):
+        """engine.consistency.view_consistency of the source's views at the threshold `min_conf_thr`"""
+        from .consistency import consistency_of_views
+        if self.focals is None:
+            raise ValueError('the consistency of a cloud needs its focals: build it with panoptic_point_cloud(..., focals)')
+        views = [(conf, pts, loc, p if labels else None) for conf, pts, loc, _, p in self.views]
+        return consistency_of_views(views, self.shapes, self.c34, self.cams2world, self.focals, min_conf_thr, rel_tol, self.local_pointmaps, pp, near)
+
+    @torch.no_grad()
+    def filtered(self, min_conf_thr, min_views=1, max_violations=0, **kw):
+        """a new source that shares everything with this one but the confidence planes: copies in which the pixels that fail
+        `ViewConsistency.keep(min_views, max_violations)` at this threshold are NaN, and the view table that points to them"""
+        from .consistency import masked_conf, check_keep
+        check_keep(min_views, max_violations)                                  # a bad argument raises before anything is launched
+        keep = self.consistency(min_conf_thr, labels=False, **kw).keep(min_views, max_violations)
+        src = copy.copy(self)
+        src.views = [(masked_conf(v[0], keep[a:b]).contiguous(),) + tuple(v[1:]) for v, a, b in zip(self.views, self.view_offsets[:-1], self.view_offsets[1:])]
+        src.table, src.nwg, src.N = hip.cloud_view_table(src.views, self.c34, self.device)
+        return src
 
     @torch.no_grad()
     def assemble(self, min_conf_thr, opacity, colors=None):
@@ -236,7 +274,7 @@ def decode_segments(res, infos, at):
 
 @torch.no_grad()
 def panoptic_point_cloud(x_out, imgs, true_shape, pan, segments_info, cams2world, focals=None, *, min_conf_thr=3.0, opacity=0.5, colors=None,
-                         local_pointmaps=False):
+                         local_pointmaps=False, consistency=None):
     """x_out: list[V] of dict(pts3d, pts3d_local [H,W,3], conf [H,W]) as `pointmaps.cameras_from_pointmaps` returns it (fp32, device); imgs: list of
     [3,H,W] in [-1, 1]; pan: list of int32 [H,W] and segments_info as `panoptic_inference_*` return them; cams2world: list of [4,4]; views may
     differ in shape.  Semantics (demo line numbers): views flattened and concatenated in order (:627-631), pts3d_local moved to the world frame
@@ -244,6 +282,23 @@ def panoptic_point_cloud(x_out, imgs, true_shape, pan, segments_info, cams2world
     (1 - opacity) * rgb + opacity * colors[pan] (:351-352, 645); per entry of segments_info with a kept point the per-axis median of its
     world-frame local points (:654-657); per camera the frustum numbers (:669-683, when focals is given).  `colors`: [n_ids, 3] float table
     indexed by segment id (default: `default_colors`).  One host sync.  The outputs are views of scene-sized buffers (M is only known on the device
-    when they are allocated): `.clone()` a tensor to keep it beyond the cloud."""
+    when they are allocated): `.clone()` a tensor to keep it beyond the cloud.
+    `consistency` (default None: off, the result is what it always was): True, or a dict of the keywords of `PanopticCloud.filter_consistent`
+    (min_views, max_violations, rel_tol, pp, near) - the cloud is then built from the pixels that pass the cross-view depth check of
+    engine/consistency.py, exactly as `panoptic_point_cloud(...).filter_consistent(...)` would; it needs `focals`."""
+    kw = consistency_keywords(consistency)
     src = _Source(x_out, imgs, true_shape, pan, segments_info, cams2world, focals, colors, local_pointmaps)
+    if kw is not None:
+        src = src.filtered(float(min_conf_thr), **kw)
     return src.assemble(min_conf_thr, opacity)
+
+
+def consistency_keywords(consistency):
+    """the `consistency=` argument of `panoptic_point_cloud` / `PanSt3R.reconstruct` -> None (off) or the keywords of `filter_consistent`"""
+    if consistency is None or consistency is False:
+        return None
+    if consistency is True:
+        return {}
+    if not isinstance(consistency, dict) or set(consistency) - {'min_views', 'max_violations', 'rel_tol', 'pp', 'near'}:
+        raise ValueError('consistency must be None, True or a dict of min_views, max_violations, rel_tol, pp, near; got %r' % (consistency,))
+    return dict(consistency)

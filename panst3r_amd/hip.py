@@ -70,6 +70,7 @@ SIGNATURES = {
     'pst_voxel_insert': 'i:plfplpppip', 'pst_voxel_count': 'i:pplpp', 'pst_voxel_rank': 'i:pplpppp', 'pst_voxel_accumulate': 'i:ppplfpppipppplppip',
     'pst_voxel_vote': 'i:pplpp', 'pst_voxel_emit': 'i:pppplfdppppiffppppppp',
     'pst_render_max_radius': 'i:', 'pst_render_splat': 'i:plpiiifiipip', 'pst_render_resolve': 'i:pllppppppppp',
+    'pst_consist_depth': 'i:ppiilfipp', 'pst_consist_count': 'i:pppiilfippppp',
     'pst_mesh_lane_pixels': 'i:', 'pst_mesh_raster': 'i:plplpiiiffppplip', 'pst_mesh_resolve': 'i:piiiplplpfpppppp', 'pst_mesh_area_count': 'i:pilpiipp',
     'pst_mesh_area_apply': 'i:pilpiipipp',
     'pst_pq_count': 'i:pplpipipiiipip', 'pst_pq_match': 'i:piiipppppppp',
@@ -1422,6 +1423,58 @@ def render_resolve(zbuf, rgb, colors, pan, index, depth, out_pan, out_rgb, out_c
     assert rgb.numel() == 3 * M and colors.numel() == 3 * M and index.numel() == n and depth.numel() == n and out_pan.numel() == n
     assert out_rgb.numel() == 3 * n and out_colors.numel() == 3 * n
     _call('pst_render_resolve', _ptr(zbuf), n, M, _ptr(rgb), _ptr(colors), _ptr(pan), _ptr(index), _ptr(depth), _ptr(out_pan), _ptr(out_rgb), _ptr(out_colors))
+
+
+# ------------------------------------------------------------------ cross-view depth consistency (csrc/consistency.hip; engine/consistency.py holds the public entry points)
+def consist_view_table(views, cams2world, cams, shapes, device):
+    """the three device tables of the consistency kernels for views = [(conf, pts3d, pts3d_local, pan or None)] (contiguous device tensors, which the
+    caller keeps alive), cams2world = [V, 3, 4] host floats, cams = float32 [V, 16] host (engine.render.camera_table of every view's own camera) and
+    shapes = [(H, W)] -> (pst_cloud_view table as a uint8 tensor - img is not read and stays NULL -, cams tensor, dims int32 [V, 2], number of
+    workgroups, total number of pixels)"""
+    assert len(views) == len(cams2world) == len(shapes) == len(cams) > 0 and tuple(cams.shape) == (len(views), RENDER_CAM_FLOATS)
+    tab = (CloudView * len(views))()
+    off = wg = 0
+    for e, (conf, pts, loc, pan), c2w, (H, W) in zip(tab, views, cams2world, shapes):
+        for t, dt in ((conf, torch.float32), (pts, torch.float32), (loc, torch.float32)) + (((pan, torch.int32),) if pan is not None else ()):
+            _dev(t, dt)
+            assert t.is_contiguous() and t.device == conf.device
+        n = conf.numel()
+        assert n > 0 and n == int(H) * int(W) and pts.numel() == 3 * n and loc.numel() == 3 * n and (pan is None or pan.numel() == n)
+        e.conf, e.pts3d, e.pts3d_local, e.img, e.pan = conf.data_ptr(), pts.data_ptr(), loc.data_ptr(), None, None if pan is None else pan.data_ptr()
+        e.offset, e.npix, e.first_wg = off, n, wg
+        e.c2w[:] = [float(x) for row in c2w for x in row]
+        off += n
+        wg += (n + CLOUD_WG - 1) // CLOUD_WG
+    if off >= 2 ** 31:
+        raise RuntimeError('a scene of %d pixels exceeds the 2^31 - 1 the consistency kernels index' % off)
+    dims = torch.tensor([(int(H), int(W)) for H, W in shapes], dtype=torch.int32).reshape(-1, 2)
+    return (torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(device), torch.from_numpy(cams).contiguous().to(device), dims.to(device), wg, off)
+
+
+def _consist_tables(table, cams, nviews):
+    _dev(table, torch.uint8); _dev(cams, torch.float32)
+    assert table.numel() == nviews * C.sizeof(CloudView) and cams.is_contiguous() and tuple(cams.shape) == (nviews, RENDER_CAM_FLOATS)
+
+
+def consist_depth(table, cams, nviews, nwg, thr, local, depth):
+    """depth fp32 [N]: every pixel's depth in its own camera, 0 where the view measured nothing (conf < thr, a non-finite point, nearer than near)"""
+    _consist_tables(table, cams, nviews)
+    _dev(depth, torch.float32)
+    assert depth.is_contiguous()
+    _call('pst_consist_depth', _ptr(table), _ptr(cams), nviews, nwg, depth.numel(), float(thr), int(bool(local)), _ptr(depth))
+
+
+def consist_count(table, cams, dims, nviews, nwg, rel_tol, local, depth, agree, violate, same_label=None):
+    """agree, violate, same_label (or None: no panoptic id is read) int32 [N] of every pixel against every other view's depth"""
+    _consist_tables(table, cams, nviews)
+    _dev(dims, torch.int32); _dev(depth, torch.float32)
+    N = depth.numel()
+    assert dims.is_contiguous() and tuple(dims.shape) == (nviews, 2) and depth.is_contiguous()
+    for t in (agree, violate) + ((same_label,) if same_label is not None else ()):
+        _dev(t, torch.int32)
+        assert t.is_contiguous() and t.numel() == N and t.device == depth.device
+    _call('pst_consist_count', _ptr(table), _ptr(cams), _ptr(dims), nviews, nwg, N, float(rel_tol), int(bool(local)), _ptr(depth), _ptr(agree), _ptr(violate),
+          _ptr(same_label))
 
 
 # ------------------------------------------------------------------ z-buffered rasterisation of a labelled mesh (csrc/mesh.hip; engine/mesh.py holds the public entry points)

@@ -363,7 +363,7 @@ class PanSt3R(nn.Module):
 
     @torch.no_grad()
     def reconstruct(self, imgs, true_shape, classes, *, postprocess='standard_v2', min_conf_thr=3.0, opacity=0.5, postprocess_kwargs=None, voxel_size=None,
-                    min_component_voxels=None, **forward_kwargs):
+                    min_component_voxels=None, consistency=None, **forward_kwargs):
         """The body of the demo's `get_reconstructed_scene` (tools/demo_panst3r.py:232-300) in one call, everything on the device:
         forward_inference_multi_ar (outputs left where they are), the chosen panoptic post-processing ('standard_v2' | 'standard_v1' | 'qubo'),
         the cameras of the pointmaps and the panoptic point cloud.  `postprocess_kwargs`: thresholds of the chosen post-processing other than its
@@ -377,6 +377,9 @@ class PanSt3R(nn.Module):
         `cloud.render(engine.orbit_cameras(...), focal, (H, W))` from any other - depth, panoptic map and colours per pixel (engine/render.py).
         A surface out of the result: `cloud.mesh()` triangulates the pointmap grids into a labelled mesh on the cloud's rows (engine/surface.py).
         A score of the result in 3-D: `evaluate_3d(cloud, gt_mesh, thresholds=..., spacing=...)` against a ground-truth mesh (engine/score3d.py).
+        `consistency` (default None: off, everything returned is what it always was): True, or a dict of the keywords of
+        `PanopticCloud.filter_consistent` (min_views, max_violations, rel_tol, pp, near) - the cloud, and the voxels fused from it, then hold only the
+        pixels that pass the cross-view depth check of engine/consistency.py (floaters that other views see through are dropped).
         It only composes the public entry points."""
         from .engine import panoptic_inference_v2, panoptic_inference_v1, panoptic_inference_qubo, panoptic_point_cloud
         from .engine.pointmaps import cameras_from_pointmaps
@@ -385,6 +388,9 @@ class PanSt3R(nn.Module):
             raise ValueError('did not recognize postprocess=%r (one of %s)' % (postprocess, sorted(fns)))
         if forward_kwargs.get('outdevice') is not None:
             raise ValueError('reconstruct keeps the outputs on the device: outdevice is not an argument of it')
+        if consistency is not None:
+            from .engine.cloud import consistency_keywords
+            consistency_keywords(consistency)                   # a bad argument raises before the forward pass, not after it
         if voxel_size is not None:
             from .engine.voxels import _check_voxel_size
             _check_voxel_size(voxel_size)                       # a bad size raises before the forward pass, not after it
@@ -399,7 +405,7 @@ class PanSt3R(nn.Module):
         x_out, focals, cams2world = cameras_from_pointmaps(pms, true_shape, getattr(self.must3r_decoder, 'pointmaps_activation', 'norm_exp'))
         dev = pms[0].device
         cloud = panoptic_point_cloud(x_out, [i.to(dev) for i in imgs], true_shape, pan_preds[0]['pan'], pan_preds[0]['segments_info'], cams2world, focals,
-                                     min_conf_thr=min_conf_thr, opacity=opacity)
+                                     min_conf_thr=min_conf_thr, opacity=opacity, **({} if consistency is None else {'consistency': consistency}))
         cameras = [dict(c, cam2world=c2w) for c, c2w in zip(cloud.cameras, cams2world)]
         if voxel_size is not None:
             voxels = cloud.voxelize(voxel_size)
