@@ -8,26 +8,23 @@
 //             contiguous runs and not 64 scattered 12-byte rows.
 //   median    exact per-segment, per-axis median of points_local by radix select on the order-preserving key of a float, most significant byte
 //             first, four passes: LDS histograms flushed with INTEGER atomics (order-independent), then a small kernel that narrows the ranks.
-// The arithmetic of compact is part of the contract (every product and every sum rounded on its own): contraction is off for the whole file.
+// The arithmetic of compact is part of the contract (every product and every sum rounded on its own; the move of points_local is pinhole.h's
+// affine34, the workgroup -> view lookup its view_of, both shared with csrc/consistency.hip): contraction is off for the whole file.
 // No float atomics, every result written with plain vector stores.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
-#include "wave_ops.h"            // rn_mul, rn_add, wg_rank, wave_scan, last_le
+#include "pinhole.h"             // affine34, view_of, PH_VIEW_WG; and through it wave_ops.h: rn_mul, rn_add, wg_rank, wave_scan
 
 #pragma clang fp contract(off)
 
 namespace pst {
 
 constexpr int CL_T = 256, CL_PT = 4, CL_WG = CL_T * CL_PT;        // threads, points per thread, points per workgroup
+static_assert(CL_WG == PH_VIEW_WG, "first_wg of a pst_cloud_view table counts workgroups of this many points");
 constexpr int CL_MAX_COLORS = 4096;                               // colour table rows that fit in LDS next to the staging buffer (48 + 12 KiB)
 constexpr int MD_SB = 8;                                          // segments per workgroup of the histogram pass: 8 x 3 axes x 2 ranks x 256 counters = 48 KiB
 constexpr int MD_SLICE = 32768;                                   // points per workgroup of the histogram pass
 constexpr int MD_ROW = 3 * 2 * 256;                               // counters per segment
-
-// the view that owns workgroup wg: the last one whose first workgroup is <= wg (uniform: scalar loads)
-__device__ __forceinline__ int view_of(const pst_cloud_view* __restrict__ views, int nviews, int wg) {
-  return last_le(nviews, wg, [&](int v) { return views[v].first_wg; });
-}
 
 // bit k = point i0 + k exists and conf >= thr (a NaN confidence is dropped, as `conf >= thr` drops it in numpy)
 __device__ __forceinline__ int keep_mask(const float* __restrict__ conf, int npix, int i0, float thr) {
@@ -131,17 +128,14 @@ __global__ __launch_bounds__(CL_T) void cloud_compact_kernel(const pst_cloud_vie
     }
   stage_out<3>(stage, val, m, slot, cnt, (uint32_t*)(points + b0 * 3));
 
-  // points_local in the world frame: ((R0 x + R1 y) + R2 z) + t, every operation rounded on its own
+  // points_local in the world frame: pinhole.h's move by c2w
 #pragma unroll
   for (int k = 0; k < CL_PT; ++k)
     if ((m >> k) & 1) {
       const float* p = v.pts3d_local + (int64_t)(i0 + k) * 3;
-      const float x = p[0], y = p[1], z = p[2];
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const float a = rn_add(rn_mul(R[4 * r], x), rn_mul(R[4 * r + 1], y));
-        val[k][r] = __float_as_uint(rn_add(rn_add(a, rn_mul(R[4 * r + 2], z)), R[4 * r + 3]));
-      }
+      float w[3], x[3] = {p[0], p[1], p[2]};
+      affine34(R, x, w);
+      val[k][0] = __float_as_uint(w[0]); val[k][1] = __float_as_uint(w[1]); val[k][2] = __float_as_uint(w[2]);
     }
   stage_out<3>(stage, val, m, slot, cnt, (uint32_t*)(points_local + b0 * 3));
 

@@ -5,12 +5,12 @@
 // pst_cloud_view (a scene of mixed shapes is one launch; a workgroup of 256 threads covers 1024 consecutive pixels of one view, thread t the
 // pixels t, t + 256, t + 512, t + 768 of them) plus two plain tables, cams float [V, 16] (engine.render.camera_table: rows of [R^T | -R^T t], f, cx,
 // cy, near) and dims int32 [V, 2] = (H, W):
-//   depth   one pass: the pixel's world point (pts3d, or with `local` pts3d_local moved by c2w in cloud_compact's arithmetic) seen from its OWN camera;
+//   depth   one pass: the pixel's world point (pts3d, or with `local` pts3d_local moved by c2w: pinhole.h's affine34, as cloud_compact) seen from its OWN camera;
 //           depth = zc if conf >= thr, the three camera coordinates are finite and zc >= near, else 0 = "this view measured nothing here"
 //   count   a lane with depth 0 writes zeros; the others hold their world points in registers and loop over the target views j != own.  The loop
 //           index and the skip are uniform over the workgroup: camera, dims and plane bases of the target come from scalar loads, and the only
 //           vector memory traffic in the loop is the gather of the target's depth (and, with labels, of its panoptic id on an agreeing pair).
-// Projection is the splatter's (csrc/render.hip: same expression tree for pc, same culls, same quotient) EXCEPT THE PIXEL: px = floor(u + 0.5), the
+// The move, the finite test and the projection are pinhole.h's, one text with the splatter (csrc/render.hip); THE PIXEL is this file's: px = floor(u + 0.5), the
 // NEAREST PIXEL CENTRE.  The pointmaps' convention puts pixel x at u = x exactly (estimate_focal_knowing_depth subtracts pp from integer pixel
 // coordinates), so a view's own points project onto integers up to rounding; the splatter's floor(u), whose pixel (i, j) covers [j, j+1) x [i, i+1),
 // would send half of them to their left neighbour.
@@ -23,47 +23,34 @@
 // the gathers' latency, not HBM (the measured times are in docs/experiments.md §6s).  Four pixels per thread keep four gathers in flight.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
-#include "wave_ops.h"            // rn_mul, rn_add, rn_sub, rn_div, last_le
+#include "pinhole.h"             // affine34, finite3, project, view_of, PH_CAM, PH_VIEW_WG; and through it wave_ops.h: rn_mul, rn_add, rn_sub
 
 #pragma clang fp contract(off)
 
 namespace pst {
 
-constexpr int CS_T = 256, CS_PT = 4, CS_WG = CS_T * CS_PT;        // threads, pixels per thread, pixels per workgroup (= cloud.hip's CL_WG: the table's first_wg)
-constexpr float CS_LIM = 1048576.f;                               // |u|, |v| <= 2^20
-constexpr int CS_CAM = 16;                                        // floats per camera, as render.hip's RD_CAM
+constexpr int CS_T = 256, CS_PT = 4, CS_WG = CS_T * CS_PT;        // threads, pixels per thread, pixels per workgroup
+static_assert(CS_WG == PH_VIEW_WG, "first_wg of a pst_cloud_view table counts workgroups of this many pixels");
+constexpr float CS_LIM = 1048576.f;                               // |u|, |v| <= 2^20: px, py and py W + px are formed without overflow
 
 // the world point of pixel i of view v
 __device__ __forceinline__ void cs_world(const pst_cloud_view& v, int i, int local, float (&P)[3]) {
-  if (local) {                                                     // uniform.  ((R0 x + R1 y) + R2 z) + t: cloud_compact's points_local
+  if (local) {                                                     // uniform
     const float* p = v.pts3d_local + (int64_t)i * 3;
-    const float x = p[0], y = p[1], z = p[2];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      const float a = rn_add(rn_mul(v.c2w[4 * r], x), rn_mul(v.c2w[4 * r + 1], y));
-      P[r] = rn_add(rn_add(a, rn_mul(v.c2w[4 * r + 2], z)), v.c2w[4 * r + 3]);
-    }
+    const float x[3] = {p[0], p[1], p[2]};
+    affine34(v.c2w, x, P);
   } else {
     const float* p = v.pts3d + (int64_t)i * 3;
     P[0] = p[0]; P[1] = p[1]; P[2] = p[2];
   }
 }
 
-// world -> camera, render_splat_kernel's pc
-__device__ __forceinline__ void cs_camera(const float* __restrict__ c, const float (&P)[3], float (&pc)[3]) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-    pc[a] = rn_add(rn_add(rn_add(rn_mul(c[4 * a + 0], P[0]), rn_mul(c[4 * a + 1], P[1])), rn_mul(c[4 * a + 2], P[2])), c[4 * a + 3]);
-}
-
-__device__ __forceinline__ bool cs_finite3(const float (&pc)[3]) { return fabsf(pc[0]) <= PST_FMAX && fabsf(pc[1]) <= PST_FMAX && fabsf(pc[2]) <= PST_FMAX; }
-
 __global__ __launch_bounds__(CS_T) void consist_depth_kernel(const pst_cloud_view* __restrict__ views, const float* __restrict__ cams, int nviews, float thr,
                                                              int local, float* __restrict__ depth) {
   const int wg = blockIdx.x;
-  const int own = last_le(nviews, wg, [&](int v) { return views[v].first_wg; });      // uniform: scalar loads
+  const int own = view_of(views, nviews, wg);
   const pst_cloud_view& v = views[own];
-  const float* __restrict__ c = cams + (int64_t)own * CS_CAM;
+  const float* __restrict__ c = cams + (int64_t)own * PH_CAM;
   const float near = c[15];
   const int npix = v.npix;
   const int i0 = (wg - v.first_wg) * CS_WG + threadIdx.x;
@@ -75,8 +62,8 @@ __global__ __launch_bounds__(CS_T) void consist_depth_kernel(const pst_cloud_vie
     if (v.conf[i] >= thr) {                                        // a NaN confidence measures nothing
       float P[3], pc[3];
       cs_world(v, i, local, P);
-      cs_camera(c, P, pc);
-      if (cs_finite3(pc) && pc[2] >= near) d = pc[2];
+      affine34(c, P, pc);
+      if (finite3(pc) && pc[2] >= near) d = pc[2];
     }
     depth[v.offset + i] = d;
   }
@@ -87,7 +74,7 @@ __global__ __launch_bounds__(CS_T) void consist_count_kernel(const pst_cloud_vie
                                                              int nviews, float rel_tol, int local, const float* __restrict__ depth, int32_t* __restrict__ agree,
                                                              int32_t* __restrict__ violate, int32_t* __restrict__ same_label) {
   const int wg = blockIdx.x;
-  const int own = last_le(nviews, wg, [&](int v) { return views[v].first_wg; });      // uniform
+  const int own = view_of(views, nviews, wg);
   const pst_cloud_view& v = views[own];
   const int npix = v.npix;
   const int i0 = (wg - v.first_wg) * CS_WG + threadIdx.x;
@@ -107,7 +94,7 @@ __global__ __launch_bounds__(CS_T) void consist_count_kernel(const pst_cloud_vie
   }
   for (int j = 0; j < nviews; ++j) {
     if (j == own) continue;                                        // uniform
-    const float* __restrict__ c = cams + (int64_t)j * CS_CAM;
+    const float* __restrict__ c = cams + (int64_t)j * PH_CAM;
     const int Hj = dims[2 * j], Wj = dims[2 * j + 1];
     if (Hj < 1 || Wj < 1 || (int64_t)Hj * Wj > views[j].npix) continue;               // uniform: a table that does not fit its planes is never indexed
     const float f = c[12], cx = c[13], cy = c[14], near = c[15];
@@ -116,12 +103,11 @@ __global__ __launch_bounds__(CS_T) void consist_count_kernel(const pst_cloud_vie
 #pragma unroll
     for (int k = 0; k < CS_PT; ++k) {
       if (!live[k]) continue;
-      float pc[3];
-      cs_camera(c, P[k], pc);
+      float pc[3], u, w;
+      affine34(c, P[k], pc);
       const float zc = pc[2];
-      if (!cs_finite3(pc) || !(zc >= near)) continue;
-      const float u = rn_add(rn_div(rn_mul(f, pc[0]), zc), cx), w = rn_add(rn_div(rn_mul(f, pc[1]), zc), cy);
-      if (!(fabsf(u) <= CS_LIM && fabsf(w) <= CS_LIM)) continue;   // before any conversion to int
+      if (!finite3(pc) || !(zc >= near)) continue;
+      if (!project(f, f, cx, cy, pc, CS_LIM, u, w)) continue;
       const int px = (int)floorf(rn_add(u, 0.5f)), py = (int)floorf(rn_add(w, 0.5f));   // the nearest pixel centre
       if (px < 0 || px >= Wj || py < 0 || py >= Hj) continue;      // unseen by j
       const int q = py * Wj + px;                                  // < Hj Wj <= npix of j

@@ -1,11 +1,10 @@
 // What the two fused ICP steps share (icp_step of csrc/nearest.hip, point to point; icp_plane_step of csrc/meshdist.hip, point to plane), written
-// once: the move of a source point by the 3 x 4 fp32 matrix (step 1 of the icp section of include/panst3r_hip.h) and the fixed order in which the
+// once: the 3 x 4 fp32 matrix that moves a source point (step 1 of the icp section of include/panst3r_hip.h; the move is pinhole.h's affine34) and the fixed order in which the
 // fp64 moments are added (step 4 of that section): the butterfly inside a wave, the four waves in order, one row per block, and the one-block
-// reducer over the rows.  Templated on the number of live moments, so that both files instantiate the same text.  Both functions set
-// `fp contract(off)` for themselves: every operation is rounded on its own, in the order written, whoever includes this header.
+// reducer over the rows.  Templated on the number of live moments, so that both files instantiate the same text.  The sums set
+// `fp contract(off)` for themselves, the move is rn_* throughout: every operation is rounded on its own, in the order written, whoever includes this header.
 #pragma once
-#include "common.h"
-#include "../../include/panst3r_hip.h"
+#include "pinhole.h"             // affine34, the move of the two steps; and through it common.h and include/panst3r_hip.h
 
 namespace pst {
 
@@ -13,14 +12,7 @@ constexpr int ICP_T = PST_ICP_LANES;                                // lanes per
 constexpr int ICP_ROWS = PST_ICP_CHUNK / ICP_T;                     // source rows per lane
 static_assert(ICP_T == 256 && PST_ICP_CHUNK % ICP_T == 0, "four waves of 64 lanes, whole rows per lane: the fixed order of the header");
 
-struct IcpMatrix { float a[3][4]; };
-
-// m_r = ((a_r0 x0 + a_r1 x1) + a_r2 x2) + a_r3 in fp32
-__device__ __forceinline__ void icp_move(const IcpMatrix& A, const float (&x)[3], float (&m)[3]) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int r = 0; r < 3; ++r) m[r] = ((A.a[r][0] * x[0] + A.a[r][1] * x[1]) + A.a[r][2] * x[2]) + A.a[r][3];
-}
+struct IcpMatrix { float a[3][4]; };                               // row-major 3 x 4: a source row is moved by affine34(&A.a[0][0], x, m)
 
 // six butterfly steps inside every wave, then ((w0 + w1) + w2) + w3 -> row[0, LIVE); row[LIVE, MOMENTS) = +0.0.  Every lane of the block calls it.
 template <int LIVE, int MOMENTS>

@@ -2,7 +2,7 @@
 // depth, index and id, and after a per-view minimum-area filter the ground-truth maps that csrc/evaluate.hip scores against.  The reference renders
 // them through pyrender / OpenGL (tools/preprocess_scannetpp.py:395-494); restated in tests/mesh_ref.py, [restated, parity unpinned].  The contract is
 // the mesh section of include/panst3r_hip.h; everything is exact, so the outputs are held to the restatement bit for bit:
-//   vertex    world -> camera in separately rounded fp32 (render.hip's step 1), the perspective quotient in fp64 rounded once, then SNAPPED to 1/256
+//   vertex    world -> camera in separately rounded fp32, the perspective quotient in fp64 rounded once (pinhole.h, one text with render.hip), then SNAPPED to 1/256
 //             pixel: from here on coverage is integer arithmetic (int64 edge functions, the top-left rule), so a pixel centre on a shared edge belongs
 //             to exactly one of the two faces - no crack, no double hit - whatever the order of evaluation.
 //   depth     perspective-correct in fp64 from the integer edge values and the three 1 / zc: one rounding to fp32 at the end.
@@ -22,7 +22,7 @@
 // `precheck`: as render.hip's - a relaxed load of the cell first, the atomic only for a key below what the load saw.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
-#include "wave_ops.h"            // rn_mul, rn_add, rn_div, vx_run, id_row
+#include "pinhole.h"             // affine34, project, PH_CAM; and through it wave_ops.h: vx_run, id_row
 
 #pragma clang fp contract(off)
 
@@ -31,7 +31,6 @@ namespace pst {
 constexpr int MS_T = 256;
 constexpr unsigned long long MS_EMPTY = ~0ull;
 constexpr float MS_LIM = 16384.f;                                  // |u|, |v| <= 2^14: |X|, |Y| <= 2^22, every edge value below 2^47
-constexpr int MS_CAM = 16;                                         // floats per camera: rows of [R^T | -R^T t], then fx, fy, cx, cy
 constexpr int MS_BIG_BLOCKS = 2048;                                // the wave path's fixed grid: 8 192 waves stride the list
 
 // a face set up for one camera: corner k's snapped position and 1 / zc, and per corner k the opposite edge a -> b
@@ -45,15 +44,12 @@ struct MsTri {
 };
 
 __device__ __forceinline__ bool ms_vertex(const float* __restrict__ c, const float* __restrict__ vertices, int64_t vi, float near, int& X, int& Y, float& zc) {
-  const float x = vertices[vi * 3 + 0], y = vertices[vi * 3 + 1], z = vertices[vi * 3 + 2];
-  float pc[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-    pc[a] = rn_add(rn_add(rn_add(rn_mul(c[4 * a + 0], x), rn_mul(c[4 * a + 1], y)), rn_mul(c[4 * a + 2], z)), c[4 * a + 3]);
+  const float P[3] = {vertices[vi * 3 + 0], vertices[vi * 3 + 1], vertices[vi * 3 + 2]};
+  float pc[3], u, v;
+  affine34(c, P, pc);
   zc = pc[2];
-  if (!(fabsf(pc[0]) <= PST_FMAX && fabsf(pc[1]) <= PST_FMAX && fabsf(zc) <= PST_FMAX) || !(zc >= near)) return false;      // a NaN fails every compare
-  const float u = rn_add(rn_div(rn_mul(c[12], pc[0]), zc), c[14]), v = rn_add(rn_div(rn_mul(c[13], pc[1]), zc), c[15]);
-  if (!(fabsf(u) <= MS_LIM && fabsf(v) <= MS_LIM)) return false;
+  if (!(fabsf(pc[0]) <= PST_FMAX && fabsf(pc[1]) <= PST_FMAX && fabsf(zc) <= PST_FMAX) || !(zc >= near)) return false;      // finite3, written out: pinhole.h says why
+  if (!project(c[12], c[13], c[14], c[15], pc, MS_LIM, u, v)) return false;
   X = (int)rintf(u * 256.f);                                        // the product is exact; rintf rounds half to even
   Y = (int)rintf(v * 256.f);
   return true;
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(MS_T) void mesh_raster_kernel(const float* __restri
   const int64_t f = (int64_t)blockIdx.x * MS_T + threadIdx.x;
   if (f >= Nf) return;
   MsTri t;
-  if (!ms_setup(cams + (int64_t)blockIdx.y * MS_CAM, vertices, Nv, faces, f, near, H, W, t)) return;
+  if (!ms_setup(cams + (int64_t)blockIdx.y * PH_CAM, vertices, Nv, faces, f, near, H, W, t)) return;
   const int64_t n = (int64_t)(t.j1 - t.j0 + 1) * (t.i1 - t.i0 + 1);
   if (n > PST_MESH_LANE_PIXELS) {
     const unsigned long long slot = atomicAdd(big_count, 1ull);
@@ -157,7 +153,7 @@ __global__ __launch_bounds__(MS_T) void mesh_raster_big_kernel(const float* __re
     const int64_t cam = (int64_t)(e >> 32), f = (int64_t)(uint32_t)e;
     if (cam >= ncams || f >= Nf) continue;                          // (cannot happen for a list the lane kernel wrote)
     MsTri t;
-    if (!ms_setup(cams + cam * MS_CAM, vertices, Nv, faces, f, near, H, W, t)) continue;
+    if (!ms_setup(cams + cam * PH_CAM, vertices, Nv, faces, f, near, H, W, t)) continue;
     const uint32_t bw = (uint32_t)(t.j1 - t.j0 + 1), n = bw * (uint32_t)(t.i1 - t.i0 + 1);      // n <= H W < 2^31
     unsigned long long* __restrict__ zb = zbuf + cam * H * W;
     for (uint32_t p = (uint32_t)lane; p < n; p += 64) ms_sample<PRECHECK>(t, t.i0 + (int)(p / bw), t.j0 + (int)(p % bw), near, far, (uint32_t)f, zb, W);
@@ -178,7 +174,7 @@ __global__ __launch_bounds__(MS_T) void mesh_resolve_kernel(const unsigned long 
   else if (hit && vertex_ids) {
     const int64_t hw = (int64_t)H * W, cam = p / hw, pix = p % hw;
     MsTri t;
-    if (ms_setup(cams + cam * MS_CAM, vertices, Nv, faces, f, near, H, W, t)) {      // (true for a face that won a pixel of this camera)
+    if (ms_setup(cams + cam * PH_CAM, vertices, Nv, faces, f, near, H, W, t)) {      // (true for a face that won a pixel of this camera)
       int64_t E[3];
       ms_edges(t, (int)(pix / W), (int)(pix % W), E);
       // the corner with the largest E_k, ties to the lowest position as listed: corner k stands at position k, 1 and 2 exchanged after a swap

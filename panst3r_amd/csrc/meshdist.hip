@@ -273,7 +273,7 @@ __global__ __launch_bounds__(MD_T) void icp_plane_step_kernel(const float* __res
     float x[3], m[3], c[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) x[a] = source[(int64_t)i * 3 + a];
-    icp_move(A, x, m);
+    affine34(&A.a[0][0], x, m);
     bool finite, ok;
     vx_cell_of(m, inv, c, finite, ok);
     bad += !finite;

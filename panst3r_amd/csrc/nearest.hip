@@ -14,7 +14,7 @@
 //                         __device__ function), the 18 live moments of the matched pairs in fp64 registers; a butterfly per wave, the four waves added
 //                         in order, one row of 20 per block
 //                  reduce one block adds the rows of the blocks the same way
-//                  (the move and the fixed order of the sums: icp_sum.h, shared with the point-to-plane step of csrc/meshdist.hip)
+//                  (the move: pinhole.h; the fixed order of the sums: icp_sum.h, shared with the point-to-plane step of csrc/meshdist.hip)
 // Integer atomics only, no float sum whose order depends on arrival (the moments are added in the order the header fixes), every probe / candidate / search loop bounded by a number known before the launch,
 // refusals through the status words, every result written with plain vector stores: two calls return identical bytes.  Contraction is off for the
 // whole file: every fp32 and fp64 operation is rounded on its own, in the order written.
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(NN_T) void nn_query_kernel(const float* __restrict_
 
 // ---------------------------------------------------------------- one fused ICP step (the icp section of include/panst3r_hip.h)
 constexpr int ICP_LIVE = 18;                                         // the moments that are sums; [18], [19] are +0.0
-static_assert(NN_T == ICP_T && ICP_LIVE + 2 == PST_ICP_MOMENTS, "the fixed order of the header (icp_sum.h: the move, the block sum and the reducer)");
+static_assert(NN_T == ICP_T && ICP_LIVE + 2 == PST_ICP_MOMENTS, "the fixed order of the header (icp_sum.h: the block sum and the reducer)");
 
 __global__ __launch_bounds__(NN_T) void icp_step_kernel(const float* __restrict__ source, int N, IcpMatrix A, const float* __restrict__ targets, int M,
                                                         float inv, float r2, const uint64_t* __restrict__ keys, uint32_t mask,
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(NN_T) void icp_step_kernel(const float* __restrict_
     float x[3], m[3], c[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) x[a] = source[(int64_t)i * 3 + a];
-    icp_move(A, x, m);
+    affine34(&A.a[0][0], x, m);
     bool finite, ok;
     vx_cell_of(m, inv, c, finite, ok);
     bad += !finite;

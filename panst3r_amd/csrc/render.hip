@@ -6,7 +6,7 @@
 //            orders as an unsigned integer: the smallest key is the nearest point, equal depths go to the smallest row.
 //   resolve  one thread per pixel: the winner's row and depth out of the key, pan / rgb / colors gathered from that row, plain vector stores.
 // The arithmetic is part of the contract (include/panst3r_hip.h): contraction is off for the whole file, every fp32 product and sum is rounded on
-// its own, and the perspective quotient is taken in fp64 and rounded once (rn_div of wave_ops.h).  INTEGER atomics only: the buffer's final state is the minimum
+// its own, and the perspective quotient is taken in fp64 and rounded once (affine34 and project of pinhole.h).  INTEGER atomics only: the buffer's final state is the minimum
 // over a fixed set of keys, whatever the schedule - two calls return identical bytes.
 // `precheck`: the buffer has far fewer cells than the cloud has points (9.8 M points on 0.2 M pixels at the benchmark's scene size), so most
 // candidates lose.  A relaxed device-scope load of the cell first, and the atomic only for a key that is smaller than what the load saw, trades
@@ -17,7 +17,7 @@
 // coalesced read of the buffer plus scattered 28-byte gathers and 44 bytes of stores per pixel: bound by the gathers' latency, small next to splat.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
-#include "wave_ops.h"            // rn_mul, rn_add, rn_div
+#include "pinhole.h"             // affine34, project, PH_CAM; and through it wave_ops.h: rn_mul, rn_div
 
 #pragma clang fp contract(off)
 
@@ -25,25 +25,20 @@ namespace pst {
 
 constexpr int RD_T = 256;
 constexpr unsigned long long RD_EMPTY = ~0ull;                     // no key is all ones: bits(zc) = 0xFFFFFFFF is a NaN, and a NaN is culled
-constexpr float RD_LIM = 1048576.f;                                // |u|, |v| <= 2^20
-constexpr int RD_CAM = 16;                                         // floats per camera: rows of [R^T | -R^T t], then f, cx, cy, near
+constexpr float RD_LIM = 1048576.f;                                // |u|, |v| <= 2^20: px +- r and py +- r cannot overflow
 
 template <bool PRECHECK>
 __global__ __launch_bounds__(RD_T) void render_splat_kernel(const float* __restrict__ points, int64_t M, const float* __restrict__ cams, int H, int W,
                                                             float half_size, int radius, int max_radius, unsigned long long* __restrict__ zbuf) {
   const int64_t i = (int64_t)blockIdx.x * RD_T + threadIdx.x;
   if (i >= M) return;
-  const float* __restrict__ c = cams + (int64_t)blockIdx.y * RD_CAM;              // uniform: scalar loads
-  const float x = points[i * 3 + 0], y = points[i * 3 + 1], z = points[i * 3 + 2];
-  float pc[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-    pc[a] = rn_add(rn_add(rn_add(rn_mul(c[4 * a + 0], x), rn_mul(c[4 * a + 1], y)), rn_mul(c[4 * a + 2], z)), c[4 * a + 3]);
-  const float f = c[12], cx = c[13], cy = c[14], near = c[15];
-  const float zc = pc[2];
-  if (!(fabsf(pc[0]) <= PST_FMAX && fabsf(pc[1]) <= PST_FMAX && fabsf(zc) <= PST_FMAX) || !(zc >= near)) return;      // a NaN fails every compare
-  const float u = rn_add(rn_div(rn_mul(f, pc[0]), zc), cx), v = rn_add(rn_div(rn_mul(f, pc[1]), zc), cy);
-  if (!(fabsf(u) <= RD_LIM && fabsf(v) <= RD_LIM)) return;
+  const float* __restrict__ c = cams + (int64_t)blockIdx.y * PH_CAM;              // uniform: scalar loads
+  const float P[3] = {points[i * 3 + 0], points[i * 3 + 1], points[i * 3 + 2]};
+  float pc[3], u, v;
+  affine34(c, P, pc);
+  const float f = c[12], cx = c[13], cy = c[14], near = c[15], zc = pc[2];
+  if (!(fabsf(pc[0]) <= PST_FMAX && fabsf(pc[1]) <= PST_FMAX && fabsf(zc) <= PST_FMAX) || !(zc >= near)) return;      // finite3, written out: pinhole.h says why
+  if (!project(f, f, cx, cy, pc, RD_LIM, u, v)) return;
   const int px = (int)floorf(u), py = (int)floorf(v);
   // r = min(max_radius, max(radius, floor(f half_size / zc))): the quotient is >= 0 (or +inf), clamped as a float before it becomes an int
   const int rs = (int)fminf(floorf(rn_div(rn_mul(f, half_size), zc)), (float)max_radius);

@@ -1,5 +1,5 @@
 // The small device helpers of the geometry stages (csrc/cloud.hip, voxel.hip, components.hip, surface.hip, render.hip, mesh.hip, evaluate.hip,
-// nearest.hip, meshdist.hip; voxel_table.h includes it for its users), written once: separately rounded fp32 operations, the stable rank of a lane's
+// nearest.hip, meshdist.hip; voxel_table.h and pinhole.h include it for their users), written once: separately rounded fp32 operations, the stable rank of a lane's
 // kept items inside its wave and its workgroup, the inclusive wave scan (plain and segmented), the runs of equal keys inside a wave, one atomic per
 // wave for a count of flagged lanes, the integer wave sum, and two table lookups.  Integer code but for the rn_* operations, which set
 // `fp contract(off)` for themselves: whoever includes this header, and with whatever flags, each of them is rounded on its own.

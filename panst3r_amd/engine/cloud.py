@@ -155,6 +155,11 @@ class PanopticCloud:
         return path
 
 
+def host_c34(cams2world):
+    """the float32 [3, 4] camera-to-world rows of every view on the host: c2w of the kernels' view table (hip.cloud_view_table)"""
+    return [np.asarray(torch.as_tensor(c).detach().cpu().numpy(), dtype=np.float32)[:3, :4] for c in cams2world]
+
+
 class _Source:
     """the inputs of a scene's cloud, kept on the device: the view table of the kernels, the tensors it points into, the segment table"""
 
@@ -178,7 +183,7 @@ class _Source:
                 raise ValueError('image %s / panoptic map %s do not match the pointmap %s' % (tuple(im.shape), tuple(p.shape), (H, W)))
             views.append(tuple(t.float().contiguous() for t in ten[:4]) + (p.to(torch.int32).contiguous(),))
         self.device = views[0][0].device
-        c34 = [np.asarray(torch.as_tensor(c).detach().cpu().numpy(), dtype=np.float32)[:3, :4] for c in cams2world]
+        c34 = host_c34(cams2world)
         self.views = views                                                     # keeps the tensors the table points into alive
         self.c34, self.cams2world, self.focals = c34, list(cams2world), focals  # (the consistency stage builds its own tables from them)
         self.table, self.nwg, self.N = hip.cloud_view_table(views, c34, self.device)

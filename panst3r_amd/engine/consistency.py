@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import hip
+from .cloud import host_c34
 from .render import camera_table, _host64
 
 
@@ -138,5 +139,4 @@ def view_consistency(x_out, cams2world, focals, *, min_conf_thr=3.0, rel_tol=0.0
         if pan is not None and tuple(pan[k].shape[-2:]) != (H, W):
             raise ValueError('panoptic map %s does not match the pointmap %s' % (tuple(pan[k].shape), (H, W)))
         views.append(tuple(t.float().contiguous() for t in ten[:3]) + (pan[k].to(torch.int32).contiguous() if pan is not None else None,))
-    c34 = [np.asarray(torch.as_tensor(c).detach().cpu().numpy(), dtype=np.float32)[:3, :4] for c in cams2world]
-    return consistency_of_views(views, shapes, c34, cams2world, focals, min_conf_thr, rel_tol, local_pointmaps, pp, near)
+    return consistency_of_views(views, shapes, host_c34(cams2world), cams2world, focals, min_conf_thr, rel_tol, local_pointmaps, pp, near)

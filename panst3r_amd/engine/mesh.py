@@ -18,9 +18,7 @@ import numpy as np
 import torch
 
 from .. import hip
-from .render import _host64
-
-ZBUF_BYTES = 256 << 20     # the z-buffer of one launch (8 bytes per camera pixel) stays under this: more cameras are rendered in chunks
+from .render import ZBUF_BYTES, _host64, image_shape, one_camera, world_to_camera, zbuf_chunks
 
 
 class MeshRender:
@@ -43,7 +41,7 @@ class MeshRender:
 
     def __getitem__(self, b):
         """the render of camera b alone, [1,H,W] views"""
-        s = slice(b, b + 1) if b >= 0 else slice(b + len(self), b + len(self) + 1)
+        s = one_camera(b, len(self))
         return MeshRender(self.depth[s], self.face[s], self.pan[s])
 
 
@@ -52,21 +50,8 @@ def mesh_camera_table(cams2world, focals, shape, pp=None):
     camera the rows of [R^T | -R^T t] rounded to float32 exactly as `camera_table` does, then fx, fy, cx, cy.  focals: one number, one per camera, or
     (fx, fy) pairs ([B, 2], or [1, 2] for all); pp: (cx, cy), one pair or one per camera, default (W / 2, H / 2).  Raises ValueError for anything
     unusable."""
-    H, W = (int(s) for s in shape)
-    if isinstance(cams2world, (list, tuple)):
-        mats = [_host64(c) for c in cams2world]
-        if any(m.shape != (4, 4) for m in mats):
-            raise ValueError('every camera-to-world matrix must be [4, 4], got %s' % sorted({tuple(m.shape) for m in mats}))
-        c = np.stack(mats) if mats else np.zeros((0, 4, 4))
-    else:
-        c = _host64(cams2world)
-        if c.ndim != 3 or c.shape[1:] != (4, 4):
-            raise ValueError('cams2world must be [B, 4, 4] (or a list of [4, 4]), got %s' % (tuple(c.shape),))
-    B = c.shape[0]
-    if B == 0:
-        raise ValueError('render_mesh needs at least one camera')
-    if not np.isfinite(c).all():
-        raise ValueError('a camera-to-world matrix has a non-finite entry')
+    rows, p = world_to_camera(cams2world, shape, pp, 'render_mesh')
+    B = rows.shape[0]
     f = _host64(focals)
     if f.ndim == 2 and f.shape[1] == 2 and f.shape[0] in (1, B):
         f = np.broadcast_to(f, (B, 2))
@@ -78,18 +63,9 @@ def mesh_camera_table(cams2world, focals, shape, pp=None):
         raise ValueError('focals must be one number, one per camera or (fx, fy) pairs [B, 2], got shape %s for %d cameras' % (tuple(f.shape), B))
     if not (np.isfinite(f).all() and (f > 0).all()):
         raise ValueError('focals must be positive finite numbers, got %s' % (f.tolist(),))
-    p = np.array([W / 2, H / 2]) if pp is None else _host64(pp)
-    if p.size not in (2, 2 * B) or not np.isfinite(p).all():
-        raise ValueError('pp must be a finite (cx, cy) pair, one per camera or one for all, got %r' % (pp,))
-    p = np.broadcast_to(p.reshape(-1, 2), (B, 2))
     tab = np.empty((B, hip.MESH_CAM_FLOATS), dtype=np.float32)
     with np.errstate(over='ignore'):
-        for b in range(B):
-            R, t = c[b, :3, :3], c[b, :3, 3]
-            for a in range(3):
-                tab[b, 4 * a:4 * a + 3] = R[:, a]                                                  # row a of R^T
-                tab[b, 4 * a + 3] = -((R[0, a] * t[0] + R[1, a] * t[1]) + R[2, a] * t[2])
-            tab[b, 12], tab[b, 13], tab[b, 14], tab[b, 15] = f[b, 0], f[b, 1], p[b, 0], p[b, 1]
+        tab[:, :12], tab[:, 12:14], tab[:, 14:16] = rows, f, p
     if not (np.isfinite(tab).all() and (tab[:, 12:14] > 0).all()):
         raise ValueError('a camera does not fit float32 (matrix, focals or principal point)')
     return tab
@@ -132,9 +108,7 @@ def render_mesh(vertices, faces, cams2world, focals, shape, *, vertex_ids=None, 
     the id of the face's nearest corner (never a blend); with neither `pan` is all zero.  A face with a vertex behind `near`, a non-finite vertex or
     an index outside the vertices is left out whole (no near-plane clipping).  Cameras are taken in chunks so that the z-buffer stays under
     `ZBUF_BYTES`.  No host sync when the cameras are host values.  GPU only: CPU tensors raise."""
-    H, W = (int(s) for s in shape)
-    if H < 1 or W < 1 or H * W > 2 ** 31 - 1:
-        raise ValueError('shape must be (H, W) with 1 <= H * W < 2^31, got %r' % (tuple(shape),))
+    H, W = image_shape(shape)
     Nv, Nf = _check_mesh(vertices, faces, vertex_ids, face_ids)
     tab = mesh_camera_table(cams2world, focals, (H, W), pp)
     near, far = _check_planes(near, far)
@@ -152,13 +126,10 @@ def render_mesh(vertices, faces, cams2world, focals, shape, *, vertex_ids=None, 
     cams = torch.from_numpy(tab).to(dev)
     out = MeshRender(torch.empty(B, H, W, dtype=torch.float32, device=dev), torch.empty(B, H, W, dtype=torch.int64, device=dev),
                      torch.empty(B, H, W, dtype=torch.int32, device=dev))
-    step = max(1, min(ZBUF_BYTES // (8 * H * W), 65535, (2 ** 31 - 1) // (H * W), B))
-    zbuf = torch.empty(step, H, W, dtype=torch.int64, device=dev)
-    ws = hip.mesh_workspace(step, Nf, dev)
-    for b0 in range(0, B, step):
-        b1 = min(b0 + step, B)
-        z = zbuf[:b1 - b0]
-        z.fill_(-1)                                                           # all ones: the empty key
+    ws = None
+    for b0, b1, z in zbuf_chunks(B, H, W, dev, ZBUF_BYTES):
+        if ws is None:
+            ws = hip.mesh_workspace(b1 - b0, Nf, dev)                         # the first chunk is the largest
         hip.mesh_raster(verts, faces, cams[b0:b1], H, W, near, far, z, ws)
         hip.mesh_resolve(z, verts, faces, cams[b0:b1], near, vid, fid, out.face[b0:b1], out.depth[b0:b1], out.pan[b0:b1])
     return out

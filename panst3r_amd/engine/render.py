@@ -16,6 +16,30 @@ from .cloud import ply_colors_u8
 ZBUF_BYTES = 256 << 20     # the z-buffer of one launch (8 bytes per camera pixel) stays under this: more cameras are rendered in chunks
 
 
+def one_camera(b, n):
+    """the slice that keeps camera b of n (b < 0 counts from the end) as a batch of one"""
+    return slice(b, b + 1) if b >= 0 else slice(b + n, b + n + 1)
+
+
+def image_shape(shape):
+    H, W = (int(s) for s in shape)
+    if H < 1 or W < 1 or H * W > 2 ** 31 - 1:
+        raise ValueError('shape must be (H, W) with 1 <= H * W < 2^31, got %r' % (tuple(shape),))
+    return H, W
+
+
+def zbuf_chunks(B, H, W, dev, budget):
+    """the z-buffer loop of `render_cloud` and `mesh.render_mesh`: B cameras in chunks whose int64 [b1 - b0, H, W] buffer stays under `budget` bytes (the
+    caller's `ZBUF_BYTES`) and inside one launch's limits -> (b0, b1, z) per chunk, z cleared to all ones, the empty key.  The first chunk is the largest."""
+    step = max(1, min(budget // (8 * H * W), 65535, (2 ** 31 - 1) // (H * W), B))
+    zbuf = torch.empty(step, H, W, dtype=torch.int64, device=dev)
+    for b0 in range(0, B, step):
+        b1 = min(b0 + step, B)
+        z = zbuf[:b1 - b0]
+        z.fill_(-1)
+        yield b0, b1, z
+
+
 class CloudRender:
     """B views of one cloud at one shape: depth [B,H,W] fp32 (the camera-frame z of the pixel's nearest point, 0 where no point landed), pan [B,H,W] int32
     (its panoptic id, 0 where empty), rgb, colors [B,H,W,3] fp32 (its image colour and its blended colour, 0 where empty), index [B,H,W] int64 (its row
@@ -41,7 +65,7 @@ class CloudRender:
 
     def __getitem__(self, b):
         """the render of camera b alone, [1,H,W] views"""
-        s = slice(b, b + 1) if b >= 0 else slice(b + len(self), b + len(self) + 1)
+        s = one_camera(b, len(self))
         return CloudRender(self.depth[s], self.pan[s], self.rgb[s], self.colors[s], self.index[s])
 
 
@@ -49,9 +73,10 @@ def _host64(x):
     return np.asarray(torch.as_tensor(x).detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
 
 
-def camera_table(cams2world, focals, shape, pp=None, near=1e-3):
-    """the float32 [B, 16] table of the kernels (include/panst3r_hip.h, step 1) of B camera-to-world matrices, on the host in float64: per camera the rows
-    of [R^T | -R^T t] rounded to float32, then focal, principal point (default (W / 2, H / 2)) and near.  Raises ValueError for anything unusable."""
+def world_to_camera(cams2world, shape, pp, who):
+    """what `camera_table` and `mesh.mesh_camera_table` share, on the host in float64: B camera-to-world matrices ([B, 4, 4] or a list of [4, 4]) ->
+    (float32 [B, 12], per camera the rows of [R^T | -R^T t] rounded to float32 (include/panst3r_hip.h, step 1), and float64 [B, 2], the principal
+    points: `pp` as one (cx, cy) pair or one per camera, default (W / 2, H / 2)).  `who` is the caller's name in the message.  Raises ValueError."""
     H, W = (int(s) for s in shape)
     if isinstance(cams2world, (list, tuple)):
         mats = [_host64(c) for c in cams2world]
@@ -64,9 +89,27 @@ def camera_table(cams2world, focals, shape, pp=None, near=1e-3):
             raise ValueError('cams2world must be [B, 4, 4] (or a list of [4, 4]), got %s' % (tuple(c.shape),))
     B = c.shape[0]
     if B == 0:
-        raise ValueError('render_cloud needs at least one camera')
+        raise ValueError('%s needs at least one camera' % who)
     if not np.isfinite(c).all():
         raise ValueError('a camera-to-world matrix has a non-finite entry')
+    p = np.array([W / 2, H / 2]) if pp is None else _host64(pp)
+    if p.size not in (2, 2 * B) or not np.isfinite(p).all():
+        raise ValueError('pp must be a finite (cx, cy) pair, one per camera or one for all, got %r' % (pp,))
+    rows = np.empty((B, 12), dtype=np.float32)
+    with np.errstate(over='ignore'):
+        for b in range(B):
+            R, t = c[b, :3, :3], c[b, :3, 3]
+            for a in range(3):
+                rows[b, 4 * a:4 * a + 3] = R[:, a]                                                 # row a of R^T
+                rows[b, 4 * a + 3] = -((R[0, a] * t[0] + R[1, a] * t[1]) + R[2, a] * t[2])
+    return rows, np.broadcast_to(p.reshape(-1, 2), (B, 2))
+
+
+def camera_table(cams2world, focals, shape, pp=None, near=1e-3):
+    """the float32 [B, 16] table of the kernels (include/panst3r_hip.h, step 1) of B camera-to-world matrices, on the host in float64: per camera the rows
+    of [R^T | -R^T t] rounded to float32, then focal, principal point (default (W / 2, H / 2)) and near.  Raises ValueError for anything unusable."""
+    rows, p = world_to_camera(cams2world, shape, pp, 'render_cloud')
+    B = rows.shape[0]
     f = _host64(focals).reshape(-1)
     if f.size == 1:
         f = np.repeat(f, B)
@@ -75,18 +118,9 @@ def camera_table(cams2world, focals, shape, pp=None, near=1e-3):
     nr = float(near)
     if not (math.isfinite(nr) and np.float32(nr) > 0):
         raise ValueError('near must be a positive finite float32, got %r' % (near,))
-    p = np.array([W / 2, H / 2]) if pp is None else _host64(pp)
-    if p.size not in (2, 2 * B) or not np.isfinite(p).all():
-        raise ValueError('pp must be a finite (cx, cy) pair, one per camera or one for all, got %r' % (pp,))
-    p = np.broadcast_to(p.reshape(-1, 2), (B, 2))
     tab = np.empty((B, hip.RENDER_CAM_FLOATS), dtype=np.float32)
     with np.errstate(over='ignore'):
-        for b in range(B):
-            R, t = c[b, :3, :3], c[b, :3, 3]
-            for a in range(3):
-                tab[b, 4 * a:4 * a + 3] = R[:, a]                                                  # row a of R^T
-                tab[b, 4 * a + 3] = -((R[0, a] * t[0] + R[1, a] * t[1]) + R[2, a] * t[2])
-            tab[b, 12], tab[b, 13], tab[b, 14], tab[b, 15] = f[b], p[b, 0], p[b, 1], nr
+        tab[:, :12], tab[:, 12], tab[:, 13:15], tab[:, 15] = rows, f, p, nr
     if not (np.isfinite(tab).all() and (tab[:, 12] > 0).all()):
         raise ValueError('a camera does not fit float32 (matrix, focal or principal point)')
     return tab
@@ -117,9 +151,7 @@ def render_cloud(cloud, cams2world, focals, shape, *, pp=None, radius=0, point_s
     holes).  Per pixel the nearest point wins (equal depths: the smallest row); points behind the camera, nearer than `near`, non-finite or off-screen
     leave no trace.  Cameras are taken in chunks so that the z-buffer stays under `ZBUF_BYTES`.  No host sync when the cameras are host values.
     GPU only: a CPU cloud raises."""
-    H, W = (int(s) for s in shape)
-    if H < 1 or W < 1 or H * W > 2 ** 31 - 1:
-        raise ValueError('shape must be (H, W) with 1 <= H * W < 2^31, got %r' % (tuple(shape),))
+    H, W = image_shape(shape)
     tab = camera_table(cams2world, focals, (H, W), pp, near)
     radius, max_radius, half = _check_footprint(cloud, radius, point_size, max_radius)
     M = int(cloud.pan.shape[0])
@@ -140,12 +172,7 @@ def render_cloud(cloud, cams2world, focals, shape, *, pp=None, radius=0, point_s
     e3 = lambda: torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
     out = CloudRender(torch.empty(B, H, W, dtype=torch.float32, device=dev), torch.empty(B, H, W, dtype=torch.int32, device=dev), e3(), e3(),
                       torch.empty(B, H, W, dtype=torch.int64, device=dev))
-    step = max(1, min(ZBUF_BYTES // (8 * H * W), 65535, (2 ** 31 - 1) // (H * W), B))
-    zbuf = torch.empty(step, H, W, dtype=torch.int64, device=dev)
-    for b0 in range(0, B, step):
-        b1 = min(b0 + step, B)
-        z = zbuf[:b1 - b0]
-        z.fill_(-1)                                                           # all ones: the empty key
+    for b0, b1, z in zbuf_chunks(B, H, W, dev, ZBUF_BYTES):
         hip.render_splat(points, cams[b0:b1], H, W, half, radius, max_radius, z)
         hip.render_resolve(z, rgb, colors, pan, out.index[b0:b1], out.depth[b0:b1], out.pan[b0:b1], out.rgb[b0:b1], out.colors[b0:b1])
     return out

@@ -1151,25 +1151,33 @@ CLOUD_WG = 1024            # points per workgroup of the count / compact passes
 CLOUD_MAX_COLORS = 4096    # colour table rows that fit in LDS
 
 
-def cloud_view_table(views, cams2world, device):
-    """device table of pst_cloud_view for views = [(conf, pts3d, pts3d_local, img, pan)] (contiguous device tensors, which the caller keeps alive)
-    and cams2world = [V, 3, 4] host floats -> (uint8 tensor, number of workgroups, total number of points)"""
+def _view_table(views, cams2world, device, what):
+    """device table of pst_cloud_view for views = [(conf, pts3d, pts3d_local, img, pan)] (contiguous device tensors, which the caller keeps alive; a
+    plane that is None stays NULL) and cams2world = [V, 3, 4] host floats -> (uint8 tensor, number of workgroups, total number of `what`)"""
     tab = (CloudView * len(views))()
     off = wg = 0
     for e, (conf, pts, loc, img, pan), c2w in zip(tab, views, cams2world):
-        for t, dt in ((conf, torch.float32), (pts, torch.float32), (loc, torch.float32), (img, torch.float32), (pan, torch.int32)):
-            _dev(t, dt)
-            assert t.is_contiguous() and t.device == conf.device
         n = conf.numel()
-        assert n > 0 and pts.numel() == 3 * n and loc.numel() == 3 * n and img.numel() == 3 * n and pan.numel() == n
-        e.conf, e.pts3d, e.pts3d_local, e.img, e.pan = conf.data_ptr(), pts.data_ptr(), loc.data_ptr(), img.data_ptr(), pan.data_ptr()
+        assert n > 0
+        for t, dt, k in ((conf, torch.float32, 1), (pts, torch.float32, 3), (loc, torch.float32, 3), (img, torch.float32, 3), (pan, torch.int32, 1)):
+            if t is not None:
+                _dev(t, dt)
+                assert t.is_contiguous() and t.device == conf.device and t.numel() == k * n
+        e.conf, e.pts3d, e.pts3d_local, e.img, e.pan = (None if t is None else t.data_ptr() for t in (conf, pts, loc, img, pan))
         e.offset, e.npix, e.first_wg = off, n, wg
         e.c2w[:] = [float(x) for row in c2w for x in row]
         off += n
         wg += (n + CLOUD_WG - 1) // CLOUD_WG
     if off >= 2 ** 31:
-        raise RuntimeError('a scene of %d points exceeds the 2^31 - 1 the cloud kernels index' % off)
+        raise RuntimeError('a scene of %d %s exceeds the 2^31 - 1 the kernels of a view table index' % (off, what))
     return torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(device), wg, off
+
+
+def cloud_view_table(views, cams2world, device):
+    """device table of pst_cloud_view for views = [(conf, pts3d, pts3d_local, img, pan)] (contiguous device tensors, which the caller keeps alive)
+    and cams2world = [V, 3, 4] host floats -> (uint8 tensor, number of workgroups, total number of points)"""
+    assert all(t is not None for v in views for t in v)
+    return _view_table(views, cams2world, device, 'points')
 
 
 def cloud_count(table, nviews, nwg, thr, counts):
@@ -1432,23 +1440,10 @@ def consist_view_table(views, cams2world, cams, shapes, device):
     shapes = [(H, W)] -> (pst_cloud_view table as a uint8 tensor - img is not read and stays NULL -, cams tensor, dims int32 [V, 2], number of
     workgroups, total number of pixels)"""
     assert len(views) == len(cams2world) == len(shapes) == len(cams) > 0 and tuple(cams.shape) == (len(views), RENDER_CAM_FLOATS)
-    tab = (CloudView * len(views))()
-    off = wg = 0
-    for e, (conf, pts, loc, pan), c2w, (H, W) in zip(tab, views, cams2world, shapes):
-        for t, dt in ((conf, torch.float32), (pts, torch.float32), (loc, torch.float32)) + (((pan, torch.int32),) if pan is not None else ()):
-            _dev(t, dt)
-            assert t.is_contiguous() and t.device == conf.device
-        n = conf.numel()
-        assert n > 0 and n == int(H) * int(W) and pts.numel() == 3 * n and loc.numel() == 3 * n and (pan is None or pan.numel() == n)
-        e.conf, e.pts3d, e.pts3d_local, e.img, e.pan = conf.data_ptr(), pts.data_ptr(), loc.data_ptr(), None, None if pan is None else pan.data_ptr()
-        e.offset, e.npix, e.first_wg = off, n, wg
-        e.c2w[:] = [float(x) for row in c2w for x in row]
-        off += n
-        wg += (n + CLOUD_WG - 1) // CLOUD_WG
-    if off >= 2 ** 31:
-        raise RuntimeError('a scene of %d pixels exceeds the 2^31 - 1 the consistency kernels index' % off)
+    assert all(t is not None for v in views for t in v[:3]) and all(v[0].numel() == int(H) * int(W) for v, (H, W) in zip(views, shapes))
+    table, wg, off = _view_table([(conf, pts, loc, None, pan) for conf, pts, loc, pan in views], cams2world, device, 'pixels')
     dims = torch.tensor([(int(H), int(W)) for H, W in shapes], dtype=torch.int32).reshape(-1, 2)
-    return (torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(device), torch.from_numpy(cams).contiguous().to(device), dims.to(device), wg, off)
+    return table, torch.from_numpy(cams).contiguous().to(device), dims.to(device), wg, off
 
 
 def _consist_tables(table, cams, nviews):
@@ -1480,7 +1475,7 @@ def consist_count(table, cams, dims, nviews, nwg, rel_tol, local, depth, agree, 
 # ------------------------------------------------------------------ z-buffered rasterisation of a labelled mesh (csrc/mesh.hip; engine/mesh.py holds the public entry points)
 MESH_PRECHECK = 0          # RENDER_PRECHECK's relaxed load before the atomic: OFF here - a mesh has a few samples per pixel, most atomics win, and the load
                            # only adds to them (0.87 against 0.56 ms for 16 cameras: tests/diag/mesh_bench.py, docs/experiments.md §6l)
-MESH_CAM_FLOATS = 16       # floats per camera of the device table: twelve world-to-camera numbers, fx, fy, cx, cy
+MESH_CAM_FLOATS = RENDER_CAM_FLOATS    # floats per camera of the device table: twelve world-to-camera numbers, fx, fy, cx, cy
 MESH_LANE_PIXELS = 64      # PST_MESH_LANE_PIXELS (pst_mesh_lane_pixels() of the built library; tests/test_mesh_host.py holds the three together)
 MESH_BIG_CAPACITY = 1 << 22    # the most (camera, face) entries the list of large faces gets (8 bytes each); beyond it a large face stays with its lane
 
