@@ -576,7 +576,9 @@ int pst_vcc_apply(const int32_t* pan, const int32_t* root, const int32_t* size, 
  *               atomics only: the result does not depend on scheduling.  `precheck` != 0 reads the cell first (relaxed) and skips an atomic that
  *               cannot win (same results).
  *   6 resolve   per pixel of zbuf (npix = B H W): an empty cell gives index -1, depth 0, pan 0, rgb = colors = 0; otherwise index int64 = the winning row,
- *               depth fp32 = its zc, and pan int32, rgb, colors fp32 [., 3] are that row's.  Plain vector stores.
+ *               depth fp32 = its zc, and pan int32, rgb, colors fp32 [., 3] are that row's.  Plain vector stores.  A cell counts as EMPTY if it is all
+ *               ones or if the row in its key is >= M (no buffer that pst_render_splat filled over the same cloud holds one: nothing is read outside the
+ *               cloud).  The depth bits of any other key come back as they are, whatever they spell.
  * 1 <= M <= 2^32 - 1 (the row is 32 bits of the key), 1 <= B <= 65535, B H W <= 2^31 - 1.  Nothing can fail on the device: there is no status word. */
 #define PST_RENDER_MAX_RADIUS 16
 int pst_render_max_radius(void);
@@ -648,7 +650,9 @@ int pst_consist_count(const pst_cloud_view* views, const float* cams, const int3
  *   7 resolve   an empty cell gives face -1, depth 0, id 0; otherwise face int64 and depth fp32 come from the key.  With face_ids int32 [Nf] the id
  *               is face_ids[face].  With vertex_ids int32 [Nv] the E_k of that face at that pixel are recomputed and the id is vertex_ids[corner] of
  *               the corner with the largest E_k (the nearest corner), ties to the lowest position as listed in `faces`; ids are never blended.
- *               With neither the id is 0.  Plain vector stores.
+ *               With neither the id is 0.  Plain vector stores.  A cell counts as EMPTY if it is all ones or if the face in its key is >= Nf.  With
+ *               vertex_ids, a key whose face is left out or has an empty bounding box in that cell's camera (steps 3 and 4: it cannot have won a pixel
+ *               there) gives id 0, with face and depth from the key.  Neither arises from a buffer pst_mesh_raster filled over the same mesh and cameras.
  *   8 area      an id i is LISTED with row id2row[i] if 0 < i < ntab and that entry is in [0, S) (as pst_pq_count maps ids).  counts int32 [B, S],
  *               cleared by the CALLER: the pixels of every (camera, listed id), int32 atomicAdd only.  pst_mesh_area_apply: out = the id if it is
  *               listed and its count in that camera is >= min_area, else 0 (min_area = 0 only removes unlisted ids).  out is not pan.

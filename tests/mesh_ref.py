@@ -12,7 +12,8 @@ include/panst3r_hip.h:
               or E_k == 0 on a top or left edge (dy < 0, or dy == 0 and dx > 0).  Only the pixels of the clipped bounding box are tested.
   5 depth     q_k = 1.0 / float64(zc_k); s = (E0 q0 + E1 q1) + E2 q2; depth = float32(float64(A) / s); left out if not finite, < near or > far.
   6 z-buffer  key = (uint64(bits(depth)) << 32) | face; np.minimum.at into a uint64 buffer of all ones.
-  7 resolve   empty: face -1, depth 0, id 0; face_ids[face], or vertex_ids of the corner with the largest E_k (ties: the lowest listed position).
+  7 resolve   empty, or a key whose face is >= Nf: face -1, depth 0, id 0; face_ids[face], or vertex_ids of the corner with the largest E_k (ties: the
+              lowest listed position; a face that is not rasterised in this camera: id 0).
   8 area      per (camera, listed id) pixel counts; an id that is not listed or has fewer than min_area pixels in its camera becomes 0.
 Elementwise numpy rounds every float32 / float64 operation on its own, which is what the kernels promise; int64 arithmetic and the minimum are exact."""
 import numpy as np
@@ -105,8 +106,9 @@ def raster(s, H, W, near, far):
 
 def resolve(zbuf, s, faces, H, W, vertex_ids=None, face_ids=None):
     """step 7 for one camera -> (face int64, depth float32, pan int32, ties) flat [H * W]; ties = the hit pixels whose largest E_k is shared"""
-    hit = zbuf != EMPTY
-    face = np.where(hit, zbuf & np.uint64(0xFFFFFFFF), np.uint64(0)).astype(np.int64)
+    low = zbuf & np.uint64(0xFFFFFFFF)
+    hit = (zbuf != EMPTY) & (low < np.uint64(len(s['ok'])))                  # a key that names a face >= Nf is an empty cell
+    face = np.where(hit, low, np.uint64(0)).astype(np.int64)
     depth = np.where(hit, (zbuf >> np.uint64(32)).astype(np.uint32).view(F), F(0)).astype(F)
     pan, ties = np.zeros(H * W, dtype=np.int32), np.zeros(H * W, dtype=bool)
     pix = np.arange(H * W)
@@ -119,8 +121,9 @@ def resolve(zbuf, s, faces, H, W, vertex_ids=None, face_ids=None):
     if face_ids is not None:
         pan = np.where(hit, np.asarray(face_ids, dtype=np.int32)[face], 0).astype(np.int32)
     elif vertex_ids is not None:
+        seen = hit & s['ok'][face]                                             # a face that leaves no trace in this camera: id 0, face and depth from the key
         corner = np.asarray(faces, dtype=np.int64).reshape(-1, 3)[face, pos]
-        pan = np.where(hit, np.asarray(vertex_ids, dtype=np.int32)[np.where(hit, corner, 0)], 0).astype(np.int32)
+        pan = np.where(seen, np.asarray(vertex_ids, dtype=np.int32)[np.where(seen, corner, 0)], 0).astype(np.int32)
     return np.where(hit, face, -1), depth, pan, ties
 
 

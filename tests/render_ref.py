@@ -10,7 +10,7 @@ Own design (the reference has no such stage).  The six steps of the contract in 
   4 footprint r = min(max_radius, max(radius, floor((f half_size) / zc))), half_size = float32(point_size / 2); the (2r + 1)^2 pixels around (px, py),
               clipped to the image.
   5 depth     key = (uint64(bits(zc)) << 32) | uint32(row); np.minimum.at into a uint64 buffer of all ones.
-  6 resolve   an empty cell: index -1, zeros; otherwise the key's row and depth, and that row's pan, rgb, colors.
+  6 resolve   an empty cell, or a key whose row is >= M: index -1, zeros; otherwise the key's row and depth, and that row's pan, rgb, colors.
 Elementwise float32 numpy rounds every operation on its own, which is what the kernels promise; the minimum of integers is exact in any order."""
 import numpy as np
 
@@ -79,6 +79,18 @@ def splat(points, cam, H, W, half_size, radius, max_radius):
     return zbuf, cand, behind
 
 
+def resolve(zbuf, rgb, colors, pan):
+    """step 6 on the flat uint64 cells of any number of cameras -> (index int64, depth float32, pan int32, rgb, colors float32 [., 3]); a cell is empty if it
+    is all ones or if its key names a row >= M = len(pan)"""
+    zbuf = np.asarray(zbuf, dtype=np.uint64).reshape(-1)
+    low = zbuf & np.uint64(0xFFFFFFFF)
+    hit = (zbuf != EMPTY) & (low < np.uint64(len(pan)))
+    row = np.where(hit, low, np.uint64(0)).astype(np.int64)
+    depth = np.where(hit, (zbuf >> np.uint64(32)).astype(np.uint32).view(F), F(0)).astype(F)
+    gather = lambda t, zero: np.where(hit.reshape((-1,) + (1,) * (t.ndim - 1)), t[row], zero).astype(t.dtype) if len(t) else np.zeros((len(zbuf),) + t.shape[1:], t.dtype)
+    return np.where(hit, row, -1), depth, gather(pan, np.int32(0)), gather(rgb, F(0)), gather(colors, F(0))
+
+
 def render(points, rgb, colors, pan, cams2world, focals, shape, pp=None, radius=0, point_size=0.0, max_radius=8, near=1e-3):
     """-> dict(depth [B,H,W] float32, pan [B,H,W] int32, rgb, colors [B,H,W,3] float32, index [B,H,W] int64) and, about the run itself,
     candidates [B,H,W] int64 and behind [B]"""
@@ -90,15 +102,12 @@ def render(points, rgb, colors, pan, cams2world, focals, shape, pp=None, radius=
     out = {k: [] for k in ('depth', 'pan', 'rgb', 'colors', 'index', 'candidates', 'behind')}
     for cam in tab:
         zbuf, cand, behind = splat(points, cam, H, W, half, int(radius), int(max_radius))
-        hit = zbuf != EMPTY                                                                          # step 6
-        row = np.where(hit, zbuf & np.uint64(0xFFFFFFFF), np.uint64(0)).astype(np.int64)
-        depth = np.where(hit, (zbuf >> np.uint64(32)).astype(np.uint32).view(F), F(0)).astype(F)
-        gather = lambda t, zero: np.where(hit.reshape((-1,) + (1,) * (t.ndim - 1)), t[row], zero).astype(t.dtype) if len(t) else np.zeros((H * W,) + t.shape[1:], t.dtype)
-        out['index'].append(np.where(hit, row, -1).reshape(H, W))
+        index, depth, opan, orgb, ocolors = resolve(zbuf, rgb, colors, pan)                          # step 6
+        out['index'].append(index.reshape(H, W))
         out['depth'].append(depth.reshape(H, W))
-        out['pan'].append(gather(pan, np.int32(0)).reshape(H, W))
-        out['rgb'].append(gather(rgb, F(0)).reshape(H, W, 3))
-        out['colors'].append(gather(colors, F(0)).reshape(H, W, 3))
+        out['pan'].append(opan.reshape(H, W))
+        out['rgb'].append(orgb.reshape(H, W, 3))
+        out['colors'].append(ocolors.reshape(H, W, 3))
         out['candidates'].append(cand.reshape(H, W))
         out['behind'].append(behind)
     return {k: np.stack(v) for k, v in out.items()}

@@ -8,6 +8,7 @@ import torch
 
 import abi_header
 import mesh_ref as M
+from camera_stage_cases import QUADS, inside_quad      # shared with the GPU cases of tests/test_hip_camera_stages.py
 from panst3r_amd import hip
 from panst3r_amd.engine import mesh as mesh_mod
 from panst3r_amd.engine import render_mesh, ground_truth_maps, mesh_camera_table, load_ply_mesh, panoptic_vertex_ids, MeshRender
@@ -26,29 +27,6 @@ def coverage(quads_as_faces, verts, shape):
     """how many faces cover each pixel centre: the candidates of the restatement"""
     r = M.render(verts, quads_as_faces, **pixel_camera(shape))
     return r['candidates'][0]
-
-
-def inside_quad(quad, H, W):
-    """exact, in integers (coordinates x 4): +1 strictly inside the convex quad, 0 on its boundary, -1 outside, per pixel centre"""
-    q = np.rint(np.asarray(quad) * 4).astype(np.int64)
-    py, px = np.meshgrid(4 * np.arange(H) + 2, 4 * np.arange(W) + 2, indexing='ij')
-    sides = []
-    for k in range(4):
-        a, b = q[k], q[(k + 1) % 4]
-        sides.append((b[0] - a[0]) * (py - a[1]) - (b[1] - a[1]) * (px - a[0]))
-    s = np.stack(sides)
-    if sum(q[k][0] * q[(k + 1) % 4][1] - q[(k + 1) % 4][0] * q[k][1] for k in range(4)) < 0:
-        s = -s                                                                 # the other orientation
-    return np.where((s > 0).all(axis=0), 1, np.where((s >= 0).all(axis=0), 0, -1))
-
-
-QUADS = [
-    [(2.5, 2.5), (9.5, 2.5), (9.5, 7.5), (2.5, 7.5)],                          # every edge through pixel centres, both diagonals too (a 7 x 5 box: one is not)
-    [(3.5, 1.5), (8.5, 1.5), (8.5, 6.5), (3.5, 6.5)],                          # a square: both diagonals through pixel centres
-    [(1.0, 1.0), (12.0, 2.0), (11.0, 9.0), (2.0, 8.0)],
-    [(4.5, 0.5), (10.5, 4.5), (6.5, 10.5), (0.5, 6.5)],                        # a tilted square, corners on pixel centres
-    [(2.25, 3.75), (11.75, 1.25), (13.5, 8.5), (3.5, 9.75)],
-]
 
 
 @pytest.mark.parametrize('quad', QUADS)
