@@ -47,7 +47,11 @@ const char* pst_last_error(void);
  * CrossAttention projections (model/blocks.py:18-26, input_mixer.py:13-20, pixel_shuffle.py:17-27), LoftUp convs
  * (loftup.py:122-130), MaskTransformer projections + FFN + MLP heads (mask_transformer.py:222-230,314,372,435-437)
  * and the query x pixel einsum "bqc,bnchw->bnqhw" (mask_transformer.py:280) with mask_feats kept pixel-major.
- * Requirements: K % 64 == 0, N % 4 == 0, lda/ldw multiples of 8, A/W 16-byte aligned, C rows 16-byte aligned.
+ * Requirements: K % 64 == 0, N % 4 == 0, lda/ldw multiples of 8, A/W 16-byte aligned; ldc % 4 == 0 with C 16-byte aligned when fp32 and
+ * 8-byte aligned when 16-bit (so rows of a 16-bit C may be 8-byte but not 16-byte aligned: the 64 x 64, 128 x 128 and non-persistent 256 x 256
+ * kernels store such rows in 8-byte halves; the persistent and row-streaming classes want ldc % 8 == 0 and a 16-byte aligned C and leave any other
+ * layout to the tiled kernels, same bits).  A 16-bit residual: ldr % 8 == 0, 16-byte aligned; an fp32 one: ldr % 4 == 0.
+ * Held to these layouts by tests/test_hip_gemm_layout.py.
  */
 typedef struct pst_gemm_params {
   const void* A;  int64_t lda;       /* bf16 [M, K] (or NHWC image stack in conv mode) */
