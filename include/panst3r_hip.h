@@ -625,6 +625,65 @@ int pst_consist_depth(const pst_cloud_view* views, const float* cams, int nviews
 int pst_consist_count(const pst_cloud_view* views, const float* cams, const int32_t* dims, int nviews, int nwg, int64_t N, float rel_tol, int local,
                       const float* depth, int32_t* agree, int32_t* violate, int32_t* same_label, void* stream);
 
+/* ---------------------------------------------------------------- one fused TSDF surface out of all views (f15; ABI 20, additive; no counterpart in the reference)
+ * A truncated signed distance averaged over the views on the lattice nodes around the occupied voxels, free space carved by the views that see
+ * through it, ONE sheet extracted by naive surface nets (no case table); restated in tests/tsdf_ref.py [restated, parity unpinned], held to it bit
+ * for bit.  Inputs: cells int32 [Mv, 3], the unique integer cells of a voxel cloud at the voxel size vs (fp32) with its count, pan and colors; the
+ * cloud's pst_cloud_view table with the consistency section's cams, dims and depth (pst_consist_depth at the cloud's own threshold); band in
+ * [1, PST_TSDF_MAX_BAND]; min_weight >= 1.  No float atomics; every fp32 product, sum and difference is rounded on its own, in the order written
+ * (contraction off); every test is written so that a NaN fails it; two calls return identical bytes.
+ *   1 nodes     A node is n in Z^3 at p_a = fp32(n_a) vs (one rounded product).  Pair p = row (2 band)^3 + offset, offset = ox + 2 band (oy + 2 band oz),
+ *               names the node n_a = c_a - band + 1 + o_a of voxel `row`: per occupied cell the (2 band)^3 nodes c_a - band + 1 <= n_a <= c_a + band are
+ *               ACTIVE (band 1: the cell's eight corners).  pst_tsdf_insert: one lane per pair, the node's 3 x 21-bit key claimed in keys uint64 [cap]
+ *               (all ones = empty, cap a power of two >= 2 pairs), atomicMin of p into first int32 [cap] (2^31 - 1 before), pair_slot int32 [pairs].
+ *               A node outside (-2^20, 2^20) is not inserted and sets PST_TSDF_RANGE in status[0], a table without a free slot PST_TSDF_FULL: no
+ *               result then.  THE ORDER: a node's rank is the order of its smallest pair: pst_voxel_count / pst_cloud_scan / pst_voxel_rank on
+ *               (pair_slot, first) give slot_rank int32 [cap], first_pair int32 [pairs] and the number of nodes Nn.  pst_tsdf_nodes: nodes int32
+ *               [Nn, 3] in rank order, and voxel_row int32 [Nn] (-1 before): the voxel whose cell IS the node, n = c.
+ *   2 integrate pst_tsdf_integrate, one lane per node, the views j in ascending order (a view whose H W exceeds its npix takes no part); S = 0, W = 0:
+ *               pc = W2C_j p (the consistency section's `camera`); left out if xc, yc or zc is not finite, then if !(zc >= near_j); u, v as its step 2
+ *               with the limit 2^20; px = floor(u + 0.5f), py likewise; outside the image: left out; d = depth[offset_j + py W_j + px]; d == 0: left
+ *               out; s = d - zc; tau = fp32(band) vs; s < -tau: occluded, the pair counts for nothing; else S = S + min(s, tau), W += 1.
+ *               sdf = fp32(fp64(S) / fp64(fp32(W))) if W > 0, else 0 (no quotient is taken); weight = W.  VALID iff W >= min_weight; INSIDE iff
+ *               sdf < 0 (sdf == 0 is outside).
+ *   3 cells     Cell c has the corner nodes c + {0,1}^3; a SURFACE CELL iff all eight are active and valid and not all on one side.  Its vertex:
+ *               the twelve edges in the order axis x, y, z, within axis a (a, b, c cyclic) the (b, c) offsets 00, 10, 01, 11; for an edge whose ends
+ *               differ in side, t = fp64(Da) / (fp64(Da) - fp64(Db)) with a the lower node, the crossing = lower corner offset + t e_a in cell units;
+ *               the crossings are summed per coordinate in fp64 in that order and divided by their number; vertex_a = fp32((fp64(c_a) + mean_a) fp64(vs)).
+ *               Vertices come in the rank order of their cell's node n = c (pst_tsdf_cells: flags and counts per 1024 nodes; pst_cloud_scan;
+ *               pst_tsdf_vertices, which leaves cell_vertex int32 [Nn]: the vertex row of the cell at each node, else -1).
+ *   4 labels    The vertex takes vertex id pan[w] and colour colors[w] of the voxel w = voxel_row of node c; without one, of the voxel with the largest
+ *               count among those of the 26 neighbouring cells (ties to the smaller row); without any, id 0 and colour 0.
+ *   5 faces     For the lattice edge from node n along axis a between two valid nodes of different sides, the four cells n + (b, c) offsets q0 = (0,0),
+ *               q1 = (-1,0), q2 = (-1,-1), q3 = (0,-1): if all are surface cells, two triangles over their vertices, (q0,q1,q2), (q0,q2,q3) when n is
+ *               inside and (q0,q2,q1), (q0,q3,q2) when it is outside: the normal (v1 - v0) x (v2 - v0) points from inside to outside, towards the
+ *               cameras.  Face id: the id two of its corners share, else 0 (the surface section's rule).  edge int64 = 3 rank(n) + a.  Faces come in
+ *               the order node rank, axis, first triangle before second (pst_tsdf_face_count: face_mask int32 [Nn], bit a, and counts in FACES per
+ *               1024 nodes; pst_cloud_scan; pst_tsdf_face_emit).
+ * Refused with PST_EINVAL before any launch: a null operand, band outside [1, PST_TSDF_MAX_BAND], min_weight < 1, Mv (2 band)^3 or Nn outside
+ * [1, 2^30 - 1], cap no power of two >= twice the pairs (insert) / the nodes (the others), nviews outside [1, 65535], a voxel size that is no
+ * positive finite number.  No confidence weighting, no bilinear depth, no marching-cubes table, no vertex normals; cells only where the cloud has
+ * points +- band. */
+#define PST_TSDF_FULL 1       /* a table ran full */
+#define PST_TSDF_RANGE 4      /* a node outside (-2^20, 2^20) */
+#define PST_TSDF_MAX_BAND 4
+int pst_tsdf_insert(const int32_t* cells, int64_t Mv, int band, uint64_t* keys, int64_t cap, int32_t* first, int32_t* pair_slot, int32_t* status, void* stream);
+int pst_tsdf_nodes(const int32_t* cells, int64_t Mv, int band, const int32_t* first_pair, int64_t Nn, const uint64_t* keys, int64_t cap,
+                   const int32_t* slot_rank, int32_t* nodes, int32_t* voxel_row, int32_t* status, void* stream);
+int pst_tsdf_integrate(const int32_t* nodes, int64_t Nn, float voxel_size, int band, const pst_cloud_view* views, const float* cams, const int32_t* dims,
+                       int nviews, const float* depth, float* sdf, int32_t* weight, void* stream);
+int pst_tsdf_cells(const int32_t* nodes, int64_t Nn, const uint64_t* keys, int64_t cap, const int32_t* slot_rank, const float* sdf, const int32_t* weight,
+                   int min_weight, int32_t* cell_vertex, int32_t* counts, int32_t* status, void* stream);
+int pst_tsdf_vertices(const int32_t* nodes, int64_t Nn, const uint64_t* keys, int64_t cap, const int32_t* slot_rank, const float* sdf, const int32_t* weight,
+                      int min_weight, const int32_t* voxel_row, const int32_t* vox_count, const int32_t* vox_pan, const float* vox_colors, int64_t Mv,
+                      double voxel_size, const int32_t* base, int32_t* cell_vertex, float* vertices, int32_t* vertex_ids, float* colors, int32_t* status,
+                      void* stream);
+int pst_tsdf_face_count(const int32_t* nodes, int64_t Nn, const uint64_t* keys, int64_t cap, const int32_t* slot_rank, const float* sdf, const int32_t* weight,
+                        int min_weight, const int32_t* cell_vertex, int32_t* face_mask, int32_t* counts, int32_t* status, void* stream);
+int pst_tsdf_face_emit(const int32_t* nodes, int64_t Nn, const uint64_t* keys, int64_t cap, const int32_t* slot_rank, const float* sdf,
+                       const int32_t* cell_vertex, const int32_t* face_mask, const int32_t* vertex_ids, const int32_t* base, int32_t* faces, int32_t* face_ids,
+                       int64_t* edge, int32_t* status, void* stream);
+
 /* ---------------------------------------------------------------- z-buffered triangle rasterisation of a labelled mesh: ground-truth depth and panoptic maps
  * A mesh (vertices fp32 [Nv, 3] in the world frame, faces int32 [Nf, 3], one panoptic id per vertex or per face) seen from B pinhole cameras at one shape
  * (H, W) -> per pixel the nearest face's depth, index and id, and after a per-view minimum-area filter the ground-truth maps pst_pq_count scores

@@ -118,6 +118,11 @@ class PanopticCloud:
         from .surface import panoptic_mesh
         return panoptic_mesh(self, **kw)
 
+    def fused_mesh(self, voxel_size, **kw):
+        """engine.tsdf.fuse_surface of this cloud: ONE surface fused from all views in a volume, where `mesh` gives a sheet per view"""
+        from .tsdf import fuse_surface
+        return fuse_surface(self, voxel_size, **kw)
+
     def consistency(self, **kw):
         """engine.consistency.view_consistency of this cloud's own source - its views, cameras, confidence threshold and `local_pointmaps` - with the
         panoptic maps (labels=False: without them); `rel_tol`, `pp`, `near` as there -> `ViewConsistency` over the pixels of the scene"""

@@ -71,6 +71,8 @@ SIGNATURES = {
     'pst_voxel_vote': 'i:pplpp', 'pst_voxel_emit': 'i:pppplfdppppiffppppppp',
     'pst_render_max_radius': 'i:', 'pst_render_splat': 'i:plpiiifiipip', 'pst_render_resolve': 'i:pllppppppppp',
     'pst_consist_depth': 'i:ppiilfipp', 'pst_consist_count': 'i:pppiilfippppp',
+    'pst_tsdf_insert': 'i:pliplpppp', 'pst_tsdf_nodes': 'i:pliplplppppp', 'pst_tsdf_integrate': 'i:plfipppipppp', 'pst_tsdf_cells': 'i:plplpppipppp',
+    'pst_tsdf_vertices': 'i:plplpppippppldppppppp', 'pst_tsdf_face_count': 'i:plplpppippppp', 'pst_tsdf_face_emit': 'i:plplppppppppppp',
     'pst_mesh_lane_pixels': 'i:', 'pst_mesh_raster': 'i:plplpiiiffppplip', 'pst_mesh_resolve': 'i:piiiplplpfpppppp', 'pst_mesh_area_count': 'i:pilpiipp',
     'pst_mesh_area_apply': 'i:pilpiipipp',
     'pst_pq_count': 'i:pplpipipiiipip', 'pst_pq_match': 'i:piiipppppppp',
@@ -1470,6 +1472,118 @@ def consist_count(table, cams, dims, nviews, nwg, rel_tol, local, depth, agree, 
         assert t.is_contiguous() and t.numel() == N and t.device == depth.device
     _call('pst_consist_count', _ptr(table), _ptr(cams), _ptr(dims), nviews, nwg, N, float(rel_tol), int(bool(local)), _ptr(depth), _ptr(agree), _ptr(violate),
           _ptr(same_label))
+
+
+# ------------------------------------------------------------------ one fused TSDF surface out of all views (csrc/tsdf.hip; engine/tsdf.py holds the public entry points)
+TSDF_FULL, TSDF_RANGE = 1, 4       # PST_TSDF_*: the bits of status[0]
+TSDF_MAX_BAND = 4                  # PST_TSDF_MAX_BAND
+TSDF_MAX_PAIRS = 2 ** 30 - 1       # what the count / rank kernels take
+
+
+def tsdf_pairs(Mv, band):
+    """the (voxel row, offset) pairs of Mv voxels at `band`: Mv (2 band)^3"""
+    return int(Mv) * (2 * int(band)) ** 3
+
+
+def tsdf_capacity(Mv, band):
+    """slots of the node table: the next power of two >= twice the pairs"""
+    return voxel_capacity(tsdf_pairs(Mv, band))
+
+
+def tsdf_table_bytes(Mv, band):
+    """device memory of the node table of one fusion: keys (8), first and slot_rank (4 + 4) per slot, pair_slot and first_pair (4 + 4) per pair"""
+    return 16 * tsdf_capacity(Mv, band) + 8 * tsdf_pairs(Mv, band)
+
+
+def tsdf_workspace(Mv, band, device):
+    """the initialised workspaces of the node table of Mv voxels at `band` (include/panst3r_hip.h): dict of device tensors.  The names are those of
+    `voxel_workspace`, so that `voxel_count` / `voxel_rank` rank the nodes: a pair is a point there, a node a voxel."""
+    P = tsdf_pairs(Mv, band)
+    cap = tsdf_capacity(Mv, band)
+    i32 = dict(dtype=torch.int32, device=device)
+    return {'cap': cap, 'keys': torch.full((cap,), -1, dtype=torch.int64, device=device), 'first': torch.full((cap,), 2 ** 31 - 1, **i32),
+            'slot_rank': torch.empty(cap, **i32), 'point_slot': torch.empty(P, **i32), 'first_row': torch.empty(P, **i32), 'status': torch.zeros(4, **i32)}
+
+
+def _tsdf_cells(cells):
+    _dev(cells, torch.int32)
+    assert cells.is_contiguous() and cells.dim() == 2 and cells.shape[1] == 3
+    return cells.shape[0]
+
+
+def tsdf_insert(cells, band, ws):
+    Mv = _tsdf_cells(cells)
+    assert ws['keys'].numel() == ws['cap'] == ws['first'].numel() and ws['point_slot'].numel() == tsdf_pairs(Mv, band)
+    _call('pst_tsdf_insert', _ptr(cells), Mv, int(band), _ptr(ws['keys']), ws['cap'], _ptr(ws['first']), _ptr(ws['point_slot']), _ptr(ws['status']))
+
+
+def tsdf_nodes(cells, band, Nn, ws, nodes, voxel_row):
+    """nodes int32 [Nn, 3] in rank order; voxel_row int32 [Nn] (filled with -1 by the caller): the voxel whose cell is the node"""
+    Mv = _tsdf_cells(cells)
+    _dev(nodes, torch.int32); _dev(voxel_row, torch.int32)
+    assert nodes.is_contiguous() and tuple(nodes.shape) == (Nn, 3) and voxel_row.numel() == Nn and ws['first_row'].numel() == tsdf_pairs(Mv, band)
+    _call('pst_tsdf_nodes', _ptr(cells), Mv, int(band), _ptr(ws['first_row']), Nn, _ptr(ws['keys']), ws['cap'], _ptr(ws['slot_rank']), _ptr(nodes), _ptr(voxel_row),
+          _ptr(ws['status']))
+
+
+def tsdf_integrate(nodes, voxel_size, band, table, cams, dims, nviews, depth, sdf, weight):
+    """sdf fp32 [Nn], weight int32 [Nn] of the nodes against the depth planes of `consist_depth` (table, cams, dims: `consist_view_table`)"""
+    _consist_tables(table, cams, nviews)
+    _dev(nodes, torch.int32); _dev(dims, torch.int32); _dev(depth, torch.float32); _dev(sdf, torch.float32); _dev(weight, torch.int32)
+    Nn = nodes.shape[0]
+    assert nodes.is_contiguous() and nodes.shape[1] == 3 and dims.is_contiguous() and tuple(dims.shape) == (nviews, 2) and depth.is_contiguous()
+    assert sdf.is_contiguous() and weight.is_contiguous() and sdf.numel() == Nn and weight.numel() == Nn
+    _call('pst_tsdf_integrate', _ptr(nodes), Nn, float(voxel_size), int(band), _ptr(table), _ptr(cams), _ptr(dims), nviews, _ptr(depth), _ptr(sdf), _ptr(weight))
+
+
+def _tsdf_nodes(nodes, ws, *per_node):
+    _dev(nodes, torch.int32)
+    Nn = nodes.shape[0]
+    assert nodes.is_contiguous() and nodes.shape[1] == 3 and ws['keys'].numel() == ws['cap'] == ws['slot_rank'].numel()
+    assert all(t.is_cuda and t.is_contiguous() and t.numel() == Nn for t in per_node)
+    return Nn
+
+
+def tsdf_cells(nodes, ws, sdf, weight, min_weight, cell_vertex, counts):
+    """cell_vertex int32 [Nn]: 1 where the cell at the node is a surface cell, else 0; counts [ceil(Nn / 1024)]"""
+    Nn = _tsdf_nodes(nodes, ws, sdf, weight, cell_vertex)
+    _dev(counts, torch.int32)
+    assert counts.numel() == (Nn + CLOUD_WG - 1) // CLOUD_WG
+    _call('pst_tsdf_cells', _ptr(nodes), Nn, _ptr(ws['keys']), ws['cap'], _ptr(ws['slot_rank']), _ptr(sdf), _ptr(weight), int(min_weight), _ptr(cell_vertex),
+          _ptr(counts), _ptr(ws['status']))
+
+
+def tsdf_vertices(nodes, ws, sdf, weight, min_weight, voxel_row, vox_count, vox_pan, vox_colors, voxel_size, base, cell_vertex, vertices, vertex_ids, colors):
+    """vertices fp32 [Nv, 3], vertex_ids int32 [Nv], colors fp32 [Nv, 3] in rank order; cell_vertex becomes the vertex row of every node's cell, or -1"""
+    Nn = _tsdf_nodes(nodes, ws, sdf, weight, voxel_row, cell_vertex)
+    Mv, Nv = vox_pan.numel(), vertex_ids.numel()
+    _dev(vox_count, torch.int32); _dev(vox_pan, torch.int32); _dev(vox_colors, torch.float32); _dev(base, torch.int32)
+    _dev(vertices, torch.float32); _dev(vertex_ids, torch.int32); _dev(colors, torch.float32)
+    assert all(t.is_contiguous() for t in (vox_count, vox_pan, vox_colors, vertices, vertex_ids, colors)) and vox_count.numel() == Mv and vox_colors.numel() == 3 * Mv
+    assert base.numel() == (Nn + CLOUD_WG - 1) // CLOUD_WG + 1 and vertices.numel() == 3 * Nv and colors.numel() == 3 * Nv
+    _call('pst_tsdf_vertices', _ptr(nodes), Nn, _ptr(ws['keys']), ws['cap'], _ptr(ws['slot_rank']), _ptr(sdf), _ptr(weight), int(min_weight), _ptr(voxel_row),
+          _ptr(vox_count), _ptr(vox_pan), _ptr(vox_colors), Mv, float(voxel_size), _ptr(base), _ptr(cell_vertex), _ptr(vertices), _ptr(vertex_ids), _ptr(colors),
+          _ptr(ws['status']))
+
+
+def tsdf_face_count(nodes, ws, sdf, weight, min_weight, cell_vertex, face_mask, counts):
+    """face_mask int32 [Nn]: bit a = the lattice edge from the node along axis a emits two triangles; counts [ceil(Nn / 1024)] in faces"""
+    Nn = _tsdf_nodes(nodes, ws, sdf, weight, cell_vertex, face_mask)
+    _dev(counts, torch.int32)
+    assert counts.numel() == (Nn + CLOUD_WG - 1) // CLOUD_WG
+    _call('pst_tsdf_face_count', _ptr(nodes), Nn, _ptr(ws['keys']), ws['cap'], _ptr(ws['slot_rank']), _ptr(sdf), _ptr(weight), int(min_weight), _ptr(cell_vertex),
+          _ptr(face_mask), _ptr(counts), _ptr(ws['status']))
+
+
+def tsdf_face_emit(nodes, ws, sdf, cell_vertex, face_mask, vertex_ids, base, faces, face_ids, edge):
+    """faces int32 [>= F, 3], face_ids int32, edge int64 [>= F]: rows [0, F) are written, F = base[-1] <= 6 Nv"""
+    Nn = _tsdf_nodes(nodes, ws, sdf, cell_vertex, face_mask)
+    _dev(vertex_ids, torch.int32); _dev(base, torch.int32); _dev(faces, torch.int32); _dev(face_ids, torch.int32); _dev(edge, torch.int64)
+    cap = face_ids.numel()
+    assert base.numel() == (Nn + CLOUD_WG - 1) // CLOUD_WG + 1 and faces.is_contiguous() and faces.numel() == 3 * cap and edge.numel() == cap
+    assert cap >= 6 * vertex_ids.numel() and vertex_ids.is_contiguous()
+    _call('pst_tsdf_face_emit', _ptr(nodes), Nn, _ptr(ws['keys']), ws['cap'], _ptr(ws['slot_rank']), _ptr(sdf), _ptr(cell_vertex), _ptr(face_mask), _ptr(vertex_ids),
+          _ptr(base), _ptr(faces), _ptr(face_ids), _ptr(edge), _ptr(ws['status']))
 
 
 # ------------------------------------------------------------------ z-buffered rasterisation of a labelled mesh (csrc/mesh.hip; engine/mesh.py holds the public entry points)

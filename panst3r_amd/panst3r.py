@@ -363,7 +363,7 @@ class PanSt3R(nn.Module):
 
     @torch.no_grad()
     def reconstruct(self, imgs, true_shape, classes, *, postprocess='standard_v2', min_conf_thr=3.0, opacity=0.5, postprocess_kwargs=None, voxel_size=None,
-                    min_component_voxels=None, consistency=None, **forward_kwargs):
+                    min_component_voxels=None, consistency=None, fused_mesh=None, **forward_kwargs):
         """The body of the demo's `get_reconstructed_scene` (tools/demo_panst3r.py:232-300) in one call, everything on the device:
         forward_inference_multi_ar (outputs left where they are), the chosen panoptic post-processing ('standard_v2' | 'standard_v1' | 'qubo'),
         the cameras of the pointmaps and the panoptic point cloud.  `postprocess_kwargs`: thresholds of the chosen post-processing other than its
@@ -380,6 +380,9 @@ class PanSt3R(nn.Module):
         `consistency` (default None: off, everything returned is what it always was): True, or a dict of the keywords of
         `PanopticCloud.filter_consistent` (min_views, max_violations, rel_tol, pp, near) - the cloud, and the voxels fused from it, then hold only the
         pixels that pass the cross-view depth check of engine/consistency.py (floaters that other views see through are dropped).
+        `fused_mesh` (default None: off, everything returned is what it always was): a voxel size, or a dict of the keywords of `engine.fuse_surface`
+        (voxel_size, band, min_weight, pp, near) - the views are also fused into ONE surface (`PanopticCloud.fused_mesh`, engine/tsdf.py) and the
+        `FusedMesh` is appended to the return value, after the voxels if there are any (whose grid it shares when the sizes are equal).
         It only composes the public entry points."""
         from .engine import panoptic_inference_v2, panoptic_inference_v1, panoptic_inference_qubo, panoptic_point_cloud
         from .engine.pointmaps import cameras_from_pointmaps
@@ -399,6 +402,10 @@ class PanSt3R(nn.Module):
             if voxel_size is None:
                 raise ValueError('min_component_voxels works on the voxels: it is valid only together with voxel_size')
             _check_min_voxels(min_component_voxels)
+        fuse_kw = None
+        if fused_mesh is not None:
+            from .engine.tsdf import fused_mesh_keywords
+            fuse_kw = fused_mesh_keywords(fused_mesh)           # a bad argument raises before the forward pass, not after it
         pms, panout = self.forward_inference_multi_ar(imgs, true_shape, classes, **forward_kwargs)
         pan_preds = fns[postprocess](panout['pred_logits'], panout['pred_masks'], true_shape, label_mode=self.panoptic_decoder.label_mode, multi_ar=True,
                                     **(postprocess_kwargs or {}))
@@ -407,10 +414,17 @@ class PanSt3R(nn.Module):
         cloud = panoptic_point_cloud(x_out, [i.to(dev) for i in imgs], true_shape, pan_preds[0]['pan'], pan_preds[0]['segments_info'], cams2world, focals,
                                      min_conf_thr=min_conf_thr, opacity=opacity, **({} if consistency is None else {'consistency': consistency}))
         cameras = [dict(c, cam2world=c2w) for c, c2w in zip(cloud.cameras, cams2world)]
+        out = (cloud, cameras, pan_preds)
+        voxels = None
         if voxel_size is not None:
             voxels = cloud.voxelize(voxel_size)
-            return cloud, cameras, pan_preds, voxels if min_component_voxels is None else voxels.clean_labels(min_component_voxels)
-        return cloud, cameras, pan_preds
+            if min_component_voxels is not None:
+                voxels = voxels.clean_labels(min_component_voxels)
+            out += (voxels,)
+        if fuse_kw is not None:
+            same_grid = voxels is not None and float(voxels.voxel_size) == float(fuse_kw['voxel_size'])
+            out += (cloud.fused_mesh(vox=voxels if same_grid else None, **fuse_kw),)
+        return out
 
     @torch.no_grad()
     def evaluate(self, pan_preds, gt_maps, gt_segments, **kw):
