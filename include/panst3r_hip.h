@@ -1020,6 +1020,57 @@ int pst_pq_count(const int32_t* pred, const int32_t* gt, int64_t N, const int64_
 int pst_pq_match(const int32_t* counts, int nslabs, int P, int G, const int32_t* cat_p, const int32_t* cat_g, int32_t* pred_area, int32_t* gt_area,
                  int32_t* match, double* iou, int32_t* pred_state, void* stream);
 
+/* ---------------------------------------------------------------- depth evaluation against ground truth (f16; ABI 20, additive; no counterpart in the reference)
+ * V predicted depth maps against V ground-truth depth maps of the same shapes (0 = no surface, as pst_mesh_resolve writes them): the moments of an
+ * alignment p' = s p + b, exact medians, and the error sums behind AbsRel, SqRel, RMSE, MAE and the inlier ratios delta < t.  Restated in numpy in
+ * tests/depth_eval_ref.py [restated, parity unpinned]; csrc/depth_eval.hip is held to that bit for bit.  Contraction is off in the kernels: every fp32
+ * and fp64 operation is rounded on its own, in the order written here.
+ *   1 valid     pixel i of a view is VALID iff g = gt[i] is finite and min_depth < g <= max_depth, p = pred[i * stride] is finite and p > 0, and, where
+ *               the view has a confidence plane, conf[i] >= conf_thr (a NaN confidence is invalid: the rule of pst_cloud_count, so a
+ *               consistency-filtered source scores only what it kept).  Validity never depends on the alignment.
+ *   2 slabs     S = nslabs slabs, each a run of consecutive views: every view its own (scope 'view'), or one slab with all views (scope 'scene').  A
+ *               slab is aligned and scored as one.
+ *   3 blocks    the view table: row v = PST_DEPTH_VIEW_WORDS int64 words - [0] the address of pred (fp32), [1] its element stride >= 1 (3 reads the z
+ *               of a pointmap in place), [2] the address of gt (fp32, stride 1), [3] the address of conf (fp32, stride 1) or 0, [4] npix >= 1, [5]
+ *               first_block, [6] slab, [7] 0.  View v owns the ceil(npix / PST_ICP_CHUNK) consecutive blocks from first_block (view 0 starts at 0, the
+ *               blocks of all views count to nblocks); slab is 0 for view 0, ascends by 0 or 1 and ends at S - 1.  `views` is the table in DEVICE
+ *               memory, `views_host` the same rows in host memory: the entry points read only the host copy for their refusals, the kernels only
+ *               the device copy.  slab_rows int32 [S + 1] (device): slab s owns the rows [slab_rows[s], slab_rows[s + 1]) of partials - the blocks
+ *               of its views.
+ *   4 align     p' = s p + b in fp64 on the widened fp32 p: one rounded product, one rounded sum.  (s, b) per slab in align double [S, 2]:
+ *               (1, 0), a given scale, fp64(median g) / fp64(median p), sum pg / sum pp, or the least-squares pair from n, sum p, sum g, sum pp,
+ *               sum pg - solved on the host in fp64 from pst_depth_moments / pst_depth_median.
+ *               pst_depth_median: the exact fp32 medians of p and of g over the valid pixels of every slab by a four-pass radix select, most
+ *               significant byte first.  Valid values are positive and finite, so their bit patterns order as the values do: the key is the bits,
+ *               with no rule for NaN or signed zero.  Histograms in LDS, flushed with int32 atomics (order-independent); a one-wave kernel narrows
+ *               the two ranks (n - 1) / 2 and n / 2 after every pass.  median fp32 [S, 2] = (of p, of g): the middle element for an odd count,
+ *               (a + b) * 0.5f in fp32 for an even one, NaN for n = 0; count int32 [S] = n.  Workspaces int32, ZEROED BY THE CALLER, left zeroed:
+ *               hist [S, 2, 2, 256] (16-byte aligned), prefix uint32 [S, 2, 2], rank [S, 2, 2].
+ *   5 terms     pst_depth_moments adds per valid pixel, widened to fp64: 1, p, g, p p, p g (products of two widened fp32 are exact) -> moments
+ *               [0, 5).  pst_depth_errors, with d = p' - g: 1, |d| / g, (d d) / g, d d, |d| -> moments [0, 5), and for each of K <= 4 thresholds
+ *               t_k (fp64): 1.0 iff p' < t_k g and g < t_k p' (two rounded products; strict: equality is no inlier; a non-positive p' fails by
+ *               itself) -> moment 5 + k.  The other moments of the PST_DEPTH_MOMENTS are +0.0.
+ *   6 order     step 4 of the icp section with PST_ICP_CHUNK and PST_ICP_LANES (csrc/icp_sum.h is the one text): lane l of block b of a view adds
+ *               the view's pixels PST_ICP_CHUNK (b - first_block) + l + PST_ICP_LANES j, j ascending, into accumulators that start at +0.0 (an
+ *               invalid pixel adds nothing), the block is reduced by the butterfly and the wave order of that step -> row b of partials double
+ *               [nblocks, PST_DEPTH_MOMENTS].  A second launch of one block per slab adds the slab's rows of partials the same way - lane l takes its
+ *               rows slab_rows[s] + l, + PST_ICP_LANES, ... ascending - into out double [S, PST_DEPTH_MOMENTS].  No float atomics: two calls give
+ *               equal bytes.
+ *   7 metrics   abs_rel = sum |d|/g / n, sq_rel = sum dd/g / n, rmse = sqrt(sum dd / n), mae = sum |d| / n, delta_k = count_k / n: float64 host
+ *               arithmetic on out (panst3r_amd/engine/depth_eval.py).  Log-space metrics are left out: a device log is not bit-identical to numpy's.
+ * PST_EINVAL before any launch: a null operand (a null pred or gt address in a row included), nviews < 1, S < 1, K < 0 or K > 4, a stride < 1, npix < 1,
+ * a total of pixels >= 2^31, first_block or slab entries that are not the ones step 3 names, a block count that is not nblocks, a hist that is not
+ * 16-byte aligned. */
+#define PST_DEPTH_VIEW_WORDS 8    /* int64 words per row of the view table */
+#define PST_DEPTH_MOMENTS 16      /* doubles per row of partials and per slab in out */
+int pst_depth_median(const int64_t* views, const int64_t* views_host, int nviews, int nblocks, int nslabs, float min_depth, float max_depth, float conf_thr,
+                     int32_t* hist, uint32_t* prefix, int32_t* rank, int32_t* count, float* median, void* stream);
+int pst_depth_moments(const int64_t* views, const int64_t* views_host, int nviews, int nblocks, const int32_t* slab_rows, int nslabs, float min_depth,
+                      float max_depth, float conf_thr, double* partials, double* out, void* stream);
+int pst_depth_errors(const int64_t* views, const int64_t* views_host, int nviews, int nblocks, const int32_t* slab_rows, int nslabs, float min_depth,
+                     float max_depth, float conf_thr, const double* align, int K, double t0, double t1, double t2, double t3, double* partials, double* out,
+                     void* stream);
+
 /* ---------------------------------------------------------------- QUBO mask selection on the device (reference engine/postprocess.py:262-336: numpy on the host)
  * Minimises E(x) = x^T W x + lambda_reg * mean(x), x in {0,1}^N, by `replicas` independent simulated anneals run at once (the reference's moves,
  * acceptance rule and geometric schedule; it runs 20 restarts one after the other) and returns the best.  W fp32 [N, N] row-major, symmetric (the -W

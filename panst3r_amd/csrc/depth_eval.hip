@@ -1,0 +1,251 @@
+// Predicted depth maps scored against ground-truth depth maps (the depth-evaluation section of include/panst3r_hip.h; restated in
+// tests/depth_eval_ref.py, [restated, parity unpinned]).  Three stages over one table of views, so that a mixed-shape scene is one launch per stage:
+//   moments   n, sum p, sum g, sum pp, sum pg over the valid pixels of every slab: what a least-squares scale (and shift) is solved from on the host
+//   median    the exact fp32 medians of p and of g per slab by radix select on the float's bits, most significant byte first, four passes: LDS
+//             histograms flushed with INTEGER atomics (order-independent), then a one-wave kernel that narrows the two ranks
+//   errors    with p' = s p + b in fp64: n, sum |d|/g, sum dd/g, sum dd, sum |d| and the inlier counts of up to four thresholds
+// The fp64 sums are added in the fixed order of icp_sum.h: a block of 256 lanes per 4096 pixels of ONE view, lane l its pixels l, l + 256, ...; the
+// butterfly, the four waves in order, one row of partials per block; then one reducer block per slab over the slab's rows.  No float atomics.
+// Every operation is part of the contract: contraction is off for the whole file.
+#include "icp_sum.h"             // icp_block_sum, ICP_T, ICP_ROWS; and through pinhole.h: common.h, wave_ops.h (last_le, rn_add, rn_mul), include/panst3r_hip.h
+
+#pragma clang fp contract(off)
+
+namespace pst {
+
+struct DepthView {                                                 // a row of the view table: PST_DEPTH_VIEW_WORDS int64 words
+  const float* pred; int64_t stride; const float* gt; const float* conf; int64_t npix, first_block, slab, reserved;
+};
+static_assert(sizeof(DepthView) == 8 * PST_DEPTH_VIEW_WORDS, "the row the header writes out");
+struct DepthThresholds { double t[4]; int K; };
+constexpr int DE_MOMENTS = PST_DEPTH_MOMENTS, DE_ALIGN = 5, DE_ERR = 9;   // doubles per row; live moments of the two sum kernels
+constexpr int DE_HIST = 2 * 2 * 256;                               // counters per slab: (p, g) x two ranks x 256 bins
+
+__device__ __forceinline__ const DepthView& depth_view_of(const DepthView* __restrict__ views, int nviews, int blk) {
+  return views[last_le(nviews, (int64_t)blk, [&](int v) { return views[v].first_block; })];
+}
+
+// step 1.  finite: fabsf(x) <= PST_FMAX, so that a NaN fails it; every comparison is false for a NaN
+__device__ __forceinline__ bool depth_valid(const DepthView& v, int64_t i, float lo, float hi, float thr, float& p, float& g) {
+  g = v.gt[i];
+  p = v.pred[i * v.stride];
+  bool ok = fabsf(g) <= PST_FMAX && g > lo && g <= hi && fabsf(p) <= PST_FMAX && p > 0.f;
+  if (v.conf) ok = ok && v.conf[i] >= thr;
+  return ok;
+}
+
+// ERRORS = false: the moments of the alignment; true: the error sums under the slab's (s, b)
+template <bool ERRORS>
+__global__ __launch_bounds__(ICP_T) void depth_sum_kernel(const DepthView* __restrict__ views, int nviews, float lo, float hi, float thr,
+                                                          const double* __restrict__ align, DepthThresholds th, double* __restrict__ partials) {
+  constexpr int LIVE = ERRORS ? DE_ERR : DE_ALIGN;
+  const int blk = blockIdx.x;
+  const DepthView v = depth_view_of(views, nviews, blk);
+  double s = 1.0, b = 0.0;
+  if constexpr (ERRORS) { s = align[2 * v.slab]; b = align[2 * v.slab + 1]; }
+  double acc[LIVE];
+#pragma unroll
+  for (int k = 0; k < LIVE; ++k) acc[k] = 0.0;
+  const int64_t i0 = ((int64_t)blk - v.first_block) * PST_ICP_CHUNK + threadIdx.x;
+#pragma unroll 4
+  for (int j = 0; j < ICP_ROWS; ++j) {
+    const int64_t i = i0 + (int64_t)j * ICP_T;
+    float pf, gf;
+    if (i >= v.npix || !depth_valid(v, i, lo, hi, thr, pf, gf)) continue;
+    const double p = (double)pf, g = (double)gf;
+    acc[0] += 1.0;
+    if constexpr (!ERRORS) {
+      acc[1] += p;
+      acc[2] += g;
+      acc[3] += p * p;
+      acc[4] += p * g;
+    } else {
+      double pa = s * p;
+      pa = pa + b;
+      const double d = pa - g, ad = fabs(d), dd = d * d;
+      acc[1] += ad / g;
+      acc[2] += dd / g;
+      acc[3] += dd;
+      acc[4] += ad;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < th.K && pa < th.t[k] * g && g < th.t[k] * pa) acc[5 + k] += 1.0;
+    }
+  }
+  icp_block_sum<LIVE, DE_MOMENTS>(acc, partials + (int64_t)blk * DE_MOMENTS);
+}
+
+// one block per slab; lane l adds the rows r0 + l, r0 + l + 256, ... of the slab's partials in ascending order, then the same butterfly and wave order
+template <int LIVE>
+__global__ __launch_bounds__(ICP_T) void depth_reduce_kernel(const double* __restrict__ partials, const int32_t* __restrict__ slab_rows, int nblocks,
+                                                             double* __restrict__ out) {
+  const int s = blockIdx.x;
+  const int r0 = max(slab_rows[s], 0), r1 = min(slab_rows[s + 1], nblocks);
+  double acc[LIVE];
+#pragma unroll
+  for (int k = 0; k < LIVE; ++k) acc[k] = 0.0;
+  for (int r = r0 + threadIdx.x; r < r1; r += ICP_T)
+#pragma unroll
+    for (int k = 0; k < LIVE; ++k) acc[k] += partials[(int64_t)r * DE_MOMENTS + k];
+  icp_block_sum<LIVE, DE_MOMENTS>(acc, out + (int64_t)s * DE_MOMENTS);
+}
+
+// ---------------------------------------------------------------- medians
+// One block per PST_ICP_CHUNK pixels of a view (the grid of the sums).  pass 0: byte 3 of the bits of p and of g (one histogram per quantity, shared by
+// both ranks); pass q: byte 3 - q of the values whose higher bytes equal the rank's prefix.  LDS counters, flushed with integer atomics.
+__global__ __launch_bounds__(ICP_T) void depth_hist_kernel(const DepthView* __restrict__ views, int nviews, float lo, float hi, float thr, int pass,
+                                                           const uint32_t* __restrict__ prefix, int32_t* __restrict__ hist) {
+  __shared__ int h[DE_HIST];
+  __shared__ uint32_t pre[4];
+  const int blk = blockIdx.x, tid = threadIdx.x;
+  const DepthView v = depth_view_of(views, nviews, blk);
+  for (int i = tid; i < DE_HIST; i += ICP_T) h[i] = 0;
+  if (tid < 4) pre[tid] = prefix[v.slab * 4 + tid];
+  __syncthreads();
+  const int shift = 24 - 8 * pass;
+  const int64_t i0 = ((int64_t)blk - v.first_block) * PST_ICP_CHUNK + tid;
+  for (int j = 0; j < ICP_ROWS; ++j) {
+    const int64_t i = i0 + (int64_t)j * ICP_T;
+    float pf, gf;
+    if (i >= v.npix || !depth_valid(v, i, lo, hi, thr, pf, gf)) continue;
+    const uint32_t u[2] = {__float_as_uint(pf), __float_as_uint(gf)};
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (pass == 0) atomicAdd(&h[q * 512 + (u[q] >> 24)], 1);
+      else {
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+          if ((u[q] >> (shift + 8)) == (pre[q * 2 + r] >> (shift + 8))) atomicAdd(&h[(q * 2 + r) * 256 + ((u[q] >> shift) & 255)], 1);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < DE_HIST; i += ICP_T) {
+    const int c = h[i];
+    if (c) atomicAdd(&hist[v.slab * DE_HIST + i], c);
+  }
+}
+
+// One wave per (slab, quantity): walks the two histograms (pass 0: the shared one), moves each rank into its bin, clears the counters for the next
+// pass.  After the last pass the prefix is the bit pattern of the order statistic: median = a for an odd count, (a + b) * 0.5f for an even one.
+__global__ __launch_bounds__(64) void depth_narrow_kernel(int32_t* __restrict__ hist, uint32_t* __restrict__ prefix, int32_t* __restrict__ rank, int pass,
+                                                          int32_t* __restrict__ count, float* __restrict__ median) {
+  const int sq = blockIdx.x, lane = threadIdx.x;                   // sq = slab * 2 + quantity
+  const int shift = 24 - 8 * pass;
+  int n = 0;
+  uint32_t key[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int4 c = ((const int4*)(hist + ((int64_t)sq * 2 + (pass == 0 ? 0 : r)) * 256))[lane];
+    const int own = c.x + c.y + c.z + c.w;
+    const int s = wave_scan(own, lane);
+    const int tot = __shfl(s, 63);
+    int k;
+    if (pass == 0) { n = tot; k = r == 0 ? (tot - 1) / 2 : tot / 2; } else k = rank[sq * 2 + r];
+    // the bin that holds rank k: the first bin whose inclusive count exceeds k
+    int below = s - own, bin = -1;
+    const int cc[4] = {c.x, c.y, c.z, c.w};
+    if (tot > 0 && k >= below && k < s) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (bin < 0) {
+          if (k < below + cc[q]) bin = 4 * lane + q; else below += cc[q];
+        }
+    }
+    const uint64_t who = __ballot(bin >= 0);
+    const int src = who ? __builtin_ctzll(who) : 0;
+    bin = __shfl(bin, src); below = __shfl(below, src);
+    const uint32_t pfx = (pass == 0 ? 0u : prefix[sq * 2 + r]) | ((uint32_t)max(bin, 0) << shift);
+    key[r] = pfx;
+    if (lane == 0) { prefix[sq * 2 + r] = pfx; rank[sq * 2 + r] = who ? k - below : 0; }
+  }
+  __syncthreads();                                                 // (one wave: both ranks have read the shared pass-0 histogram)
+  const int4 z = {0, 0, 0, 0};
+  ((int4*)(hist + (int64_t)sq * 512))[lane] = z;
+  ((int4*)(hist + (int64_t)sq * 512))[lane + 64] = z;
+  if (pass == 0 && lane == 0 && (sq & 1) == 0) count[sq >> 1] = n;
+  if (pass == 3 && lane == 0) {
+    const int cnt = count[sq >> 1];                                // written by pass 0, three launches ago
+    const float a = __uint_as_float(key[0]), b = __uint_as_float(key[1]);
+    float med = (cnt & 1) ? a : rn_mul(rn_add(a, b), 0.5f);
+    if (cnt == 0) med = __uint_as_float(0x7fc00000u);
+    median[sq] = med;
+    prefix[sq * 2] = 0u; prefix[sq * 2 + 1] = 0u;                  // the workspaces are left as they came: zeroed
+    rank[sq * 2] = 0; rank[sq * 2 + 1] = 0;
+  }
+}
+
+}  // namespace pst
+
+// the refusals that the host copy of the table decides (step 3 of the header's section)
+static int depth_table_ok(const char* what, const int64_t* views, const int64_t* host, int nviews, int nblocks, int nslabs) {
+  using namespace pst;
+  if (!views || !host) { set_error("%s: null view table", what); return PST_EINVAL; }
+  if (nviews < 1 || nslabs < 1 || nblocks < 1) { set_error("%s: bad shape (nviews=%d, nslabs=%d, nblocks=%d)", what, nviews, nslabs, nblocks); return PST_EINVAL; }
+  int64_t blocks = 0, total = 0, slab = 0;
+  for (int v = 0; v < nviews; ++v) {
+    const int64_t* r = host + (int64_t)v * PST_DEPTH_VIEW_WORDS;
+    if (!r[0] || !r[2]) { set_error("%s: view %d has a null pred or gt", what, v); return PST_EINVAL; }
+    if (r[1] < 1) { set_error("%s: view %d has the stride %lld < 1", what, v, (long long)r[1]); return PST_EINVAL; }
+    if (r[4] < 1 || r[4] > 0x7fffffffLL) { set_error("%s: view %d has %lld pixels", what, v, (long long)r[4]); return PST_EINVAL; }
+    if (r[5] != blocks) { set_error("%s: view %d starts at block %lld, not %lld", what, v, (long long)r[5], (long long)blocks); return PST_EINVAL; }
+    if (r[6] != slab && r[6] != slab + (v > 0 ? 1 : 0)) { set_error("%s: view %d is in slab %lld after slab %lld", what, v, (long long)r[6], (long long)slab); return PST_EINVAL; }
+    slab = r[6];
+    blocks += (r[4] + PST_ICP_CHUNK - 1) / PST_ICP_CHUNK;
+    total += r[4];
+  }
+  if (slab != nslabs - 1) { set_error("%s: the table ends in slab %lld of %d", what, (long long)slab, nslabs); return PST_EINVAL; }
+  if (total > 0x7fffffffLL) { set_error("%s: %lld pixels; one call takes at most 2^31 - 1", what, (long long)total); return PST_EINVAL; }
+  if (blocks != nblocks) { set_error("%s: the table holds %lld blocks, not %d", what, (long long)blocks, nblocks); return PST_EINVAL; }
+  return 0;
+}
+
+extern "C" int pst_depth_median(const int64_t* views, const int64_t* views_host, int nviews, int nblocks, int nslabs, float min_depth, float max_depth,
+                                float conf_thr, int32_t* hist, uint32_t* prefix, int32_t* rank, int32_t* count, float* median, void* stream) {
+  using namespace pst;
+  if (depth_table_ok("depth_median", views, views_host, nviews, nblocks, nslabs)) return PST_EINVAL;
+  if (!hist || !prefix || !rank || !count || !median) { set_error("depth_median: null operand"); return PST_EINVAL; }
+  if (((uintptr_t)hist) & 15) { set_error("depth_median: the histogram workspace must be 16-byte aligned"); return PST_EINVAL; }
+  hipStream_t st = (hipStream_t)stream;
+  for (int pass = 0; pass < 4; ++pass) {
+    hipLaunchKernelGGL(depth_hist_kernel, dim3((unsigned)nblocks), dim3(ICP_T), 0, st, (const DepthView*)views, nviews, min_depth, max_depth, conf_thr, pass,
+                       prefix, hist);
+    int rc = check_launch("depth_median (histogram)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(depth_narrow_kernel, dim3((unsigned)nslabs * 2), dim3(64), 0, st, hist, prefix, rank, pass, count, median);
+    rc = check_launch("depth_median (narrow)");
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+extern "C" int pst_depth_moments(const int64_t* views, const int64_t* views_host, int nviews, int nblocks, const int32_t* slab_rows, int nslabs,
+                                 float min_depth, float max_depth, float conf_thr, double* partials, double* out, void* stream) {
+  using namespace pst;
+  if (depth_table_ok("depth_moments", views, views_host, nviews, nblocks, nslabs)) return PST_EINVAL;
+  if (!slab_rows || !partials || !out) { set_error("depth_moments: null operand"); return PST_EINVAL; }
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(depth_sum_kernel<false>, dim3((unsigned)nblocks), dim3(ICP_T), 0, st, (const DepthView*)views, nviews, min_depth, max_depth, conf_thr,
+                     (const double*)nullptr, DepthThresholds{}, partials);
+  const int rc = check_launch("depth_moments");
+  if (rc) return rc;
+  hipLaunchKernelGGL(depth_reduce_kernel<DE_ALIGN>, dim3((unsigned)nslabs), dim3(ICP_T), 0, st, partials, slab_rows, nblocks, out);
+  return check_launch("depth_moments (reduce)");
+}
+
+extern "C" int pst_depth_errors(const int64_t* views, const int64_t* views_host, int nviews, int nblocks, const int32_t* slab_rows, int nslabs,
+                                float min_depth, float max_depth, float conf_thr, const double* align, int K, double t0, double t1, double t2, double t3,
+                                double* partials, double* out, void* stream) {
+  using namespace pst;
+  if (depth_table_ok("depth_errors", views, views_host, nviews, nblocks, nslabs)) return PST_EINVAL;
+  if (!slab_rows || !align || !partials || !out) { set_error("depth_errors: null operand"); return PST_EINVAL; }
+  if (K < 0 || K > 4) { set_error("depth_errors: %d thresholds; one call takes 0 .. 4", K); return PST_EINVAL; }
+  hipStream_t st = (hipStream_t)stream;
+  const DepthThresholds th = {{t0, t1, t2, t3}, K};
+  hipLaunchKernelGGL(depth_sum_kernel<true>, dim3((unsigned)nblocks), dim3(ICP_T), 0, st, (const DepthView*)views, nviews, min_depth, max_depth, conf_thr, align,
+                     th, partials);
+  const int rc = check_launch("depth_errors");
+  if (rc) return rc;
+  hipLaunchKernelGGL(depth_reduce_kernel<DE_ERR>, dim3((unsigned)nslabs), dim3(ICP_T), 0, st, partials, slab_rows, nblocks, out);
+  return check_launch("depth_errors (reduce)");
+}

@@ -15,4 +15,6 @@ from .surface import panoptic_mesh, PanopticMesh  # noqa: F401,E402  (the pointm
 from .score3d import sample_mesh, nearest_points, similarity_from_cameras, score_reconstruction, MeshSamples  # noqa: F401,E402  (a reconstruction scored against a ground-truth mesh in 3-D: F-score, chamfer, a panoptic quality on the surface; not in the reference)
 from .score3d import icp, refine_alignment, Alignment  # noqa: F401,E402  (the alignment to the ground truth refined on the geometry by ICP, one fused kernel per step; not in the reference)
 from .meshdist import mesh_distance, icp_to_mesh  # noqa: F401,E402  (icp_to_mesh: point-to-plane ICP against the triangles, f13; mesh_distance: the exact distance from points to a triangle mesh within a radius - squared distance, face, closest point - behind score_reconstruction(metric='surface'); not in the reference)
-from .tsdf import fuse_surface, FusedMesh  # noqa: F401,E402  (f15: the views fused in a truncated signed distance volume and ONE surface extracted by surface nets - PanopticCloud.fused_mesh; not in the reference)
+from .depth_eval import depth_quality  # noqa: F401,E402  (f16: predicted depths against ground-truth depths on the device - AbsRel, SqRel, RMSE, MAE, delta < t after a median / least-squares alignment, per view or per scene; not in the reference)
+from .camera_eval import camera_quality  # noqa: F401,E402  (f16: predicted cameras against ground-truth cameras - RRA, RTA, mAA, ATE, focal error; host float64; not in the reference)
+from .tsdf import fuse_surface, FusedMesh  # noqa: F401,E402  (f15:the views fused in a truncated signed distance volume and ONE surface extracted by surface nets - PanopticCloud.fused_mesh; not in the reference)

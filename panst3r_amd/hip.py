@@ -86,6 +86,7 @@ SIGNATURES = {
     'pst_meshdist_count': 'i:plplfpppp', 'pst_meshdist_insert': 'i:plplfplplpppp', 'pst_meshdist_scatter': 'i:ppllpppppp',
     'pst_meshdist_query': 'i:plplplffplppplippppp',
     'pst_plane_icp_step': 'i:plfffffffffffffffplplffplppplipppppp',
+    'pst_depth_median': 'i:ppiiifffpppppp', 'pst_depth_moments': 'i:ppiipifffppp', 'pst_depth_errors': 'i:ppiipifffpiddddppp',
 }
 EXPORTS = list(SIGNATURES)
 
@@ -1973,3 +1974,84 @@ def icp_plane_step(source, A, c0, vertices, faces, inv, cell_r2, r2, ws, max_cel
           _ptr(ws['start']), _ptr(ws['cell_count']), _ptr(ws['rows']), ws['P'], int(max_cell_faces), _ptr(d2), _ptr(face), _ptr(iws['partials']),
           _ptr(iws['out']), _ptr(iws['status']))
     return iws['out']
+
+
+# ------------------------------------------------------------------ depth evaluation against ground truth (csrc/depth_eval.hip; engine/depth_eval.py holds the public entry point)
+DEPTH_VIEW_WORDS, DEPTH_MOMENTS = 8, 16      # PST_DEPTH_VIEW_WORDS, PST_DEPTH_MOMENTS
+DEPTH_MAX_THRESHOLDS = 4
+
+
+class DepthTable:
+    """the view table of the depth-evaluation entry points: `host` int64 [V, 8] (numpy; the refusals read it), `dev` the same rows on the device (the
+    kernels read it), `slab_rows` int32 [S + 1] on the device, and the tensors the rows point into, kept alive here"""
+
+    def __init__(self, rows, slabs, device, keep=()):
+        import numpy as np
+        self.host = np.zeros((len(rows), DEPTH_VIEW_WORDS), dtype=np.int64)
+        blocks, edges = 0, [0]
+        for v, ((pred, stride, gt, conf, npix), slab) in enumerate(zip(rows, slabs)):
+            if v and slab != slabs[v - 1]:
+                edges.append(blocks)
+            self.host[v] = (pred, stride, gt, conf or 0, npix, blocks, slab, 0)
+            blocks += (npix + ICP_CHUNK - 1) // ICP_CHUNK
+        edges.append(blocks)
+        self.nviews, self.nblocks, self.nslabs, self.keep = len(rows), blocks, len(edges) - 1, keep
+        blob = torch.from_numpy(np.concatenate([self.host.reshape(-1), np.array(edges, dtype=np.int64)])).to(device)      # one copy
+        self.dev, self.slab_rows = blob[:self.host.size], blob[self.host.size:].to(torch.int32)
+
+    def _args(self):
+        return self.dev.data_ptr(), self.host.ctypes.data, self.nviews, self.nblocks
+
+
+def depth_table(views, slabs, device):
+    """views = [(pred, stride, gt, conf or None)]: fp32 device tensors, pred read at the element stride `stride` from its first element, gt and conf
+    contiguous; slabs = the slab of every view, ascending from 0 by steps of 0 or 1 -> DepthTable"""
+    rows, keep = [], []
+    for pred, stride, gt, conf in views:
+        for t in (pred, gt) + ((conf,) if conf is not None else ()):
+            _dev(t, torch.float32)
+            assert t.device == pred.device
+        assert gt.is_contiguous() and (conf is None or (conf.is_contiguous() and conf.numel() == gt.numel()))
+        rows.append((pred.data_ptr(), int(stride), gt.data_ptr(), None if conf is None else conf.data_ptr(), gt.numel()))
+        keep += [pred, gt, conf]
+    return DepthTable(rows, [int(s) for s in slabs], device, keep)
+
+
+def depth_median(table, min_depth, max_depth, conf_thr, count, median):
+    """count int32 [S], median fp32 [S, 2] = the exact medians (of pred, of gt) over the valid pixels of every slab"""
+    _dev(count, torch.int32); _dev(median, torch.float32)
+    S = table.nslabs
+    assert count.numel() == S and median.numel() == 2 * S and median.is_contiguous()
+    ws = torch.zeros(S * (2 * 2 * 256 + 4 + 4), dtype=torch.int32, device=count.device)
+    hist, prefix, rank = ws[:S * 1024], ws[S * 1024:S * 1028], ws[S * 1028:]
+    _call('pst_depth_median', *table._args(), S, float(min_depth), float(max_depth), float(conf_thr), _ptr(hist), _ptr(prefix), _ptr(rank), _ptr(count),
+          _ptr(median))
+
+
+def depth_workspace(table, device):
+    """partials double [nblocks, 16] and out double [S, 16] of depth_moments / depth_errors"""
+    return {'partials': torch.empty(table.nblocks, DEPTH_MOMENTS, dtype=torch.float64, device=device),
+            'out': torch.empty(table.nslabs, DEPTH_MOMENTS, dtype=torch.float64, device=device)}
+
+
+def _depth_ws(table, ws):
+    _dev(ws['partials'], torch.float64); _dev(ws['out'], torch.float64)
+    assert ws['partials'].numel() == table.nblocks * DEPTH_MOMENTS and ws['out'].numel() == table.nslabs * DEPTH_MOMENTS
+    assert ws['partials'].is_contiguous() and ws['out'].is_contiguous() and table.slab_rows.numel() == table.nslabs + 1
+
+
+def depth_moments(table, min_depth, max_depth, conf_thr, ws):
+    """ws['out'][s, :5] = n, sum p, sum g, sum pp, sum pg over the valid pixels of slab s, in the fixed order of the contract"""
+    _depth_ws(table, ws)
+    _call('pst_depth_moments', *table._args(), _ptr(table.slab_rows), table.nslabs, float(min_depth), float(max_depth), float(conf_thr), _ptr(ws['partials']),
+          _ptr(ws['out']))
+
+
+def depth_errors(table, min_depth, max_depth, conf_thr, align, thresholds, ws):
+    """ws['out'][s, :5 + K] = n, sum |d|/g, sum dd/g, sum dd, sum |d| and the inlier counts of the K thresholds under p' = align[s, 0] p + align[s, 1]"""
+    _depth_ws(table, ws)
+    _dev(align, torch.float64)
+    t = [float(x) for x in thresholds]
+    assert align.is_contiguous() and align.numel() == 2 * table.nslabs
+    _call('pst_depth_errors', *table._args(), _ptr(table.slab_rows), table.nslabs, float(min_depth), float(max_depth), float(conf_thr), _ptr(align), len(t),
+          *(t + [0.0] * DEPTH_MAX_THRESHOLDS)[:DEPTH_MAX_THRESHOLDS], _ptr(ws['partials']), _ptr(ws['out']))      # (K > 4 is the library's refusal)

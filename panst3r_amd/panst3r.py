@@ -449,6 +449,24 @@ class PanSt3R(nn.Module):
             kw = dict(kw, gt_vertex_ids=gt_mesh[2], gt_segments=gt_mesh[3])
         return score_reconstruction(cloud_or_voxels_or_mesh, gt_mesh[0], gt_mesh[1], **kw)
 
+    def evaluate_depth(self, x_out, gt_depths, **kw):
+        """The predicted per-view depth against ground-truth depth maps: `engine.depth_quality` of `x_out` (the dicts of `cameras_from_pointmaps`:
+        the z of 'pts3d_local', filtered by 'conf' where `min_conf_thr=` is given) and e.g. `engine.ground_truth_maps(...)[2]` (align=, scope=,
+        min_depth=, max_depth=, thresholds=).  It only composes."""
+        from .engine import depth_quality
+        return depth_quality(x_out, gt_depths, **kw)
+
+    def evaluate_cameras(self, cameras, gt_cams2world, **kw):
+        """The cameras of a reconstruction against ground-truth poses: `engine.camera_quality` of `cameras` - the dicts `reconstruct` returns (their
+        'cam2world'; their 'focal', if they hold one and `gt_focals=` is given), or plain cam2world matrices.  It only composes."""
+        from .engine import camera_quality
+        cams = list(cameras)
+        if cams and all(isinstance(c, dict) for c in cams):
+            if 'gt_focals' in kw and 'pred_focals' not in kw and all('focal' in c for c in cams):
+                kw = dict(kw, pred_focals=[c['focal'] for c in cams])
+            cams = [c['cam2world'] for c in cams]
+        return camera_quality(cams, gt_cams2world, **kw)
+
     @torch.no_grad()
     def _forward_inference_once(self, imgs, true_shape, classes, num_keyframes=None, use_retrieval=False, max_bs=None,
                                 outdevice=None, amp=False, sim_matrix=None, keyframes=None, check_finite=True, cache_graphs=False,
