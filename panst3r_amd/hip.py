@@ -3,6 +3,12 @@
 PyTorch is plumbing here: it owns the HBM buffers and the HIP stream; every op below passes raw device pointers,
 sizes and `torch.cuda.current_stream().cuda_stream` across the C ABI.  There is NO fallback: if the library is
 missing or an argument is rejected the op raises (RuntimeError), it never silently computes with torch.
+
+The library sees addresses and a few integers, so the wrapper is the only bounds check of a call.  Every engine entry point (from the panoptic
+post-processing section to the end of the file) takes each address from `_Operands`, where the argument goes: a tensor on the GPU, on the device of
+the call's other operands, of the header's dtype, contiguous, holding the elements the header states - exactly, or at least (`ge`) for a capacity.
+A failure is a RuntimeError naming the wrapper, the operand, what was expected and what was found; none is an `assert`, so `python -O` checks the
+same.  The GEMM / attention builders (the library checks their bounds itself) and the streaming model-path wrappers (strided arena views) are not.
 """
 import ctypes as C
 import os
@@ -165,6 +171,71 @@ def _dev(t, *dtypes):
     if dtypes and t.dtype not in dtypes:
         raise RuntimeError('unexpected dtype %s (want %s)' % (t.dtype, dtypes))
     return t
+
+
+I32, I64, F32, F64, U8 = torch.int32, torch.int64, torch.float32, torch.float64, torch.uint8
+
+
+def _check_operand(what, name, t, dtypes, n, at_least=False, optional=False, layout='dense'):
+    """the part of an operand check that asks no device (tests/test_operand_check_host.py runs it on CPU tensors): `t` is a tensor of `dtypes` (one or a
+    tuple) that holds `n` elements - at least `n` with at_least - or, for a tuple `n`, has exactly that shape (-1: any extent).  layout 'dense':
+    contiguous; 'rows': a 2-D view with unit column stride (its leading dimension goes to the library); 'any': strides are the caller's business.
+    None passes only where `optional`.  Raises RuntimeError naming the wrapper `what` and the operand."""
+    if t is None and optional:
+        return
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError('%s: %s must be a torch tensor, got %s' % (what, name, type(t).__name__))
+    if t.dtype != dtypes and (not isinstance(dtypes, tuple) or t.dtype not in dtypes):
+        raise RuntimeError('%s: %s: unexpected dtype %s (want %s)' % (what, name, t.dtype, dtypes))
+    if isinstance(n, tuple):
+        sh = t.shape
+        if sh != n and (len(sh) != len(n) or [w for w, s in zip(n, sh) if w >= 0 and w != s]):
+            raise RuntimeError('%s: %s must have the shape %s (-1: any), got %s' % (what, name, n, tuple(sh)))
+    elif t.numel() != n and not (at_least and t.numel() > n):
+        raise RuntimeError('%s: %s must hold %s%d elements, got %d' % (what, name, 'at least ' if at_least else '', n, t.numel()))
+    if (layout == 'dense' and not t.is_contiguous()) or (layout == 'rows' and (t.dim() != 2 or t.stride(1) != 1)):
+        raise RuntimeError('%s: %s must be %s, got shape %s, strides %s' % (what, name, 'contiguous' if layout == 'dense' else 'a row-major 2-D view', tuple(t.shape), t.stride()))
+
+
+class _Operands:
+    """the operand checks of ONE call of the wrapper `what`.  `b(name, t, dtypes, n)` is written where the address goes and returns t.data_ptr() - or
+    None for an absent optional operand - after `_check_operand` and the device tests: a GPU tensor, on the device of the operands before it."""
+    __slots__ = ('what', 'device')
+
+    def __init__(self, what):
+        self.what, self.device = what, None
+
+    def __call__(self, name, t, dtypes, n, at_least=False, optional=False, layout='dense'):
+        _check_operand(self.what, name, t, dtypes, n, at_least, optional, layout)
+        if t is None:
+            return None
+        device = t.get_device()                 # -1: not on a GPU
+        if device != self.device:
+            if device < 0:
+                raise RuntimeError('%s: %s is a %s tensor: the HIP path runs on the GPU only (no CPU fallback)' % (self.what, name, t.device))
+            if self.device is not None:
+                raise RuntimeError('%s: %s is on %s, the operands before it on GPU %d' % (self.what, name, t.device, self.device))
+            self.device = device
+        return t.data_ptr()
+
+    def ge(self, name, t, dtypes, n, optional=False):       # a capacity: at least n elements
+        return self(name, t, dtypes, n, True, optional)
+
+    def sized(self, name, t, dtype, n=0):
+        """an operand whose own length (n at the least) sizes its call -> (address, elements)"""
+        return self(name, t, dtype, n, True), t.numel()
+
+    def rows3(self, name, t, dtype):
+        """an [n, 3] operand that sizes its call -> (address, n): the two consecutive arguments of the entry points"""
+        return self(name, t, dtype, (-1, 3)), t.shape[0]
+
+    def require(self, ok, msg, *args):                      # a condition on the sizes of a call that is no single operand's
+        if not ok:
+            raise RuntimeError('%s: %s' % (self.what, msg % args))
+
+
+def _wgs(n, wg=1024):       # workgroups of wg items (CLOUD_WG by default) over n
+    return (n + wg - 1) // wg
 
 
 class KernelTimer:
@@ -995,27 +1066,34 @@ def loftup_lr_pe(biases, out, col0, nimg, h, w):
 
 # ------------------------------------------------------------------ panoptic post-processing
 def pp_scores(logits, cls_threshold, temperature, scores, labels, keep):
-    _dev(logits, torch.float32); _dev(scores, torch.float32); _dev(labels, torch.int32); _dev(keep, torch.int32)
+    b = _Operands('pp_scores')
+    p = b('logits', logits, F32, (-1, -1))
     Q, Ncls = logits.shape
-    _call('pst_pp_scores', _ptr(logits), Q, Ncls, float(cls_threshold), float(temperature or 0.0), _ptr(scores), _ptr(labels), _ptr(keep))
+    _call('pst_pp_scores', p, Q, Ncls, float(cls_threshold), float(temperature or 0.0), b.ge('scores', scores, F32, Q), b.ge('labels', labels, I32, Q),
+          b.ge('keep', keep, I32, Q))
 
 
 def pp_scores_softmax(logits, cls_threshold, scores, labels, keep):
-    _dev(logits, torch.float32); _dev(scores, torch.float32); _dev(labels, torch.int32); _dev(keep, torch.int32)
+    b = _Operands('pp_scores_softmax')
+    p = b('logits', logits, F32, (-1, -1))
     Q, Ncls = logits.shape
-    _call('pst_pp_scores_softmax', _ptr(logits), Q, Ncls, float(cls_threshold), _ptr(scores), _ptr(labels), _ptr(keep))
+    _call('pst_pp_scores_softmax', p, Q, Ncls, float(cls_threshold), b.ge('scores', scores, F32, Q), b.ge('labels', labels, I32, Q), b.ge('keep', keep, I32, Q))
 
 
 def pp_sigmoid(logits, keep, probs, Q, P):
-    _dev(logits, torch.float32); _dev(keep, torch.int32); _dev(probs, torch.float32)
-    _call('pst_pp_sigmoid', _ptr(logits), _ptr(keep), _ptr(probs), Q, P)
+    b = _Operands('pp_sigmoid')
+    _call('pst_pp_sigmoid', b.ge('logits', logits, F32, Q * P), b.ge('keep', keep, I32, Q), b.ge('probs', probs, F32, Q * P), Q, P)
+
+
+def _pp_argmax(what, masks, scores, keep, Q, Hm, Wm, H, W, mask_threshold, best_q, best_m, cnt_orig, cnt_mask):
+    b = _Operands(what)
+    _call('pst_' + what, b.ge('logits' if what.endswith('logits') else 'probs', masks, F32, Q * Hm * Wm), b.ge('scores', scores, F32, Q), b.ge('keep', keep, I32, Q),
+          Q, Hm, Wm, H, W, float(mask_threshold), b.ge('best_q', best_q, I32, H * W), b.ge('best_m', best_m, F32, H * W), b.ge('cnt_orig', cnt_orig, I32, Q),
+          b.ge('cnt_mask', cnt_mask, I32, Q))
 
 
 def pp_argmax(probs, scores, keep, Q, Hm, Wm, H, W, mask_threshold, best_q, best_m, cnt_orig, cnt_mask):
-    for t, dt in ((probs, torch.float32), (scores, torch.float32), (keep, torch.int32), (best_q, torch.int32), (best_m, torch.float32),
-                  (cnt_orig, torch.int32), (cnt_mask, torch.int32)):
-        _dev(t, dt)
-    _call('pst_pp_argmax', _ptr(probs), _ptr(scores), _ptr(keep), Q, Hm, Wm, H, W, float(mask_threshold), _ptr(best_q), _ptr(best_m), _ptr(cnt_orig), _ptr(cnt_mask))
+    _pp_argmax('pp_argmax', probs, scores, keep, Q, Hm, Wm, H, W, mask_threshold, best_q, best_m, cnt_orig, cnt_mask)
 
 
 def pp_fused_fits(Q, Hm, Wm, H, W):
@@ -1027,75 +1105,78 @@ def pp_fused_fits(Q, Hm, Wm, H, W):
 
 
 def pp_argmax_logits(logits, scores, keep, Q, Hm, Wm, H, W, mask_threshold, best_q, best_m, cnt_orig, cnt_mask):
-    for t, dt in ((logits, torch.float32), (scores, torch.float32), (keep, torch.int32), (best_q, torch.int32), (best_m, torch.float32),
-                  (cnt_orig, torch.int32), (cnt_mask, torch.int32)):
-        _dev(t, dt)
-    _call('pst_pp_argmax_logits', _ptr(logits), _ptr(scores), _ptr(keep), Q, Hm, Wm, H, W, float(mask_threshold), _ptr(best_q), _ptr(best_m), _ptr(cnt_orig),
-          _ptr(cnt_mask))
+    _pp_argmax('pp_argmax_logits', logits, scores, keep, Q, Hm, Wm, H, W, mask_threshold, best_q, best_m, cnt_orig, cnt_mask)
 
 
 def pp_select(keep, cnt_orig, cnt_mask, Q, overlap_threshold, keep_out, seg_id):
-    for t in (keep, cnt_orig, cnt_mask, keep_out, seg_id):
-        _dev(t, torch.int32)
-    _call('pst_pp_select', _ptr(keep), _ptr(cnt_orig), _ptr(cnt_mask), Q, float(overlap_threshold), _ptr(keep_out), _ptr(seg_id))
+    b = _Operands('pp_select')
+    _call('pst_pp_select', b.ge('keep', keep, I32, Q), b.ge('cnt_orig', cnt_orig, I32, Q), b.ge('cnt_mask', cnt_mask, I32, Q), Q, float(overlap_threshold),
+          b.ge('keep_out', keep_out, I32, Q), b.ge('seg_id', seg_id, I32, Q))
 
 
 def pp_finalize(best_q, best_m, seg_id, n, mask_threshold, void_confidence, pan, conf):
-    _dev(best_q, torch.int32); _dev(best_m, torch.float32); _dev(seg_id, torch.int32); _dev(pan, torch.int32); _dev(conf, torch.float32)
-    _call('pst_pp_finalize', _ptr(best_q), _ptr(best_m), _ptr(seg_id), n, float(mask_threshold), float(void_confidence), _ptr(pan), _ptr(conf))
+    """seg_id int32 [Q] is read at best_q: the entry point does not take Q, so its length is the caller's"""
+    b = _Operands('pp_finalize')
+    _call('pst_pp_finalize', b.ge('best_q', best_q, I32, n), b.ge('best_m', best_m, F32, n), b.ge('seg_id', seg_id, I32, 1), n, float(mask_threshold),
+          float(void_confidence), b.ge('pan', pan, I32, n), b.ge('conf', conf, F32, n))
 
 
 # ------------------------------------------------------------------ pointmap post-processing (SURVEY 8(f) row 4)
 def pointmap_activate(raw, pts3d, pts3d_local, conf, mode=0):
-    for t in (raw, pts3d, pts3d_local, conf):
-        _dev(t, torch.float32)
-        assert t.is_contiguous()
+    b = _Operands('pointmap_activate')
+    p = b.ge('raw', raw, F32, 0)
     npix = raw.numel() // 7
-    _call('pst_pointmap_activate', _ptr(raw), _ptr(pts3d), _ptr(pts3d_local), _ptr(conf), npix, mode)
+    _call('pst_pointmap_activate', p, b.ge('pts3d', pts3d, F32, 3 * npix), b.ge('pts3d_local', pts3d_local, F32, 3 * npix), b.ge('conf', conf, F32, npix), npix, mode)
 
 
 def focal_weiszfeld(pts3d_local, pp, focal, H, W, iters=10):
-    _dev(pts3d_local, torch.float32); _dev(pp, torch.float32); _dev(focal, torch.float32)
-    assert pts3d_local.is_contiguous() and pp.is_contiguous() and focal.numel() * H * W * 3 == pts3d_local.numel()
-    _call('pst_focal_weiszfeld', _ptr(pts3d_local), _ptr(pp), _ptr(focal), focal.numel(), H, W, iters)
+    b = _Operands('focal_weiszfeld')
+    pf, V = b.sized('focal', focal, F32)
+    _call('pst_focal_weiszfeld', b('pts3d_local', pts3d_local, F32, V * H * W * 3), b.ge('pp', pp, F32, 2 * V), pf, V, H, W, iters)
     return focal
 
 
 def rigid_moments(x, y, conf, out, weight_offset=-1.0):
-    _dev(x, torch.float32); _dev(y, torch.float32); _dev(conf, torch.float32); _dev(out, torch.float64)
+    b = _Operands('rigid_moments')
+    po = b('out', out, F64, (-1, 16))
     V = out.shape[0]
-    assert x.is_contiguous() and y.is_contiguous() and conf.is_contiguous() and out.is_contiguous() and out.shape[1] == 16
-    _call('pst_rigid_moments', _ptr(x), _ptr(y), _ptr(conf), _ptr(out), V, conf.numel() // V, float(weight_offset))
+    pc = b.ge('conf', conf, F32, 0)
+    npix = conf.numel() // V
+    _call('pst_rigid_moments', b.ge('x', x, F32, 3 * V * npix), b.ge('y', y, F32, 3 * V * npix), pc, po, V, npix, float(weight_offset))
     return out
 
 
 # ------------------------------------------------------------------ QUBO post-processing (engine/postprocess.py:135-336)
 def qubo_upsample(logits, probs, Q, hm, wm, H, W):
-    _dev(logits, torch.float32); _dev(probs, torch.float32)
-    _call('pst_qubo_upsample', _ptr(logits), _ptr(probs), Q, hm, wm, H, W)
+    b = _Operands('qubo_upsample')
+    _call('pst_qubo_upsample', b.ge('logits', logits, F32, Q * hm * wm), b.ge('probs', probs, F32, Q * H * W), Q, hm, wm, H, W)
 
 
 def qubo_overlap(probs, Q, P, Wacc):
-    _dev(probs, torch.float32); _dev(Wacc, torch.float64)
-    ws = torch.empty(lib().pst_qubo_workspace_floats(Q, P), dtype=torch.float32, device=probs.device)
-    _call('pst_qubo_overlap', _ptr(probs), Q, P, _ptr(ws), _ptr(Wacc))
+    b = _Operands('qubo_overlap')
+    pp = b.ge('probs', probs, F32, Q * P)
+    nws = lib().pst_qubo_workspace_floats(Q, P)
+    ws = torch.empty(nws, dtype=torch.float32, device=probs.device)
+    _call('pst_qubo_overlap', pp, Q, P, b('ws', ws, F32, nws), b.ge('Wacc', Wacc, F64, Q * Q))
 
 
 def qubo_argmax(probs, sel, P, conf, inst):
-    _dev(probs, torch.float32); _dev(sel, torch.int32); _dev(conf, torch.float32); _dev(inst, torch.int32)
-    _call('pst_qubo_argmax', _ptr(probs), _ptr(sel), sel.numel(), P, _ptr(conf), _ptr(inst))
+    """probs fp32 [Q, P] is read at the rows sel names (ascending, so Q >= their number): the entry point does not take Q"""
+    b = _Operands('qubo_argmax')
+    ps, nsel = b.sized('sel', sel, I32)
+    _call('pst_qubo_argmax', b.ge('probs', probs, F32, nsel * P), ps, nsel, P, b.ge('conf', conf, F32, P), b.ge('inst', inst, I32, P))
 
 
 # ------------------------------------------------------------------ ASMK retrieval (SURVEY 8(f) row 3; model/retrieval.py restates the algorithm)
 def retrieval_select(x, in_off, out_off, out, max_t, sel_idx=None):
     """per view v (rows [in_off[v], in_off[v+1]) of the fp32 head output x): the out_off[v+1] - out_off[v] rows of largest norm (ties to the lower
     token), in that order, L2-normalised into rows [out_off[v], out_off[v+1]) of out; sel_idx (int32, optional) gets their token indices"""
-    _dev(x, torch.float32); _dev(in_off, torch.int32); _dev(out_off, torch.int32); _dev(out, torch.float32)
-    if sel_idx is not None:
-        _dev(sel_idx, torch.int32)
-    assert in_off.is_contiguous() and out_off.is_contiguous() and in_off.numel() == out_off.numel() and x.shape[1] == out.shape[1]
-    _call('pst_retrieval_select', _ptr(x), _rowmajor(x), _ptr(in_off), _ptr(out_off), in_off.numel() - 1, int(max_t), x.shape[1], _ptr(out), _rowmajor(out),
-          _ptr(sel_idx))
+    b = _Operands('retrieval_select')
+    px = b('x', x, F32, (-1, -1), layout='rows')
+    pi = b.ge('in_off', in_off, I32, 1)
+    V, D = in_off.numel() - 1, x.shape[1]
+    _call('pst_retrieval_select', px, x.stride(0), pi, b('out_off', out_off, I32, V + 1), V, int(max_t), D, b('out', out, F32, (-1, D), layout='rows'),
+          out.stride(0), b.ge('sel_idx', sel_idx, I32, 0, optional=True))
     return out
 
 
@@ -1109,68 +1190,65 @@ def retrieval_nsplit(n, k):
 def retrieval_assign(x3, c3, cnorm, m, ids, dist, nsplit=None):
     """ids [n, m] / dist [n, m] = the m nearest centroids of each descriptor (ascending ||c||^2 - 2 x.c, ties to the lower index): x3 / c3 the split-f16
     descriptors (split_operand side 0) and centroids (side 1), cnorm fp32 [k].  The partial lists of the centroid splits live in a workspace of this call."""
-    _dev(x3, X3_FMT); _dev(c3, X3_FMT); _dev(cnorm, torch.float32); _dev(ids, torch.int32); _dev(dist, torch.float32)
-    n, k = x3.shape[0], c3.shape[0]
-    assert x3.shape[1] == c3.shape[1] and cnorm.numel() == k and ids.shape == (n, m) and dist.shape == (n, m) and ids.is_contiguous() and dist.is_contiguous()
+    b = _Operands('retrieval_assign')
+    px = b('x3', x3, X3_FMT, (-1, -1), layout='rows')
+    n, K3 = x3.shape
+    pc = b('c3', c3, X3_FMT, (-1, K3), layout='rows')
+    k = c3.shape[0]
     nsplit = retrieval_nsplit(n, k) if nsplit is None else int(nsplit)
     ws_d = ws_i = None
     if nsplit > 1:
         ws_d = torch.empty(nsplit * n * m, dtype=torch.float32, device=x3.device)
         ws_i = torch.empty(nsplit * n * m, dtype=torch.int32, device=x3.device)
-    _call('pst_retrieval_assign', _ptr(x3), _rowmajor(x3), _ptr(c3), _rowmajor(c3), _ptr(cnorm), n, k, x3.shape[1], int(m), nsplit, _ptr(ws_d), _ptr(ws_i),
-          _ptr(ids), _ptr(dist), _tc(x3))
+    _call('pst_retrieval_assign', px, x3.stride(0), pc, c3.stride(0), b('cnorm', cnorm, F32, k), n, k, K3, int(m), nsplit,
+          b('ws_dist', ws_d, F32, nsplit * n * m, optional=True), b('ws_ids', ws_i, I32, nsplit * n * m, optional=True), b('ids', ids, I32, (n, m)),
+          b('dist', dist, F32, (n, m)), _tc(x3))
     return ids, dist
 
 
 def retrieval_aggregate(x, cent, member, gstart, gword, bits, sums=None):
     """per (view, word) group g: fp32 sum of the residuals x[member] - cent[gword[g]] over members gstart[g] .. gstart[g+1] (ascending) -> packed sign
     bits [G, D / 32] (int32 storage of the uint32 words; bit j of word w = component 32 w + j) and, optionally, the sums [G, D]"""
-    _dev(x, torch.float32); _dev(cent, torch.float32); _dev(member, torch.int32); _dev(gstart, torch.int32); _dev(gword, torch.int32); _dev(bits, torch.int32)
-    G, D = gword.numel(), x.shape[1]
-    assert cent.shape[1] == D and gstart.numel() == G + 1 and bits.shape == (G, D // 32) and bits.is_contiguous()
-    assert member.is_contiguous() and gstart.is_contiguous() and gword.is_contiguous()
-    if sums is not None:
-        _dev(sums, torch.float32)
-        assert sums.shape == (G, D) and sums.is_contiguous()
-    _call('pst_retrieval_aggregate', _ptr(x), _rowmajor(x), _ptr(cent), _rowmajor(cent), _ptr(member), _ptr(gstart), _ptr(gword), G, D, _ptr(sums), _ptr(bits))
+    b = _Operands('retrieval_aggregate')
+    px = b('x', x, F32, (-1, -1), layout='rows')
+    (pw, G), D = b.sized('gword', gword, I32), x.shape[1]
+    _call('pst_retrieval_aggregate', px, x.stride(0), b('cent', cent, F32, (-1, D), layout='rows'), cent.stride(0), b.ge('member', member, I32, 0),
+          b('gstart', gstart, I32, G + 1), pw, G, D, b('sums', sums, F32, (G, D), optional=True), b('bits', bits, I32, (G, D // 32)))
     return bits
 
 
 def retrieval_scores(q_off, q_word, q_bits, db_off, db_word, db_bits, D, alpha, tau, S, max_q):
     """S [Vq, Vdb] fp32: ASMK binary-kernel similarity of every query view (groups [q_off[i], q_off[i+1]), sorted by word) against every database view"""
-    for t in (q_off, q_word, q_bits, db_off, db_word, db_bits):
-        _dev(t, torch.int32)
-        assert t.is_contiguous()
-    _dev(S, torch.float32)
+    b = _Operands('retrieval_scores')
+    pq, pd = b.ge('q_off', q_off, I32, 1), b.ge('db_off', db_off, I32, 1)
     Vq, Vdb = q_off.numel() - 1, db_off.numel() - 1
-    assert S.shape == (Vq, Vdb) and S.is_contiguous() and q_bits.shape[1] == D // 32 and db_bits.shape[1] == D // 32
-    _call('pst_retrieval_scores', _ptr(q_off), _ptr(q_word), _ptr(q_bits), _ptr(db_off), _ptr(db_word), _ptr(db_bits), Vq, Vdb, int(max(1, max_q)), int(D),
-          float(alpha), float(tau), _ptr(S))
+    _call('pst_retrieval_scores', pq, b.ge('q_word', q_word, I32, 0), b('q_bits', q_bits, I32, (-1, D // 32)), pd, b.ge('db_word', db_word, I32, 0),
+          b('db_bits', db_bits, I32, (-1, D // 32)), Vq, Vdb, int(max(1, max_q)), int(D), float(alpha), float(tau), b('S', S, F32, (Vq, Vdb)))
     return S
 
 
 # ------------------------------------------------------------------ panoptic point cloud (csrc/cloud.hip; engine/cloud.py holds the public entry point)
 CLOUD_WG = 1024            # points per workgroup of the count / compact passes
 CLOUD_MAX_COLORS = 4096    # colour table rows that fit in LDS
+_VIEW_BYTES = C.sizeof(CloudView)
 
 
-def _view_table(views, cams2world, device, what):
+def _view_table(views, cams2world, device, what, absent=()):
     """device table of pst_cloud_view for views = [(conf, pts3d, pts3d_local, img, pan)] (contiguous device tensors, which the caller keeps alive; a
-    plane that is None stays NULL) and cams2world = [V, 3, 4] host floats -> (uint8 tensor, number of workgroups, total number of `what`)"""
+    plane named in `absent` may be None and stays NULL) and cams2world = [V, 3, 4] host floats -> (uint8 tensor, number of workgroups, total number
+    of `what`)"""
     tab = (CloudView * len(views))()
+    b = _Operands('view table of %s' % what)
     off = wg = 0
     for e, (conf, pts, loc, img, pan), c2w in zip(tab, views, cams2world):
+        e.conf = b.ge('conf', conf, F32, 1)
         n = conf.numel()
-        assert n > 0
-        for t, dt, k in ((conf, torch.float32, 1), (pts, torch.float32, 3), (loc, torch.float32, 3), (img, torch.float32, 3), (pan, torch.int32, 1)):
-            if t is not None:
-                _dev(t, dt)
-                assert t.is_contiguous() and t.device == conf.device and t.numel() == k * n
-        e.conf, e.pts3d, e.pts3d_local, e.img, e.pan = (None if t is None else t.data_ptr() for t in (conf, pts, loc, img, pan))
+        e.pts3d, e.pts3d_local = b('pts3d', pts, F32, 3 * n), b('pts3d_local', loc, F32, 3 * n)
+        e.img, e.pan = b('img', img, F32, 3 * n, optional='img' in absent), b('pan', pan, I32, n, optional='pan' in absent)
         e.offset, e.npix, e.first_wg = off, n, wg
         e.c2w[:] = [float(x) for row in c2w for x in row]
         off += n
-        wg += (n + CLOUD_WG - 1) // CLOUD_WG
+        wg += _wgs(n)
     if off >= 2 ** 31:
         raise RuntimeError('a scene of %d %s exceeds the 2^31 - 1 the kernels of a view table index' % (off, what))
     return torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(device), wg, off
@@ -1179,20 +1257,17 @@ def _view_table(views, cams2world, device, what):
 def cloud_view_table(views, cams2world, device):
     """device table of pst_cloud_view for views = [(conf, pts3d, pts3d_local, img, pan)] (contiguous device tensors, which the caller keeps alive)
     and cams2world = [V, 3, 4] host floats -> (uint8 tensor, number of workgroups, total number of points)"""
-    assert all(t is not None for v in views for t in v)
     return _view_table(views, cams2world, device, 'points')
 
 
 def cloud_count(table, nviews, nwg, thr, counts):
-    _dev(table, torch.uint8); _dev(counts, torch.int32)
-    assert table.numel() == nviews * C.sizeof(CloudView) and counts.numel() >= nwg
-    _call('pst_cloud_count', _ptr(table), nviews, nwg, float(thr), _ptr(counts))
+    b = _Operands('cloud_count')
+    _call('pst_cloud_count', b('table', table, U8, nviews * _VIEW_BYTES), nviews, nwg, float(thr), b.ge('counts', counts, I32, nwg))
 
 
 def cloud_scan(counts, base):
-    _dev(counts, torch.int32); _dev(base, torch.int32)
-    assert base.numel() == counts.numel() + 1
-    _call('pst_cloud_scan', _ptr(counts), counts.numel(), _ptr(base))
+    b = _Operands('cloud_scan')
+    _call('pst_cloud_scan', b.ge('counts', counts, I32, 0), counts.numel(), b('base', base, I32, counts.numel() + 1))
 
 
 def scan_buffers(device, n=None, wg=CLOUD_WG, *, nwg=None):
@@ -1202,25 +1277,23 @@ def scan_buffers(device, n=None, wg=CLOUD_WG, *, nwg=None):
 
 
 def cloud_compact(table, nviews, nwg, thr, base, colors, w1, w2, points, points_local, rgb, pan, colors_out, index):
-    _dev(table, torch.uint8); _dev(base, torch.int32); _dev(colors, torch.float32); _dev(pan, torch.int32); _dev(index, torch.int64)
-    n = pan.numel()
-    for t in (points, points_local, rgb, colors_out):
-        _dev(t, torch.float32)
-        assert t.is_contiguous() and t.numel() == 3 * n
-    assert table.numel() == nviews * C.sizeof(CloudView) and base.numel() == nwg + 1 and index.numel() == n and colors.is_contiguous() and colors.shape[1] == 3
-    _call('pst_cloud_compact', _ptr(table), nviews, nwg, float(thr), _ptr(base), _ptr(colors), colors.shape[0], float(w1), float(w2), _ptr(points),
-          _ptr(points_local), _ptr(rgb), _ptr(pan), _ptr(colors_out), _ptr(index))
+    b = _Operands('cloud_compact')
+    pp, n = b.sized('pan', pan, I32)
+    _call('pst_cloud_compact', b('table', table, U8, nviews * _VIEW_BYTES), nviews, nwg, float(thr), b('base', base, I32, nwg + 1),
+          b('colors', colors, F32, (-1, 3)), colors.shape[0], float(w1), float(w2), b('points', points, F32, 3 * n), b('points_local', points_local, F32, 3 * n),
+          b('rgb', rgb, F32, 3 * n), pp, b('colors_out', colors_out, F32, 3 * n), b('index', index, I64, n))
 
 
 def cloud_segment_median(points_local, pan, m_ptr, id2row, nseg, count, median):
     """count int32 [nseg], median fp32 [nseg, 3] of the rows [0, M) of points_local by segment row (id2row int32, -1 = none); m_ptr = one-element int32
     device tensor holding M"""
-    _dev(points_local, torch.float32); _dev(pan, torch.int32); _dev(m_ptr, torch.int32); _dev(id2row, torch.int32); _dev(count, torch.int32); _dev(median, torch.float32)
-    assert points_local.is_contiguous() and pan.numel() * 3 == points_local.numel() and count.numel() == nseg and median.numel() == 3 * nseg and median.is_contiguous()
+    b = _Operands('cloud_segment_median')
+    pp, pi = b.ge('pan', pan, I32, 0), b.ge('id2row', id2row, I32, 0)
     ws = torch.zeros(nseg * (3 * 2 * 256 + 6 + 6 + 3), dtype=torch.int32, device=pan.device)
     hist, prefix, rank, nan = ws[:nseg * 1536], ws[nseg * 1536:nseg * 1542], ws[nseg * 1542:nseg * 1548], ws[nseg * 1548:]
-    _call('pst_cloud_segment_median', _ptr(points_local), _ptr(pan), _ptr(m_ptr), pan.numel(), _ptr(id2row), id2row.numel(), nseg, _ptr(hist), _ptr(prefix),
-          _ptr(rank), _ptr(nan), _ptr(count), _ptr(median))
+    _call('pst_cloud_segment_median', b('points_local', points_local, F32, 3 * pan.numel()), pp, b.ge('m_ptr', m_ptr, I32, 1), pan.numel(), pi, id2row.numel(),
+          nseg, b('hist', hist, I32, 1536 * nseg), b('prefix', prefix, I32, 6 * nseg), b('rank', rank, I32, 6 * nseg), b('nan', nan, I32, 3 * nseg),
+          b('count', count, I32, nseg), b('median', median, F32, 3 * nseg))
 
 
 # ------------------------------------------------------------------ QUBO mask selection (csrc/qubo_solve.hip; engine/postprocess.py holds the public entry points)
@@ -1232,12 +1305,12 @@ def qubo_anneal_max_n():
 def qubo_anneal(W, replicas, num_iters, T0, T_end, lambda_reg, seed, x_all, e_all, best_x, best_e):
     """`replicas` independent simulated anneals of E(x) = x^T W x + lambda_reg mean(x) (W fp32 [N, N]) -> x_all uint8 [replicas, N], e_all fp32 [replicas],
     best_x uint8 [N], best_e fp32 [1]; a pure function of its arguments (include/panst3r_hip.h).  An N the kernel does not take raises, outputs untouched."""
-    _dev(W, torch.float32); _dev(x_all, torch.uint8); _dev(e_all, torch.float32); _dev(best_x, torch.uint8); _dev(best_e, torch.float32)
+    b = _Operands('qubo_anneal')
+    pw = b('W', W, F32, (-1, -1))
     N = W.shape[0]
-    assert W.dim() == 2 and W.shape[1] == N and all(t.is_contiguous() and t.device == W.device for t in (W, x_all, e_all, best_x, best_e))
-    assert x_all.numel() == replicas * N and e_all.numel() == replicas and best_x.numel() == N and best_e.numel() == 1
-    _call('pst_qubo_anneal', _ptr(W), N, int(replicas), int(num_iters), float(T0), float(T_end), float(lambda_reg), int(seed) & (2 ** 64 - 1), _ptr(x_all),
-          _ptr(e_all), _ptr(best_x), _ptr(best_e))
+    b.require(W.shape[1] == N, 'W must be square, got %s', tuple(W.shape))
+    _call('pst_qubo_anneal', pw, N, int(replicas), int(num_iters), float(T0), float(T_end), float(lambda_reg), int(seed) & (2 ** 64 - 1),
+          b('x_all', x_all, U8, replicas * N), b('e_all', e_all, F32, replicas), b('best_x', best_x, U8, N), b('best_e', best_e, F32, 1))
 
 
 # ------------------------------------------------------------------ voxel fusion of the point cloud (csrc/voxel.hip; engine/voxels.py holds the public entry point)
@@ -1260,53 +1333,49 @@ def voxel_workspace(M, device):
 
 
 def voxel_insert(points, inv, ws, merge=None):
-    _dev(points, torch.float32)
-    M = points.shape[0]
-    assert points.is_contiguous() and points.dim() == 2 and points.shape[1] == 3 and ws['point_slot'].numel() == M and ws['keys'].numel() == ws['cap']
-    _call('pst_voxel_insert', _ptr(points), M, float(inv), _ptr(ws['keys']), ws['cap'], _ptr(ws['first']), _ptr(ws['point_slot']), _ptr(ws['status']),
-          int(VOXEL_MERGE if merge is None else merge))
+    b = _Operands('voxel_insert')
+    pts = b.rows3('points', points, F32)
+    _call('pst_voxel_insert', *pts, float(inv), b('keys', ws['keys'], I64, ws['cap']), ws['cap'], b.ge('first', ws['first'], I32, ws['cap']),
+          b('point_slot', ws['point_slot'], I32, pts[1]), b.ge('status', ws['status'], I32, 2), int(VOXEL_MERGE if merge is None else merge))
 
 
 def voxel_count(ws, counts):
-    _dev(counts, torch.int32)
-    M = ws['point_slot'].numel()
-    assert counts.numel() == (M + CLOUD_WG - 1) // CLOUD_WG
-    _call('pst_voxel_count', _ptr(ws['point_slot']), _ptr(ws['first']), M, _ptr(counts))
+    """the capacity of `first` is no argument of the entry point: a table of M points has at least 2 M slots"""
+    b = _Operands('voxel_count')
+    ps, M = b.sized('point_slot', ws['point_slot'], I32)
+    _call('pst_voxel_count', ps, b.ge('first', ws['first'], I32, 2 * M), M, b('counts', counts, I32, _wgs(M)))
 
 
 def voxel_rank(ws, base):
-    _dev(base, torch.int32)
-    M = ws['point_slot'].numel()
-    assert base.numel() == (M + CLOUD_WG - 1) // CLOUD_WG + 1
-    _call('pst_voxel_rank', _ptr(ws['point_slot']), _ptr(ws['first']), M, _ptr(base), _ptr(ws['slot_rank']), _ptr(ws['first_row']))
+    b = _Operands('voxel_rank')
+    ps, M = b.sized('point_slot', ws['point_slot'], I32)
+    _call('pst_voxel_rank', ps, b.ge('first', ws['first'], I32, 2 * M), M, b('base', base, I32, _wgs(M) + 1), b.ge('slot_rank', ws['slot_rank'], I32, 2 * M),
+          b.ge('first_row', ws['first_row'], I32, M))
 
 
 def voxel_accumulate(points, rgb, pan, inv, id2row, ws, point_voxel, merge=None):
-    _dev(points, torch.float32); _dev(rgb, torch.float32); _dev(pan, torch.int32); _dev(id2row, torch.int32); _dev(point_voxel, torch.int32)
-    M = pan.numel()
-    assert points.is_contiguous() and rgb.is_contiguous() and points.numel() == 3 * M and rgb.numel() == 3 * M and point_voxel.numel() == M
-    assert ws['point_slot'].numel() == M and pan.is_contiguous() and id2row.is_contiguous()
-    _call('pst_voxel_accumulate', _ptr(points), _ptr(rgb), _ptr(pan), M, float(inv), _ptr(ws['point_slot']), _ptr(ws['slot_rank']), _ptr(id2row), id2row.numel(),
-          _ptr(ws['cnt']), _ptr(ws['sums']), _ptr(ws['pair_keys']), _ptr(ws['pair_cnt']), ws['cap'], _ptr(point_voxel), _ptr(ws['status']),
-          int(VOXEL_MERGE if merge is None else merge))
+    b = _Operands('voxel_accumulate')
+    (pp, M), cap = b.sized('pan', pan, I32), ws['cap']
+    _call('pst_voxel_accumulate', b('points', points, F32, 3 * M), b('rgb', rgb, F32, 3 * M), pp, M, float(inv), b('point_slot', ws['point_slot'], I32, M),
+          b.ge('slot_rank', ws['slot_rank'], I32, cap), b.ge('id2row', id2row, I32, 0), id2row.numel(), b.ge('cnt', ws['cnt'], I32, M),
+          b.ge('sums', ws['sums'], I64, 6 * M), b.ge('pair_keys', ws['pair_keys'], I64, cap), b.ge('pair_cnt', ws['pair_cnt'], I32, cap), cap,
+          b('point_voxel', point_voxel, I32, M), b.ge('status', ws['status'], I32, 2), int(VOXEL_MERGE if merge is None else merge))
 
 
 def voxel_vote(ws):
-    _call('pst_voxel_vote', _ptr(ws['pair_keys']), _ptr(ws['pair_cnt']), ws['cap'], _ptr(ws['best']))
+    """best int64 [M] is written at the rows the pair keys name: the entry point does not take M"""
+    b = _Operands('voxel_vote')
+    _call('pst_voxel_vote', b.ge('pair_keys', ws['pair_keys'], I64, ws['cap']), b.ge('pair_cnt', ws['pair_cnt'], I32, ws['cap']), ws['cap'],
+          b.ge('best', ws['best'], I64, 1))
 
 
 def voxel_emit(points, index, mv_ptr, inv, voxel_size, ws, colors, w1, w2, out_points, out_rgb, out_pan, out_colors, out_votes, out_first):
-    _dev(points, torch.float32); _dev(index, torch.int64); _dev(mv_ptr, torch.int32); _dev(colors, torch.float32); _dev(out_pan, torch.int32)
-    _dev(out_votes, torch.int32); _dev(out_first, torch.int64)
-    M = index.numel()
-    for t in (out_points, out_rgb, out_colors):
-        _dev(t, torch.float32)
-        assert t.is_contiguous() and t.numel() == 3 * M
-    assert points.is_contiguous() and index.is_contiguous() and colors.is_contiguous() and colors.shape[1] == 3 and ws['first_row'].numel() == M
-    assert out_pan.numel() == M and out_votes.numel() == M and out_first.numel() == M
-    _call('pst_voxel_emit', _ptr(points), _ptr(index), _ptr(ws['first_row']), _ptr(mv_ptr), M, float(inv), float(voxel_size), _ptr(ws['cnt']), _ptr(ws['sums']),
-          _ptr(ws['best']), _ptr(colors), colors.shape[0], float(w1), float(w2), _ptr(out_points), _ptr(out_rgb), _ptr(out_pan), _ptr(out_colors), _ptr(out_votes),
-          _ptr(out_first))
+    b = _Operands('voxel_emit')
+    pi, M = b.sized('index', index, I64)
+    _call('pst_voxel_emit', b.ge('points', points, F32, 3 * M), pi, b('first_row', ws['first_row'], I32, M), b.ge('mv_ptr', mv_ptr, I32, 1), M, float(inv),
+          float(voxel_size), b.ge('cnt', ws['cnt'], I32, M), b.ge('sums', ws['sums'], I64, 6 * M), b.ge('best', ws['best'], I64, M),
+          b('colors', colors, F32, (-1, 3)), colors.shape[0], float(w1), float(w2), b('out_points', out_points, F32, 3 * M), b('out_rgb', out_rgb, F32, 3 * M),
+          b('out_pan', out_pan, I32, M), b('out_colors', out_colors, F32, 3 * M), b('out_votes', out_votes, I32, M), b('out_first', out_first, I64, M))
 
 
 # ------------------------------------------------------------------ connected components of the voxels (csrc/components.hip; engine/voxels.py holds the public entry points)
@@ -1316,10 +1385,9 @@ VCC_FULL, VCC_DUPLICATE, VCC_RANGE, VCC_LOOP = 1, 2, 4, 8      # PST_VCC_*: the 
 
 def vcc_cells(points, first_row, mv_ptr, inv, cells):
     """cells int32 [M, 3]: rows [0, *mv_ptr) = the integer cell of every voxel's first point (first_row: the fusion's workspace)"""
-    _dev(points, torch.float32); _dev(first_row, torch.int32); _dev(mv_ptr, torch.int32); _dev(cells, torch.int32)
-    M = first_row.numel()
-    assert points.is_contiguous() and points.numel() == 3 * M and cells.is_contiguous() and cells.numel() == 3 * M
-    _call('pst_vcc_cells', _ptr(points), _ptr(first_row), _ptr(mv_ptr), M, float(inv), _ptr(cells))
+    b = _Operands('vcc_cells')
+    pf, M = b.sized('first_row', first_row, I32)
+    _call('pst_vcc_cells', b('points', points, F32, 3 * M), pf, b.ge('mv_ptr', mv_ptr, I32, 1), M, float(inv), b('cells', cells, I32, 3 * M))
 
 
 def vcc_pair_capacity(Mv, nids):
@@ -1340,68 +1408,65 @@ def vcc_workspace(Mv, device, pairs=0):
     return ws
 
 
-def _vcc_voxels(cells, pan):
-    _dev(cells, torch.int32); _dev(pan, torch.int32)
-    Mv = pan.numel()
-    assert cells.is_contiguous() and pan.is_contiguous() and tuple(cells.shape) == (Mv, 3) and cells.device == pan.device
-    return Mv
+def _vcc_voxels(b, cells, pan):
+    """-> (cells, pan, Mv): the three leading arguments of the entry points over cells int32 [Mv, 3] and pan int32 [Mv]"""
+    pp, Mv = b.sized('pan', pan, I32)
+    return b('cells', cells, I32, (Mv, 3)), pp, Mv
 
 
 def vcc_build(cells, pan, ws):
-    Mv = _vcc_voxels(cells, pan)
-    assert ws['keys'].numel() == ws['cap'] == ws['rows'].numel() and ws['parent'].numel() == Mv
-    _call('pst_vcc_build', _ptr(cells), _ptr(pan), Mv, _ptr(ws['keys']), _ptr(ws['rows']), ws['cap'], _ptr(ws['parent']), _ptr(ws['status']))
+    b = _Operands('vcc_build')
+    vox = _vcc_voxels(b, cells, pan)
+    _call('pst_vcc_build', *vox, b('keys', ws['keys'], I64, ws['cap']), b('rows', ws['rows'], I32, ws['cap']), ws['cap'], b('parent', ws['parent'], I32, vox[2]),
+          b.ge('status', ws['status'], I32, 4))
 
 
 def vcc_link(cells, pan, connectivity, ws):
-    Mv = _vcc_voxels(cells, pan)
-    assert ws['parent'].numel() == Mv
-    _call('pst_vcc_link', _ptr(cells), _ptr(pan), Mv, _ptr(ws['keys']), _ptr(ws['rows']), ws['cap'], int(connectivity), _ptr(ws['parent']), _ptr(ws['status']))
+    b = _Operands('vcc_link')
+    vox = _vcc_voxels(b, cells, pan)
+    _call('pst_vcc_link', *vox, b.ge('keys', ws['keys'], I64, ws['cap']), b.ge('rows', ws['rows'], I32, ws['cap']), ws['cap'], int(connectivity),
+          b('parent', ws['parent'], I32, vox[2]), b.ge('status', ws['status'], I32, 4))
 
 
 def vcc_flatten(count, cells, ws, merge=None):
-    _dev(count, torch.int32); _dev(cells, torch.int32)
-    Mv = count.numel()
-    assert count.is_contiguous() and cells.is_contiguous() and cells.numel() == 3 * Mv and all(ws[k].numel() == Mv for k in ('parent', 'root', 'size', 'points'))
-    assert ws['lo'].numel() == 3 * Mv and ws['hi'].numel() == 3 * Mv
-    _call('pst_vcc_flatten', _ptr(ws['parent']), _ptr(count), _ptr(cells), Mv, _ptr(ws['root']), _ptr(ws['size']), _ptr(ws['points']), _ptr(ws['lo']), _ptr(ws['hi']),
-          _ptr(ws['status']), int(VCC_MERGE if merge is None else merge))
+    b = _Operands('vcc_flatten')
+    pc, Mv = b.sized('count', count, I32)
+    _call('pst_vcc_flatten', b('parent', ws['parent'], I32, Mv), pc, b('cells', cells, I32, 3 * Mv), Mv, b('root', ws['root'], I32, Mv),
+          b('size', ws['size'], I32, Mv), b('points', ws['points'], I64, Mv), b('lo', ws['lo'], I32, 3 * Mv), b('hi', ws['hi'], I32, 3 * Mv),
+          b.ge('status', ws['status'], I32, 4), int(VCC_MERGE if merge is None else merge))
 
 
 def vcc_count(ws, counts):
-    _dev(counts, torch.int32)
+    b = _Operands('vcc_count')
     Mv = ws['root'].numel()
-    assert counts.numel() == (Mv + CLOUD_WG - 1) // CLOUD_WG
-    _call('pst_vcc_count', _ptr(ws['root']), Mv, _ptr(counts))
+    _call('pst_vcc_count', b('root', ws['root'], I32, Mv), Mv, b('counts', counts, I32, _wgs(Mv)))
 
 
 def vcc_rank(pan, ws, base, component, table):
     """component int32 [Mv]; table: dict of root, pan, size int32 [Mv], points int64 [Mv], cell_lo, cell_hi int32 [Mv, 3] - rows [0, C) are written"""
-    _dev(pan, torch.int32); _dev(base, torch.int32); _dev(component, torch.int32)
-    Mv = pan.numel()
-    assert base.numel() == (Mv + CLOUD_WG - 1) // CLOUD_WG + 1 and component.numel() == Mv and ws['root'].numel() == Mv
-    for k in ('root', 'pan', 'size', 'points', 'cell_lo', 'cell_hi'):
-        t = table[k]
-        _dev(t, torch.int64 if k == 'points' else torch.int32)
-        assert t.is_contiguous() and t.numel() == (3 * Mv if k.startswith('cell') else Mv)
-    _call('pst_vcc_rank', _ptr(ws['root']), _ptr(pan), Mv, _ptr(base), _ptr(ws['size']), _ptr(ws['points']), _ptr(ws['lo']), _ptr(ws['hi']), _ptr(ws['rank_of']),
-          _ptr(component), _ptr(table['root']), _ptr(table['pan']), _ptr(table['size']), _ptr(table['points']), _ptr(table['cell_lo']), _ptr(table['cell_hi']))
+    b = _Operands('vcc_rank')
+    pp, Mv = b.sized('pan', pan, I32)
+    _call('pst_vcc_rank', b('root', ws['root'], I32, Mv), pp, Mv, b('base', base, I32, _wgs(Mv) + 1), b.ge('size', ws['size'], I32, Mv),
+          b.ge('points', ws['points'], I64, Mv), b.ge('lo', ws['lo'], I32, 3 * Mv), b.ge('hi', ws['hi'], I32, 3 * Mv), b.ge('rank_of', ws['rank_of'], I32, Mv),
+          b('component', component, I32, Mv), b('table root', table['root'], I32, Mv), b('table pan', table['pan'], I32, Mv),
+          b('table size', table['size'], I32, Mv), b('table points', table['points'], I64, Mv), b('table cell_lo', table['cell_lo'], I32, 3 * Mv),
+          b('table cell_hi', table['cell_hi'], I32, 3 * Mv))
 
 
 def vcc_votes(cells, pan, connectivity, min_voxels, ws):
-    Mv = _vcc_voxels(cells, pan)
-    assert ws['root'].numel() == Mv and ws['pair_keys'].numel() == ws['pair_cap'] == ws['pair_cnt'].numel()
-    _call('pst_vcc_votes', _ptr(cells), _ptr(pan), _ptr(ws['root']), _ptr(ws['size']), Mv, _ptr(ws['keys']), _ptr(ws['rows']), ws['cap'], int(connectivity),
-          int(min_voxels), _ptr(ws['pair_keys']), _ptr(ws['pair_cnt']), ws['pair_cap'], _ptr(ws['status']))
+    b = _Operands('vcc_votes')
+    vox = _vcc_voxels(b, cells, pan)
+    _call('pst_vcc_votes', vox[0], vox[1], b('root', ws['root'], I32, vox[2]), b.ge('size', ws['size'], I32, vox[2]), vox[2], b.ge('keys', ws['keys'], I64, ws['cap']),
+          b.ge('rows', ws['rows'], I32, ws['cap']), ws['cap'], int(connectivity), int(min_voxels), b('pair_keys', ws['pair_keys'], I64, ws['pair_cap']),
+          b('pair_cnt', ws['pair_cnt'], I32, ws['pair_cap']), ws['pair_cap'], b.ge('status', ws['status'], I32, 4))
 
 
 def vcc_apply(pan, min_voxels, rgb, colors, w1, w2, ws, out_pan, out_colors):
-    _dev(pan, torch.int32); _dev(rgb, torch.float32); _dev(colors, torch.float32); _dev(out_pan, torch.int32); _dev(out_colors, torch.float32)
-    Mv = pan.numel()
-    assert all(t.is_contiguous() for t in (pan, rgb, colors, out_pan, out_colors)) and rgb.numel() == 3 * Mv and out_colors.numel() == 3 * Mv and out_pan.numel() == Mv
-    assert colors.dim() == 2 and colors.shape[1] == 3 and ws['root'].numel() == Mv and ws['best'].numel() == Mv
-    _call('pst_vcc_apply', _ptr(pan), _ptr(ws['root']), _ptr(ws['size']), _ptr(ws['best']), Mv, int(min_voxels), _ptr(rgb), _ptr(colors), colors.shape[0], float(w1),
-          float(w2), _ptr(out_pan), _ptr(out_colors), _ptr(ws['status']))
+    b = _Operands('vcc_apply')
+    pp, Mv = b.sized('pan', pan, I32)
+    _call('pst_vcc_apply', pp, b('root', ws['root'], I32, Mv), b.ge('size', ws['size'], I32, Mv), b('best', ws['best'], I64, Mv), Mv, int(min_voxels),
+          b('rgb', rgb, F32, 3 * Mv), b('colors', colors, F32, (-1, 3)), colors.shape[0], float(w1), float(w2), b('out_pan', out_pan, I32, Mv),
+          b('out_colors', out_colors, F32, 3 * Mv), b.ge('status', ws['status'], I32, 4))
 
 
 # ------------------------------------------------------------------ z-buffered rendering of a cloud (csrc/render.hip; engine/render.py holds the public entry points)
@@ -1417,23 +1482,19 @@ def render_max_radius():
 
 def render_splat(points, cams, H, W, half_size, radius, max_radius, zbuf, precheck=None):
     """atomicMin of every point's key into zbuf int64 [B, H, W] (cleared to all ones by the caller) for the B cameras of cams fp32 [B, 16]"""
-    _dev(points, torch.float32); _dev(cams, torch.float32); _dev(zbuf, torch.int64)
+    b = _Operands('render_splat')
+    pts, pc = b.rows3('points', points, F32), b('cams', cams, F32, (-1, RENDER_CAM_FLOATS))
     B = cams.shape[0]
-    assert points.is_contiguous() and points.dim() == 2 and points.shape[1] == 3 and cams.is_contiguous() and tuple(cams.shape) == (B, RENDER_CAM_FLOATS)
-    assert zbuf.is_contiguous() and tuple(zbuf.shape) == (B, H, W) and cams.device == points.device == zbuf.device
-    _call('pst_render_splat', _ptr(points), points.shape[0], _ptr(cams), B, int(H), int(W), float(half_size), int(radius), int(max_radius), _ptr(zbuf),
+    _call('pst_render_splat', *pts, pc, B, int(H), int(W), float(half_size), int(radius), int(max_radius), b('zbuf', zbuf, I64, (B, H, W)),
           int(RENDER_PRECHECK if precheck is None else precheck))
 
 
 def render_resolve(zbuf, rgb, colors, pan, index, depth, out_pan, out_rgb, out_colors):
     """per cell of zbuf: the winner's row, depth, pan, rgb and colours (an empty cell: -1 and zeros)"""
-    _dev(zbuf, torch.int64); _dev(rgb, torch.float32); _dev(colors, torch.float32); _dev(pan, torch.int32)
-    _dev(index, torch.int64); _dev(depth, torch.float32); _dev(out_pan, torch.int32); _dev(out_rgb, torch.float32); _dev(out_colors, torch.float32)
-    n, M = zbuf.numel(), pan.numel()
-    assert all(t.is_contiguous() and t.device == zbuf.device for t in (zbuf, rgb, colors, pan, index, depth, out_pan, out_rgb, out_colors))
-    assert rgb.numel() == 3 * M and colors.numel() == 3 * M and index.numel() == n and depth.numel() == n and out_pan.numel() == n
-    assert out_rgb.numel() == 3 * n and out_colors.numel() == 3 * n
-    _call('pst_render_resolve', _ptr(zbuf), n, M, _ptr(rgb), _ptr(colors), _ptr(pan), _ptr(index), _ptr(depth), _ptr(out_pan), _ptr(out_rgb), _ptr(out_colors))
+    b = _Operands('render_resolve')
+    (pz, n), (pp, M) = b.sized('zbuf', zbuf, I64), b.sized('pan', pan, I32)
+    _call('pst_render_resolve', pz, n, M, b('rgb', rgb, F32, 3 * M), b('colors', colors, F32, 3 * M), pp, b('index', index, I64, n), b('depth', depth, F32, n),
+          b('out_pan', out_pan, I32, n), b('out_rgb', out_rgb, F32, 3 * n), b('out_colors', out_colors, F32, 3 * n))
 
 
 # ------------------------------------------------------------------ cross-view depth consistency (csrc/consistency.hip; engine/consistency.py holds the public entry points)
@@ -1442,37 +1503,33 @@ def consist_view_table(views, cams2world, cams, shapes, device):
     caller keeps alive), cams2world = [V, 3, 4] host floats, cams = float32 [V, 16] host (engine.render.camera_table of every view's own camera) and
     shapes = [(H, W)] -> (pst_cloud_view table as a uint8 tensor - img is not read and stays NULL -, cams tensor, dims int32 [V, 2], number of
     workgroups, total number of pixels)"""
-    assert len(views) == len(cams2world) == len(shapes) == len(cams) > 0 and tuple(cams.shape) == (len(views), RENDER_CAM_FLOATS)
-    assert all(t is not None for v in views for t in v[:3]) and all(v[0].numel() == int(H) * int(W) for v, (H, W) in zip(views, shapes))
-    table, wg, off = _view_table([(conf, pts, loc, None, pan) for conf, pts, loc, pan in views], cams2world, device, 'pixels')
+    b = _Operands('consist_view_table')
+    b.require(len(views) == len(cams2world) == len(shapes) == len(cams) > 0 and tuple(cams.shape) == (len(views), RENDER_CAM_FLOATS),
+              'one camera-to-world matrix, one row of cams float32 [V, %d] and one shape per view, V >= 1' % RENDER_CAM_FLOATS)
+    table, wg, off = _view_table([(conf, pts, loc, None, pan) for conf, pts, loc, pan in views], cams2world, device, 'pixels', absent=('img', 'pan'))
+    b.require(all(v[0].numel() == int(H) * int(W) for v, (H, W) in zip(views, shapes)), 'every view holds the H W pixels of its shape')
     dims = torch.tensor([(int(H), int(W)) for H, W in shapes], dtype=torch.int32).reshape(-1, 2)
     return table, torch.from_numpy(cams).contiguous().to(device), dims.to(device), wg, off
 
 
-def _consist_tables(table, cams, nviews):
-    _dev(table, torch.uint8); _dev(cams, torch.float32)
-    assert table.numel() == nviews * C.sizeof(CloudView) and cams.is_contiguous() and tuple(cams.shape) == (nviews, RENDER_CAM_FLOATS)
+def _consist_tables(b, table, cams, nviews):
+    """-> (table, cams): the scene's view table and its cameras float32 [nviews, 16], the two leading arguments of the consistency entry points"""
+    return b('table', table, U8, nviews * _VIEW_BYTES), b('cams', cams, F32, (nviews, RENDER_CAM_FLOATS))
 
 
 def consist_depth(table, cams, nviews, nwg, thr, local, depth):
     """depth fp32 [N]: every pixel's depth in its own camera, 0 where the view measured nothing (conf < thr, a non-finite point, nearer than near)"""
-    _consist_tables(table, cams, nviews)
-    _dev(depth, torch.float32)
-    assert depth.is_contiguous()
-    _call('pst_consist_depth', _ptr(table), _ptr(cams), nviews, nwg, depth.numel(), float(thr), int(bool(local)), _ptr(depth))
+    b = _Operands('consist_depth')
+    pd, N = b.sized('depth', depth, F32)
+    _call('pst_consist_depth', *_consist_tables(b, table, cams, nviews), nviews, nwg, N, float(thr), int(bool(local)), pd)
 
 
 def consist_count(table, cams, dims, nviews, nwg, rel_tol, local, depth, agree, violate, same_label=None):
     """agree, violate, same_label (or None: no panoptic id is read) int32 [N] of every pixel against every other view's depth"""
-    _consist_tables(table, cams, nviews)
-    _dev(dims, torch.int32); _dev(depth, torch.float32)
-    N = depth.numel()
-    assert dims.is_contiguous() and tuple(dims.shape) == (nviews, 2) and depth.is_contiguous()
-    for t in (agree, violate) + ((same_label,) if same_label is not None else ()):
-        _dev(t, torch.int32)
-        assert t.is_contiguous() and t.numel() == N and t.device == depth.device
-    _call('pst_consist_count', _ptr(table), _ptr(cams), _ptr(dims), nviews, nwg, N, float(rel_tol), int(bool(local)), _ptr(depth), _ptr(agree), _ptr(violate),
-          _ptr(same_label))
+    b = _Operands('consist_count')
+    pd, N = b.sized('depth', depth, F32)
+    _call('pst_consist_count', *_consist_tables(b, table, cams, nviews), b('dims', dims, I32, (nviews, 2)), nviews, nwg, N, float(rel_tol), int(bool(local)), pd,
+          b('agree', agree, I32, N), b('violate', violate, I32, N), b('same_label', same_label, I32, N, optional=True))
 
 
 # ------------------------------------------------------------------ one fused TSDF surface out of all views (csrc/tsdf.hip; engine/tsdf.py holds the public entry points)
@@ -1506,85 +1563,71 @@ def tsdf_workspace(Mv, band, device):
             'slot_rank': torch.empty(cap, **i32), 'point_slot': torch.empty(P, **i32), 'first_row': torch.empty(P, **i32), 'status': torch.zeros(4, **i32)}
 
 
-def _tsdf_cells(cells):
-    _dev(cells, torch.int32)
-    assert cells.is_contiguous() and cells.dim() == 2 and cells.shape[1] == 3
-    return cells.shape[0]
-
-
 def tsdf_insert(cells, band, ws):
-    Mv = _tsdf_cells(cells)
-    assert ws['keys'].numel() == ws['cap'] == ws['first'].numel() and ws['point_slot'].numel() == tsdf_pairs(Mv, band)
-    _call('pst_tsdf_insert', _ptr(cells), Mv, int(band), _ptr(ws['keys']), ws['cap'], _ptr(ws['first']), _ptr(ws['point_slot']), _ptr(ws['status']))
+    b = _Operands('tsdf_insert')
+    vox = b.rows3('cells', cells, I32)
+    _call('pst_tsdf_insert', *vox, int(band), b('keys', ws['keys'], I64, ws['cap']), ws['cap'], b('first', ws['first'], I32, ws['cap']),
+          b('point_slot', ws['point_slot'], I32, tsdf_pairs(vox[1], band)), b.ge('status', ws['status'], I32, 4))
 
 
 def tsdf_nodes(cells, band, Nn, ws, nodes, voxel_row):
     """nodes int32 [Nn, 3] in rank order; voxel_row int32 [Nn] (filled with -1 by the caller): the voxel whose cell is the node"""
-    Mv = _tsdf_cells(cells)
-    _dev(nodes, torch.int32); _dev(voxel_row, torch.int32)
-    assert nodes.is_contiguous() and tuple(nodes.shape) == (Nn, 3) and voxel_row.numel() == Nn and ws['first_row'].numel() == tsdf_pairs(Mv, band)
-    _call('pst_tsdf_nodes', _ptr(cells), Mv, int(band), _ptr(ws['first_row']), Nn, _ptr(ws['keys']), ws['cap'], _ptr(ws['slot_rank']), _ptr(nodes), _ptr(voxel_row),
-          _ptr(ws['status']))
+    b = _Operands('tsdf_nodes')
+    vox = b.rows3('cells', cells, I32)
+    _call('pst_tsdf_nodes', *vox, int(band), b('first_row', ws['first_row'], I32, tsdf_pairs(vox[1], band)), Nn, b.ge('keys', ws['keys'], I64, ws['cap']), ws['cap'],
+          b.ge('slot_rank', ws['slot_rank'], I32, ws['cap']), b('nodes', nodes, I32, (Nn, 3)), b('voxel_row', voxel_row, I32, Nn), b.ge('status', ws['status'], I32, 4))
 
 
 def tsdf_integrate(nodes, voxel_size, band, table, cams, dims, nviews, depth, sdf, weight):
-    """sdf fp32 [Nn], weight int32 [Nn] of the nodes against the depth planes of `consist_depth` (table, cams, dims: `consist_view_table`)"""
-    _consist_tables(table, cams, nviews)
-    _dev(nodes, torch.int32); _dev(dims, torch.int32); _dev(depth, torch.float32); _dev(sdf, torch.float32); _dev(weight, torch.int32)
-    Nn = nodes.shape[0]
-    assert nodes.is_contiguous() and nodes.shape[1] == 3 and dims.is_contiguous() and tuple(dims.shape) == (nviews, 2) and depth.is_contiguous()
-    assert sdf.is_contiguous() and weight.is_contiguous() and sdf.numel() == Nn and weight.numel() == Nn
-    _call('pst_tsdf_integrate', _ptr(nodes), Nn, float(voxel_size), int(band), _ptr(table), _ptr(cams), _ptr(dims), nviews, _ptr(depth), _ptr(sdf), _ptr(weight))
+    """sdf fp32 [Nn], weight int32 [Nn] of the nodes against the depth planes of `consist_depth` (table, cams, dims: `consist_view_table`); depth fp32
+    [N] holds the scene's pixels, which the view table counts on the device"""
+    b = _Operands('tsdf_integrate')
+    nd = b.rows3('nodes', nodes, I32)
+    _call('pst_tsdf_integrate', *nd, float(voxel_size), int(band), *_consist_tables(b, table, cams, nviews), b('dims', dims, I32, (nviews, 2)), nviews,
+          b.ge('depth', depth, F32, 1), b('sdf', sdf, F32, nd[1]), b('weight', weight, I32, nd[1]))
 
 
-def _tsdf_nodes(nodes, ws, *per_node):
-    _dev(nodes, torch.int32)
-    Nn = nodes.shape[0]
-    assert nodes.is_contiguous() and nodes.shape[1] == 3 and ws['keys'].numel() == ws['cap'] == ws['slot_rank'].numel()
-    assert all(t.is_cuda and t.is_contiguous() and t.numel() == Nn for t in per_node)
-    return Nn
+def _tsdf_nodes(b, nodes, ws):
+    """-> (nodes, Nn, keys, cap, slot_rank): the five leading arguments of the entry points over the ranked nodes int32 [Nn, 3] and their table"""
+    return (*b.rows3('nodes', nodes, I32), b('keys', ws['keys'], I64, ws['cap']), ws['cap'], b('slot_rank', ws['slot_rank'], I32, ws['cap']))
 
 
 def tsdf_cells(nodes, ws, sdf, weight, min_weight, cell_vertex, counts):
     """cell_vertex int32 [Nn]: 1 where the cell at the node is a surface cell, else 0; counts [ceil(Nn / 1024)]"""
-    Nn = _tsdf_nodes(nodes, ws, sdf, weight, cell_vertex)
-    _dev(counts, torch.int32)
-    assert counts.numel() == (Nn + CLOUD_WG - 1) // CLOUD_WG
-    _call('pst_tsdf_cells', _ptr(nodes), Nn, _ptr(ws['keys']), ws['cap'], _ptr(ws['slot_rank']), _ptr(sdf), _ptr(weight), int(min_weight), _ptr(cell_vertex),
-          _ptr(counts), _ptr(ws['status']))
+    b = _Operands('tsdf_cells')
+    tab = _tsdf_nodes(b, nodes, ws)
+    Nn = tab[1]
+    _call('pst_tsdf_cells', *tab, b('sdf', sdf, F32, Nn), b('weight', weight, I32, Nn), int(min_weight), b('cell_vertex', cell_vertex, I32, Nn),
+          b('counts', counts, I32, _wgs(Nn)), b.ge('status', ws['status'], I32, 4))
 
 
 def tsdf_vertices(nodes, ws, sdf, weight, min_weight, voxel_row, vox_count, vox_pan, vox_colors, voxel_size, base, cell_vertex, vertices, vertex_ids, colors):
     """vertices fp32 [Nv, 3], vertex_ids int32 [Nv], colors fp32 [Nv, 3] in rank order; cell_vertex becomes the vertex row of every node's cell, or -1"""
-    Nn = _tsdf_nodes(nodes, ws, sdf, weight, voxel_row, cell_vertex)
-    Mv, Nv = vox_pan.numel(), vertex_ids.numel()
-    _dev(vox_count, torch.int32); _dev(vox_pan, torch.int32); _dev(vox_colors, torch.float32); _dev(base, torch.int32)
-    _dev(vertices, torch.float32); _dev(vertex_ids, torch.int32); _dev(colors, torch.float32)
-    assert all(t.is_contiguous() for t in (vox_count, vox_pan, vox_colors, vertices, vertex_ids, colors)) and vox_count.numel() == Mv and vox_colors.numel() == 3 * Mv
-    assert base.numel() == (Nn + CLOUD_WG - 1) // CLOUD_WG + 1 and vertices.numel() == 3 * Nv and colors.numel() == 3 * Nv
-    _call('pst_tsdf_vertices', _ptr(nodes), Nn, _ptr(ws['keys']), ws['cap'], _ptr(ws['slot_rank']), _ptr(sdf), _ptr(weight), int(min_weight), _ptr(voxel_row),
-          _ptr(vox_count), _ptr(vox_pan), _ptr(vox_colors), Mv, float(voxel_size), _ptr(base), _ptr(cell_vertex), _ptr(vertices), _ptr(vertex_ids), _ptr(colors),
-          _ptr(ws['status']))
+    b = _Operands('tsdf_vertices')
+    tab = _tsdf_nodes(b, nodes, ws)
+    Nn, (pp, Mv), (pi, Nv) = tab[1], b.sized('vox_pan', vox_pan, I32), b.sized('vertex_ids', vertex_ids, I32)
+    _call('pst_tsdf_vertices', *tab, b('sdf', sdf, F32, Nn), b('weight', weight, I32, Nn), int(min_weight), b('voxel_row', voxel_row, I32, Nn),
+          b('vox_count', vox_count, I32, Mv), pp, b('vox_colors', vox_colors, F32, 3 * Mv), Mv, float(voxel_size), b('base', base, I32, _wgs(Nn) + 1),
+          b('cell_vertex', cell_vertex, I32, Nn), b('vertices', vertices, F32, 3 * Nv), pi, b('colors', colors, F32, 3 * Nv), b.ge('status', ws['status'], I32, 4))
 
 
 def tsdf_face_count(nodes, ws, sdf, weight, min_weight, cell_vertex, face_mask, counts):
     """face_mask int32 [Nn]: bit a = the lattice edge from the node along axis a emits two triangles; counts [ceil(Nn / 1024)] in faces"""
-    Nn = _tsdf_nodes(nodes, ws, sdf, weight, cell_vertex, face_mask)
-    _dev(counts, torch.int32)
-    assert counts.numel() == (Nn + CLOUD_WG - 1) // CLOUD_WG
-    _call('pst_tsdf_face_count', _ptr(nodes), Nn, _ptr(ws['keys']), ws['cap'], _ptr(ws['slot_rank']), _ptr(sdf), _ptr(weight), int(min_weight), _ptr(cell_vertex),
-          _ptr(face_mask), _ptr(counts), _ptr(ws['status']))
+    b = _Operands('tsdf_face_count')
+    tab = _tsdf_nodes(b, nodes, ws)
+    Nn = tab[1]
+    _call('pst_tsdf_face_count', *tab, b('sdf', sdf, F32, Nn), b('weight', weight, I32, Nn), int(min_weight), b('cell_vertex', cell_vertex, I32, Nn),
+          b('face_mask', face_mask, I32, Nn), b('counts', counts, I32, _wgs(Nn)), b.ge('status', ws['status'], I32, 4))
 
 
 def tsdf_face_emit(nodes, ws, sdf, cell_vertex, face_mask, vertex_ids, base, faces, face_ids, edge):
     """faces int32 [>= F, 3], face_ids int32, edge int64 [>= F]: rows [0, F) are written, F = base[-1] <= 6 Nv"""
-    Nn = _tsdf_nodes(nodes, ws, sdf, cell_vertex, face_mask)
-    _dev(vertex_ids, torch.int32); _dev(base, torch.int32); _dev(faces, torch.int32); _dev(face_ids, torch.int32); _dev(edge, torch.int64)
-    cap = face_ids.numel()
-    assert base.numel() == (Nn + CLOUD_WG - 1) // CLOUD_WG + 1 and faces.is_contiguous() and faces.numel() == 3 * cap and edge.numel() == cap
-    assert cap >= 6 * vertex_ids.numel() and vertex_ids.is_contiguous()
-    _call('pst_tsdf_face_emit', _ptr(nodes), Nn, _ptr(ws['keys']), ws['cap'], _ptr(ws['slot_rank']), _ptr(sdf), _ptr(cell_vertex), _ptr(face_mask), _ptr(vertex_ids),
-          _ptr(base), _ptr(faces), _ptr(face_ids), _ptr(edge), _ptr(ws['status']))
+    b = _Operands('tsdf_face_emit')
+    tab = _tsdf_nodes(b, nodes, ws)
+    Nn, (pv, Nv) = tab[1], b.sized('vertex_ids', vertex_ids, I32)
+    pf, cap = b.sized('face_ids', face_ids, I32, 6 * Nv)
+    _call('pst_tsdf_face_emit', *tab, b('sdf', sdf, F32, Nn), b('cell_vertex', cell_vertex, I32, Nn), b('face_mask', face_mask, I32, Nn), pv,
+          b('base', base, I32, _wgs(Nn) + 1), b('faces', faces, I32, 3 * cap), pf, b('edge', edge, I64, cap), b.ge('status', ws['status'], I32, 4))
 
 
 # ------------------------------------------------------------------ z-buffered rasterisation of a labelled mesh (csrc/mesh.hip; engine/mesh.py holds the public entry points)
@@ -1607,57 +1650,51 @@ def mesh_workspace(B, Nf, device, capacity=None):
     return {'big': torch.empty(max(cap, 1), dtype=torch.int64, device=device), 'count': torch.zeros(1, dtype=torch.int64, device=device), 'capacity': cap}
 
 
+def _mesh(b, vertices, faces):
+    """-> (vertices, Nv, faces, F): the four consecutive arguments of the entry points over a mesh of vertices fp32 [Nv, 3] and faces int32 [F, 3]"""
+    return (*b.rows3('vertices', vertices, F32), *b.rows3('faces', faces, I32))
+
+
 def mesh_raster(vertices, faces, cams, H, W, near, far, zbuf, ws, precheck=None):
     """atomicMin of every covered sample's key into zbuf int64 [B, H, W] (cleared to all ones by the caller) for the B cameras of cams fp32 [B, 16];
     ws = mesh_workspace(...)"""
-    _dev(vertices, torch.float32); _dev(faces, torch.int32); _dev(cams, torch.float32); _dev(zbuf, torch.int64); _dev(ws['big'], torch.int64); _dev(ws['count'], torch.int64)
+    b = _Operands('mesh_raster')
+    mesh, pc = _mesh(b, vertices, faces), b('cams', cams, F32, (-1, MESH_CAM_FLOATS))
     B = cams.shape[0]
-    assert vertices.is_contiguous() and vertices.dim() == 2 and vertices.shape[1] == 3 and faces.is_contiguous() and faces.dim() == 2 and faces.shape[1] == 3
-    assert cams.is_contiguous() and tuple(cams.shape) == (B, MESH_CAM_FLOATS) and zbuf.is_contiguous() and tuple(zbuf.shape) == (B, H, W)
-    assert cams.device == vertices.device == faces.device == zbuf.device == ws['big'].device == ws['count'].device
-    assert 0 <= ws['capacity'] <= ws['big'].numel() and ws['count'].numel() == 1
+    b.require(ws['capacity'] >= 0, 'the capacity of the list of large faces is not negative')
+    out = (b('zbuf', zbuf, I64, (B, H, W)), b.ge('big', ws['big'], I64, ws['capacity']), b('count', ws['count'], I64, 1))
     ws['count'].zero_()
-    _call('pst_mesh_raster', _ptr(vertices), vertices.shape[0], _ptr(faces), faces.shape[0], _ptr(cams), B, int(H), int(W), float(near), float(far), _ptr(zbuf),
-          _ptr(ws['big']), _ptr(ws['count']), ws['capacity'], int(MESH_PRECHECK if precheck is None else precheck))
+    _call('pst_mesh_raster', *mesh, pc, B, int(H), int(W), float(near), float(far), *out, ws['capacity'], int(MESH_PRECHECK if precheck is None else precheck))
 
 
 def mesh_resolve(zbuf, vertices, faces, cams, near, vertex_ids, face_ids, face, depth, pan):
     """per cell of zbuf int64 [B, H, W]: the winning face, its depth and its id (face_ids, the nearest corner's vertex_ids, or 0); an empty cell: -1, 0, 0"""
-    _dev(zbuf, torch.int64); _dev(vertices, torch.float32); _dev(faces, torch.int32); _dev(cams, torch.float32)
-    _dev(face, torch.int64); _dev(depth, torch.float32); _dev(pan, torch.int32)
-    B, H, W = zbuf.shape
-    Nv, Nf = vertices.shape[0], faces.shape[0]
-    ts = [zbuf, vertices, faces, cams, face, depth, pan]
-    for t, n in ((vertex_ids, Nv), (face_ids, Nf)):
-        if t is not None:
-            _dev(t, torch.int32)
-            assert t.numel() == n
-            ts.append(t)
-    assert all(t.is_contiguous() and t.device == zbuf.device for t in ts) and tuple(cams.shape) == (B, MESH_CAM_FLOATS)
-    assert face.numel() == depth.numel() == pan.numel() == zbuf.numel() and vertices.shape[1] == 3 and faces.shape[1] == 3
-    _call('pst_mesh_resolve', _ptr(zbuf), B, H, W, _ptr(vertices), Nv, _ptr(faces), Nf, _ptr(cams), float(near), _ptr(vertex_ids), _ptr(face_ids), _ptr(face),
-          _ptr(depth), _ptr(pan))
+    b = _Operands('mesh_resolve')
+    pz, mesh = b('zbuf', zbuf, I64, (-1, -1, -1)), _mesh(b, vertices, faces)
+    (B, H, W), n = zbuf.shape, zbuf.numel()
+    _call('pst_mesh_resolve', pz, B, H, W, *mesh, b('cams', cams, F32, (B, MESH_CAM_FLOATS)), float(near), b('vertex_ids', vertex_ids, I32, mesh[1], optional=True),
+          b('face_ids', face_ids, I32, mesh[3], optional=True), b('face', face, I64, n), b('depth', depth, F32, n), b('pan', pan, I32, n))
 
 
-def _mesh_area_args(pan, id2row, counts):
-    _dev(pan, torch.int32); _dev(id2row, torch.int32); _dev(counts, torch.int32)
-    B, S = counts.shape
-    assert pan.dim() == 3 and pan.shape[0] == B and S >= 1 and all(t.is_contiguous() and t.device == pan.device for t in (pan, id2row, counts))
-    return B, pan.shape[1] * pan.shape[2], S
+def _mesh_area_args(b, pan, id2row, counts):
+    """-> (pan, B, H W, id2row, ntab, S, counts): the seven leading arguments of the two area entry points"""
+    pp, pc = b('pan', pan, I32, (-1, -1, -1)), b('counts', counts, I32, (pan.shape[0], -1))
+    b.require(counts.shape[1] >= 1, 'counts int32 [B, S] needs S >= 1')
+    return pp, pan.shape[0], pan.shape[1] * pan.shape[2], b.ge('id2row', id2row, I32, 0), id2row.numel(), counts.shape[1], pc
 
 
 def mesh_area_count(pan, id2row, counts):
     """counts int32 [B, S] (cleared by the caller) += the pixels of pan int32 [B, H, W] per (camera, listed id)"""
-    B, hw, S = _mesh_area_args(pan, id2row, counts)
-    _call('pst_mesh_area_count', _ptr(pan), B, hw, _ptr(id2row), id2row.numel(), S, _ptr(counts))
+    _call('pst_mesh_area_count', *_mesh_area_args(_Operands('mesh_area_count'), pan, id2row, counts))
 
 
 def mesh_area_apply(pan, id2row, counts, min_area, out):
     """out = pan where the id is listed and has at least min_area pixels in its camera, else 0"""
-    B, hw, S = _mesh_area_args(pan, id2row, counts)
-    _dev(out, torch.int32)
-    assert out.is_contiguous() and out.shape == pan.shape and out.device == pan.device and out.data_ptr() != pan.data_ptr()
-    _call('pst_mesh_area_apply', _ptr(pan), B, hw, _ptr(id2row), id2row.numel(), S, _ptr(counts), int(min_area), _ptr(out))
+    b = _Operands('mesh_area_apply')
+    args = _mesh_area_args(b, pan, id2row, counts)
+    po = b('out', out, I32, tuple(pan.shape))
+    b.require(po != args[0], 'out is not pan')
+    _call('pst_mesh_area_apply', *args, int(min_area), po)
 
 
 # ------------------------------------------------------------------ panoptic evaluation (csrc/evaluate.hip; engine/evaluate.py holds the public entry point)
@@ -1668,24 +1705,22 @@ EVAL_MAX_ID = 1 << 24               # segment ids are below this (a COCO panopti
 
 def pq_count(pred, gt, slab_off, id2row_p, id2row_g, P, G, counts, merge=None):
     """counts int32 [S, P+1, G+1] (cleared by the caller) += the pixels of pred / gt int32 [N] per (slab, row, column); slab_off int64 [S + 1]"""
-    _dev(pred, torch.int32); _dev(gt, torch.int32); _dev(slab_off, torch.int64); _dev(id2row_p, torch.int32); _dev(id2row_g, torch.int32); _dev(counts, torch.int32)
-    N, S = pred.numel(), slab_off.numel() - 1
-    assert all(t.is_contiguous() and t.device == pred.device for t in (pred, gt, slab_off, id2row_p, id2row_g, counts))
-    assert gt.numel() == N and S >= 1 and tuple(counts.shape) == (S, P + 1, G + 1)
-    _call('pst_pq_count', _ptr(pred), _ptr(gt), N, _ptr(slab_off), S, _ptr(id2row_p), id2row_p.numel(), _ptr(id2row_g), id2row_g.numel(), int(P), int(G),
-          _ptr(counts), int(EVAL_MERGE if merge is None else merge))
+    b = _Operands('pq_count')
+    (pp, N), (ps, S1) = b.sized('pred', pred, I32), b.sized('slab_off', slab_off, I64, 2)
+    _call('pst_pq_count', pp, b('gt', gt, I32, N), N, ps, S1 - 1,b.ge('id2row_p', id2row_p, I32, 0), id2row_p.numel(), b.ge('id2row_g', id2row_g, I32, 0),
+          id2row_g.numel(), int(P), int(G), b('counts', counts, I32, (S1 - 1, P + 1, G + 1)), int(EVAL_MERGE if merge is None else merge))
 
 
 def pq_match(counts, cat_p, cat_g, pred_area, gt_area, match, iou, pred_state):
-    """areas, match / iou per (slab, gt column) and the state per (slab, predicted row) of a counts table [S, P+1, G+1]"""
-    _dev(counts, torch.int32); _dev(cat_p, torch.int32); _dev(cat_g, torch.int32); _dev(pred_area, torch.int32); _dev(gt_area, torch.int32)
-    _dev(match, torch.int32); _dev(iou, torch.float64); _dev(pred_state, torch.int32)
+    """areas, match / iou per (slab, gt column) and the state per (slab, predicted row) of a counts table [S, P+1, G+1]; an operand of P (or G) rows
+    is NULL when P (or G) is 0"""
+    b = _Operands('pq_match')
+    pc = b('counts', counts, I32, (-1, -1, -1))
     S, P, G = counts.shape[0], counts.shape[1] - 1, counts.shape[2] - 1
-    assert all(t.is_contiguous() and t.device == counts.device for t in (counts, cat_p, cat_g, pred_area, gt_area, match, iou, pred_state))
-    assert cat_p.numel() == P and cat_g.numel() == G and tuple(pred_area.shape) == tuple(pred_state.shape) == (S, P)
-    assert tuple(gt_area.shape) == tuple(match.shape) == tuple(iou.shape) == (S, G)
-    nz = lambda t: _ptr(t) if t.numel() else None
-    _call('pst_pq_match', _ptr(counts), S, P, G, nz(cat_p), nz(cat_g), nz(pred_area), nz(gt_area), nz(match), nz(iou), nz(pred_state))
+    nz = lambda p, rows: p if rows else None
+    _call('pst_pq_match', pc, S, P, G, nz(b('cat_p', cat_p, I32, P), P), nz(b('cat_g', cat_g, I32, G), G), nz(b('pred_area', pred_area, I32, (S, P)), S * P),
+          nz(b('gt_area', gt_area, I32, (S, G)), S * G), nz(b('match', match, I32, (S, G)), S * G), nz(b('iou', iou, F64, (S, G)), S * G),
+          nz(b('pred_state', pred_state, I32, (S, P)), S * P))
 
 
 # ------------------------------------------------------------------ surface mesh of the pointmap grids (csrc/surface.hip; engine/surface.py holds the public entry points)
@@ -1698,38 +1733,37 @@ def surface_dims(shapes, device):
     rows, wg = [], 0
     for H, W in shapes:
         rows.append((int(H), int(W), wg, 0))
-        wg += (max(H - 1, 0) * max(W - 1, 0) + SURFACE_WG - 1) // SURFACE_WG
+        wg += _wgs(max(H - 1, 0) * max(W - 1, 0), SURFACE_WG)
     return torch.tensor(rows, dtype=torch.int32).reshape(-1, 4).to(device), wg
 
 
 def surface_rows(index, N, row):
     """row int32 [N]: the cloud row of every scene pixel (index int64 [M] of the cloud), -1 for a pixel that was filtered out"""
-    _dev(index, torch.int64); _dev(row, torch.int32)
-    assert index.is_contiguous() and row.is_contiguous() and row.numel() == N and index.numel() <= N
-    _call('pst_surface_rows', _ptr(index) if index.numel() else None, index.numel(), N, _ptr(row))
+    b = _Operands('surface_rows')
+    pi = b.ge('index', index, I64, 0)
+    b.require(index.numel() <= N, 'index holds %d rows of a scene of %d pixels', index.numel(), N)
+    _call('pst_surface_rows', pi if index.numel() else None, index.numel(), N, b('row', row, I32, N))
 
 
-def _surface_quads(table, dims, nviews, nwg, row):
-    _dev(table, torch.uint8); _dev(dims, torch.int32); _dev(row, torch.int32)
-    assert table.numel() == nviews * C.sizeof(CloudView) and dims.is_contiguous() and tuple(dims.shape) == (nviews, 4) and row.is_contiguous() and nwg > 0
+def _surface_quads(b, table, dims, nviews, nwg, row):
+    """-> (table, dims, nviews, nwg, row): the five leading arguments of the quad entry points; row int32 [N] over the pixels the view table counts"""
+    b.require(nwg > 0, 'a scene without quads')
+    return b('table', table, U8, nviews * _VIEW_BYTES), b('dims', dims, I32, (nviews, 4)), nviews, nwg, b.ge('row', row, I32, 1)
 
 
 def surface_count(table, dims, nviews, nwg, row, k, counts):
     """counts int32 [nwg]: the faces of every workgroup's quads (table: the cloud's view table, dims: `surface_dims`, k = float32(1 + max_depth_ratio) or inf)"""
-    _surface_quads(table, dims, nviews, nwg, row)
-    _dev(counts, torch.int32)
-    assert counts.numel() == nwg
-    _call('pst_surface_count', _ptr(table), _ptr(dims), nviews, nwg, _ptr(row), float(k), _ptr(counts))
+    b = _Operands('surface_count')
+    _call('pst_surface_count', *_surface_quads(b, table, dims, nviews, nwg, row), float(k), b('counts', counts, I32, nwg))
 
 
 def surface_emit(table, dims, nviews, nwg, row, k, vertex_ids, base, faces, face_ids, quad):
-    """faces int32 [., 3], face_ids int32 [.], quad int64 [.]: rows [0, base[nwg]) are written; each holds two rows per quad of the scene"""
-    _surface_quads(table, dims, nviews, nwg, row)
-    _dev(vertex_ids, torch.int32); _dev(base, torch.int32); _dev(faces, torch.int32); _dev(face_ids, torch.int32); _dev(quad, torch.int64)
-    cap = face_ids.numel()
-    assert base.numel() == nwg + 1 and cap >= 2 * SURFACE_WG * nwg and quad.numel() == cap and faces.numel() == 3 * cap
-    assert all(t.is_contiguous() for t in (vertex_ids, faces, face_ids, quad))
-    _call('pst_surface_emit', _ptr(table), _ptr(dims), nviews, nwg, _ptr(row), float(k), _ptr(vertex_ids), _ptr(base), _ptr(faces), _ptr(face_ids), _ptr(quad))
+    """faces int32 [., 3], face_ids int32 [.], quad int64 [.]: rows [0, base[nwg]) are written; each holds two rows per quad of the scene; vertex_ids
+    int32 holds the cloud's rows, which `row` names"""
+    b = _Operands('surface_emit')
+    quads, (pf, cap) = _surface_quads(b, table, dims, nviews, nwg, row), b.sized('face_ids', face_ids, I32, 2 * SURFACE_WG * nwg)
+    _call('pst_surface_emit', *quads, float(k), b.ge('vertex_ids', vertex_ids, I32, 1), b('base', base, I32, nwg + 1), b('faces', faces, I32, 3 * cap), pf,
+          b('quad', quad, I64, cap))
 
 
 def surface_workspace(M, device):
@@ -1738,44 +1772,41 @@ def surface_workspace(M, device):
             'status': torch.zeros(1, dtype=torch.int32, device=device)}
 
 
-def _surface_faces(faces, ws):
-    _dev(faces, torch.int32)
-    F, M = faces.shape[0], ws['parent'].numel()
-    assert faces.is_contiguous() and tuple(faces.shape) == (F, 3) and F > 0 and M > 0 and ws['size'].numel() == M
-    return F, M
+def _surface_faces(b, faces, ws):
+    """-> (faces, F, M): the three leading arguments of the island entry points over faces int32 [F, 3] on M vertex rows"""
+    pf, F = b.rows3('faces', faces, I32)
+    b.require(F > 0 and ws['parent'].numel() > 0, 'a mesh without faces or vertex rows')
+    return pf, F, ws['parent'].numel()
 
 
 def surface_link(faces, ws):
-    F, M = _surface_faces(faces, ws)
-    _call('pst_surface_link', _ptr(faces), F, M, _ptr(ws['parent']), _ptr(ws['size']), _ptr(ws['status']))
+    b = _Operands('surface_link')
+    mesh = _surface_faces(b, faces, ws)
+    _call('pst_surface_link', *mesh, b('parent', ws['parent'], I32, mesh[2]), b('size', ws['size'], I32, mesh[2]), b.ge('status', ws['status'], I32, 1))
 
 
 def surface_components(faces, ws, component):
     """component int32 [F] = the smallest vertex row of every face's component; ws['size'][root] = the component's faces"""
-    F, M = _surface_faces(faces, ws)
-    _dev(component, torch.int32)
-    assert component.is_contiguous() and component.numel() == F
-    _call('pst_surface_components', _ptr(faces), F, M, _ptr(ws['parent']), _ptr(component), _ptr(ws['size']), _ptr(ws['status']))
+    b = _Operands('surface_components')
+    mesh = _surface_faces(b, faces, ws)
+    _call('pst_surface_components', *mesh, b('parent', ws['parent'], I32, mesh[2]), b('component', component, I32, mesh[1]), b('size', ws['size'], I32, mesh[2]),
+          b.ge('status', ws['status'], I32, 1))
 
 
 def surface_keep_count(component, ws, min_faces, counts):
-    _dev(component, torch.int32); _dev(counts, torch.int32)
-    F = component.numel()
-    assert counts.numel() == (F + SURFACE_WG - 1) // SURFACE_WG
-    _call('pst_surface_keep_count', _ptr(component), _ptr(ws['size']), F, int(min_faces), _ptr(counts))
+    """ws['size'] int32 [M] is read at the roots `component` names: the entry point does not take M"""
+    b = _Operands('surface_keep_count')
+    pc, F = b.sized('component', component, I32)
+    _call('pst_surface_keep_count', pc, b.ge('size', ws['size'], I32, 1), F, int(min_faces), b('counts', counts, I32, _wgs(F, SURFACE_WG)))
 
 
 def surface_keep_emit(faces, face_ids, quad, component, ws, min_faces, base, out_faces, out_face_ids, out_quad):
     """the faces whose component has at least min_faces faces, in their order -> rows [0, base[-1]) of the outputs (each as long as its input)"""
-    F, _ = _surface_faces(faces, ws)
-    for t, dt in ((face_ids, torch.int32), (quad, torch.int64), (component, torch.int32), (base, torch.int32), (out_faces, torch.int32),
-                  (out_face_ids, torch.int32), (out_quad, torch.int64)):
-        _dev(t, dt)
-        assert t.is_contiguous()
-    assert face_ids.numel() == quad.numel() == component.numel() == out_face_ids.numel() == out_quad.numel() == F and out_faces.numel() == 3 * F
-    assert base.numel() == (F + SURFACE_WG - 1) // SURFACE_WG + 1
-    _call('pst_surface_keep_emit', _ptr(faces), _ptr(face_ids), _ptr(quad), _ptr(component), _ptr(ws['size']), F, int(min_faces), _ptr(base), _ptr(out_faces),
-          _ptr(out_face_ids), _ptr(out_quad))
+    b = _Operands('surface_keep_emit')
+    pf, F, M = _surface_faces(b, faces, ws)
+    _call('pst_surface_keep_emit', pf, b('face_ids', face_ids, I32, F), b('quad', quad, I64, F), b('component', component, I32, F), b('size', ws['size'], I32, M), F,
+          int(min_faces), b('base', base, I32, _wgs(F, SURFACE_WG) + 1), b('out_faces', out_faces, I32, 3 * F), b('out_face_ids', out_face_ids, I32, F),
+          b('out_quad', out_quad, I64, F))
 
 
 # ------------------------------------------------------------------ 3-D scores: mesh surface sampler and fixed-radius nearest neighbour (csrc/nearest.hip; engine/score3d.py holds the public entry points)
@@ -1786,32 +1817,19 @@ NN_FULL, NN_LISTS = 1, 2            # PST_NN_*: the bits of the search's status[
 NN_MAX_POINTS = 1 << 30
 
 
-def _mesh_sample_mesh(vertices, faces):
-    _dev(vertices, torch.float32); _dev(faces, torch.int32)
-    assert vertices.is_contiguous() and faces.is_contiguous() and vertices.dim() == 2 and vertices.shape[1] == 3 and faces.dim() == 2 and faces.shape[1] == 3
-    return vertices.shape[0], faces.shape[0]
-
-
 def mesh_sample_count(vertices, faces, spacing, max_subdiv, counts, total, status):
     """counts int32 [F]; total int64 [1] and status int32 [4] zeroed by the caller (include/panst3r_hip.h)"""
-    Nv, F = _mesh_sample_mesh(vertices, faces)
-    _dev(counts, torch.int32); _dev(total, torch.int64); _dev(status, torch.int32)
-    assert counts.numel() == F and total.numel() == 1 and status.numel() == 4
-    _call('pst_mesh_sample_count', _ptr(vertices), Nv, _ptr(faces), F, float(spacing), int(max_subdiv), _ptr(counts), _ptr(total), _ptr(status))
+    b = _Operands('mesh_sample_count')
+    mesh = _mesh(b, vertices, faces)
+    _call('pst_mesh_sample_count', *mesh, float(spacing), int(max_subdiv), b('counts', counts, I32, mesh[3]), b('total', total, I64, 1), b('status', status, I32, 4))
 
 
 def mesh_sample_emit(vertices, faces, prefix, total, vertex_ids, face_ids, points, face, ids, status):
     """the outputs' rows are the capacity: a `total` beyond them is refused before the launch"""
-    Nv, F = _mesh_sample_mesh(vertices, faces)
-    _dev(prefix, torch.int32); _dev(points, torch.float32); _dev(face, torch.int32); _dev(ids, torch.int32); _dev(status, torch.int32)
-    capacity = face.numel()
-    assert prefix.numel() == F + 1 and points.is_contiguous() and points.numel() == 3 * capacity and ids.numel() == capacity and status.numel() == 4
-    for t, n in ((vertex_ids, Nv), (face_ids, F)):
-        if t is not None:
-            _dev(t, torch.int32)
-            assert t.is_contiguous() and t.numel() == n
-    _call('pst_mesh_sample_emit', _ptr(vertices), Nv, _ptr(faces), F, _ptr(prefix), int(total), capacity, _ptr(vertex_ids), _ptr(face_ids), _ptr(points),
-          _ptr(face), _ptr(ids), _ptr(status))
+    b = _Operands('mesh_sample_emit')
+    (pv, Nv, pf, F), (pface, capacity) = _mesh(b, vertices, faces), b.sized('face', face, I32)
+    _call('pst_mesh_sample_emit', pv, Nv, pf, F, b('prefix', prefix, I32, F + 1), int(total), capacity, b('vertex_ids', vertex_ids, I32, Nv, optional=True),
+          b('face_ids', face_ids, I32, F, optional=True), b('points', points, F32, 3 * capacity), pface, b('ids', ids, I32, capacity), b('status', status, I32, 4))
 
 
 def _lists_workspace(n, device, slot_name):
@@ -1822,55 +1840,63 @@ def _lists_workspace(n, device, slot_name):
             'fill': torch.zeros(cap, **i32), slot_name: torch.empty(n, **i32), 'rows': torch.empty(n, **i32)}
 
 
+def _lists(b, ws, n):
+    """-> (keys, cap, start, cell_count, rows): the five consecutive arguments of the entry points that search the built lists `ws` of n entries"""
+    return (b.ge('keys', ws['keys'], I64, ws['cap']), ws['cap'], b.ge('start', ws['start'], I32, ws['cap']),
+            b.ge('cell_count', ws['cell_count'], I32, ws['cap']), b('rows', ws['rows'], I32, n))
+
+
 def nn_workspace(M, device):
     """the initialised workspaces of one search structure over M targets (include/panst3r_hip.h): dict of device tensors"""
     return dict(_lists_workspace(M, device, 'point_slot'), status=torch.zeros(4, dtype=torch.int32, device=device))
 
 
-def _nn_points(points):
-    _dev(points, torch.float32)
-    assert points.is_contiguous() and points.dim() == 2 and points.shape[1] == 3
-    return points.shape[0]
-
-
 def nn_insert(targets, inv, ws):
-    M = _nn_points(targets)
-    assert ws['point_slot'].numel() == M and ws['keys'].numel() == ws['cap'] == ws['cell_count'].numel()
-    _call('pst_nn_insert', _ptr(targets), M, float(inv), _ptr(ws['keys']), ws['cap'], _ptr(ws['cell_count']), _ptr(ws['point_slot']), _ptr(ws['status']))
+    b = _Operands('nn_insert')
+    tg = b.rows3('targets', targets, F32)
+    _call('pst_nn_insert', *tg, float(inv), b('keys', ws['keys'], I64, ws['cap']), ws['cap'], b('cell_count', ws['cell_count'], I32, ws['cap']),
+          b('point_slot', ws['point_slot'], I32, tg[1]), b.ge('status', ws['status'], I32, 4))
 
 
 def nn_scatter(ws):
     """ws['start'] = the exclusive prefix sum of ws['cell_count'] (int32 [cap]), made by the caller"""
-    M = ws['point_slot'].numel()
-    _dev(ws['start'], torch.int32)
-    assert ws['start'].is_contiguous() and ws['start'].numel() == ws['cap'] == ws['fill'].numel() and ws['rows'].numel() == M
-    _call('pst_nn_scatter', _ptr(ws['point_slot']), M, _ptr(ws['start']), _ptr(ws['cell_count']), _ptr(ws['fill']), _ptr(ws['rows']), _ptr(ws['status']))
+    b = _Operands('nn_scatter')
+    M, cap = ws['point_slot'].numel(), ws['cap']
+    _call('pst_nn_scatter', b('point_slot', ws['point_slot'], I32, M), M, b('start', ws['start'], I32, cap), b.ge('cell_count', ws['cell_count'], I32, cap),
+          b('fill', ws['fill'], I32, cap), b('rows', ws['rows'], I32, M), b.ge('status', ws['status'], I32, 4))
 
 
 def nn_query(queries, targets, inv, r2, ws, max_cell_points, d2, row):
-    Nq, M = _nn_points(queries), _nn_points(targets)
-    _dev(d2, torch.float32); _dev(row, torch.int32)
-    assert ws['rows'].numel() == M and d2.numel() == Nq and row.numel() == Nq and d2.is_contiguous() and row.is_contiguous()
-    _call('pst_nn_query', _ptr(queries), Nq, _ptr(targets), M, float(inv), float(r2), _ptr(ws['keys']), ws['cap'], _ptr(ws['start']), _ptr(ws['cell_count']),
-          _ptr(ws['rows']), int(max_cell_points), _ptr(d2), _ptr(row), _ptr(ws['status']))
+    b = _Operands('nn_query')
+    q, tg = b.rows3('queries', queries, F32), b.rows3('targets', targets, F32)
+    keys, cap, start, cell_count, rows = _lists(b, ws, tg[1])
+    _call('pst_nn_query', *q, *tg, float(inv), float(r2), keys, cap, start, cell_count, rows, int(max_cell_points), b('d2', d2, F32, q[1]), b('row', row, I32, q[1]),
+          b.ge('status', ws['status'], I32, 4))
 
 
 # ------------------------------------------------------------------ one fused ICP step (csrc/nearest.hip; engine/score3d.py's icp / refine_alignment)
 ICP_CHUNK, ICP_LANES, ICP_MOMENTS = 4096, 256, 20      # PST_ICP_CHUNK, PST_ICP_LANES, PST_ICP_MOMENTS: the fixed order of the sums (tests/icp_ref.py reads them here)
 
 
-def icp_workspace(N, device):
+def icp_workspace(N, device, moments=ICP_MOMENTS):
     """the workspaces of `icp_step` over N source points: partials double [ceil(N / ICP_CHUNK), 20], out double [20], status int32 [4] (zeroed here;
     the caller clears it between steps if it reads it per step)"""
-    return {'N': int(N), 'partials': torch.empty((int(N) + ICP_CHUNK - 1) // ICP_CHUNK, ICP_MOMENTS, dtype=torch.float64, device=device),
-            'out': torch.empty(ICP_MOMENTS, dtype=torch.float64, device=device), 'status': torch.zeros(4, dtype=torch.int32, device=device)}
+    return {'N': int(N), 'partials': torch.empty(_wgs(int(N), ICP_CHUNK), moments, dtype=torch.float64, device=device),
+            'out': torch.empty(moments, dtype=torch.float64, device=device), 'status': torch.zeros(4, dtype=torch.int32, device=device)}
+
+
+def _icp_sums(b, iws, N, moments):
+    """-> (partials, out, status): the three trailing arguments of the two ICP steps over N source points, `moments` doubles per row"""
+    b.require(iws['N'] == N, 'the workspace is one of %d source points, the call has %d', iws['N'], N)
+    return (b('partials', iws['partials'], F64, _wgs(N, ICP_CHUNK) * moments), b('out', iws['out'], F64, moments), b('status', iws['status'], I32, 4))
 
 
 def icp_step(source, A, targets, inv, cell_r2, r2, ws, max_cell_points, iws, d2=None, row=None):
     """one fused ICP step (include/panst3r_hip.h): `source` moved by the 3 x 4 matrix A (12 numbers, rounded to fp32 here), searched in the built
     structure `ws` of `targets` (cell edge 1 / inv, cell_r2 = its squared edge), accepted within r2 <= cell_r2 -> iws['out'] double [20]; d2 / row
     [N] are written when given (both or neither).  A larger r2 raises ValueError: the 27 cells would not hold every match."""
-    N, M = _nn_points(source), _nn_points(targets)
+    b = _Operands('icp_step')
+    src, tg = b.rows3('source', source, F32), b.rows3('targets', targets, F32)
     A = [float(a) for a in (A.reshape(-1).tolist() if hasattr(A, 'reshape') else A)]
     if len(A) != 12:
         raise ValueError('icp_step takes a 3 x 4 matrix, got %d numbers' % len(A))
@@ -1878,14 +1904,10 @@ def icp_step(source, A, targets, inv, cell_r2, r2, ws, max_cell_points, iws, d2=
         raise ValueError('icp_step: the squared radius %g exceeds the squared cell edge %g of the search structure' % (r2, cell_r2))
     if (d2 is None) != (row is None):
         raise ValueError('icp_step: d2 and row go together')
-    if d2 is not None:
-        _dev(d2, torch.float32); _dev(row, torch.int32)
-        assert d2.numel() == N and row.numel() == N and d2.is_contiguous() and row.is_contiguous()
-    _dev(iws['partials'], torch.float64); _dev(iws['out'], torch.float64); _dev(iws['status'], torch.int32)
-    assert lib().pst_icp_chunk() == ICP_CHUNK and iws['N'] == N and iws['partials'].numel() == (N + ICP_CHUNK - 1) // ICP_CHUNK * ICP_MOMENTS
-    assert ws['rows'].numel() == M and iws['out'].numel() == ICP_MOMENTS and iws['status'].numel() == 4
-    _call('pst_icp_step', _ptr(source), N, *A, _ptr(targets), M, float(inv), float(r2), _ptr(ws['keys']), ws['cap'], _ptr(ws['start']),
-          _ptr(ws['cell_count']), _ptr(ws['rows']), int(max_cell_points), _ptr(d2), _ptr(row), _ptr(iws['partials']), _ptr(iws['out']), _ptr(iws['status']))
+    b.require(lib().pst_icp_chunk() == ICP_CHUNK, 'the library does not sum in the chunks of %d the workspaces are made for', ICP_CHUNK)
+    keys, cap, start, cell_count, rows = _lists(b, ws, tg[1])
+    _call('pst_icp_step', *src, *A, *tg, float(inv), float(r2), keys, cap, start, cell_count, rows, int(max_cell_points),
+          b('d2', d2, F32, src[1], optional=True), b('row', row, I32, src[1], optional=True), *_icp_sums(b, iws, src[1], ICP_MOMENTS))
     return iws['out']
 
 
@@ -1897,10 +1919,9 @@ MESHDIST_MAX = 1 << 30                                       # queries, faces an
 
 def meshdist_count(vertices, faces, inv, counts, total, status):
     """counts int32 [F]; total int64 [1] and status int32 [4] zeroed by the caller (include/panst3r_hip.h)"""
-    Nv, F = _mesh_sample_mesh(vertices, faces)
-    _dev(counts, torch.int32); _dev(total, torch.int64); _dev(status, torch.int32)
-    assert counts.numel() == F and total.numel() == 1 and status.numel() == 4
-    _call('pst_meshdist_count', _ptr(vertices), Nv, _ptr(faces), F, float(inv), _ptr(counts), _ptr(total), _ptr(status))
+    b = _Operands('meshdist_count')
+    mesh = _mesh(b, vertices, faces)
+    _call('pst_meshdist_count', *mesh, float(inv), b('counts', counts, I32, mesh[3]), b('total', total, I64, 1), b('status', status, I32, 4))
 
 
 def meshdist_workspace(P, device):
@@ -1910,32 +1931,26 @@ def meshdist_workspace(P, device):
 
 def meshdist_insert(vertices, faces, inv, prefix, ws, status):
     """the workspaces' rows are `total`: a prefix that ends elsewhere sets MESHDIST_TOTAL and nothing is written"""
-    Nv, F = _mesh_sample_mesh(vertices, faces)
-    _dev(prefix, torch.int32); _dev(status, torch.int32)
-    assert prefix.numel() == F + 1 and status.numel() == 4 and ws['pair_slot'].numel() == ws['P'] and ws['keys'].numel() == ws['cap'] == ws['cell_count'].numel()
-    _call('pst_meshdist_insert', _ptr(vertices), Nv, _ptr(faces), F, float(inv), _ptr(prefix), ws['P'], _ptr(ws['keys']), ws['cap'], _ptr(ws['cell_count']),
-          _ptr(ws['pair_slot']), _ptr(status))
+    b = _Operands('meshdist_insert')
+    mesh = _mesh(b, vertices, faces)
+    _call('pst_meshdist_insert', *mesh, float(inv), b('prefix', prefix, I32, mesh[3] + 1), ws['P'], b('keys', ws['keys'], I64, ws['cap']), ws['cap'],
+          b('cell_count', ws['cell_count'], I32, ws['cap']), b('pair_slot', ws['pair_slot'], I32, ws['P']), b('status', status, I32, 4))
 
 
 def meshdist_scatter(prefix, ws, status):
     """ws['start'] = the exclusive prefix sum of ws['cell_count'] (int32 [cap]), made by the caller"""
-    _dev(prefix, torch.int32); _dev(ws['start'], torch.int32); _dev(status, torch.int32)
-    assert ws['start'].is_contiguous() and ws['start'].numel() == ws['cap'] == ws['fill'].numel() and ws['rows'].numel() == ws['P'] and status.numel() == 4
-    _call('pst_meshdist_scatter', _ptr(ws['pair_slot']), _ptr(prefix), prefix.numel() - 1, ws['P'], _ptr(ws['start']), _ptr(ws['cell_count']), _ptr(ws['fill']),
-          _ptr(ws['rows']), _ptr(status))
+    b = _Operands('meshdist_scatter')
+    pp, P, cap = b.ge('prefix', prefix, I32, 1), ws['P'], ws['cap']
+    _call('pst_meshdist_scatter', b.ge('pair_slot', ws['pair_slot'], I32, P), pp, prefix.numel() - 1, P, b('start', ws['start'], I32, cap),
+          b.ge('cell_count', ws['cell_count'], I32, cap), b('fill', ws['fill'], I32, cap), b('rows', ws['rows'], I32, P), b('status', status, I32, 4))
 
 
 def meshdist_query(queries, vertices, faces, inv, r2, ws, max_cell_faces, d2, face, closest, status):
     """d2 fp32 [Nq], face int32 [Nq], closest fp32 [Nq, 3] or None"""
-    Nq = _nn_points(queries)
-    Nv, F = _mesh_sample_mesh(vertices, faces)
-    _dev(d2, torch.float32); _dev(face, torch.int32); _dev(status, torch.int32)
-    assert d2.numel() == Nq and face.numel() == Nq and d2.is_contiguous() and face.is_contiguous() and status.numel() == 4 and ws['rows'].numel() == ws['P']
-    if closest is not None:
-        _dev(closest, torch.float32)
-        assert closest.is_contiguous() and closest.numel() == 3 * Nq
-    _call('pst_meshdist_query', _ptr(queries), Nq, _ptr(vertices), Nv, _ptr(faces), F, float(inv), float(r2), _ptr(ws['keys']), ws['cap'], _ptr(ws['start']),
-          _ptr(ws['cell_count']), _ptr(ws['rows']), ws['P'], int(max_cell_faces), _ptr(d2), _ptr(face), _ptr(closest), _ptr(status))
+    b = _Operands('meshdist_query')
+    q, mesh = b.rows3('queries', queries, F32), _mesh(b, vertices, faces)
+    _call('pst_meshdist_query', *q, *mesh, float(inv), float(r2), *_lists(b, ws, ws['P']), ws['P'], int(max_cell_faces), b('d2', d2, F32, q[1]),
+          b('face', face, I32, q[1]), b('closest', closest, F32, 3 * q[1], optional=True), b('status', status, I32, 4))
 
 
 # ------------------------------------------------------------------ one fused point-to-plane ICP step against the triangles (csrc/meshdist.hip; engine/meshdist.py's icp_to_mesh)
@@ -1943,10 +1958,8 @@ ICP_PLANE_MOMENTS = 40      # PST_ICP_PLANE_MOMENTS: doubles per row of partials
 
 
 def icp_plane_workspace(N, device):
-    """the workspaces of `icp_plane_step` over N source points: partials double [ceil(N / ICP_CHUNK), 40], out double [40], status int32 [4] (zeroed
-    here; the caller clears it between steps if it reads it per step)"""
-    return {'N': int(N), 'partials': torch.empty((int(N) + ICP_CHUNK - 1) // ICP_CHUNK, ICP_PLANE_MOMENTS, dtype=torch.float64, device=device),
-            'out': torch.empty(ICP_PLANE_MOMENTS, dtype=torch.float64, device=device), 'status': torch.zeros(4, dtype=torch.int32, device=device)}
+    """the workspaces of `icp_plane_step` over N source points: `icp_workspace` with 40 doubles per row of partials and in out"""
+    return icp_workspace(N, device, ICP_PLANE_MOMENTS)
 
 
 def icp_plane_step(source, A, c0, vertices, faces, inv, cell_r2, r2, ws, max_cell_faces, iws, d2=None, face=None):
@@ -1954,8 +1967,8 @@ def icp_plane_step(source, A, c0, vertices, faces, inv, cell_r2, r2, ws, max_cel
     built lists `ws` of the mesh (cell edge 1 / inv, cell_r2 = its squared edge), accepted within r2 <= cell_r2, the normal equations about the centre
     c0 (3 numbers) -> iws['out'] double [40]; d2 / face [N] are written when given (both or neither).  A larger r2 raises ValueError: the lists
     would not hold every match."""
-    N = _nn_points(source)
-    Nv, F = _mesh_sample_mesh(vertices, faces)
+    b = _Operands('icp_plane_step')
+    src, mesh = b.rows3('source', source, F32), _mesh(b, vertices, faces)
     A = [float(a) for a in (A.reshape(-1).tolist() if hasattr(A, 'reshape') else A)]
     c0 = [float(c) for c in (c0.reshape(-1).tolist() if hasattr(c0, 'reshape') else c0)]
     if len(A) != 12 or len(c0) != 3:
@@ -1964,15 +1977,8 @@ def icp_plane_step(source, A, c0, vertices, faces, inv, cell_r2, r2, ws, max_cel
         raise ValueError('icp_plane_step: the squared radius %g exceeds the squared cell edge %g of the search structure' % (r2, cell_r2))
     if (d2 is None) != (face is None):
         raise ValueError('icp_plane_step: d2 and face go together')
-    if d2 is not None:
-        _dev(d2, torch.float32); _dev(face, torch.int32)
-        assert d2.numel() == N and face.numel() == N and d2.is_contiguous() and face.is_contiguous()
-    _dev(iws['partials'], torch.float64); _dev(iws['out'], torch.float64); _dev(iws['status'], torch.int32)
-    assert iws['N'] == N and iws['partials'].numel() == (N + ICP_CHUNK - 1) // ICP_CHUNK * ICP_PLANE_MOMENTS and iws['partials'].is_contiguous()
-    assert ws['rows'].numel() == ws['P'] and iws['out'].numel() == ICP_PLANE_MOMENTS and iws['status'].numel() == 4
-    _call('pst_plane_icp_step', _ptr(source), N, *A, *c0, _ptr(vertices), Nv, _ptr(faces), F, float(inv), float(r2), _ptr(ws['keys']), ws['cap'],
-          _ptr(ws['start']), _ptr(ws['cell_count']), _ptr(ws['rows']), ws['P'], int(max_cell_faces), _ptr(d2), _ptr(face), _ptr(iws['partials']),
-          _ptr(iws['out']), _ptr(iws['status']))
+    _call('pst_plane_icp_step', *src, *A, *c0, *mesh, float(inv), float(r2), *_lists(b, ws, ws['P']), ws['P'], int(max_cell_faces),
+          b('d2', d2, F32, src[1], optional=True), b('face', face, I32, src[1], optional=True), *_icp_sums(b, iws, src[1], ICP_PLANE_MOMENTS))
     return iws['out']
 
 
@@ -1999,33 +2005,34 @@ class DepthTable:
         blob = torch.from_numpy(np.concatenate([self.host.reshape(-1), np.array(edges, dtype=np.int64)])).to(device)      # one copy
         self.dev, self.slab_rows = blob[:self.host.size], blob[self.host.size:].to(torch.int32)
 
-    def _args(self):
-        return self.dev.data_ptr(), self.host.ctypes.data, self.nviews, self.nblocks
+    def _args(self, b):
+        """the four leading arguments of the entry points"""
+        return b('views', self.dev, I64, self.nviews * DEPTH_VIEW_WORDS), self.host.ctypes.data, self.nviews, self.nblocks
 
 
 def depth_table(views, slabs, device):
     """views = [(pred, stride, gt, conf or None)]: fp32 device tensors, pred read at the element stride `stride` from its first element, gt and conf
     contiguous; slabs = the slab of every view, ascending from 0 by steps of 0 or 1 -> DepthTable"""
     rows, keep = [], []
+    b = _Operands('depth_table')
     for pred, stride, gt, conf in views:
-        for t in (pred, gt) + ((conf,) if conf is not None else ()):
-            _dev(t, torch.float32)
-            assert t.device == pred.device
-        assert gt.is_contiguous() and (conf is None or (conf.is_contiguous() and conf.numel() == gt.numel()))
-        rows.append((pred.data_ptr(), int(stride), gt.data_ptr(), None if conf is None else conf.data_ptr(), gt.numel()))
+        pp, (pg, npix) = b('pred', pred, F32, 1, True, layout='any'), b.sized('gt', gt, F32)
+        reach = pred.untyped_storage().nbytes() // pred.element_size() - pred.storage_offset()
+        b.require(int(stride) >= 1 and reach >= (npix - 1) * int(stride) + 1, 'pred is read at %d elements with the stride %s from its first element: '
+                  'its storage holds %d from there', npix, stride, reach)
+        rows.append((pp, int(stride), pg, b('conf', conf, F32, npix, optional=True), npix))
         keep += [pred, gt, conf]
     return DepthTable(rows, [int(s) for s in slabs], device, keep)
 
 
 def depth_median(table, min_depth, max_depth, conf_thr, count, median):
     """count int32 [S], median fp32 [S, 2] = the exact medians (of pred, of gt) over the valid pixels of every slab"""
-    _dev(count, torch.int32); _dev(median, torch.float32)
-    S = table.nslabs
-    assert count.numel() == S and median.numel() == 2 * S and median.is_contiguous()
+    b = _Operands('depth_median')
+    S, pc = table.nslabs, b('count', count, I32, table.nslabs)
     ws = torch.zeros(S * (2 * 2 * 256 + 4 + 4), dtype=torch.int32, device=count.device)
     hist, prefix, rank = ws[:S * 1024], ws[S * 1024:S * 1028], ws[S * 1028:]
-    _call('pst_depth_median', *table._args(), S, float(min_depth), float(max_depth), float(conf_thr), _ptr(hist), _ptr(prefix), _ptr(rank), _ptr(count),
-          _ptr(median))
+    _call('pst_depth_median', *table._args(b), S, float(min_depth), float(max_depth), float(conf_thr), b('hist', hist, I32, 1024 * S), b('prefix', prefix, I32, 4 * S),
+          b('rank', rank, I32, 4 * S), pc, b('median', median, F32, 2 * S))
 
 
 def depth_workspace(table, device):
@@ -2034,24 +2041,17 @@ def depth_workspace(table, device):
             'out': torch.empty(table.nslabs, DEPTH_MOMENTS, dtype=torch.float64, device=device)}
 
 
-def _depth_ws(table, ws):
-    _dev(ws['partials'], torch.float64); _dev(ws['out'], torch.float64)
-    assert ws['partials'].numel() == table.nblocks * DEPTH_MOMENTS and ws['out'].numel() == table.nslabs * DEPTH_MOMENTS
-    assert ws['partials'].is_contiguous() and ws['out'].is_contiguous() and table.slab_rows.numel() == table.nslabs + 1
-
-
 def depth_moments(table, min_depth, max_depth, conf_thr, ws):
     """ws['out'][s, :5] = n, sum p, sum g, sum pp, sum pg over the valid pixels of slab s, in the fixed order of the contract"""
-    _depth_ws(table, ws)
-    _call('pst_depth_moments', *table._args(), _ptr(table.slab_rows), table.nslabs, float(min_depth), float(max_depth), float(conf_thr), _ptr(ws['partials']),
-          _ptr(ws['out']))
+    b = _Operands('depth_moments')
+    _call('pst_depth_moments', *table._args(b), b('slab_rows', table.slab_rows, I32, table.nslabs + 1), table.nslabs, float(min_depth), float(max_depth),
+          float(conf_thr), b('partials', ws['partials'], F64, table.nblocks * DEPTH_MOMENTS), b('out', ws['out'], F64, table.nslabs * DEPTH_MOMENTS))
 
 
 def depth_errors(table, min_depth, max_depth, conf_thr, align, thresholds, ws):
     """ws['out'][s, :5 + K] = n, sum |d|/g, sum dd/g, sum dd, sum |d| and the inlier counts of the K thresholds under p' = align[s, 0] p + align[s, 1]"""
-    _depth_ws(table, ws)
-    _dev(align, torch.float64)
+    b = _Operands('depth_errors')
     t = [float(x) for x in thresholds]
-    assert align.is_contiguous() and align.numel() == 2 * table.nslabs
-    _call('pst_depth_errors', *table._args(), _ptr(table.slab_rows), table.nslabs, float(min_depth), float(max_depth), float(conf_thr), _ptr(align), len(t),
-          *(t + [0.0] * DEPTH_MAX_THRESHOLDS)[:DEPTH_MAX_THRESHOLDS], _ptr(ws['partials']), _ptr(ws['out']))      # (K > 4 is the library's refusal)
+    _call('pst_depth_errors', *table._args(b), b('slab_rows', table.slab_rows, I32, table.nslabs + 1), table.nslabs, float(min_depth), float(max_depth),
+          float(conf_thr), b('align', align, F64, 2 * table.nslabs), len(t), *(t + [0.0] * DEPTH_MAX_THRESHOLDS)[:DEPTH_MAX_THRESHOLDS],
+          b('partials', ws['partials'], F64, table.nblocks * DEPTH_MOMENTS), b('out', ws['out'], F64, table.nslabs * DEPTH_MOMENTS))      # (K > 4: the library refuses)
