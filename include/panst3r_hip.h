@@ -148,6 +148,19 @@ int pst_mask_head(const void* E, int64_t lde, const void* F, int64_t f_view_stri
  * Replaces: xFormers memory-efficient attention / SDPA inside croco Attention & CrossAttention, HF Dinov2
  * attention, and nn.MultiheadAttention incl. its bool attn_mask (mask_transformer.py:264-272,314,372).
  * Strides are in elements.  mask: uint8 [B, Nq, Nk] (1 = blocked), shared by all heads, or NULL.
+ *
+ * The operand contract (all formats: 16-bit, fp32 operands, and the split planes of pst_attn_x3; tests/test_hip_attn_layout.py holds every kernel to it):
+ *   strides  Batch and head strides of Q, K, Vt, O and m_bs, and the row strides q_rs, o_rs, m_rs, may be negative or zero: they only enter 64-bit
+ *            address arithmetic (a zero m_bs shares one mask among the batches, a zero m_rs one row among the queries, a negative k_bs / v_bs walks the
+ *            batches backwards).  k_rs and v_ds must be >= 0: the 16-bit kernels add them as 32-bit unsigned offsets, and every format refuses a negative
+ *            one with PST_EINVAL.  The strides of O must send distinct (b, h, q) to distinct rows; that is not checked.
+ *   read     Q rows [0, Nq) and K rows [0, Nk), hd columns each.  Of every V^T row the columns [0, Nk) and, in the 16-bit formats and in pst_attn_x3 (both
+ *            planes), the rest of the last 8-key chunk [Nk, roundup8(Nk)): those values are multiplied by a probability of exactly 0, so they must be
+ *            FINITE (any finite value; they do not reach the result).  The fp32-operand kernel does not read them.  Of every mask row the bytes [0, Nk)
+ *            and, except in the fp32-operand kernel, [Nk, roundup4(Nk)), whose values are ignored.
+ *   never    Q rows >= Nq, K rows >= Nk, V^T columns >= roundup8(Nk), mask bytes >= roundup4(Nk) and the other columns of a shared buffer are not read.
+ *            Of O only the hd columns of the B H Nq logical rows are written, of `ws` only its first pst_attn_workspace_bytes; nothing else of either is
+ *            read or written.
  */
 typedef struct pst_attn_params {
   const void* Q;  int64_t q_bs, q_hs, q_rs;   /* batch / head / row strides */
@@ -245,7 +258,7 @@ int pst_transpose_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int ro
 int pst_rope2d_split(const float* x, int64_t ld, const int32_t* pos, const float* cs, void* hi, void* lo, int64_t ldo, int rows, int nheads, int hd, int dtype16,
                      void* stream);
 int pst_attn_x3(const pst_attn_params* p, const void* Q_lo, const void* K_lo, const void* Vt_lo, int out_type, int64_t out_block, void* stream);
-const char* pst_attn_x3_variant(const pst_attn_params* p);
+const char* pst_attn_x3_variant(const pst_attn_params* p);   /* as pst_attn_variant: NULL for parameters pst_attn_x3 refuses */
 
 /* ---------------------------------------------------------------- RoPE-2D (in place on bf16 q and k)
  * Replaces cuRoPE2D / RoPE2D 'RoPE100' (README.md:67-71, input_mixer.py:16): per head the first hd/2 channels

@@ -494,6 +494,10 @@ static int attn_validate(const pst_attn_params* pp) {
   if (((uintptr_t)p.Q | (uintptr_t)p.K | (uintptr_t)p.Vt) & 15 || ((uintptr_t)p.O & 7)) {
     set_error("attn: operands must be 16-byte aligned"); return PST_EINVAL;
   }
+  // the full-tile source offsets are 32-bit unsigned (k_off / v_off of attn_body): a negative row stride would become an offset of about +4 GB.  Batch
+  // and head strides, q_rs, o_rs and m_rs only ever enter 64-bit arithmetic and may be negative.
+  if (p.k_rs < 0) { set_error("attn: k_rs must not be negative"); return PST_EINVAL; }
+  if (p.v_ds < 0) { set_error("attn: v_ds must not be negative"); return PST_EINVAL; }
   if (p.k_rs * 64 * 2 >= (1ll << 31) || p.v_ds * (int64_t)p.hd * 2 >= (1ll << 31)) { set_error("attn: K row / V^T row stride too large"); return PST_EINVAL; }
   if (p.mask && ((p.m_rs | p.m_bs) % 4 || ((uintptr_t)p.mask & 3))) { set_error("attn: mask rows must be 4-byte aligned"); return PST_EINVAL; }
   if (p.nsplit > 1) {

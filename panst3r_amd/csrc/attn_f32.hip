@@ -132,6 +132,9 @@ int attn_f32_validate(const pst_attn_params& p) {
     set_error("attn (fp32 operands): Q / K / O rows must be 16-byte aligned"); return PST_EINVAL;
   }
   if ((uintptr_t)p.Vt & 3) { set_error("attn (fp32 operands): Vt misaligned"); return PST_EINVAL; }
+  // this kernel's addresses are all 64-bit; refused so that one contract holds for every operand format (include/panst3r_hip.h)
+  if (p.k_rs < 0) { set_error("attn (fp32 operands): k_rs must not be negative"); return PST_EINVAL; }
+  if (p.v_ds < 0) { set_error("attn (fp32 operands): v_ds must not be negative"); return PST_EINVAL; }
   if (p.nsplit > 1) { set_error("attn (fp32 operands): no split-K (nsplit must be <= 1)"); return PST_EINVAL; }
   return PST_OK;
 }

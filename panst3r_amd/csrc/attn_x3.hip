@@ -409,6 +409,9 @@ static int x3_validate(const pst_attn_params* pp, const void* Qlo, const void* K
   if ((p.q_rs | p.q_hs | p.q_bs | p.k_rs | p.k_hs | p.k_bs | p.v_ds | p.v_hs | p.v_bs) % 8) { set_error("attn_x3: Q/K/Vt strides must be multiples of 8 elements"); return PST_EINVAL; }
   if ((p.o_rs | p.o_hs | p.o_bs) % 4) { set_error("attn_x3: O strides must be multiples of 4"); return PST_EINVAL; }
   if ((((uintptr_t)p.Q | (uintptr_t)p.K | (uintptr_t)p.Vt | (uintptr_t)Qlo | (uintptr_t)Klo | (uintptr_t)Vlo | (uintptr_t)p.O) & 15)) { set_error("attn_x3: operands must be 16-byte aligned"); return PST_EINVAL; }
+  // (32-bit unsigned full-tile offsets k_off / v_off, as in attention.hip; every other stride only enters 64-bit arithmetic and may be negative)
+  if (p.k_rs < 0) { set_error("attn_x3: k_rs must not be negative"); return PST_EINVAL; }
+  if (p.v_ds < 0) { set_error("attn_x3: v_ds must not be negative"); return PST_EINVAL; }
   if (p.k_rs * 64 * 2 >= (1ll << 31) || p.v_ds * (int64_t)p.hd * 2 >= (1ll << 31)) { set_error("attn_x3: K row / V^T row stride too large"); return PST_EINVAL; }
   if (p.mask && ((p.m_rs | p.m_bs) % 4 || ((uintptr_t)p.mask & 3))) { set_error("attn_x3: mask rows must be 4-byte aligned"); return PST_EINVAL; }
   if (p.nsplit > 1) {
@@ -437,7 +440,8 @@ extern "C" int pst_attn_x3(const pst_attn_params* pp, const void* Q_lo, const vo
 }
 
 extern "C" const char* pst_attn_x3_variant(const pst_attn_params* pp) {
-  if (!pp || (pp->hd != 64 && pp->hd != 96)) return nullptr;
+  // NULL for parameters pst_attn_x3 refuses whatever its lo planes and output form are (checked with the hi planes in their place and an fp32 output)
+  if (!pp || x3_validate(pp, pp->Q, pp->K, pp->Vt, DT_F32, 0)) return nullptr;
   if (pp->hd == 64) return x3_big(*pp) ? "attn_x3_kernel<64,2>" : "attn_x3_kernel<64,1>";
   return x3_big(*pp) ? "attn_x3_kernel<96,2>" : "attn_x3_kernel<96,1>";
 }
