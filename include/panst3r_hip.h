@@ -747,6 +747,53 @@ int pst_mesh_area_count(const int32_t* pan, int ncams, int64_t hw, const int32_t
 int pst_mesh_area_apply(const int32_t* pan, int ncams, int64_t hw, const int32_t* id2row, int ntab, int S, const int32_t* counts, int min_area, int32_t* out,
                         void* stream);
 
+/* ---------------------------------------------------------------- mesh shading: vertex normals, interpolated attributes and a headlight shade (f17; ABI 20, additive; no counterpart in the reference)
+ * What turns a face map of the section above into a picture: area-weighted vertex normals of the mesh, any per-vertex quantity interpolated
+ * perspective-correctly over the rendered pixels, and a two-sided headlight shade term.  Restated in tests/mesh_shade_ref.py [restated, parity unpinned]
+ * and held to it bit for bit.  Contraction is off: every fp64 operation is rounded on its own, in the order written.  No float atomics.
+ * VERTEX NORMALS  vertices fp32 [Nv, 3], faces int32 [Nf, 3], sh int, acc int64 [Nv, 3, 2] cleared by the CALLER, normals fp32 [Nv, 3]:
+ *   1 valid     face f takes part iff its three indices are inside [0, Nv) and its nine coordinates are finite; any other face adds nothing.
+ *   2 vector    e1 = v1 - v0, e2 = v2 - v0 in fp64 from the fp32 coordinates; c = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), every product
+ *               and every difference rounded on its own.  |c| is twice the face's area: the weighting is by AREA, not by angle.
+ *   3 scale     sh is chosen by the host: D = the largest axis extent (max - min) over the finite vertex coordinates, formed in fp64 from the fp32 extrema;
+ *               ex = the frexp exponent of D (D = m 2^ex, 0.5 <= m < 1); sh = 51 - 2 ex, or 0 when D == 0 or no coordinate is finite.  Then
+ *               |c_a 2^sh| < 2^52 for every valid face.  |sh| <= PST_MESH_NORMALS_MAX_SHIFT.
+ *   4 quantise  q = int64(rint(ldexp(c_a, sh))), half to even; hi = q >> 26 (arithmetic: floor), lo = q & (2^26 - 1), so q = hi 2^26 + lo, 0 <= lo < 2^26.
+ *   5 sum       for each of the face's three corners v and each axis a: acc[v][a][0] += hi, acc[v][a][1] += lo, 64-bit integer atomics, one lane per
+ *               face.  Integer sums are exact and commute: the result does not depend on the order of the faces or on scheduling.
+ *   6 bounds    fewer than 2^33 additions of magnitude below 2^26 per word: nothing overflows for any Nf <= 2^31 - 1.
+ *   7 finish    pst_mesh_normals_finish, one lane per vertex: S_a = fp64(acc[v][a][0]) 67108864.0 + fp64(acc[v][a][1]); len2 = (Sx Sx + Sy Sy) + Sz Sz;
+ *               len2 == 0 gives the normal (0, 0, 0) (a vertex on no valid face, or whose faces cancel); otherwise n_a = fp32(S_a / sqrt_heron(len2)).
+ *   8 sqrt_heron(x) for finite x > 0: (., e) = frexp(x), e2 = e - (e & 1), r = ldexp(x, -e2) in [0.5, 2); s = 1.0, then six times s = 0.5 (s + r / s);
+ *               the result is ldexp(s, e2 / 2).  Only IEEE add, multiply and divide: within 1 ulp of the correctly rounded root on [0.5, 2).
+ * INTERPOLATION AND SHADE  pst_mesh_interp, one lane per pixel of face int64 [B, H, W] (as pst_mesh_resolve writes it; ANY values are legal), with
+ *   vertices, faces, cams fp32 [B, 16] and near as pst_mesh_resolve takes them.  Optional: attr fp32 [Nv, C], 1 <= C <= PST_MESH_INTERP_MAX_CHANNELS, with
+ *   fill (finite) and out_attr fp32 [B, H, W, C] (both pointers or neither); shade_mode PST_MESH_SHADE_NONE / _FLAT / _SMOOTH with out_shade fp32
+ *   [B, H, W] (given iff the mode is not NONE) and normals fp32 [Nv, 3] (given iff the mode is SMOOTH).  At least one output.
+ *   9 hit       the pixel (i, j) of camera b with f = face[b][i][j] is a HIT iff 0 <= f < Nf, face f is rasterised in camera b (mesh steps 2 and 3 and a
+ *               bounding box that is not empty) and the pixel passes the coverage test of mesh step 4.  Anything else - -1, an index >= Nf, a face that
+ *               is not drawn in that camera or does not cover the pixel - is a MISS: `fill` in every channel, shade 0.  So s below is never 0.
+ *  10 weights   w_k = fp64(E_k) q_k with E_k and q_k of mesh steps 4 and 5, s = (w0 + w1) + w2: the depth's own sum.  SET-UP corner k is listed position
+ *               k of the face, with positions 1 and 2 exchanged when mesh step 3 exchanged them.
+ *  11 attribute out[c] = fp32(((w0 a0 + w1 a1) + w2 a2) / s), a_k = fp64(attr[vertex at set-up corner k][c]).
+ *  12 shade     N, world frame: SMOOTH (w0 n0 + w1 n1) + w2 n2 per axis of the three corners' normals (no division by s: only the direction counts);
+ *               FLAT the c of step 2 of the corners AS LISTED (no exchange).  Camera frame: n_r = (fp64(W_r0) N_x + fp64(W_r1) N_y) + fp64(W_r2) N_z for
+ *               the rows r of the camera's world-to-camera rotation.  View ray d = (((j + 0.5) - cx) / fx, ((i + 0.5) - cy) / fy, 1) in fp64.
+ *               dot = (n0 d0 + n1 d1) + n2, nn = (n0 n0 + n1 n1) + n2 n2, dd = (d0 d0 + d1 d1) + 1, x = nn dd;
+ *               shade = fp32(|dot| / sqrt_heron(x)), or 0 when x is zero or not finite.  Two-sided (the rasteriser sees both sides of a face): a
+ *               headlight at the camera, in [0, 1] up to rounding; no shadows, no textures.
+ * 1 <= Nf, Nv <= 2^31 - 1, 1 <= B <= 65535, B H W <= 2^31 - 1, 0 < near finite.  Nothing can fail on the device: there is no status word.  A refusal
+ * (PST_EINVAL) comes before any launch and leaves every output untouched. */
+#define PST_MESH_INTERP_MAX_CHANNELS 16
+#define PST_MESH_NORMALS_MAX_SHIFT 1100
+#define PST_MESH_SHADE_NONE 0
+#define PST_MESH_SHADE_FLAT 1
+#define PST_MESH_SHADE_SMOOTH 2
+int pst_mesh_normals_accumulate(const float* vertices, int64_t Nv, const int32_t* faces, int64_t Nf, int sh, int64_t* acc, void* stream);
+int pst_mesh_normals_finish(const int64_t* acc, int64_t Nv, float* normals, void* stream);
+int pst_mesh_interp(const int64_t* face, int ncams, int H, int W, const float* vertices, int64_t Nv, const int32_t* faces, int64_t Nf, const float* cams,
+                    float near_z, const float* attr, int C, float fill, float* out_attr, int shade_mode, const float* normals, float* out_shade, void* stream);
+
 /* ---------------------------------------------------------------- surface: the pointmap grids triangulated into one labelled mesh (no counterpart in the reference)
  * Every view's pointmap is a grid, so pixel neighbours are surface neighbours.  The mesh's vertices ARE the rows of the panoptic cloud (points, pan
  * and colors of pst_cloud_compact: nothing is copied or compacted, a vertex that no face uses is allowed); these entry points only make the faces.

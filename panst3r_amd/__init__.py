@@ -11,6 +11,7 @@ _LAZY = {
     'Dust3rEncoder': 'panst3r_amd.model', 'MUSt3R': 'panst3r_amd.model', 'DinoV2Encoder': 'panst3r_amd.model',
     'PanopticDecoder': 'panst3r_amd.model', 'PixelShuffleUpscaler': 'panst3r_amd.model',
     'LoftUpUpscaler': 'panst3r_amd.model', 'InputMixer': 'panst3r_amd.model',
+    'vertex_normals': 'panst3r_amd.engine', 'interpolate_render': 'panst3r_amd.engine', 'shade_render': 'panst3r_amd.engine',      # f17: engine/shade.py
 }
 
 

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "../../include/panst3r_hip.h"
 #include "pinhole.h"             // affine34, project, PH_CAM; and through it wave_ops.h: vx_run, id_row
+#include "heron.h"               // sqrt_heron: the square root of the shading contract (pst_mesh_interp, at the end of this file)
 
 #pragma clang fp contract(off)
 
@@ -294,4 +295,108 @@ extern "C" int pst_mesh_area_apply(const int32_t* pan, int ncams, int64_t hw, co
   hipLaunchKernelGGL(mesh_area_apply_kernel, blocks_for(npix, MS_T), dim3(MS_T), 0, (hipStream_t)stream, pan, npix, hw, id2row, ntab, S, counts,
                      min_area, out);
   return check_launch("mesh_area_apply");
+}
+
+// ---------------------------------------------------------------- f17: per-vertex attributes and a headlight shade over a rendered face map
+// The mesh shading section of include/panst3r_hip.h, steps 9 - 12.  One lane per pixel of a face map int64 [B, H, W] (MeshRender.face, or any values): the
+// pixel's face is set up again for the pixel's camera with the rasteriser's own ms_setup / ms_edges, so the weights w_k = fp64(E_k) q_k and their sum s
+// are the numbers the depth was made of.  A pixel whose entry is no face of the mesh, whose face leaves no trace in that camera or does not cover the
+// pixel is a MISS: `fill` in every channel, shade 0 - so the outputs are defined for any map and s is never 0.  Plain vector stores, no atomics.
+namespace pst {
+
+constexpr int MS_MAX_CHANNELS = PST_MESH_INTERP_MAX_CHANNELS;
+
+// N = (w0 a0 + w1 a1) + w2 a2 of three fp32 values widened to fp64
+__device__ __forceinline__ double ms_blend(const double (&w)[3], float a0, float a1, float a2) {
+  return (w[0] * (double)a0 + w[1] * (double)a1) + w[2] * (double)a2;
+}
+
+__global__ __launch_bounds__(MS_T) void mesh_interp_kernel(const int64_t* __restrict__ face, int64_t npix, int H, int W, const float* __restrict__ vertices, int64_t Nv,
+                                                           const int32_t* __restrict__ faces, int64_t Nf, const float* __restrict__ cams, float near,
+                                                           const float* __restrict__ attr, int C, float fill, float* __restrict__ out_attr, int shade_mode,
+                                                           const float* __restrict__ normals, float* __restrict__ out_shade) {
+  const int64_t p = (int64_t)blockIdx.x * MS_T + threadIdx.x;
+  if (p >= npix) return;
+  const int64_t hw = (int64_t)H * W, cam = p / hw, pix = p % hw, f = face[p];
+  const int i = (int)(pix / W), j = (int)(pix % W);
+  const float* __restrict__ c = cams + cam * PH_CAM;
+  MsTri t;
+  double w[3];
+  bool hit = f >= 0 && f < Nf && ms_setup(c, vertices, Nv, faces, f, near, H, W, t);
+  if (hit) hit = i >= t.i0 && i <= t.i1 && j >= t.j0 && j <= t.j1;   // a covered pixel lies in the box (mesh step 4); outside it the edge values are not bounded
+  if (hit) {
+    int64_t E[3];
+    ms_edges(t, i, j, E);
+    hit = E[0] >= t.least[0] && E[1] >= t.least[1] && E[2] >= t.least[2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) w[k] = (double)E[k] * t.q[k];
+  }
+  if (!hit) {
+    if (out_attr)
+      for (int ch = 0; ch < C; ++ch) out_attr[p * C + ch] = fill;
+    if (out_shade) out_shade[p] = 0.f;
+    return;
+  }
+  // the vertex at set-up corner k: listed position k, 1 and 2 exchanged after a swap (ms_setup checked the three indices)
+  const int64_t v0 = faces[f * 3 + 0], v1 = faces[f * 3 + (t.swapped ? 2 : 1)], v2 = faces[f * 3 + (t.swapped ? 1 : 2)];
+  if (out_attr) {
+    const double s = (w[0] + w[1]) + w[2];                          // the depth's own sum: E0 + E1 + E2 = A > 0 and every q_k > 0
+    for (int ch = 0; ch < C; ++ch) out_attr[p * C + ch] = (float)(ms_blend(w, attr[v0 * C + ch], attr[v1 * C + ch], attr[v2 * C + ch]) / s);
+  }
+  if (out_shade) {
+    double N[3];
+    if (shade_mode == PST_MESH_SHADE_SMOOTH) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) N[a] = ms_blend(w, normals[v0 * 3 + a], normals[v1 * 3 + a], normals[v2 * 3 + a]);
+    } else {                                                        // flat: e1 x e2 of the corners AS LISTED, as mesh_face.h writes it
+      const int64_t l1 = faces[f * 3 + 1], l2 = faces[f * 3 + 2];
+      double e1[3], e2[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        e1[a] = (double)vertices[l1 * 3 + a] - (double)vertices[v0 * 3 + a];
+        e2[a] = (double)vertices[l2 * 3 + a] - (double)vertices[v0 * 3 + a];
+      }
+      N[0] = e1[1] * e2[2] - e1[2] * e2[1]; N[1] = e1[2] * e2[0] - e1[0] * e2[2]; N[2] = e1[0] * e2[1] - e1[1] * e2[0];
+    }
+    double n[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) n[r] = ((double)c[4 * r] * N[0] + (double)c[4 * r + 1] * N[1]) + (double)c[4 * r + 2] * N[2];
+    const double d0 = (((double)j + 0.5) - (double)c[14]) / (double)c[12], d1 = (((double)i + 0.5) - (double)c[15]) / (double)c[13];
+    const double dot = (n[0] * d0 + n[1] * d1) + n[2], nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2], dd = (d0 * d0 + d1 * d1) + 1.0;
+    const double x = nn * dd;
+    out_shade[p] = (x > 0.0 && x <= 1.7976931348623157e308) ? (float)(fabs(dot) / sqrt_heron(x)) : 0.f;      // zero, NaN or infinite: 0
+  }
+}
+
+}  // namespace pst
+
+extern "C" int pst_mesh_interp(const int64_t* face, int ncams, int H, int W, const float* vertices, int64_t Nv, const int32_t* faces, int64_t Nf, const float* cams,
+                               float near_z, const float* attr, int C, float fill, float* out_attr, int shade_mode, const float* normals, float* out_shade,
+                               void* stream) {
+  using namespace pst;
+  if (Nv <= 0 || Nv > 0x7fffffffLL || Nf <= 0 || Nf > 0x7fffffffLL || !ms_shape_ok(ncams, H, W)) {
+    set_error("mesh_interp: bad shape (Nv=%lld, Nf=%lld in [1, 2^31 - 1], %d cameras in [1, 65535], %d x %d pixels, cameras x pixels < 2^31)", (long long)Nv,
+              (long long)Nf, ncams, H, W);
+    return PST_EINVAL;
+  }
+  if (!(near_z > 0.f) || !(near_z <= PST_FMAX)) { set_error("mesh_interp: needs 0 < near, finite; got %g", (double)near_z); return PST_EINVAL; }
+  if (!face || !vertices || !faces || !cams) { set_error("mesh_interp: null operand"); return PST_EINVAL; }
+  if ((attr != nullptr) != (out_attr != nullptr)) { set_error("mesh_interp: attr and out_attr go together"); return PST_EINVAL; }
+  if (attr && (C < 1 || C > MS_MAX_CHANNELS || !(fabsf(fill) <= PST_FMAX))) {
+    set_error("mesh_interp: needs 1 <= C <= %d channels and a finite fill; got %d, %g", MS_MAX_CHANNELS, C, (double)fill);
+    return PST_EINVAL;
+  }
+  if (shade_mode != PST_MESH_SHADE_NONE && shade_mode != PST_MESH_SHADE_FLAT && shade_mode != PST_MESH_SHADE_SMOOTH) {
+    set_error("mesh_interp: shade_mode is 0 (none), 1 (flat) or 2 (smooth), got %d", shade_mode);
+    return PST_EINVAL;
+  }
+  if ((shade_mode != PST_MESH_SHADE_NONE) != (out_shade != nullptr) || (shade_mode == PST_MESH_SHADE_SMOOTH) != (normals != nullptr)) {
+    set_error("mesh_interp: out_shade goes with a shade mode, normals with the smooth mode (mode %d)", shade_mode);
+    return PST_EINVAL;
+  }
+  if (!out_attr && !out_shade) { set_error("mesh_interp: neither attributes nor a shade asked for"); return PST_EINVAL; }
+  const int64_t npix = (int64_t)ncams * H * W;
+  hipLaunchKernelGGL(mesh_interp_kernel, blocks_for(npix, MS_T), dim3(MS_T), 0, (hipStream_t)stream, face, npix, H, W, vertices, Nv, faces, Nf, cams, near_z, attr,
+                     attr ? C : 0, fill, out_attr, shade_mode, normals, out_shade);
+  return check_launch("mesh_interp");
 }

@@ -11,6 +11,7 @@ from .render import render_cloud, render_cameras, orbit_cameras, CloudRender  # 
 from .consistency import view_consistency, ViewConsistency  # noqa: F401,E402  (f14: every pixel checked against every other view's depth - agreeing views, views that see through it, agreeing labels - and the floater filter PanopticCloud.filter_consistent; not in the reference)
 from .evaluate import panoptic_quality  # noqa: F401,E402  (PQ / SQ / RQ and mIoU of panoptic maps against ground truth, per scene or per view; not in the reference)
 from .mesh import render_mesh, ground_truth_maps, mesh_camera_table, load_ply_mesh, panoptic_vertex_ids, MeshRender  # noqa: F401,E402  (ground-truth depth and panoptic maps rasterised from a labelled mesh; reference tools/preprocess_scannetpp.py:395-494 through OpenGL)
+from .shade import vertex_normals, interpolate_render, shade_render  # noqa: F401,E402  (f17: area-weighted vertex normals, per-vertex attributes interpolated over a MeshRender, a headlight shade - colour and shaded views of every mesh, PanopticMesh.render_color; not in the reference)
 from .surface import panoptic_mesh, PanopticMesh  # noqa: F401,E402  (the pointmap grids triangulated into one labelled surface mesh on the cloud's rows; not in the reference)
 from .score3d import sample_mesh, nearest_points, similarity_from_cameras, score_reconstruction, MeshSamples  # noqa: F401,E402  (a reconstruction scored against a ground-truth mesh in 3-D: F-score, chamfer, a panoptic quality on the surface; not in the reference)
 from .score3d import icp, refine_alignment, Alignment  # noqa: F401,E402  (the alignment to the ground truth refined on the geometry by ICP, one fused kernel per step; not in the reference)

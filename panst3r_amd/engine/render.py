@@ -28,10 +28,16 @@ def image_shape(shape):
     return H, W
 
 
+def chunk_step(B, H, W, budget):
+    """cameras per launch of the z-buffer loop (and of what walks a render in the same chunks, engine/shade.py): a chunk's int64 [step, H, W] buffer
+    stays under `budget` bytes and inside one launch's limits (65 535 cameras, 2^31 - 1 pixels); at least one camera"""
+    return max(1, min(budget // (8 * H * W), 65535, (2 ** 31 - 1) // (H * W), B))
+
+
 def zbuf_chunks(B, H, W, dev, budget):
     """the z-buffer loop of `render_cloud` and `mesh.render_mesh`: B cameras in chunks whose int64 [b1 - b0, H, W] buffer stays under `budget` bytes (the
     caller's `ZBUF_BYTES`) and inside one launch's limits -> (b0, b1, z) per chunk, z cleared to all ones, the empty key.  The first chunk is the largest."""
-    step = max(1, min(budget // (8 * H * W), 65535, (2 ** 31 - 1) // (H * W), B))
+    step = chunk_step(B, H, W, budget)
     zbuf = torch.empty(step, H, W, dtype=torch.int64, device=dev)
     for b0 in range(0, B, step):
         b1 = min(b0 + step, B)

@@ -17,6 +17,7 @@ import torch
 from .. import hip
 from .cloud import ply_colors_u8
 from .mesh import MeshRender, mesh_camera_table, render_mesh
+from .shade import color_and_shade, vertex_normals
 
 FACE_ROW_BYTES = 17        # a face of the PLY file: uchar 3, three int vertex indices, int label
 
@@ -48,6 +49,7 @@ class PanopticMesh:
         self.vertices, self.faces, self.face_ids, self.vertex_ids, self.colors, self.quad = vertices, faces, face_ids, vertex_ids, colors, quad
         self.view_offsets, self.segments, self.cameras = view_offsets, segments, cameras
         self._labelled = None                                                    # (component, workspace) of the islands, once computed
+        self._normals = None                                                     # vertex_normals() of THESE faces, once computed (_with_faces starts anew)
 
     def __len__(self):
         return int(self.faces.shape[0])
@@ -119,22 +121,70 @@ class PanopticMesh:
         self._check_status(status)
         return self._with_faces(faces[:kept], face_ids[:kept], quad[:kept])
 
-    def write_ply(self, path):
+    def vertex_normals(self):
+        """engine.shade.vertex_normals of this mesh, fp32 [M,3], computed once (a mesh made by `drop_small` computes its own); an empty mesh: all zero"""
+        self._on_device('PanopticMesh.vertex_normals')
+        if self._normals is None:
+            self._normals = torch.zeros(int(self.vertices.shape[0]), 3, dtype=torch.float32, device=self.faces.device) if len(self) == 0 or \
+                self.vertices.shape[0] == 0 else vertex_normals(self.vertices, self.faces)
+        return self._normals
+
+    @torch.no_grad()
+    def render_color(self, cams2world, focals, shape, *, colors=None, shading='smooth', ambient=0.3, background=(0, 0, 0), **kw):
+        """`render` and a colour picture of it -> (`MeshRender`, rgb uint8 [B,H,W,3]): the vertex colours interpolated over every face (engine.shade),
+        times ambient + (1 - ambient) * shade, the headlight shade of the interpolated vertex normals ('smooth'), of the face's own normal ('flat') or
+        none (None: the colours as they are).  rgb = ply_colors_u8(colour * (ambient + (1 - ambient) * shade)), the product in separately issued fp32
+        operations; `background` (three floats in [0, 1]) fills the pixels without a face.  `colors` [M,3] overrides `self.colors`, for example with a
+        palette colour per `vertex_ids`.  `ambient` = 0.3 is a choice, not a measured optimum.  **kw: pp, near, far as `render` takes them.  An empty
+        mesh renders as background."""
+        self._on_device('PanopticMesh.render_color')
+        if shading not in ('smooth', 'flat', None):
+            raise ValueError("shading must be 'smooth', 'flat' or None, got %r" % (shading,))
+        if isinstance(ambient, bool) or not isinstance(ambient, (int, float)) or not 0 <= float(ambient) <= 1:
+            raise ValueError('ambient must be a number in [0, 1], got %r' % (ambient,))
+        bg = [float(x) for x in background]
+        if len(bg) != 3 or not all(math.isfinite(x) for x in bg):
+            raise ValueError('background must be three finite numbers, got %r' % (background,))
+        colors = self.colors if colors is None else colors
+        M = int(self.vertices.shape[0])
+        if not isinstance(colors, torch.Tensor) or tuple(colors.shape) != (M, 3) or not colors.dtype.is_floating_point:
+            raise ValueError('colors must be a floating-point [%d, 3] tensor' % M)
+        views = self.render(cams2world, focals, shape, **kw)
+        dev = self.faces.device
+        back = ply_colors_u8(torch.tensor(bg, dtype=torch.float32, device=dev))
+        if len(self) == 0:
+            return views, back.expand(*views.face.shape, 3).contiguous()
+        col, shade = color_and_shade(views, self.vertices, self.faces, cams2world, focals, colors, normals=self.vertex_normals() if shading == 'smooth' else None,
+                                     flat=shading == 'flat', pp=kw.get('pp'), near=kw.get('near', 0.05))
+        if shade is not None:
+            a = float(ambient)
+            light = shade * torch.tensor(1.0 - a, dtype=torch.float32, device=dev)       # fp32(1 - ambient), the difference taken in double
+            light = light + torch.tensor(a, dtype=torch.float32, device=dev)
+            col = col * light.unsqueeze(-1)
+        rgb = torch.where(views.hit.unsqueeze(-1), ply_colors_u8(col), back)
+        return views, rgb
+
+    def write_ply(self, path, normals=False):
         """binary little-endian PLY that `load_ply_mesh` reads back: the vertex element is the cloud's 19-byte rows (x y z float, red green blue uchar of
         `colors`, label int = the vertex id), the face element `list uchar int vertex_indices` plus `int label` (the face id).  Both are packed where the
-        mesh lives, into one buffer: one device-to-host copy."""
+        mesh lives, into one buffer: one device-to-host copy.  normals=True adds `float nx, ny, nz` (`vertex_normals()`) to the vertex element, 31-byte
+        rows; the default writes the same bytes as before the argument existed."""
         M, F, dev = int(self.vertices.shape[0]), len(self), self.faces.device
-        buf = torch.empty(M * 19 + F * FACE_ROW_BYTES, dtype=torch.uint8, device=dev)
-        v, f = buf[:M * 19].view(M, 19), buf[M * 19:].view(F, FACE_ROW_BYTES)
+        row = 31 if normals else 19
+        buf = torch.empty(M * row + F * FACE_ROW_BYTES, dtype=torch.uint8, device=dev)
+        v, f = buf[:M * row].view(M, row), buf[M * row:].view(F, FACE_ROW_BYTES)
         v[:, 0:12] = self.vertices.contiguous().view(torch.uint8).reshape(M, 12)
         v[:, 12:15] = ply_colors_u8(self.colors)
         v[:, 15:19] = self.vertex_ids.contiguous().view(torch.uint8).reshape(M, 4)
+        if normals:
+            v[:, 19:31] = self.vertex_normals().contiguous().view(torch.uint8).reshape(M, 12)
         f[:, 0] = 3
         f[:, 1:13] = self.faces.contiguous().view(torch.uint8).reshape(F, 12)
         f[:, 13:17] = self.face_ids.contiguous().view(torch.uint8).reshape(F, 4)
         header = ('ply\nformat binary_little_endian 1.0\ncomment panst3r_amd panoptic surface mesh\nelement vertex %d\nproperty float x\nproperty float y\n'
-                  'property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nproperty int label\nelement face %d\n'
-                  'property list uchar int vertex_indices\nproperty int label\nend_header\n' % (M, F))
+                  'property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nproperty int label\n%selement face %d\n'
+                  'property list uchar int vertex_indices\nproperty int label\nend_header\n' %
+                  (M, 'property float nx\nproperty float ny\nproperty float nz\n' if normals else '', F))
         with open(path, 'wb') as fh:
             fh.write(header.encode('ascii'))
             fh.write(buf.cpu().numpy().tobytes())

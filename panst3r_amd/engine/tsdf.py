@@ -10,8 +10,8 @@ No counterpart in the reference: *restated, unpinned*.  The contract is the tsdf
 tests/tsdf_ref.py; csrc/tsdf.hip is held to it bit for bit (separately rounded fp32 operations, fp64 crossings in a stated order, no float atomics).
 
 What it does not do: no confidence weighting of a view (every measured pair counts once), no bilinear sampling of the depth (the nearest pixel centre),
-no marching-cubes case table (one vertex per surface cell, so thin features collapse), no vertex normals.  Cells exist only where the cloud has
-points +- band: a hole in the cloud is a hole in the mesh."""
+no marching-cubes case table (one vertex per surface cell, so thin features collapse), no vertex normals of its own (stage f17 computes area-weighted
+ones on demand: `mesh.vertex_normals()`, engine/shade.py).  Cells exist only where the cloud has points +- band: a hole in the cloud is a hole in the mesh."""
 import numpy as np
 import torch
 

@@ -11,6 +11,7 @@ A failure is a RuntimeError naming the wrapper, the operand, what was expected a
 same.  The GEMM / attention builders (the library checks their bounds itself) and the streaming model-path wrappers (strided arena views) are not.
 """
 import ctypes as C
+import math
 import os
 import torch
 
@@ -81,6 +82,7 @@ SIGNATURES = {
     'pst_tsdf_vertices': 'i:plplpppippppldppppppp', 'pst_tsdf_face_count': 'i:plplpppippppp', 'pst_tsdf_face_emit': 'i:plplppppppppppp',
     'pst_mesh_lane_pixels': 'i:', 'pst_mesh_raster': 'i:plplpiiiffppplip', 'pst_mesh_resolve': 'i:piiiplplpfpppppp', 'pst_mesh_area_count': 'i:pilpiipp',
     'pst_mesh_area_apply': 'i:pilpiipipp',
+    'pst_mesh_normals_accumulate': 'i:plplipp', 'pst_mesh_normals_finish': 'i:plpp', 'pst_mesh_interp': 'i:piiiplplpfpifpippp',
     'pst_pq_count': 'i:pplpipipiiipip', 'pst_pq_match': 'i:piiipppppppp',
     'pst_vcc_cells': 'i:ppplfpp', 'pst_vcc_build': 'i:pplpplppp', 'pst_vcc_link': 'i:pplpplippp', 'pst_vcc_flatten': 'i:ppplppppppip', 'pst_vcc_count': 'i:plpp',
     'pst_vcc_rank': 'i:pplpppppppppppppp', 'pst_vcc_votes': 'i:pppplppliipplpp', 'pst_vcc_apply': 'i:pppplippiffpppp',
@@ -1695,6 +1697,51 @@ def mesh_area_apply(pan, id2row, counts, min_area, out):
     po = b('out', out, I32, tuple(pan.shape))
     b.require(po != args[0], 'out is not pan')
     _call('pst_mesh_area_apply', *args, int(min_area), po)
+
+
+# ------------------------------------------------------------------ mesh shading: vertex normals, interpolated attributes, a headlight shade (csrc/mesh_normals.hip and the
+# end of csrc/mesh.hip; engine/shade.py holds the public entry points)
+MESH_INTERP_MAX_CHANNELS = 16      # PST_MESH_INTERP_MAX_CHANNELS
+MESH_NORMALS_MAX_SHIFT = 1100      # PST_MESH_NORMALS_MAX_SHIFT
+MESH_SHADE_NONE, MESH_SHADE_FLAT, MESH_SHADE_SMOOTH = 0, 1, 2      # PST_MESH_SHADE_*
+
+
+def mesh_normals(vertices, faces, sh, acc, out):
+    """out fp32 [Nv, 3] = the area-weighted unit normals of vertices fp32 [Nv, 3] over faces int32 [Nf, 3], (0, 0, 0) for a vertex on no valid face;
+    sh: the scale exponent of the contract's step 3 (engine/shade.py computes it); acc int64 [Nv, 3, 2]: the two-limb sums, cleared here"""
+    b = _Operands('mesh_normals')
+    mesh = _mesh(b, vertices, faces)
+    Nv = mesh[1]
+    b.require(isinstance(sh, int) and not isinstance(sh, bool) and abs(sh) <= MESH_NORMALS_MAX_SHIFT, 'sh is an int with |sh| <= %d, got %r', MESH_NORMALS_MAX_SHIFT, sh)
+    pa, po = b('acc', acc, I64, (Nv, 3, 2)), b('out', out, F32, (Nv, 3))
+    acc.zero_()
+    _call('pst_mesh_normals_accumulate', *mesh, sh, pa)
+    _call('pst_mesh_normals_finish', pa, Nv, po)
+
+
+def mesh_interp(face, vertices, faces, cams, near, *, attr=None, fill=0.0, out_attr=None, shade_mode=MESH_SHADE_NONE, normals=None, out_shade=None):
+    """per pixel of face int64 [B, H, W] (MeshRender.face, or any values): out_attr fp32 [B, H, W, C] = attr fp32 [Nv, C] interpolated perspective-correctly
+    over the pixel's face, `fill` on a miss; out_shade fp32 [B, H, W] = the headlight shade of the face's normal (shade_mode MESH_SHADE_FLAT) or of the
+    interpolated normals fp32 [Nv, 3] (MESH_SHADE_SMOOTH), 0 on a miss.  Either output or both."""
+    b = _Operands('mesh_interp')
+    pf = b('face', face, I64, (-1, -1, -1))                                   # raises unless face is a 3-D tensor: the shape is read after it
+    B, H, W = face.shape
+    mesh = _mesh(b, vertices, faces)
+    Nv, pc = mesh[1], b('cams', cams, F32, (B, MESH_CAM_FLOATS))
+    b.require(shade_mode in (MESH_SHADE_NONE, MESH_SHADE_FLAT, MESH_SHADE_SMOOTH), 'shade_mode is 0 (none), 1 (flat) or 2 (smooth), got %r', shade_mode)
+    b.require((attr is None) == (out_attr is None), 'attr and out_attr go together')
+    b.require((shade_mode != MESH_SHADE_NONE) == (out_shade is not None), 'out_shade goes with a shade mode (mode %d)', shade_mode)
+    b.require((shade_mode == MESH_SHADE_SMOOTH) == (normals is not None), 'normals go with the smooth shade mode, and it needs them (mode %d)', shade_mode)
+    b.require(attr is not None or out_shade is not None, 'neither attributes nor a shade asked for')
+    nc = 0
+    if attr is not None:
+        nc = int(attr.shape[1]) if isinstance(attr, torch.Tensor) and attr.dim() == 2 else 0
+        b.require(1 <= nc <= MESH_INTERP_MAX_CHANNELS, 'attr is fp32 [Nv, C] with 1 <= C <= %d, got %s', MESH_INTERP_MAX_CHANNELS,
+                  tuple(attr.shape) if isinstance(attr, torch.Tensor) else type(attr).__name__)
+        b.require(isinstance(fill, (int, float)) and not isinstance(fill, bool) and math.isfinite(fill) and abs(fill) <= 3.4028234663852886e38, 'fill must be a finite float32, got %r', fill)
+    pa, po = b('attr', attr, F32, (Nv, nc), optional=True), b('out_attr', out_attr, F32, (B, H, W, nc), optional=True)
+    pn, ps = b('normals', normals, F32, (Nv, 3), optional=True), b('out_shade', out_shade, F32, (B, H, W), optional=True)
+    _call('pst_mesh_interp', pf, B, H, W, *mesh, pc, float(near), pa, nc, float(fill), po, int(shade_mode), pn, ps)
 
 
 # ------------------------------------------------------------------ panoptic evaluation (csrc/evaluate.hip; engine/evaluate.py holds the public entry point)
