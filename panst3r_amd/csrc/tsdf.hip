@@ -402,7 +402,7 @@ extern "C" int pst_tsdf_vertices(const int32_t* nodes, int64_t Nn, const uint64_
       !colors || !status) {
     set_error("tsdf_vertices: null operand"); return PST_EINVAL;
   }
-  if (min_weight < 1 || Mv < 1 || Mv > TS_MAX || !(voxel_size > 0.0)) {
+  if (min_weight < 1 || Mv < 1 || Mv > TS_MAX || !(voxel_size > 0.0 && voxel_size <= (double)PST_FMAX)) {     // positive and finite, as pst_tsdf_integrate's
     set_error("tsdf_vertices: bad shape (min_weight=%d >= 1, Mv=%lld in [1, 2^30 - 1]) or voxel size", min_weight, (long long)Mv); return PST_EINVAL;
   }
   if (tsdf_table_ok("tsdf_vertices", Nn, cap)) return PST_EINVAL;

@@ -13,7 +13,9 @@ Own design (the reference has no such stage).  The five steps of the contract in
   4 labels     the voxel of the cell, else the fullest voxel among the 26 neighbouring cells (ties to the smaller row), else id 0 and colour 0.
   5 faces      per lattice edge (node, axis) between valid nodes of different sides whose four cells are surface cells: two triangles, normals from
                inside to outside; face id = the id two corners share, else 0; key 3 rank + axis; order rank, axis, first before second.
-Elementwise float32 numpy rounds every operation on its own, which is what the kernels promise; the float64 sums are taken in the stated order."""
+Elementwise float32 numpy rounds every operation on its own, which is what the kernels promise; the float64 sums are taken in the stated order.
+`fuse` = NodeTable -> `integrate` -> `extract`; `integrate_planes` (step 2 on depth planes and dims as given) and `extract` (steps 3 - 5 on a field as
+given) are the stages on their own, which tests/tsdf_stage_cases.py feeds by hand."""
 import numpy as np
 
 import cloud_ref
@@ -64,18 +66,20 @@ class NodeTable:
         return np.where(ok & (self.sorted_keys[i] == k), self.rank_of_sorted[i], -1)
 
 
-def integrate(nodes, x_out, cams2world, focals, voxel_size, min_conf_thr, band, local_pointmaps=False, pp=None, near=1e-3):
-    """-> (sdf float32 [Nn], weight int32 [Nn])"""
+def integrate_planes(nodes, cam_table, depths, dims, npix, voxel_size, band):
+    """step 2 on depth planes as they are given: cam_table float32 [V, 16], depths = one float32 plane per view (its first H W values are the image),
+    dims int [V, 2] = (H, W), npix int [V] = the length of each plane.  A view with H W > npix or a dim < 1 takes no part.
+    -> (sdf float32 [Nn], weight int32 [Nn])"""
     vs = F(voxel_size)
     tau = F(F(band) * vs)
-    shapes = [tuple(x['conf'].shape) for x in x_out]
-    tab = consistency_ref.camera_tables(cams2world, focals, shapes, pp, near)
-    world = consistency_ref.world_points(x_out, cams2world, local_pointmaps)
-    p = (np.asarray(nodes).astype(F) * vs).astype(F)
+    p = (np.asarray(nodes).reshape(-1, 3).astype(F) * vs).astype(F)
     S, W = np.zeros(len(p), dtype=F), np.zeros(len(p), dtype=np.int32)
-    for j, (H, Wd) in enumerate(shapes):
-        depth = consistency_ref.own_depth(world[j], x_out[j]['conf'], tab[j], min_conf_thr)
-        inside, cell, zc = consistency_ref.project(p, tab[j], H, Wd)
+    for j in range(len(dims)):
+        H, Wd = int(dims[j][0]), int(dims[j][1])
+        if H < 1 or Wd < 1 or H * Wd > int(npix[j]):
+            continue
+        depth = np.asarray(depths[j], dtype=F).reshape(-1)
+        inside, cell, zc = consistency_ref.project(p, cam_table[j], H, Wd)
         with np.errstate(over='ignore', invalid='ignore'):
             d = np.where(inside, depth[cell], F(0)).astype(F)
             s = (d - zc).astype(F)
@@ -85,6 +89,15 @@ def integrate(nodes, x_out, cams2world, focals, voxel_size, min_conf_thr, band, 
     with np.errstate(divide='ignore', invalid='ignore'):
         sdf = np.where(W > 0, (S / W.astype(F)).astype(F), F(0)).astype(F)
     return sdf, W
+
+
+def integrate(nodes, x_out, cams2world, focals, voxel_size, min_conf_thr, band, local_pointmaps=False, pp=None, near=1e-3):
+    """-> (sdf float32 [Nn], weight int32 [Nn])"""
+    shapes = [tuple(x['conf'].shape) for x in x_out]
+    tab = consistency_ref.camera_tables(cams2world, focals, shapes, pp, near)
+    world = consistency_ref.world_points(x_out, cams2world, local_pointmaps)
+    depths = [consistency_ref.own_depth(world[j], x_out[j]['conf'], tab[j], min_conf_thr) for j in range(len(shapes))]
+    return integrate_planes(nodes, tab, depths, shapes, [H * Wd for H, Wd in shapes], voxel_size, band)
 
 
 CORNERS = np.array([[k & 1, (k >> 1) & 1, k >> 2] for k in range(8)])                                      # x fastest
@@ -182,8 +195,20 @@ def fuse(cells, count, pan, colors, x_out, cams2world, focals, voxel_size, min_c
     """cells int [Mv, 3], count, pan int [Mv], colors float32 [Mv, 3] of the voxels; the views as consistency_ref.consistency takes them.
     -> dict(nodes int32 [Nn, 3], sdf, weight, voxel_row, vertices, vertex_ids, colors, faces, face_ids, edge, cell_vertex, stats)"""
     tab = NodeTable(cells, band)
-    Nn = len(tab)
     sdf, weight = integrate(tab.nodes, x_out, cams2world, focals, voxel_size, min_conf_thr, band, local_pointmaps, pp, near)
+    return extract(tab, sdf, weight, min_weight, count, pan, colors, voxel_size)
+
+
+WG_NODES = 1024                                                                                              # nodes per workgroup of the count / emit kernels
+
+
+def extract(tab, sdf, weight, min_weight, count, pan, colors, voxel_size):
+    """steps 3 - 5 on a field as it is given: sdf float32 [Nn], weight int [Nn] on the nodes of `tab`; count, pan int [Mv], colors float32 [Mv, 3] of
+    the voxels.  -> the dict of `fuse`, and with it what the kernels hand from stage to stage: is_cell bool [Nn], cell_counts and face_counts int64
+    [ceil(Nn / 1024)] (the surface cells and the faces per 1024 nodes in rank order), face_mask int32 [Nn] (bit a: the edge from the node along
+    axis a emits its two triangles)"""
+    Nn = len(tab)
+    sdf, weight = np.asarray(sdf, dtype=F), np.asarray(weight)
     is_cell, q = surface_cells(tab, sdf, weight, min_weight)
     rows = np.nonzero(is_cell)[0]
     cell_vertex = np.full(Nn, -1, dtype=np.int64)
@@ -195,8 +220,13 @@ def fuse(cells, count, pan, colors, x_out, cams2world, focals, voxel_size, min_c
     vcol = np.where((w >= 0)[:, None], colors[np.maximum(w, 0)] if len(pan) else F(0), F(0)).astype(F).reshape(-1, 3)
     faces, face_ids, edge = build_faces(tab, sdf, weight, min_weight, cell_vertex, vertex_ids)
     stats = {'active_nodes': Nn, 'valid_nodes': int((weight >= min_weight).sum()), 'surface_cells': len(rows)}
+    nwg = (Nn + WG_NODES - 1) // WG_NODES
+    face_mask = np.zeros(Nn, dtype=np.int32)
+    np.bitwise_or.at(face_mask, edge // 3, (1 << (edge % 3)).astype(np.int32))
     return {'nodes': tab.nodes.astype(np.int32), 'sdf': sdf, 'weight': weight.astype(np.int32), 'voxel_row': tab.voxel_row, 'vertices': vertices,
-            'vertex_ids': vertex_ids, 'colors': vcol, 'faces': faces, 'face_ids': face_ids, 'edge': edge, 'cell_vertex': cell_vertex, 'stats': stats}
+            'vertex_ids': vertex_ids, 'colors': vcol, 'faces': faces, 'face_ids': face_ids, 'edge': edge, 'cell_vertex': cell_vertex, 'stats': stats,
+            'is_cell': is_cell, 'cell_counts': np.bincount(rows // WG_NODES, minlength=nwg), 'face_counts': np.bincount(edge // 3 // WG_NODES, minlength=nwg),
+            'face_mask': face_mask}
 
 
 def voxel_cells(points, voxel_size, point_voxel, Mv):
