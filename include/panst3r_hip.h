@@ -838,6 +838,49 @@ int pst_surface_keep_count(const int32_t* component, const int32_t* size, int64_
 int pst_surface_keep_emit(const int32_t* faces, const int32_t* face_ids, const int64_t* quad, const int32_t* component, const int32_t* size, int64_t F,
                           int min_faces, const int32_t* base, int32_t* out_faces, int32_t* out_face_ids, int64_t* out_quad, void* stream);
 
+/* ---------------------------------------------------------------- mesh simplification by vertex clustering (f18; ABI 20, additive; no counterpart in the reference)
+ * Rossignac-Borrel on the cell grid of the voxel section: the vertices that fall into one cubic cell of edge cell_size become ONE vertex, the faces
+ * are rewritten onto the new vertices, those that collapsed are dropped and those that then coincide are removed.  Restated in tests/simplify_ref.py
+ * [restated, parity unpinned]; integer work plus the voxel section's separately rounded operations, so every output is held to the restatement bit
+ * for bit.  Inputs: vertices fp32 [M, 3], colors fp32 [M, 3], vertex_ids int32 [M], faces int32 [F, 3], quad int64 [F], cell_size > 0 and finite.
+ *   1 used      a vertex takes part iff at least one face names it; the others vanish.  A face with a corner outside [0, M) is an error: the
+ *               PST_SIMPLIFY_RANGE bit of status[0], raised on the host; nothing is read or written through such a corner.
+ *               pst_simplify_used: used int32 [M], ZEROED BY THE CALLER, = 1 for every named vertex.  pst_simplify_mask: masked fp32 [M, 3] = the
+ *               vertex where used, NaN where not (the voxel section leaves a non-finite point out: the rows keep their order); status[1] += the used
+ *               vertices.
+ *   2 cluster   steps 1-5 of the voxel section on the used vertices in increasing row order with voxel_size = cell_size - the pst_voxel_* entry
+ *               points themselves, on `masked`, colors and vertex_ids: inv = fp32(1 / fp64(cell_size)), c = floor(fp32(p * inv)) in (-2^20, 2^20);
+ *               position = the mean of the 16-bit in-cell offsets summed as integers; colour = the mean of the 8-bit quantised colours (palette
+ *               weight 0: w1 = 1, w2 = 0, the mean itself); id = the vote over the listed ids (id2row), ties to the smallest id, void only alone.  New
+ *               vertices come in increasing order of their smallest member row.  cluster int32 [M] (the voxel section's point_voxel) = the new row of
+ *               vertex v; -1 for an unused vertex and for one left out (non-finite, or a cell out of range).  Mv = the new vertices.
+ *   3 remap     face f becomes (cluster[a], cluster[b], cluster[c]).  LEFT OUT if a corner is -1, else DEGENERATE if two new corners are equal:
+ *               both are dropped, status[2] and status[3] count them; the others are CANDIDATES, counted in status[4].
+ *   4 dedupe    (dedupe != 0) among the candidates with one unordered corner set the one with the smallest f survives, whatever its winding.  An
+ *               open-addressing table of the voxel section's kind (keys uint64 [cap] filled with ~0, cap a power of two >= 2 F, linear probing bounded
+ *               by cap, PST_SIMPLIFY_FULL if it ran full): key = the sorted corners + 1, 21 bits each, smallest lowest; winner int32 [cap], FILLED
+ *               WITH INT32_MAX BY THE CALLER, takes a 32-bit atomicMin of f.  The key needs Mv <= 2^21 - 2: a larger Mv with dedupe is PST_EINVAL.
+ *               Without dedupe every candidate survives, keys and winner may be null and Mv has no such limit.
+ *               pst_simplify_remap: face_slot int32 [F] = the face's slot (0 without dedupe), -1 left out, -2 degenerate.  merge != 0 lets the first
+ *               lane of a run of adjacent lanes with one key probe for the run: same results.
+ *   5 emit      survivors in the order of the originals: pst_simplify_count -> counts int32 [ceil(F / PST_SURFACE_WG)], one face per thread;
+ *               pst_cloud_scan -> base, base[last] = F'; pst_simplify_emit -> rows [0, F') of out_faces int32 [., 3] (the remapped corners in their
+ *               original order), out_quad int64 [.] (the original's), src_face int32 [.] (f) and out_face_ids int32 [.]: the id at least two of the
+ *               corners' NEW vertex_ids (int32 [Mv], the vote of step 2) share, else 0 - the surface section's rule.  Every output holds F rows.
+ * status int32 [8], zeroed by the caller.  Integer atomics only, no float atomics; every result written with plain vector stores; two calls return
+ * equal bytes.  Clustering preserves neither topology nor manifoldness, a collapse can flip a face's winding and nothing corrects it, and the
+ * representative is the cell's mean, not a quadric optimum.  1 <= F <= 2^31 - 256, 1 <= Mv <= M <= 2^30. */
+#define PST_SIMPLIFY_FULL 1       /* status[0]: the face table ran full (never: cap >= 2 F) */
+#define PST_SIMPLIFY_RANGE 4      /* status[0]: a face corner outside [0, M), or a cluster outside [-1, Mv) */
+int pst_simplify_used(const int32_t* faces, int64_t F, int64_t M, int32_t* used, int32_t* status, void* stream);
+int pst_simplify_mask(const float* vertices, const int32_t* used, int64_t M, float* masked, int32_t* status, void* stream);
+int pst_simplify_remap(const int32_t* faces, int64_t F, int64_t M, const int32_t* cluster, int64_t Mv, int dedupe, uint64_t* keys, int64_t cap,
+                       int32_t* winner, int32_t* face_slot, int32_t* status, int merge, void* stream);
+int pst_simplify_count(const int32_t* face_slot, const int32_t* winner, int64_t F, int dedupe, int32_t* counts, void* stream);
+int pst_simplify_emit(const int32_t* faces, const int64_t* quad, const int32_t* cluster, const int32_t* vertex_ids, const int32_t* face_slot,
+                      const int32_t* winner, int64_t F, int64_t M, int64_t Mv, int dedupe, const int32_t* base, int32_t* out_faces,
+                      int32_t* out_face_ids, int64_t* out_quad, int32_t* src_face, void* stream);
+
 /* ---------------------------------------------------------------- score3d: a mesh's surface as points, and the nearest point within a radius (no counterpart in the reference)
  * The two primitives of engine/score3d.py (F-score, chamfer and a 3-D panoptic quality of a reconstruction against a ground-truth mesh, point to
  * point).  Restated in tests/nearest_ref.py [restated, parity unpinned]: the sampler as written here, the search by brute force over all pairs.  Every

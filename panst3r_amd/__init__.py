@@ -12,6 +12,7 @@ _LAZY = {
     'PanopticDecoder': 'panst3r_amd.model', 'PixelShuffleUpscaler': 'panst3r_amd.model',
     'LoftUpUpscaler': 'panst3r_amd.model', 'InputMixer': 'panst3r_amd.model',
     'vertex_normals': 'panst3r_amd.engine', 'interpolate_render': 'panst3r_amd.engine', 'shade_render': 'panst3r_amd.engine',      # f17: engine/shade.py
+    'simplify_mesh': 'panst3r_amd.engine',                                                                                         # f18: engine/simplify.py
 }
 
 

@@ -19,3 +19,4 @@ from .meshdist import mesh_distance, icp_to_mesh  # noqa: F401,E402  (icp_to_mes
 from .depth_eval import depth_quality  # noqa: F401,E402  (f16: predicted depths against ground-truth depths on the device - AbsRel, SqRel, RMSE, MAE, delta < t after a median / least-squares alignment, per view or per scene; not in the reference)
 from .camera_eval import camera_quality  # noqa: F401,E402  (f16: predicted cameras against ground-truth cameras - RRA, RTA, mAA, ATE, focal error; host float64; not in the reference)
 from .tsdf import fuse_surface, FusedMesh  # noqa: F401,E402  (f15:the views fused in a truncated signed distance volume and ONE surface extracted by surface nets - PanopticCloud.fused_mesh; not in the reference)
+from .simplify import simplify_mesh, SimplifiedMesh  # noqa: F401,E402  (f18: any mesh made smaller by vertex clustering on the voxel grid - one vertex per cell with the voted id, collapsed and coinciding faces removed - PanopticMesh.simplify; not in the reference)

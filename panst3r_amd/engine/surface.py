@@ -121,6 +121,21 @@ class PanopticMesh:
         self._check_status(status)
         return self._with_faces(faces[:kept], face_ids[:kept], quad[:kept])
 
+    def simplify(self, cell_size, *, dedupe=True):
+        """a new, smaller `PanopticMesh` by vertex clustering (engine/simplify.py, stage f18): the vertices that a face uses and that fall into one cubic
+        cell of edge `cell_size` become one vertex - the voxel stage's mean position, mean colour and voted id (ties to the smallest id, void only
+        alone) - in the order of their first rows; a face is rewritten onto them and dropped if it lost a corner (a non-finite vertex, a cell beyond
+        +-2^20) or if two of its corners merged; with `dedupe` only the first of the faces with one unordered corner set stays, whatever its winding.
+        Survivors keep their order, their corner order and their `quad`; face ids are re-derived from the new vertex ids.  segments, cameras and
+        view_offsets are carried over.  The result holds `simplify_stats` (vertices_in, vertices_used, vertices_left_out, vertices_out, faces_in,
+        faces_left_out, faces_degenerate, faces_duplicate, faces_out), `src_face` int32 [F'] (the face of THIS mesh behind every new face) and
+        `cluster` int32 [M] (the new row of every vertex of this mesh, -1 for none).  A `FusedMesh` gives a plain `PanopticMesh`: the volume no longer
+        describes it.  An empty mesh, or one whose every face collapses, gives zero faces and zero vertices.  dedupe=True takes at most 2^21 - 2 new
+        vertices (ValueError: use a larger cell or dedupe=False); a face naming a row outside the vertices is a ValueError.  Neither topology nor
+        winding is preserved.  Two host syncs.  GPU only."""
+        from .simplify import simplify_panoptic_mesh
+        return simplify_panoptic_mesh(self, cell_size, dedupe=dedupe)
+
     def vertex_normals(self):
         """engine.shade.vertex_normals of this mesh, fp32 [M,3], computed once (a mesh made by `drop_small` computes its own); an empty mesh: all zero"""
         self._on_device('PanopticMesh.vertex_normals')

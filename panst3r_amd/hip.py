@@ -88,6 +88,8 @@ SIGNATURES = {
     'pst_vcc_rank': 'i:pplpppppppppppppp', 'pst_vcc_votes': 'i:pppplppliipplpp', 'pst_vcc_apply': 'i:pppplippiffpppp',
     'pst_surface_rows': 'i:pllpp', 'pst_surface_count': 'i:ppiipfpp', 'pst_surface_emit': 'i:ppiipfpppppp', 'pst_surface_link': 'i:pllpppp',
     'pst_surface_components': 'i:pllppppp', 'pst_surface_keep_count': 'i:pplipp', 'pst_surface_keep_emit': 'i:ppppplippppp',
+    'pst_simplify_used': 'i:pllppp', 'pst_simplify_mask': 'i:pplppp', 'pst_simplify_remap': 'i:pllpliplpppip', 'pst_simplify_count': 'i:pplipp',
+    'pst_simplify_emit': 'i:pppppplllipppppp',
     'pst_mesh_sample_count': 'i:plplfipppp', 'pst_mesh_sample_emit': 'i:plplpllppppppp',
     'pst_nn_insert': 'i:plfplpppp', 'pst_nn_scatter': 'i:plpppppp', 'pst_nn_query': 'i:plplffplpppipppp',
     'pst_icp_chunk': 'i:', 'pst_icp_step': 'i:plffffffffffffplffplpppipppppp',
@@ -1854,6 +1856,81 @@ def surface_keep_emit(faces, face_ids, quad, component, ws, min_faces, base, out
     _call('pst_surface_keep_emit', pf, b('face_ids', face_ids, I32, F), b('quad', quad, I64, F), b('component', component, I32, F), b('size', ws['size'], I32, M), F,
           int(min_faces), b('base', base, I32, _wgs(F, SURFACE_WG) + 1), b('out_faces', out_faces, I32, 3 * F), b('out_face_ids', out_face_ids, I32, F),
           b('out_quad', out_quad, I64, F))
+
+
+# ------------------------------------------------------------------ mesh simplification by vertex clustering (csrc/simplify.hip; engine/simplify.py holds the public entry points)
+SIMPLIFY_MERGE = 1                  # let the first lane of a run of adjacent faces with one key probe for the run (same results)
+SIMPLIFY_FULL, SIMPLIFY_RANGE = 1, 4                 # PST_SIMPLIFY_*: the bits of status[0]
+SIMPLIFY_MAX_KEYED = 2 ** 21 - 2    # the new vertices a 3 x 21-bit face key takes (dedupe)
+SIMPLIFY_STATUS_WORDS = 8
+
+
+def simplify_workspace(M, F, device):
+    """used int32 [M] (zeroed), face_slot int32 [F] and the zeroed status words of one simplification; `simplify_table` adds the face table"""
+    return {'used': torch.zeros(M, dtype=torch.int32, device=device), 'face_slot': torch.empty(F, dtype=torch.int32, device=device),
+            'status': torch.zeros(SIMPLIFY_STATUS_WORDS, dtype=torch.int32, device=device), 'cap': 0, 'keys': None, 'winner': None}
+
+
+def simplify_table(ws):
+    """the initialised open-addressing table of the faces (dedupe): keys all ones, winner INT32_MAX, capacity the next power of two >= 2 F"""
+    F, dev = ws['face_slot'].numel(), ws['face_slot'].device
+    ws['cap'] = voxel_capacity(F)
+    ws['keys'] = torch.full((ws['cap'],), -1, dtype=torch.int64, device=dev)
+    ws['winner'] = torch.full((ws['cap'],), 2 ** 31 - 1, dtype=torch.int32, device=dev)
+    return ws
+
+
+def _simplify_status(b, ws):
+    return b('status', ws['status'], I32, SIMPLIFY_STATUS_WORDS)
+
+
+def simplify_used(faces, ws):
+    """ws['used'][v] = 1 for every vertex row a face names; a corner outside the rows sets SIMPLIFY_RANGE"""
+    b = _Operands('simplify_used')
+    pf, F = b.rows3('faces', faces, I32)
+    pu, M = b.sized('used', ws['used'], I32)
+    b.require(F > 0 and M > 0, 'a mesh without faces or vertex rows')
+    _call('pst_simplify_used', pf, F, M, pu, _simplify_status(b, ws))
+
+
+def simplify_mask(vertices, ws, masked):
+    """masked fp32 [M, 3] = the used vertices, NaN for the others; status[1] += the used vertices"""
+    b = _Operands('simplify_mask')
+    pv, M = b.rows3('vertices', vertices, F32)
+    b.require(M > 0, 'a mesh without vertex rows')
+    _call('pst_simplify_mask', pv, b('used', ws['used'], I32, M), M, b('masked', masked, F32, 3 * M), _simplify_status(b, ws))
+
+
+def simplify_remap(faces, cluster, Mv, dedupe, ws, merge=None):
+    """ws['face_slot'] int32 [F]: every face's slot in the face table (0 without dedupe), -1 left out, -2 degenerate; status[2 .. 4] count the faces
+    left out, degenerate and remaining"""
+    b = _Operands('simplify_remap')
+    pf, F = b.rows3('faces', faces, I32)
+    pc, M = b.sized('cluster', cluster, I32)
+    b.require(F > 0 and 0 < Mv <= M, 'a mesh without faces, or %d new vertices of %d', Mv, M)
+    cap = ws['cap'] if dedupe else 0
+    b.require(not dedupe or cap >= 2 * F, 'dedupe without a face table (simplify_table) of at least 2 F slots')
+    _call('pst_simplify_remap', pf, F, M, pc, int(Mv), int(bool(dedupe)), b('keys', ws['keys'], I64, cap) if dedupe else None, cap,
+          b('winner', ws['winner'], I32, cap) if dedupe else None, b('face_slot', ws['face_slot'], I32, F), _simplify_status(b, ws),
+          int(SIMPLIFY_MERGE if merge is None else merge))
+
+
+def simplify_count(dedupe, ws, counts):
+    b = _Operands('simplify_count')
+    ps, F = b.sized('face_slot', ws['face_slot'], I32, 1)
+    _call('pst_simplify_count', ps, b('winner', ws['winner'], I32, ws['cap']) if dedupe else None, F, int(bool(dedupe)),
+          b('counts', counts, I32, _wgs(F, SURFACE_WG)))
+
+
+def simplify_emit(faces, quad, cluster, vertex_ids, Mv, dedupe, ws, base, out_faces, out_face_ids, out_quad, src_face):
+    """the surviving faces in their order -> rows [0, base[-1]) of the outputs (each F rows); vertex_ids int32: the NEW vertices' ids, at least Mv"""
+    b = _Operands('simplify_emit')
+    pf, F = b.rows3('faces', faces, I32)
+    pc, M = b.sized('cluster', cluster, I32)
+    b.require(F > 0 and 0 < Mv <= M, 'a mesh without faces, or %d new vertices of %d', Mv, M)
+    _call('pst_simplify_emit', pf, b('quad', quad, I64, F), pc, b.ge('vertex_ids', vertex_ids, I32, Mv), b('face_slot', ws['face_slot'], I32, F),
+          b('winner', ws['winner'], I32, ws['cap']) if dedupe else None, F, M, int(Mv), int(bool(dedupe)), b('base', base, I32, _wgs(F, SURFACE_WG) + 1),
+          b('out_faces', out_faces, I32, 3 * F), b('out_face_ids', out_face_ids, I32, F), b('out_quad', out_quad, I64, F), b('src_face', src_face, I32, F))
 
 
 # ------------------------------------------------------------------ 3-D scores: mesh surface sampler and fixed-radius nearest neighbour (csrc/nearest.hip; engine/score3d.py holds the public entry points)
