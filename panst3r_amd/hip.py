@@ -928,23 +928,45 @@ def dino_preprocess(img, out):
 def image_prepare(src_u8, out, resized, crop_origin):
     """decoded uint8 [Hs, Ws, 3] (device) -> fp32 `out` [3, H, W] in [-1, 1]: ImgNorm, antialiased bilinear resize to `resized` = (Hr, Wr),
     crop of out's size at `crop_origin` = (top, left)."""
-    _dev(src_u8, torch.uint8); _dev(out, torch.float32)
-    assert src_u8.dim() == 3 and src_u8.shape[2] == 3 and src_u8.is_contiguous() and out.is_contiguous() and out.shape[0] == 3
-    Hs, Ws = src_u8.shape[:2]
-    _call('pst_image_prepare', _ptr(src_u8), Hs, Ws, _ptr(out), int(resized[0]), int(resized[1]), int(crop_origin[0]), int(crop_origin[1]), out.shape[1],
-          out.shape[2])
+    b = _Operands('image_prepare')
+    src, dst = b('src_u8', src_u8, U8, (-1, -1, 3)), b('out', out, F32, (3, -1, -1))
+    (Hs, Ws), (H, W) = src_u8.shape[:2], out.shape[1:]
+    Hr, Wr, top, left = int(resized[0]), int(resized[1]), int(crop_origin[0]), int(crop_origin[1])
+    b.require(min(Hs, Ws, H, W, Hr, Wr) > 0, 'every size must be positive, got src %d x %d, resized %d x %d, out %d x %d', Hs, Ws, Hr, Wr, H, W)
+    b.require(top >= 0 and left >= 0 and top + H <= Hr and left + W <= Wr,
+              'the crop must lie inside the resized image %d x %d, got %d x %d at (%d, %d)', Hr, Wr, H, W, top, left)
+    _call('pst_image_prepare', src, Hs, Ws, dst, Hr, Wr, top, left, H, W)
     return out
 
 
 @hbm_timed('patch_rows', lambda img, enc=None, dino=None, **k: img.numel() * 4 + (enc.numel() * 2 if enc is not None else 0) + (dino.numel() * 2 if dino is not None else 0))
 def patch_rows(img, enc=None, dino=None, p_enc=16, p_dino=14, dino_transposed=False):
     """fp32 images [n, 3, H, W] -> patch rows of the encoder (`enc` 16-bit [n*T, >= 3 p^2]) and / or DINOv2 (`dino`) in one launch."""
-    _dev(img, torch.float32)
-    assert img.is_contiguous() and (enc is not None or dino is not None)
+    b = _Operands('patch_rows')
+    p_enc, p_dino = int(p_enc), int(p_dino)
+    pimg = b('img', img, F32, (-1, 3, -1, -1))
     n, _, H, W = img.shape
-    d16 = _fmt(enc, dino)
-    _call('pst_patch_rows', _ptr(img), _ptr(enc), (_rowmajor(enc) if enc is not None else 0), _ptr(dino), (_rowmajor(dino) if dino is not None else 0), n, H, W,
-          p_enc, p_dino, dino_transposed, d16)
+    b.require(enc is not None or dino is not None, 'needs enc or dino (or both), got neither')
+    b.require(n > 0 and p_enc > 0 and H > 0 and W > 0 and H % p_enc == 0 and W % p_enc == 0,
+              'img must hold images whose sides are multiples of p_enc = %d, got %d of %d x %d', p_enc, n, H, W)
+    rows = n * (H // p_enc) * (W // p_enc)
+    ptr = {}
+    for name, t, p in (('enc', enc, p_enc), ('dino', dino, p_dino)):
+        ptr[name] = b(name, t, FMT, (-1, -1), optional=True, layout='rows')
+        if t is None:
+            continue
+        ld = t.stride(0)
+        b.require(p > 0 and t.shape[1] >= 3 * p * p, '%s must have at least 3 p^2 = %d columns (p = %d), got %d', name, 3 * p * p, p, t.shape[1])
+        b.require(t.shape[0] >= rows, '%s must have at least n (H / p_enc) (W / p_enc) = %d rows, got %d', name, rows, t.shape[0])
+        b.require(ld >= t.shape[1], '%s must have a leading dimension of at least its %d columns, got stride %d', name, t.shape[1], ld)
+        # every row is zero-filled up to its leading dimension: the last row's padding must still lie in the storage
+        held = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+        b.require(held >= rows * ld, '%s: %d rows of leading dimension %d need %d elements of storage behind the first, got %d',
+                  name, rows, ld, rows * ld, held)
+    b.require(enc is None or dino is None or enc.dtype == dino.dtype, 'enc and dino must share one of the formats bf16 / f16 / f32, got %s and %s',
+              getattr(enc, 'dtype', None), getattr(dino, 'dtype', None))
+    _call('pst_patch_rows', pimg, ptr['enc'], (enc.stride(0) if enc is not None else 0), ptr['dino'], (dino.stride(0) if dino is not None else 0), n, H, W,
+          p_enc, p_dino, bool(dino_transposed), _tc(enc if enc is not None else dino))
     return enc, dino
 
 

@@ -7,7 +7,8 @@ derived from the kernel's rounding steps does not.  References are float64 evalu
 Notation: u(f) = unit roundoff of format f (bf16 2^-8, f16 2^-11, fp32 2^-24); tiny(f) = half the smallest subnormal spacing (the absolute error of a rounding
 near zero).  tests/test_errbound.py proves on the CPU, for every bound here, that an emulation of the kernel's rounding path stays below half the bound and that
 the typical kernel mistakes (accumulator through a 16-bit format, P rounded to the wrong format, a dropped key, a negated fragment, wrong LayerNorm eps, ...)
-exceed it; tests/test_smallops_host.py does the same for the small row and pixel operations at the end of this file.
+exceed it; tests/test_smallops_host.py does the same for the small row and pixel operations and tests/test_input_host.py for the image input at the end of
+this file.
 
 PST_ERRBOUND_LOG=<path>: every check() appends one JSON line {what, ratio, n} there (the per-family maxima the GPU run reports).
 """
@@ -532,3 +533,84 @@ def dino_tap_err(t, nv, std):
     u32 (|t| / std + 2 |nv|) - three roundings per tap."""
     t, nv = torch.as_tensor(t, dtype=torch.float64), torch.as_tensor(nv, dtype=torch.float64)
     return U32 * (t.abs() / torch.as_tensor(std, dtype=torch.float64) + 2 * nv.abs())
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------- image input
+# image.hip's image_prepare (tests/test_hip_input.py; soundness and tightness: tests/test_input_host.py).  patch_rows has no bound of its own: its encoder
+# half is exact and its DINOv2 half is dino_preprocess's expression, held under resize_bound with dino_tap_err.
+def aa_axis(n_in, n_out, lo, n):
+    """The per-axis terms of aa_resize_bound for the outputs lo .. lo + n - 1 of an antialiased resize of n_in source pixels to n_out.
+
+    Exact rule (float64): raw weight t_j = tri((j + 0.5 - c) / s), c = (i + 0.5) n_in / n_out, s = max(n_in / n_out, 1), w_j = t_j / T, T = sum_j t_j.
+    The kernel (aa_window): scale' = fl(n_in / n_out), c' = fl(scale' (i + 0.5)) (no fma can form: the sum is inside the product), inv' = fl(1 / scale') or 1,
+    window [max((int)(c' - s' + 0.5f), 0), min((int)(c' + s' + 0.5f), n_in)).  These are evaluated HERE in numpy fp32, operation by operation: they are the
+    rule's definition in fp32, not an observation of the kernel, and they make the coordinate term exactly zero where scale', c' and inv' are exact.
+
+    Arithmetic, relative to the window (`arith`, in units of u32 |pixel|max).  x'_j = ((float)j - c' + 0.5f) inv' rounds three times: the two sums are each
+    relative to at most |j - c'| <= s |x_j| + 0.5, the product to |x_j|; 1 - |x| rounds once (t_j): a_j = (3 |x_j| + t_j + inv' / 2) u32 per raw weight
+    (tri is 1-Lipschitz, so the error of x' is the error of t' also where one of the two is clipped to 0).  The sum T' of the nk window taps: sum_j a_j and
+    nk - 1 additions of partial sums <= T.  w'_j = fl(t'_j / T'): a_j / T + w_j ((sum a + (nk - 1) u32 T) / T + u32).  Summed over the window:
+        sum_j |w'_j - w_j| <= (2 sum_j a_j / T + nk) u32                                                    [weights]
+    and the convex sum over the nk taps itself, product and addition rounded separately (an fma only removes the first): (nk + 1) u32  [accumulation].
+    Coordinate (`coord`, in units of the half-range of the pixels under the window: both weight sets sum to 1, so only differences of pixels pass).  With
+    dc = |c' - c| and dinv = |inv' - 1 / s|, t_j moves by dt_j <= dc inv' + |j + 0.5 - c| dinv (tri is 1-Lipschitz).  A tap with t_j > 0 that the fp32 window
+    leaves out moves by its whole weight, dt_j = t_j (at most the window edge's own error over the support); a tap the window adds beyond the support has
+    t_j = 0 and is one of the nk taps above.  |w'_j - w_j| <= dt_j / T~ + t_j |1 / T~ - 1 / T| with T~ >= T - sum dt:
+        sum_j |w'_j - w_j| <= 2 sum_j dt_j / (T - sum_j dt_j).
+    A worst case in its own right (nothing here is a rounding of unknown sign and size): not doubled.
+    -> dict of float64 [n]: arith, coord; int64 [n]: nk (fp32 window's taps), wlo, whi (the union of the fp32 window and the exact support, [wlo, whi))."""
+    import numpy as np
+    f32 = np.float32
+    i = np.arange(lo, lo + n)
+    j = np.arange(n_in)
+    scale = n_in / n_out
+    s = max(scale, 1.0)
+    c = (i + 0.5) * scale
+    x = (j[None, :] + 0.5 - c[:, None]) / s
+    t = np.clip(1.0 - np.abs(x), 0.0, None)
+    T = t.sum(1)
+    sk = f32(n_in) / f32(n_out)
+    ck = (sk * (i.astype(f32) + f32(0.5))).astype(f32)
+    supk = sk if sk >= 1 else f32(1.0)
+    invk = f32(1.0) / sk if sk >= 1 else f32(1.0)
+    klo = np.maximum((ck - supk + f32(0.5)).astype(f32).astype(np.int64), 0)
+    khi = np.minimum((ck + supk + f32(0.5)).astype(f32).astype(np.int64), n_in)
+    inwin = (j[None, :] >= klo[:, None]) & (j[None, :] < khi[:, None])
+    nk = inwin.sum(1)
+    a = (3.0 * np.abs(x) + t + 0.5 * float(invk)) * inwin
+    arith = 2.0 * a.sum(1) / T + nk + (nk + 1)
+    dc = np.abs(ck.astype(np.float64) - c)
+    dinv = abs(float(invk) - 1.0 / s)
+    dt = np.where(inwin, dc[:, None] * float(invk) + np.abs(j[None, :] + 0.5 - c[:, None]) * dinv, t)
+    dt = np.where(inwin | (t > 0), dt, 0.0)
+    sdt = dt.sum(1)
+    coord = 2.0 * sdt / np.clip(T - sdt, 1e-300, None)
+    has = inwin | (t > 0)
+    wlo = np.where(has.any(1), has.argmax(1), 0)
+    whi = np.where(has.any(1), n_in - has[:, ::-1].argmax(1), 1)
+    as64 = lambda v: torch.from_numpy(np.asarray(v, dtype=np.float64))
+    return dict(arith=as64(arith), coord=as64(coord), nk=torch.from_numpy(nk), wlo=torch.from_numpy(wlo), whi=torch.from_numpy(whi))
+
+
+def aa_resize_bound(p, n_out, crop):
+    """Per-element bound of image_prepare against input_ref.aa_resize.  p = the ImgNorm pixels in float64 [3, Hs, Ws]; n_out = (Hr, Wr);
+    crop = (top, left, H, W).  -> float64 [3, H, W].
+
+    Pixel normalisation: t = fl(v / 255) (IEEE division), fl(t - 0.5), and / 0.5 is exact: 2 u32 (t + |t - 0.5|) = u32 (1 + p + |p|) <= u32 (1 + 2 |p|) per
+    pixel; the two nested sums are convex and pass it on unchanged.
+    Arithmetic and coordinate: aa_axis per axis.  The inner sum (x) errs by arith_x u32 pmax, the outer (y) by arith_y u32 pmax and passes the inner sum's
+    error on unchanged (convex); pmax = the largest |pixel| under the window - not the result, which cancels.  The coordinate terms add likewise, times the
+    half-range of the pixels under the window: (coord_y + coord_x) (max - min) / 2, zero on a constant image and wherever the fp32 scale and centres are exact.
+        bound = R u32 (pmax (arith_y + arith_x) + 1 + 2 pmax) + (coord_y + coord_x) halfrange + TINY32,
+    every rounding allowed twice (R) as everywhere here."""
+    p = p.double()
+    top, left, H, W = crop
+    ay, ax = aa_axis(p.shape[1], n_out[0], top, H), aa_axis(p.shape[2], n_out[1], left, W)
+    hi = torch.stack([p[:, int(a):int(b)].amax(1) for a, b in zip(ay['wlo'], ay['whi'])], 1)                 # [3, H, Ws]
+    lo = torch.stack([p[:, int(a):int(b)].amin(1) for a, b in zip(ay['wlo'], ay['whi'])], 1)
+    hi = torch.stack([hi[:, :, int(a):int(b)].amax(2) for a, b in zip(ax['wlo'], ax['whi'])], 2)             # [3, H, W]
+    lo = torch.stack([lo[:, :, int(a):int(b)].amin(2) for a, b in zip(ax['wlo'], ax['whi'])], 2)
+    pmax = torch.maximum(hi.abs(), lo.abs())
+    arith = ay['arith'][None, :, None] + ax['arith'][None, None, :]
+    coord = ay['coord'][None, :, None] + ax['coord'][None, None, :]
+    return R * U32 * (pmax * arith + 1.0 + 2.0 * pmax) + coord * (hi - lo) / 2.0 + TINY32
