@@ -4,11 +4,11 @@ PyTorch is plumbing here: it owns the HBM buffers and the HIP stream; every op b
 sizes and `torch.cuda.current_stream().cuda_stream` across the C ABI.  There is NO fallback: if the library is
 missing or an argument is rejected the op raises (RuntimeError), it never silently computes with torch.
 
-The library sees addresses and a few integers, so the wrapper is the only bounds check of a call.  Every engine entry point (from the panoptic
-post-processing section to the end of the file) takes each address from `_Operands`, where the argument goes: a tensor on the GPU, on the device of
-the call's other operands, of the header's dtype, contiguous, holding the elements the header states - exactly, or at least (`ge`) for a capacity.
+The library sees addresses and a few integers, so the wrapper is the only bounds check of a call.  Every entry point takes each address from
+`_Operands`, where the argument goes: a tensor on the GPU, on the device of the call's other operands, of the header's dtype, contiguous - or
+(`rows`) a row view at its leading dimension - holding the elements the header states: exactly, or at least (`ge`, `rows`) for a capacity.
 A failure is a RuntimeError naming the wrapper, the operand, what was expected and what was found; none is an `assert`, so `python -O` checks the
-same.  The GEMM / attention builders (the library checks their bounds itself) and the streaming model-path wrappers (strided arena views) are not.
+same.  The GEMM / attention builders name tensor, dtype and device the same way (`any`); the library checks their bounds itself.
 """
 import ctypes as C
 import math
@@ -53,7 +53,7 @@ class CloudView(C.Structure):
 # The C prototypes, one entry per exported function: 'return:arguments' in the type codes of _CODES; tests/test_abi.py checks every entry against the
 # header, and lib() declares them, so a call site passes plain Python numbers and ctypes converts (or refuses) them by the prototype.  The two parameter
 # structs the host fills are declared as pointers to them: only that struct is accepted, by reference.  Every other pointer - device memory (the
-# pst_cloud_view table included) and the stream - is an address: `_ptr` / `_stream` give plain ints or None.
+# pst_cloud_view table included) and the stream - is an address: `_Operands` / `_stream` give plain ints or None.
 _CODES = {'i': C.c_int, 'l': C.c_int64, 'u': C.c_uint64, 'f': C.c_float, 'd': C.c_double, 'p': vp, 's': C.c_char_p,
           'G': C.POINTER(GemmParams), 'A': C.POINTER(AttnParams)}
 SIGNATURES = {
@@ -132,10 +132,6 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _call(what, *args):
     """one launch of the entry point `what` on torch's current stream (every launching entry point takes the stream last); a refusal raises with the
     library's message.  Scalars go in as plain Python numbers: the declared prototype converts them, and refuses what does not fit its type."""
@@ -169,36 +165,39 @@ def _fmt(*ts):
     return _TC[dts.pop()]
 
 
-def _dev(t, *dtypes):
-    if not t.is_cuda:
-        raise RuntimeError('panst3r_amd HIP op got a %s tensor: the HIP path runs on the GPU only (no CPU fallback)' % t.device)
-    if dtypes and t.dtype not in dtypes:
-        raise RuntimeError('unexpected dtype %s (want %s)' % (t.dtype, dtypes))
-    return t
-
-
 I32, I64, F32, F64, U8 = torch.int32, torch.int64, torch.float32, torch.float64, torch.uint8
 
 
-def _check_operand(what, name, t, dtypes, n, at_least=False, optional=False, layout='dense'):
+def _check_operand(what, name, t, dtypes, n, at_least=False, optional=False, layout='dense', fill=False):
     """the part of an operand check that asks no device (tests/test_operand_check_host.py runs it on CPU tensors): `t` is a tensor of `dtypes` (one or a
-    tuple) that holds `n` elements - at least `n` with at_least - or, for a tuple `n`, has exactly that shape (-1: any extent).  layout 'dense':
-    contiguous; 'rows': a 2-D view with unit column stride (its leading dimension goes to the library); 'any': strides are the caller's business.
-    None passes only where `optional`.  Raises RuntimeError naming the wrapper `what` and the operand."""
+    tuple) that holds `n` elements - at least `n` with at_least - or, for a tuple `n`, has exactly that shape, at least those extents with at_least (-1: any).
+    layout 'dense': contiguous; 'any': strides are the caller's business; 'rows': a 2-D view with unit column stride (its leading dimension goes to the library) -
+    with at_least its rows must not overlap, and where the kernel fills every row up to the leading dimension (`fill`) rows x ld elements lie in the storage behind
+    the first.  None passes only where `optional`.  Raises RuntimeError naming the wrapper `what` and the operand."""
     if t is None and optional:
         return
     if not isinstance(t, torch.Tensor):
         raise RuntimeError('%s: %s must be a torch tensor, got %s' % (what, name, type(t).__name__))
-    if t.dtype != dtypes and (not isinstance(dtypes, tuple) or t.dtype not in dtypes):
-        raise RuntimeError('%s: %s: unexpected dtype %s (want %s)' % (what, name, t.dtype, dtypes))
+    dt, rowview = t.dtype, layout == 'rows' and at_least
+    if dt != dtypes and (not isinstance(dtypes, tuple) or dt not in dtypes):
+        raise RuntimeError('%s: %s: unexpected dtype %s (want %s)' % (what, name, dt, dtypes))
+    if rowview and t.dim() == 2:                                # the model path's operand, the one check of every eager launch: accepted here, refused below
+        (r, c), (ld, unit), (rows, cols) = t.shape, t.stride(), n
+        rows, cols = (r if rows < 0 else rows), (c if cols < 0 else cols)
+        held = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset() if fill else rows * ld
+        if unit == 1 and r >= rows and c >= cols and (ld >= cols or rows <= 1) and held >= rows * ld:
+            return
     if isinstance(n, tuple):
         sh = t.shape
-        if sh != n and (len(sh) != len(n) or [w for w, s in zip(n, sh) if w >= 0 and w != s]):
-            raise RuntimeError('%s: %s must have the shape %s (-1: any), got %s' % (what, name, n, tuple(sh)))
+        if sh != n and (len(sh) != len(n) or [w for w, s in zip(n, sh) if w >= 0 and (w > s if at_least else w != s)]):
+            raise RuntimeError('%s: %s must have the shape %s%s (-1: any), got %s' % (what, name, n, ' or more' if at_least else '', tuple(sh)))
     elif t.numel() != n and not (at_least and t.numel() > n):
         raise RuntimeError('%s: %s must hold %s%d elements, got %d' % (what, name, 'at least ' if at_least else '', n, t.numel()))
     if (layout == 'dense' and not t.is_contiguous()) or (layout == 'rows' and (t.dim() != 2 or t.stride(1) != 1)):
         raise RuntimeError('%s: %s must be %s, got shape %s, strides %s' % (what, name, 'contiguous' if layout == 'dense' else 'a row-major 2-D view', tuple(t.shape), t.stride()))
+    if rowview:
+        raise RuntimeError('%s: %s: %d rows of %d columns%s need a leading dimension of no less and %d elements of storage behind the first, got strides %s and %d'
+                           % (what, name, rows, cols, ' filled up to it' if fill else '', rows * ld, t.stride(), held))
 
 
 class _Operands:
@@ -209,21 +208,33 @@ class _Operands:
     def __init__(self, what):
         self.what, self.device = what, None
 
-    def __call__(self, name, t, dtypes, n, at_least=False, optional=False, layout='dense'):
-        _check_operand(self.what, name, t, dtypes, n, at_least, optional, layout)
+    def __call__(self, name, t, dtypes, n, at_least=False, optional=False, layout='dense', fill=False):
+        _check_operand(self.what, name, t, dtypes, n, at_least, optional, layout, fill)
         if t is None:
             return None
-        device = t.get_device()                 # -1: not on a GPU
-        if device != self.device:
-            if device < 0:
-                raise RuntimeError('%s: %s is a %s tensor: the HIP path runs on the GPU only (no CPU fallback)' % (self.what, name, t.device))
-            if self.device is not None:
-                raise RuntimeError('%s: %s is on %s, the operands before it on GPU %d' % (self.what, name, t.device, self.device))
-            self.device = device
+        if t.get_device() != self.device:
+            self._place(name, t)
         return t.data_ptr()
+
+    def _place(self, name, t):                  # the first operand sets the device of the call
+        if t.get_device() < 0:                  # -1: not on a GPU
+            raise RuntimeError('%s: %s is a %s tensor: the HIP path runs on the GPU only (no CPU fallback)' % (self.what, name, t.device))
+        if self.device is not None:
+            raise RuntimeError('%s: %s is on %s, the operands before it on GPU %d' % (self.what, name, t.device, self.device))
+        self.device = t.get_device()
 
     def ge(self, name, t, dtypes, n, optional=False):       # a capacity: at least n elements
         return self(name, t, dtypes, n, True, optional)
+
+    def any(self, name, t, dtypes, optional=False):         # a GEMM / attention operand: its strides go to the library, which checks its bounds
+        return self(name, t, dtypes, 0, True, optional, 'any')
+
+    def rows(self, name, t, dtypes, rows, cols, fill=False, optional=False):
+        """a row view of `rows` x `cols` or more (-1: its own extent) -> (address, leading dimension); (None, 0) for an absent optional operand"""
+        return self(name, t, dtypes, (rows, cols), True, optional, 'rows', fill), (0 if t is None else t.stride(0))
+
+    def own(self, name, t, dtypes):                         # a row view whose own shape sizes its call -> (address, leading dimension, rows, columns)
+        return self.rows(name, t, dtypes, -1, -1) + tuple(t.shape)
 
     def sized(self, name, t, dtype, n=0):
         """an operand whose own length (n at the least) sizes its call -> (address, elements)"""
@@ -336,10 +347,6 @@ def maxabs_report(log, top=None):
     return rows[:top] if top else rows
 
 
-def _esz(t):
-    return t.element_size()
-
-
 def hbm_timed(name, nbytes):
     """Decorator for the HBM-bound streaming ops: with a KernelTimer installed the launch is bracketed by HIP events on the launch stream
     and recorded with its ALGORITHMIC byte count nbytes(*args) (bench.py reports GB/s per stage against the 8 TB/s HBM peak)."""
@@ -379,11 +386,6 @@ def zeros_page(device):
     return z
 
 
-def _rowmajor(t):
-    assert t.dim() == 2 and t.stride(1) == 1, 'need a row-major 2-D view, got strides %s' % (t.stride(),)
-    return t.stride(0)
-
-
 # ----------------------------------------------------------------------------------------------------------- GEMM
 ACT = {None: 0, 'none': 0, 'gelu': 1, 'relu': 2, 'gelu_tanh': 3}      # 'gelu_tanh' (ABI 20): fp32 operands only (the SigLIP text tower's MLP)
 
@@ -395,60 +397,52 @@ def _gemm_params(a, w, out, bias=None, gamma=None, res=None, res_mod=0, act=None
     a, w, out (and res) all fp32: the amp=False mode's fp32-input-MFMA GEMM (same epilogues; no fused RoPE, no LayerNorm fold).
     LayerNorm fold (include/panst3r_hip.h): producer side `xcopy` (16-bit copy of an fp32 out) and `stats_out` (fp32 [M, N/64, 2]);
     consumer side `ln` = (stats [M, groups, 2], colsum [N], eps) with `a` the raw rows and `w` / `bias` folded at pack time."""
-    _dev(a, *FMT); _dev(w, *FMT); _dev(out, *FMT)
+    b = _Operands('gemm')
     p = GemmParams()
-    p.dtype16 = _fmt(a, w) if a.dtype == torch.float32 else _same16(a, w, out, res)       # fp32 operands: C / res must be fp32 too (checked by the C side)
+    p.W, p.ldw = b.rows('w', w, FMT, 0, 0)
     N, K = w.shape
     if conv is not None:
         cc, ch, cw = conv
         p.conv_c, p.conv_h, p.conv_w = cc, ch, cw
-        Mv = a.numel() // cc
-        p.lda = cc
-        assert K == 9 * cc
+        p.A, p.lda, Mv = b.any('a', a, FMT), cc, a.numel() // cc
+        b.require(K == 9 * cc, 'a 3x3 conv over %d channels needs K = %d, got w %s', cc, 9 * cc, tuple(w.shape))
     else:
-        Mv = a.shape[0] if M is None else M
-        assert a.shape[1] == K, (a.shape, w.shape)
-        p.lda = _rowmajor(a)
-    p.A, p.W, p.C = _ptr(a), _ptr(w), _ptr(out)
-    p.ldw = _rowmajor(w)
-    p.M, p.N, p.K = Mv, N, K
-    p.zeros = _ptr(zeros_page(a.device))
+        (p.A, p.lda), Mv = b.rows('a', a, FMT, 0, 0), (a.shape[0] if M is None else M)
+        b.require(a.shape[1] == K, 'a %s and w %s must share K', tuple(a.shape), tuple(w.shape))
     if ps is not None:
         p.ps_p, p.ps_c, p.ps_h, p.ps_w = ps
-        p.ldc = 0
+        p.C, p.ldc = b.any('out', out, FMT), 0
     else:
-        p.ldc = _rowmajor(out)
-    if bias is not None:
-        p.bias = _ptr(_dev(bias, torch.float32))
-    if gamma is not None:
-        p.gamma = _ptr(_dev(gamma, torch.float32))
+        p.C, p.ldc = b.rows('out', out, FMT, 0, 0)
+    p.dtype16 = _fmt(a, w) if a.dtype == torch.float32 else _same16(a, w, out, res)       # fp32 operands: C / res must be fp32 too (checked by the C side)
+    p.M, p.N, p.K = Mv, N, K
+    p.zeros = zeros_page(a.device).data_ptr()
+    p.bias, p.gamma = b.any('bias', bias, F32, True), b.any('gamma', gamma, F32, True)
     if res is not None:
-        p.res, p.ldr, p.res_mod = _ptr(_dev(res, torch.float32, *H16)), _rowmajor(res), res_mod
+        (p.res, p.ldr), p.res_mod = b.rows('res', res, FMT, 0, 0), res_mod
         p.res_bf16 = int(res.dtype in H16)
     if batch is not None:        # (count, a_bs, w_bs, c_bs, bias_bs): `a`, `w`, `out`, `bias` are problem 0 of a strided batch
         p.batch, p.a_bs, p.w_bs, p.c_bs, p.bias_bs = batch
     p.act = ACT[act]
     p.out_fp32 = int(out.dtype == torch.float32)
     if x3_block:                    # split store: the fp32 result as the f16 A-operand rows [hi | hi | lo] of the next 3 x f16 GEMM (pst_gemm_params.x3_block)
-        assert out.dtype == X3_FMT and out.shape[1] >= 3 * x3_block
+        b.require(out.dtype == X3_FMT and out.shape[1] >= 3 * x3_block, 'a split store needs an f16 out of at least 3 x3_block columns, got %s %s', out.dtype, tuple(out.shape))
         p.out_fp32, p.x3_block = 1, int(x3_block)
     p.trans_out = int(trans_out)
     p.kernel = kernel
     if rope is not None:            # (pos int32 [rows,2], table fp32 [npos,16,2]): RoPE-2D fused into the store, hd 64
-        p.rope_pos, p.rope_cs, p.rope_hd = _ptr(_dev(rope[0], torch.int32)), _ptr(_dev(rope[1], torch.float32)), 64
+        p.rope_pos, p.rope_cs, p.rope_hd = b.any('rope pos', rope[0], I32), b.any('rope table', rope[1], F32), 64
         p.rope_npos = int(rope[1].shape[0])
     if grp is not None:
         p.grp_in, p.grp_out, p.grp_off = grp
     if xcopy is not None:
-        p.xcopy, p.ldxc = _ptr(_dev(xcopy, a.dtype)), _rowmajor(xcopy)
+        p.xcopy, p.ldxc = b.rows('xcopy', xcopy, a.dtype, 0, 0)
     if stats_out is not None:
-        assert stats_out.dtype == torch.float32 and stats_out.dim() == 3 and stats_out.shape[2] == 2 and stats_out.is_contiguous()
-        p.stats_out, p.stats_ld = _ptr(_dev(stats_out)), stats_out.shape[1]
+        p.stats_out, p.stats_ld = b('stats_out', stats_out, F32, (-1, -1, 2)), stats_out.shape[1]
     if ln is not None:
         st, cs, eps = ln
-        assert st.dtype == torch.float32 and st.dim() == 3 and st.shape[2] == 2 and st.is_contiguous() and st.shape[1] * 64 >= K
-        p.ln_stats, p.ln_groups, p.ln_colsum, p.ln_eps = _ptr(_dev(st)), K // 64, _ptr(_dev(cs, torch.float32)), float(eps)
-        assert K % 64 == 0 and st.shape[1] == K // 64, 'LayerNorm fold: the statistics must cover exactly the K columns of A'
+        p.ln_stats, p.ln_groups, p.ln_colsum, p.ln_eps = b('ln stats', st, F32, (-1, -1, 2)), K // 64, b.any('ln colsum', cs, F32), float(eps)
+        b.require(K % 64 == 0 and st.shape[1] == K // 64, 'LayerNorm fold: the statistics must cover exactly the K = %d columns of a, got %s', K, tuple(st.shape))
     tag = (Mv, N, K, 'f32' if out.dtype == torch.float32 else '16', act or '', 'res' if res is not None else '',
            'grp' if grp is not None else '', 'rope' if rope is not None else '', 'conv' if conv is not None else '', 'ps' if ps is not None else '')
     return p, 2.0 * Mv * N * K * (batch[0] if batch else 1), tag
@@ -467,42 +461,45 @@ X3H = 4            # PST_X3H: output type code of layernorm / attention - f16 ro
 
 def split_operand(x, side, kpad=None, out=None, fmt=None):
     """fp32 x [rows, K] -> 16-bit [rows, 3 kpad] = [hi | hi | lo] (side 0: a GEMM's A operand) or [hi | lo | hi] (side 1: its W operand); zero beyond K"""
-    _dev(x, torch.float32)
-    rows, K = x.shape
+    b = _Operands('split_operand')
+    px, ldx, rows, K = b.own('x', x, F32)
     kpad = (K + 63) // 64 * 64 if kpad is None else kpad
     if out is None:
         out = torch.empty(rows, 3 * kpad, dtype=fmt or X3_FMT, device=x.device)
-    _call('pst_split_operand', _ptr(x), _rowmajor(x), _ptr(out), _rowmajor(out), rows, K, kpad, side, _tc(out))
+    _call('pst_split_operand', px, ldx, *b.rows('out', out, H16, rows, 3 * kpad), rows, K, kpad, side, _tc(out))
     return out
 
 
 def split2(x, transpose=False, hi=None, lo=None, fmt=None):
     """fp32 x [rows, K] -> (hi, lo) 16-bit planes of x (or of x^T: [K, rows rounded up to 8])"""
-    _dev(x, torch.float32)
-    rows, K = x.shape
+    b = _Operands('split2')
+    px, ldx, rows, K = b.own('x', x, F32)
+    shape = (K, (rows + 7) // 8 * 8) if transpose else (rows, K)
     if hi is None:
-        shape = (K, (rows + 7) // 8 * 8) if transpose else (rows, K)
         hi, lo = torch.empty(shape, dtype=fmt or X3_FMT, device=x.device), torch.empty(shape, dtype=fmt or X3_FMT, device=x.device)
-    _call('pst_split2', _ptr(x), _rowmajor(x), _ptr(hi), _ptr(lo), _rowmajor(hi), rows, K, transpose, _tc(hi))
+    (ph, ldo), (pl, ldl) = b.rows('hi', hi, H16, *shape), b.rows('lo', lo, H16, *shape)
+    b.require(ldl == ldo and lo.dtype == hi.dtype, 'hi and lo must share one format and leading dimension, got %s at %d and %s at %d', hi.dtype, ldo, lo.dtype, ldl)
+    _call('pst_split2', px, ldx, ph, pl, ldo, rows, K, transpose, _tc(hi))
     return hi, lo
 
 
 def rope2d_split(x, pos, table, nheads, hd, fmt=None):
     """RoPE-2D of the first nheads*hd columns of the fp32 rows x -> Planes(hi, lo) [rows, nheads*hd] of the rotated values (the q | k operand of attention on
     split operands; x is not modified): rope2d_ + split2 in one pass"""
-    _dev(x, torch.float32); _dev(pos, torch.int32); _dev(table, torch.float32)
-    rows, cols = x.shape[0], nheads * hd
+    b = _Operands('rope2d_split')
+    cols = nheads * hd
+    (px, ldx), rows = b.rows('x', x, F32, -1, cols), x.shape[0]
     hi = torch.empty(rows, cols, dtype=fmt or X3_FMT, device=x.device)
     lo = torch.empty(rows, cols, dtype=fmt or X3_FMT, device=x.device)
-    _call('pst_rope2d_split', _ptr(x), _rowmajor(x), _ptr(pos), _ptr(table), _ptr(hi), _ptr(lo), cols, rows, nheads, hd, _tc(hi))
+    _call('pst_rope2d_split', px, ldx, b('pos', pos, I32, 2 * rows), b('table', table, F32, (-1, hd // 4, 2)), hi.data_ptr(), lo.data_ptr(), cols, rows, nheads, hd, _tc(hi))
     return Planes(hi, lo)
 
 
 def transpose_f32(x, out):
     """out[c, r] = x[r, c] (fp32; out row-major with leading dimension >= rows)"""
-    _dev(x, torch.float32); _dev(out, torch.float32)
-    rows, cols = x.shape
-    _call('pst_transpose_f32', _ptr(x), _rowmajor(x), _ptr(out), _rowmajor(out), rows, cols)
+    b = _Operands('transpose_f32')
+    px, ldx, rows, cols = b.own('x', x, F32)
+    _call('pst_transpose_f32', px, ldx, *b.rows('out', out, F32, cols, rows), rows, cols)
     return out
 
 
@@ -521,7 +518,7 @@ def _trans_f32(M, N, out, kw):
     dst, c_bs = out, (batch[3] if batch else 0)
     if batch:
         kw['batch'] = batch[:3] + (M * N, batch[4])
-    ld_out = _rowmajor(dst)
+    ld_out = _Operands('gemm').rows('out', dst, FMT, 0, 0)[1]
 
     def finish():
         for i in range(cnt):
@@ -534,7 +531,7 @@ def _x3_prepare(a, w, out, kw):
     """One fp32-operand GEMM as a 16-bit GEMM over the 3 x longer K: returns (a3, w3, out', kw', finish).  `w` is a pre-split weight (16-bit [N, 3 Kpad],
     model.common.Packed) or an fp32 matrix split here; `finish()` runs what follows the launch (the transpose of a trans_out result: the 16-bit kernels
     store transposed results in 16 bit only)."""
-    kw = dict(kw)
+    kw, b = dict(kw), _Operands('gemm')
     if out.dtype != torch.float32 and not kw.get('x3_block'):
         raise RuntimeError('fp32-operand GEMM: the output must be fp32 (or the split form, x3_block=)')
     conv, batch = kw.get('conv'), kw.get('batch')
@@ -546,9 +543,10 @@ def _x3_prepare(a, w, out, kw):
             w = split_operand(w.reshape(N * 9, cc), 1, kpad=c64(cc)).reshape(N, 27 * c64(cc))
         elif batch is not None:
             count, a_bs, w_bs, c_bs, bias_bs = batch
-            if w_bs != N * _rowmajor(w):
+            ldw = b.rows('w', w, F32, 0, 0)[1]
+            if w_bs != N * ldw:
                 raise RuntimeError('fp32-operand GEMM: batched W problems must be stacked row blocks')
-            w = split_operand(w.as_strided((count * N, w.shape[1]), (_rowmajor(w), 1)), 1)
+            w = split_operand(w.as_strided((count * N, w.shape[1]), (ldw, 1)), 1)
             kw['batch'] = batch = (count, a_bs, N * w.shape[1], c_bs, bias_bs)
             w = w[:N]
         else:
@@ -557,7 +555,7 @@ def _x3_prepare(a, w, out, kw):
     if conv is not None:
         cc, ch, cw = conv
         a3 = split_operand(a.reshape(-1, cc), 0, kpad=c64(cc), fmt=fmt)
-        assert w.shape[1] == 27 * c64(cc), (tuple(w.shape), cc)
+        b.require(w.shape[1] == 27 * c64(cc), 'a split-packed 3x3 conv weight over %d channels has %d columns, got w %s', cc, 27 * c64(cc), tuple(w.shape))
         kw['conv'] = (3 * c64(cc), ch, cw)
     else:
         kpad = w.shape[1] // 3
@@ -568,7 +566,7 @@ def _x3_prepare(a, w, out, kw):
         src = a[:rows]
         if batch is not None:
             count, a_bs, w_bs, c_bs, bias_bs = batch
-            lda = _rowmajor(a)
+            lda = b.rows('a', a, F32, 0, 0)[1]
             if a_bs != rows * lda:
                 raise RuntimeError('fp32-operand GEMM: batched A problems must be stacked row blocks')
             src = a.as_strided((count * rows, a.shape[1]), (lda, 1))
@@ -662,13 +660,14 @@ def mask_head_supported(Q, P, C):
 def mask_head(embed, feats, out):
     """pred_masks of ALL views of a shape group in one launch (pst_mask_head): embed 16-bit [Q, C], feats 16-bit [n, P, C] (or [n, Hm, Wm, C]),
     out fp32 [n, Q, P] (or [n, Q, Hm, Wm]); bit-identical to n calls of gemm(embed, feats[i], out[i])."""
-    _dev(embed, *H16); _dev(feats, *H16); _dev(out, torch.float32)
-    n, C = feats.shape[0], feats.shape[-1]
+    b = _Operands('mask_head')
+    pe, lde, Q, C = b.own('embed', embed, H16)
+    pf = b.ge('feats', feats, H16, 1)
+    b.require(feats.dim() >= 2 and feats.shape[-1] == C, 'feats %s must end in the %d channels of embed', tuple(feats.shape), C)
+    n = feats.shape[0]
     P = feats.numel() // (n * C)
-    Q = embed.shape[0]
-    assert feats.is_contiguous() and out.is_contiguous() and out.numel() == n * Q * P and embed.shape[1] == C and embed.stride(1) == 1
     _timed('mask_head_kernel', 2.0 * n * Q * P * C, ('bytes', float(n * (C * P * 2 + Q * P * 4))), _call,
-           'pst_mask_head', _ptr(embed), embed.stride(0), _ptr(feats), P * C, _ptr(out), Q * P, n, Q, P, C, _same16(embed, feats))
+           'pst_mask_head', pe, lde, pf, P * C, b('out', out, F32, n * Q * P), Q * P, n, Q, P, C, _same16(embed, feats))
     return out
 
 
@@ -702,36 +701,36 @@ def attn_workspace_floats(B, H, Nq, Nk, hd, nsplit=None):
 def _attn_struct(fmt, q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides, scale, mask, mask_strides, ns, ws, prescaled):
     """pst_attn_params of operands in the format code `fmt`, q / k / vt given as addresses, over `ns` key-range splits (+ the workspace the caller
     must keep alive)"""
-    p = AttnParams()
+    p, b = AttnParams(), _Operands('attention')
     p.dtype16 = fmt
     p.Q, (p.q_bs, p.q_hs, p.q_rs) = q, q_strides
     p.K, (p.k_bs, p.k_hs, p.k_rs) = k, k_strides
     p.Vt, (p.v_bs, p.v_hs, p.v_ds) = vt, v_strides
-    p.O, (p.o_bs, p.o_hs, p.o_rs) = _ptr(out), o_strides
+    p.O, (p.o_bs, p.o_hs, p.o_rs) = out.data_ptr(), o_strides
     if mask is not None:
-        _dev(mask, torch.uint8)
-        p.mask, (p.m_bs, p.m_rs) = _ptr(mask), mask_strides
+        p.mask, (p.m_bs, p.m_rs) = b.any('mask', mask, U8), mask_strides
     p.B, p.H, p.Nq, p.Nk, p.hd = B, H, Nq, Nk, hd
     p.scale = float(hd ** -0.5 if scale is None else scale)
     p.prescaled = 1 if prescaled else 0
-    p.zeros = _ptr(zeros_page(out.device))
+    p.zeros = zeros_page(out.device).data_ptr()
     if ns > 1:
         n = attn_workspace_floats(B, H, Nq, Nk, hd, ns)
         if ws is None:          # caller-owned workspace preferred (C ABI: the caller owns every buffer); else one from torch's caching allocator
             ws = torch.empty(n, dtype=torch.float32, device=out.device)
-        assert ws.dtype == torch.float32 and ws.numel() >= n
-        p.nsplit, p.ws, p.ws_bytes = ns, _ptr(ws), ws.numel() * 4
+        p.nsplit, p.ws, p.ws_bytes = ns, b.ge('ws', ws, F32, n), ws.numel() * 4
     return p, ws
 
 
 def _attn_params(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides, scale=None, mask=None,
                  mask_strides=(0, 0), nsplit=None, ws=None, prescaled=False):
     """pst_attn_params of one hip.attention call (+ the tensors it must keep alive, flops, shape tag)"""
-    _dev(q, *FMT); _dev(k, *FMT); _dev(vt, *FMT); _dev(out, *FMT)
+    b = _Operands('attention')
+    pq, pk, pv = b.any('q', q, FMT), b.any('k', k, FMT), b.any('vt', vt, FMT)
+    b.any('out', out, FMT)
     ns = auto_nsplit(B, H, Nq, Nk) if nsplit is None else nsplit
     if q.dtype == torch.float32 and nsplit is None:
         ns = 1                      # the fp32 kernel does not split the key range
-    p, ws = _attn_struct(_fmt(q, k, vt, out), _ptr(q), _ptr(k), _ptr(vt), out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides,
+    p, ws = _attn_struct(_fmt(q, k, vt, out), pq, pk, pv, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides,
                          scale, mask, mask_strides, ns, ws, prescaled)
     return p, ws, 4.0 * B * H * Nq * Nk * hd, (B, H, Nq, Nk, hd)
 
@@ -759,17 +758,18 @@ def _span(B, H, N, strides, width):
 def _attention_x3(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides, scale, mask, mask_strides, nsplit, ws, prescaled):
     """attention on fp32 operands as 3 x 16-bit MFMA (pst_attn_x3): the memory spans the call touches are split into (hi, lo) planes once - operands
     that share a buffer (q | k of one projection, both halves of a pair) share the pass - and the kernel reads the planes with the caller's strides."""
-    _dev(out, torch.float32, X3_FMT)            # fp32, or (16-bit `out` [rows, 3 x block]) the split A operand of the output projection: PST_X3H
+    b = _Operands('attention')
+    b.any('out', out, (F32, X3_FMT))            # fp32, or (16-bit `out` [rows, 3 x block]) the split A operand of the output projection: PST_X3H
     out_type, out_block = (1, 0) if out.dtype == torch.float32 else (X3H, out.shape[-1] // 3)
     dev = out.device
     spans = []
-    for t, (lo_, hi_) in ((q, _span(B, H, Nq, q_strides, hd)), (k, _span(B, H, Nk, k_strides, hd)),
-                          (vt, _span(B, H, hd, v_strides, (Nk + 7) // 8 * 8))):         # (the kernel reads V^T in 8-key chunks: the last one may reach into the row's pad)
+    for name, t, (lo_, hi_) in (('q', q, _span(B, H, Nq, q_strides, hd)), ('k', k, _span(B, H, Nk, k_strides, hd)),
+                                ('vt', vt, _span(B, H, hd, v_strides, (Nk + 7) // 8 * 8))):         # (the kernel reads V^T in 8-key chunks: the last one may reach into the row's pad)
         if isinstance(t, Planes):               # prepared by the caller
             continue
-        _dev(t, torch.float32)
+        addr = b.any(name, t, F32)
         # (whole 16-byte groups: a key count that is not a multiple of 4 - DINOv2's 769 - ends inside the pad columns every V^T buffer carries)
-        spans.append([t.data_ptr() + 4 * lo_, t.data_ptr() + 4 * ((hi_ + 3) // 4 * 4)])
+        spans.append([addr + 4 * lo_, addr + 4 * ((hi_ + 3) // 4 * 4)])
     merged = []
     for a0, a1 in sorted(spans):
         if merged and a0 <= merged[-1][1]:
@@ -779,10 +779,10 @@ def _attention_x3(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strid
     planes = []
     for a0, a1 in merged:
         n = (a1 - a0) // 4
-        assert a0 % 16 == 0 and n % 4 == 0, 'attention operands must be 16-byte aligned with strides that are multiples of 8'
+        b.require(a0 % 16 == 0 and n % 4 == 0, 'the operands must be 16-byte aligned with strides that are multiples of 8')
         hi = torch.empty(n, dtype=X3_FMT, device=dev)
         lo = torch.empty(n, dtype=X3_FMT, device=dev)
-        _call('pst_split2', a0, n, _ptr(hi), _ptr(lo), n, 1, n, 0, _TC[X3_FMT])
+        _call('pst_split2', a0, n, hi.data_ptr(), lo.data_ptr(), n, 1, n, 0, _TC[X3_FMT])
         planes.append((a0, a1, hi, lo))
 
     def plane_ptrs(t):
@@ -793,7 +793,7 @@ def _attention_x3(q, k, vt, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strid
             if a0 <= addr < a1:                   # (an operand's own span always contains its pointer: offset 0 is one of the offsets it touches)
                 off = (addr - a0) // 2            # fp32 byte offset -> 16-bit byte offset
                 return hi.data_ptr() + off, lo.data_ptr() + off
-        raise AssertionError('attention operand outside the planes')
+        raise RuntimeError('attention: operand outside the planes')
     (qh, ql), (kh, kl), (vh, vl) = plane_ptrs(q), plane_ptrs(k), plane_ptrs(vt)
     p, ws = _attn_struct(_TC[X3_FMT], qh, kh, vh, out, B, H, Nq, Nk, hd, q_strides, k_strides, v_strides, o_strides, scale, mask, mask_strides,
                          auto_nsplit(B, H, Nq, Nk) if nsplit is None else nsplit, ws, prescaled)
@@ -824,65 +824,72 @@ def attention_pair(first, second):
 
 
 # ----------------------------------------------------------------------------------------------------------- the rest
+def _ln_views(b, x, add, out, rows, D, grp, split):
+    """the checked row views of a LayerNorm call -> ((x, ldx, type, add, ld_add, out, ldo, type), grp): `x` and `add` hold the remapped last row (the kernel reads
+    irow = (row / grp_in) * grp_out + grp_off + row % grp_in), `out` holds `rows` rows - as a split store (PST_X3H) three blocks of ldo / 3 >= D columns"""
+    g = grp or (0, 0, 0)
+    last = rows - 1
+    xrows = max(0, ((last // g[0]) * g[1] + g[2] + last % g[0] if g[0] > 0 else last) + 1)
+    px, ldx = b.rows('x', x, FMT, xrows, D)
+    pa, lda = b.rows('add', add, F32, xrows, D, optional=True)
+    po, ldo = b.rows('out', out, X3_FMT if split else FMT, rows, 3 * D if split else D, fill=split)
+    return (px, ldx, _tc(x), pa, lda, po, ldo, X3H if split else _tc(out)), g
+
+
 def layernorm_batch(x_all, gamma_all, beta_all, out_all, eps, rows=None, grp=None, add=None, split=False):
     """out_all[i] = LN(x_all[i] [+ add]) * gamma_all[i] + beta_all[i] for i < n in ONE launch; x_all [n, R, D], out_all [n, rows, D]
     (split=True: out_all f16 [n, rows, 3 D] = the split A operand rows [hi | hi | lo], PST_X3H)."""
-    _dev(x_all, torch.float32, *H16); _dev(out_all, torch.float32, *H16)
+    b = _Operands('layernorm_batch')
+    pg = b('gamma_all', gamma_all, F32, (-1, -1))
+    pb = b('beta_all', beta_all, F32, tuple(gamma_all.shape))
+    px, po = b.any('x_all', x_all, FMT), b.any('out_all', out_all, FMT)
     n, D = x_all.shape[0], gamma_all.shape[1]
-    assert x_all.dim() == 3 and out_all.dim() == 3 and x_all.stride(2) == 1 and out_all.stride(2) == 1 and gamma_all.is_contiguous() and beta_all.is_contiguous()
+    b.require(x_all.dim() == 3 and out_all.dim() == 3 and 0 < n <= min(out_all.shape[0], gamma_all.shape[0]), 'x_all and out_all must be [n, rows, columns] next to '
+              'gamma_all / beta_all [n or more, D], got %s, %s and %s', tuple(x_all.shape), tuple(out_all.shape), tuple(gamma_all.shape))
     rows = out_all.shape[1] if rows is None else rows
-    g = grp or (0, 0, 0)
-    _call('pst_layernorm_add_batch', _ptr(x_all), x_all.stride(1), _tc(x_all), _ptr(_dev(add, torch.float32)) if add is not None else None,
-          _rowmajor(add) if add is not None else 0, _ptr(out_all), out_all.stride(1), X3H if split else _tc(out_all), _ptr(_dev(gamma_all, torch.float32)),
-          _ptr(_dev(beta_all, torch.float32)), rows, D, eps, g[0], g[1], g[2], n, x_all.stride(0), out_all.stride(0), D)
+    v, g = _ln_views(b, x_all[n - 1], add, out_all[n - 1], rows, D, grp, split)      # the last problem: the batch strides keep every one inside the operands
+    _call('pst_layernorm_add_batch', px, *v[1:5], po, *v[6:], pg, pb, rows, D, eps, *g, n, x_all.stride(0), out_all.stride(0), D)
     return out_all
 
 
-@hbm_timed('layernorm', lambda x, gamma, beta, out, eps, rows=None, grp=None, add=None, split=False: (out.shape[0] if rows is None else rows) * gamma.numel() * (_esz(x) + (6 if split else _esz(out)) + (4 if add is not None else 0)))
+@hbm_timed('layernorm', lambda x, gamma, beta, out, eps, rows=None, grp=None, add=None, split=False: (out.shape[0] if rows is None else rows) * gamma.numel() * (x.element_size() + (6 if split else out.element_size()) + (4 if add is not None else 0)))
 def layernorm(x, gamma, beta, out, eps, rows=None, grp=None, add=None, split=False):
     """out = LN(x [+ add]); `add`: optional fp32 rows indexed like x (fused residual-style addend).  split=True: `out` f16 [rows, 3 x block] receives the
     result as the split A operand of a 3 x f16 GEMM (rows [hi | hi | lo], PST_X3H) - what split_operand(side 0) would make of the fp32 result."""
-    _dev(x, torch.float32, *H16); _dev(out, torch.float32, *H16)
-    D = gamma.numel()
+    b = _Operands('layernorm')
+    pg, D = b.sized('gamma', gamma, F32)
+    b.require(add is None or not split, 'a split output takes no addend')
     rows = out.shape[0] if rows is None else rows
-    g = grp or (0, 0, 0)
-    if split:
-        assert add is None and out.dtype == X3_FMT
-        _call('pst_layernorm', _ptr(x), _rowmajor(x), _tc(x), _ptr(out), _rowmajor(out), X3H, _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)),
-              rows, D, eps, g[0], g[1], g[2])
-        return out
+    v, g = _ln_views(b, x, add, out, rows, D, grp, split)
+    tail = (pg, b('beta', beta, F32, D), rows, D, eps, *g)
     if add is not None:
-        _call('pst_layernorm_add', _ptr(x), _rowmajor(x), _tc(x), _ptr(_dev(add, torch.float32)), _rowmajor(add), _ptr(out), _rowmajor(out), _tc(out),
-              _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)), rows, D, eps, g[0], g[1], g[2])
-        return out
-    _call('pst_layernorm', _ptr(x), _rowmajor(x), _tc(x), _ptr(out), _rowmajor(out), _tc(out), _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)),
-          rows, D, eps, g[0], g[1], g[2])
-    note_maxabs(out, 'layernorm D=%d out' % D)
+        _call('pst_layernorm_add', *v, *tail)
+    else:
+        _call('pst_layernorm', *v[:3], *v[5:], *tail)
+        note_maxabs(out[:rows, :D] if MAXABS is not None and not split else None, 'layernorm D=%d out' % D)      # only the region the launch wrote
     return out
 
 
-@hbm_timed('rowstats', lambda x, xcopy, stats: x.numel() * (_esz(x) + (2 if xcopy is not None else 0)))
+@hbm_timed('rowstats', lambda x, xcopy, stats: x.numel() * (x.element_size() + (2 if xcopy is not None else 0)))
 def rowstats(x, xcopy, stats):
     """LayerNorm-fold producer outputs for a stream no GEMM wrote: per-row (sum, sumsq) per 64-column group, plus the 16-bit copy of an
     fp32 stream (xcopy=None when x already is the 16-bit stream)."""
-    _dev(x, torch.float32, *H16); _dev(stats, torch.float32)
-    rows, D = x.shape
-    assert stats.dim() == 3 and stats.shape[2] == 2 and stats.is_contiguous() and stats.shape[1] * 64 >= D
-    if xcopy is None:
-        assert x.dtype in H16
-        d16 = _tc(x)
-    else:
-        d16 = _tc(_dev(xcopy, *H16))
-    _call('pst_rowstats', _ptr(x), _rowmajor(x), _tc(x), _ptr(xcopy), (_rowmajor(xcopy) if xcopy is not None else 0), _ptr(stats), stats.shape[1], rows, D, d16)
-    note_maxabs(xcopy, 'rowstats D=%d 16-bit copy of the residual stream' % D)
+    b = _Operands('rowstats')
+    px, ldx, rows, D = b.own('x', x, FMT if xcopy is not None else H16)         # (no 16-bit copy: x is the 16-bit stream)
+    pc, ldc = b.rows('xcopy', xcopy, H16, rows, D, optional=True)
+    ps = b('stats', stats, F32, (-1, -1, 2))
+    b.require(stats.shape[0] >= rows and stats.shape[1] * 64 >= D, 'stats must be [%d or more, %d or more, 2], got %s', rows, (D + 63) // 64, tuple(stats.shape))
+    _call('pst_rowstats', px, ldx, _tc(x), pc, ldc, ps, stats.shape[1], rows, D, _tc(x if xcopy is None else xcopy))
+    if MAXABS is not None and xcopy is not None:
+        note_maxabs(xcopy[:rows, :D], 'rowstats D=%d 16-bit copy of the residual stream' % D)
     return xcopy, stats
 
 
 def split3(x, out):
     """fp32 x [rows, K] -> bf16 out [rows, 3K] = [x_hi | x_hi | x_lo] (operand of a split-precision GEMM, see pack_split3)."""
-    _dev(x, torch.float32); _dev(out, *H16)
-    rows, K = x.shape
-    _call('pst_split3', _ptr(x), _rowmajor(x), _ptr(out), _rowmajor(out), rows, K, _tc(out))
+    b = _Operands('split3')
+    px, ldx, rows, K = b.own('x', x, F32)
+    _call('pst_split3', px, ldx, *b.rows('out', out, H16, rows, 3 * K), rows, K, _tc(out))
     return out
 
 
@@ -896,8 +903,9 @@ def pack_split3(weight, dtype=torch.bfloat16):
 
 def rope2d_(x, pos, table, nheads, hd):
     """In-place RoPE-2D on the first nheads*hd columns of the row-major bf16 view x; pos int32 [rows,2]."""
-    _dev(x, *FMT); _dev(pos, torch.int32); _dev(table, torch.float32)
-    _call('pst_rope2d', _ptr(x), _rowmajor(x), _ptr(pos), _ptr(table), x.shape[0], nheads, hd, _tc(x))
+    b = _Operands('rope2d_')
+    (px, ldx), rows = b.rows('x', x, FMT, -1, nheads * hd), x.shape[0]
+    _call('pst_rope2d', px, ldx, b('pos', pos, I32, 2 * rows), b('table', table, F32, (-1, hd // 4, 2)), rows, nheads, hd, _tc(x))
     return x
 
 
@@ -910,18 +918,19 @@ def rope_table(npos, hd, base=100.0, device='cuda'):
 
 
 def patchify(img, out, p):
-    _dev(img, torch.float32); _dev(out, *FMT)
+    b = _Operands('patchify')
+    pimg = b('img', img, F32, (-1, -1, -1, -1))
     n, c, h, w = img.shape
-    assert img.is_contiguous()
-    _call('pst_patchify', _ptr(img), _ptr(out), _rowmajor(out), n, c, h, w, p, _tc(out))
+    rows = n * (h // p) * (w // p) if p > 0 else 0
+    _call('pst_patchify', pimg, *b.rows('out', out, FMT, rows, c * p * p, fill=True), n, c, h, w, p, _tc(out))
     return out
 
 
 def dino_preprocess(img, out):
-    _dev(img, torch.float32); _dev(out, torch.float32)
+    b = _Operands('dino_preprocess')
+    pimg = b('img', img, F32, (-1, 3, -1, -1))
     n, _, h, w = img.shape
-    assert img.is_contiguous() and out.is_contiguous()
-    _call('pst_dino_preprocess', _ptr(img), _ptr(out), n, h, w, out.shape[-2], out.shape[-1])
+    _call('pst_dino_preprocess', pimg, b('out', out, F32, (n, 3, -1, -1)), n, h, w, out.shape[-2], out.shape[-1])
     return out
 
 
@@ -949,34 +958,22 @@ def patch_rows(img, enc=None, dino=None, p_enc=16, p_dino=14, dino_transposed=Fa
     b.require(enc is not None or dino is not None, 'needs enc or dino (or both), got neither')
     b.require(n > 0 and p_enc > 0 and H > 0 and W > 0 and H % p_enc == 0 and W % p_enc == 0,
               'img must hold images whose sides are multiples of p_enc = %d, got %d of %d x %d', p_enc, n, H, W)
+    b.require(p_dino > 0 or dino is None, 'p_dino must be positive, got %d', p_dino)
     rows = n * (H // p_enc) * (W // p_enc)
-    ptr = {}
-    for name, t, p in (('enc', enc, p_enc), ('dino', dino, p_dino)):
-        ptr[name] = b(name, t, FMT, (-1, -1), optional=True, layout='rows')
-        if t is None:
-            continue
-        ld = t.stride(0)
-        b.require(p > 0 and t.shape[1] >= 3 * p * p, '%s must have at least 3 p^2 = %d columns (p = %d), got %d', name, 3 * p * p, p, t.shape[1])
-        b.require(t.shape[0] >= rows, '%s must have at least n (H / p_enc) (W / p_enc) = %d rows, got %d', name, rows, t.shape[0])
-        b.require(ld >= t.shape[1], '%s must have a leading dimension of at least its %d columns, got stride %d', name, t.shape[1], ld)
-        # every row is zero-filled up to its leading dimension: the last row's padding must still lie in the storage
-        held = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
-        b.require(held >= rows * ld, '%s: %d rows of leading dimension %d need %d elements of storage behind the first, got %d',
-                  name, rows, ld, rows * ld, held)
+    views = b.rows('enc', enc, FMT, rows, 3 * p_enc * p_enc, True, True) + b.rows('dino', dino, FMT, rows, 3 * p_dino * p_dino, True, True)
     b.require(enc is None or dino is None or enc.dtype == dino.dtype, 'enc and dino must share one of the formats bf16 / f16 / f32, got %s and %s',
               getattr(enc, 'dtype', None), getattr(dino, 'dtype', None))
-    _call('pst_patch_rows', pimg, ptr['enc'], (enc.stride(0) if enc is not None else 0), ptr['dino'], (dino.stride(0) if dino is not None else 0), n, H, W,
-          p_enc, p_dino, bool(dino_transposed), _tc(enc if enc is not None else dino))
+    _call('pst_patch_rows', pimg, *views, n, H, W, p_enc, p_dino, bool(dino_transposed), _tc(enc if enc is not None else dino))
     return enc, dino
 
 
 def add_cast(a, out, b=None, b_mod=0):
-    _dev(a); _dev(out)
-    rows, D = out.shape
-    fp = _tc
-    _call('pst_add_cast', _ptr(a), _rowmajor(a), fp(a), _ptr(b), (_rowmajor(b) if b is not None else 0), fp(b) if b is not None else 0, b_mod, _ptr(out),
-          _rowmajor(out), fp(out), rows, D)
-    note_maxabs(out, 'add_cast D=%d out' % D)
+    c = _Operands('add_cast')
+    po, ldo, rows, D = c.own('out', out, FMT)
+    _call('pst_add_cast', *c.rows('a', a, FMT, rows, D), _tc(a), *c.rows('b', b, FMT, b_mod if b_mod > 0 else rows, D, optional=True),
+          _tc(b) if b is not None else 0, b_mod, po, ldo, _tc(out), rows, D)
+    if MAXABS is not None:
+        note_maxabs(out[:rows, :D], 'add_cast D=%d out' % D)
     return out
 
 
@@ -985,40 +982,40 @@ def token_embed(ids, tok, pos, out, status=None):
     """out[b L + l] = tok[ids[b, l]] + pos[l]: ids int32 [B, L], tok fp32 [vocab, D], pos fp32 [npos, D], out fp32 [B L, D] rows (the SigLIP text
     tower's embeddings).  The ids must be in range (the tower checks them on the host); the kernel never reads outside `tok` - an id that is not
     writes a zero row and PST_EINVAL into the optional int32 device scalar `status`."""
-    _dev(ids, torch.int32); _dev(tok, torch.float32); _dev(pos, torch.float32); _dev(out, torch.float32)
-    if status is not None:
-        _dev(status, torch.int32)
-    assert ids.dim() == 2 and ids.is_contiguous() and tok.is_contiguous() and pos.is_contiguous()
-    B, L = ids.shape
-    D = tok.shape[1]
-    assert pos.shape[1] == D and out.shape[0] >= B * L and out.shape[1] == D
-    _call('pst_token_embed', _ptr(ids), B, L, _ptr(tok), tok.shape[0], _ptr(pos), pos.shape[0], D, _ptr(out), _rowmajor(out), _ptr(status))
+    b = _Operands('token_embed')
+    pi, pt = b('ids', ids, I32, (-1, -1)), b('tok', tok, F32, (-1, -1))
+    (B, L), (vocab, D) = ids.shape, tok.shape
+    pp = b('pos', pos, F32, (-1, D))
+    po, ldo = b.rows('out', out, F32, B * L, D)
+    b.require(out.shape[1] == D, 'out must have the %d columns of tok, got %s', D, tuple(out.shape))
+    _call('pst_token_embed', pi, B, L, pt, vocab, pp, pos.shape[0], D, po, ldo, b.ge('status', status, I32, 1, optional=True))
     return out
 
 
 def l2norm_rows(x, out, eps):
-    _dev(x, torch.float32); _dev(out, *FMT)
-    _call('pst_l2norm_rows', _ptr(x), _rowmajor(x), _ptr(out), _rowmajor(out), x.shape[0], x.shape[1], eps, _tc(out))
+    b = _Operands('l2norm_rows')
+    px, ldx, rows, D = b.own('x', x, F32)
+    _call('pst_l2norm_rows', px, ldx, *b.rows('out', out, FMT, rows, D), rows, D, eps, _tc(out))
     return out
 
 
 @hbm_timed('mean4', lambda F, Fm, nimg, Hm, Wm, Cc: Fm.numel() * 2 * 5)
 def mean4(F, Fm, nimg, Hm, Wm, Cc):
-    _dev(F, *FMT); _dev(Fm, *FMT)
-    _call('pst_mean4', _ptr(F), _ptr(Fm), nimg, Hm, Wm, Cc, _fmt(F, Fm))
+    b, fmt = _Operands('mean4'), _fmt(F, Fm)
+    _call('pst_mean4', b('F', F, FMT, nimg * Hm * Wm * Cc), b('Fm', Fm, FMT, nimg * (Hm // 8) * (Wm // 8) * Cc), nimg, Hm, Wm, Cc, fmt)
     return Fm
 
 
 def resize_bilinear(F, Fd, nimg, Hs, Ws, Hd, Wd, Cc):
-    _dev(F, *FMT); _dev(Fd, *FMT)
-    _call('pst_resize_bilinear', _ptr(F), _ptr(Fd), nimg, Hs, Ws, Hd, Wd, Cc, _fmt(F, Fd))
+    b, fmt = _Operands('resize_bilinear'), _fmt(F, Fd)
+    _call('pst_resize_bilinear', b('F', F, FMT, nimg * Hs * Ws * Cc), b('Fd', Fd, FMT, nimg * Hd * Wd * Cc), nimg, Hs, Ws, Hd, Wd, Cc, fmt)
     return Fd
 
 
 def attn_mask_from_logits(logits, mask):
-    _dev(logits, torch.float32); _dev(mask, torch.uint8)
-    Q, Nk = logits.shape
-    _call('pst_attn_mask_from_logits', _ptr(logits), _rowmajor(logits), _ptr(mask), _rowmajor(mask), Q, Nk)
+    b = _Operands('attn_mask_from_logits')
+    pl, ldl, Q, Nk = b.own('logits', logits, F32)
+    _call('pst_attn_mask_from_logits', pl, ldl, *b.rows('mask', mask, U8, Q, Nk), Q, Nk)
     return mask
 
 
@@ -1031,47 +1028,49 @@ def stats_buffer(nimg, G, device):
 def loftup_guidance_gn(img, biases, gamma, beta, eps, scratch, stats, out, nf, mm=None):
     """Fourier guidance features + GroupNorm(1) straight to bf16 `out` [nimg*P, ld] (zero-padded columns); no fp32 feature buffer.
     mm: None = MinMaxScaler per view; else fp32 [nimg, 3, 2] (min, max) to scale with (loftup_minmax / minmax_merge: a scope of several views)."""
-    _dev(img, torch.float32); _dev(biases, torch.float32); _dev(scratch, torch.float32); _dev(stats, torch.float32); _dev(out, *FMT)
+    b = _Operands('loftup_guidance_gn')
+    pimg = b('img', img, F32, (-1, 3, -1, -1))
     n, _, h, w = img.shape
-    assert img.is_contiguous() and scratch.numel() >= n * (3 * (h // 2) * (w // 2) + 6)
-    if mm is not None:
-        _dev(mm, torch.float32)
-        assert mm.is_contiguous() and tuple(mm.shape) == (n, 3, 2)
-    _call('pst_loftup_guidance_gn', _ptr(img), _ptr(biases), _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)), eps, _ptr(scratch), _ptr(stats),
-          _ptr(out), _rowmajor(out), n, h, w, nf, _tc(out), _ptr(mm))
+    P, ch = (h // 2) * (w // 2), 10 * nf + 3
+    _call('pst_loftup_guidance_gn', pimg, b('biases', biases, F32, 10 * nf), b.ge('gamma', gamma, F32, ch), b.ge('beta', beta, F32, ch), eps,
+          b.ge('scratch', scratch, F32, n * (3 * P + 6)), b.ge('stats', stats, F32, n * 2 * (1 + STATS_BLOCKS)),
+          *b.rows('out', out, FMT, n * P, ch, fill=True), n, h, w, nf, _tc(out), b('mm', mm, F32, (n, 3, 2), optional=True))
     return out
 
 
 def loftup_minmax(img, mm):
     """per (view, channel) (min, max) of the 2x2-mean (= bilinear x0.5) image: img fp32 [n, 3, H, W] -> mm fp32 [n, 3, 2]"""
-    _dev(img, torch.float32); _dev(mm, torch.float32)
-    n, c, h, w = img.shape
-    assert c == 3 and img.is_contiguous() and mm.is_contiguous() and tuple(mm.shape) == (n, 3, 2)
-    _call('pst_loftup_minmax', _ptr(img), _ptr(mm), n, h, w)
+    b = _Operands('loftup_minmax')
+    pimg = b('img', img, F32, (-1, 3, -1, -1))
+    n, _, h, w = img.shape
+    _call('pst_loftup_minmax', pimg, b('mm', mm, F32, (n, 3, 2)), n, h, w)
     return mm
 
 
 def minmax_merge(mm, scope, out):
     """out[v] = (min, max) over the views u with scope[u] == scope[v] of mm[u] (the reference's MinMaxScaler over a chunk of views, loftup.py:14-19)"""
-    _dev(mm, torch.float32); _dev(scope, torch.int32); _dev(out, torch.float32)
-    n = scope.numel()
-    assert mm.is_contiguous() and out.is_contiguous() and tuple(mm.shape) == (n, 3, 2) and tuple(out.shape) == (n, 3, 2) and mm.data_ptr() != out.data_ptr()
-    _call('pst_minmax_merge', _ptr(mm), _ptr(scope), _ptr(out), n)
+    b = _Operands('minmax_merge')
+    ps, n = b.sized('scope', scope, I32)
+    pm, po = b('mm', mm, F32, (n, 3, 2)), b('out', out, F32, (n, 3, 2))
+    b.require(pm != po, 'out of place only: mm and out are the same buffer')
+    _call('pst_minmax_merge', pm, ps, po, n)
     return out
 
 
-@hbm_timed('groupnorm_stats', lambda x, stats, nimg, P, Cc, G: nimg * P * Cc * _esz(x))
+@hbm_timed('groupnorm_stats', lambda x, stats, nimg, P, Cc, G: nimg * P * Cc * x.element_size())
 def groupnorm_stats(x, stats, nimg, P, Cc, G):
-    _dev(x); _dev(stats, torch.float32)
-    _call('pst_groupnorm_stats', _ptr(x), _rowmajor(x), _tc(x), _ptr(stats), nimg, P, Cc, G)
+    """(sum, sum of squares) per (view, group) of the pixel-major x [nimg P, Cc] -> stats (stats_buffer: the result [nimg, G, 2], per-block partial sums behind it)"""
+    b = _Operands('groupnorm_stats')
+    _call('pst_groupnorm_stats', *b.rows('x', x, FMT, nimg * P, Cc), _tc(x), b.ge('stats', stats, F32, nimg * G * 2 * (1 + STATS_BLOCKS)), nimg, P, Cc, G)
 
 
-@hbm_timed('groupnorm_apply', lambda x, stats, gamma, beta, out, nimg, P, Cc, G, eps, relu, split=False: nimg * P * (Cc * _esz(x) + out.shape[1] * 2))
+@hbm_timed('groupnorm_apply', lambda x, stats, gamma, beta, out, nimg, P, Cc, G, eps, relu, split=False: nimg * P * (Cc * x.element_size() + out.shape[1] * 2))
 def groupnorm_apply(x, stats, gamma, beta, out, nimg, P, Cc, G, eps, relu, split=False):
-    """split=True: `out` f16 [rows, 3 x block] receives the split A operand rows [hi | hi | lo] (PST_X3H) of the conv that follows"""
-    _dev(x); _dev(out, *FMT)
-    _call('pst_groupnorm_apply', _ptr(x), _rowmajor(x), _tc(x), _ptr(stats), _ptr(gamma), _ptr(beta), _ptr(out), _rowmajor(out), nimg, P, Cc, G, eps, relu,
-          X3H if split else _tc(out))
+    """out [nimg P, >= Cc] = relu?(GroupNorm(x)) from stats [nimg, G, 2] (the head of a stats_buffer), every row zero-filled up to its leading dimension.
+    split=True: `out` f16 [rows, 3 x block] receives the split A operand rows [hi | hi | lo] (PST_X3H) of the conv that follows"""
+    b = _Operands('groupnorm_apply')
+    _call('pst_groupnorm_apply', *b.rows('x', x, FMT, nimg * P, Cc), _tc(x), b.ge('stats', stats, F32, nimg * G * 2), b('gamma', gamma, F32, Cc), b('beta', beta, F32, Cc),
+          *b.rows('out', out, X3_FMT if split else FMT, nimg * P, 3 * Cc if split else Cc, fill=True), nimg, P, Cc, G, eps, relu, X3H if split else _tc(out))
     return out
 
 
@@ -1080,13 +1079,15 @@ class Planes:
     __slots__ = ('hi', 'lo')
 
     def __init__(self, hi, lo):
-        assert hi.dtype == lo.dtype and hi.shape == lo.shape and hi.stride() == lo.stride()
+        if not (hi.dtype == lo.dtype and hi.shape == lo.shape and hi.stride() == lo.stride()):
+            raise RuntimeError('Planes: hi and lo must share dtype, shape and strides, got %s %s %s and %s %s %s' % (hi.dtype, tuple(hi.shape), hi.stride(), lo.dtype, tuple(lo.shape), lo.stride()))
         self.hi, self.lo = hi, lo
 
 
 def loftup_lr_pe(biases, out, col0, nimg, h, w):
-    _dev(biases, torch.float32); _dev(out, *FMT)
-    _call('pst_loftup_lr_pe', _ptr(biases), _ptr(out), _rowmajor(out), col0, nimg, h, w, _tc(out))
+    """the 20 low-res positional features of the h x w token grid into columns [col0, col0 + 20) of every view's rows of `out` [nimg h w, >= col0 + 20]"""
+    b = _Operands('loftup_lr_pe')
+    _call('pst_loftup_lr_pe', b.ge('biases', biases, F32, 20), *b.rows('out', out, FMT, nimg * h * w, col0 + 20), col0, nimg, h, w, _tc(out))
     return out
 
 
@@ -1124,7 +1125,6 @@ def pp_argmax(probs, scores, keep, Q, Hm, Wm, H, W, mask_threshold, best_q, best
 
 def pp_fused_fits(Q, Hm, Wm, H, W):
     """host copy of pst_pp_argmax_logits' footprint rule (8x32 output tiles, <= 1024 staged low-res pixels per query)."""
-    import math
     rh = min(Hm, math.ceil(8 * Hm / H) + 2)
     rw = min(Wm, math.ceil(32 * Wm / W) + 2)
     return 1024 // (rh * rw) >= 1

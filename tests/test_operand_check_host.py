@@ -1,5 +1,5 @@
-"""The host half of the binding's operand check (hip._check_operand: dtype, element count or shape, layout) on CPU tensors, and the structural
-property that `python -O` cannot remove a check: no `assert` statement in any engine wrapper of hip.py that reaches `_call`."""
+"""The host half of the binding's operand check (hip._check_operand: dtype, element count or shape, layout, the extent of a row view) on CPU tensors,
+and the structural property that `python -O` cannot remove a check: no `assert` statement anywhere in hip.py."""
 import ast
 import os
 
@@ -66,6 +66,57 @@ def test_views_that_are_not_dense():
     ok(torch.zeros(24)[::2], F32, 12, layout='any')
 
 
+def rows_ok(t, rows, cols, **kw):
+    ok(t, F32, (rows, cols), at_least=True, layout='rows', **kw)
+
+
+def rows_refused(t, rows, cols, needle, **kw):
+    refused(t, F32, (rows, cols), needle, at_least=True, layout='rows', **kw)
+
+
+def test_row_views():
+    """the host half of _Operands.rows: at least rows x cols at a leading dimension that keeps the rows apart"""
+    pad = torch.zeros(4, 6)[:, :3]
+    rows_ok(pad, 4, 3)                                                  # a padded view: leading dimension 6 over 3 columns
+    rows_ok(pad, 3, 2)                                                  # more than asked for
+    rows_ok(pad, -1, -1)                                                # its own extent
+    rows_ok(pad, 0, 0)
+    rows_refused(pad, 5, 3, 'shape')                                    # one row short
+    rows_refused(pad, 4, 4, 'shape')                                    # one column narrow
+    rows_refused(torch.zeros(3, 4).t(), 4, 3, 'row-major')              # a transposed view
+    rows_refused(torch.zeros(12), 4, 3, 'shape')                        # a 1-D tensor
+    rows_refused(torch.zeros(4, 3, 1), 4, 3, 'shape')
+    rows_refused(torch.zeros(24).as_strided((4, 3), (2, 1)), 4, 3, 'leading dimension')        # rows that overlap
+    rows_refused(torch.zeros(4, 1).expand(4, 3), 4, 3, 'row-major')
+    for ld in (0, 1, 2, 7):                                             # ONE row: any stride
+        rows_ok(torch.zeros(24).as_strided((1, 3), (ld, 1)), 1, 3)
+    rows_ok(torch.zeros(24).as_strided((4, 3), (2, 1)), 1, 3)           # ... also the first row of a view whose further rows overlap
+    refused(pad.double(), F32, (4, 3), 'dtype', at_least=True, layout='rows')
+    ok(None, F32, (4, 3), at_least=True, layout='rows', optional=True)
+    refused(None, F32, (4, 3), 'torch tensor', at_least=True, layout='rows')
+
+
+def test_row_views_that_the_kernel_fills_up_to_the_leading_dimension():
+    pad = torch.zeros(4, 6)[:, :3]                                      # the last row's padding reaches past the view, not past the storage
+    rows_ok(pad, 4, 3, fill=True)
+    cut = torch.zeros(23).as_strided((4, 3), (6, 1))                    # the same view of a buffer cut by one element
+    rows_ok(cut, 4, 3)
+    rows_refused(cut, 4, 3, 'storage', fill=True)
+    rows_ok(cut, 3, 3, fill=True)                                       # fewer rows filled: inside again
+    rows_ok(torch.zeros(30)[6:].as_strided((4, 3), (6, 1)), 4, 3, fill=True)
+    rows_refused(torch.zeros(30)[7:].as_strided((4, 3), (6, 1)), 4, 3, 'storage', fill=True)   # the storage offset counts
+    rows_refused(cut, -1, -1, 'storage', fill=True)
+
+
+def test_cpu_row_view_is_refused_by_the_device_half():
+    b = hip._Operands('some_wrapper')
+    assert b.rows('an_operand', None, F32, 4, 3, optional=True) == (None, 0)
+    with pytest.raises(RuntimeError, match='some_wrapper: an_operand .*shape'):
+        b.rows('an_operand', torch.zeros(3, 3), F32, 4, 3)
+    with pytest.raises(RuntimeError, match='some_wrapper: an_operand .*no CPU fallback'):
+        b.rows('an_operand', torch.zeros(4, 6)[:, :3], F32, 4, 3)
+
+
 def test_not_a_tensor():
     import numpy as np
     for t in (np.zeros(12, np.float32), [0.0] * 12, 12, 'x'):
@@ -90,37 +141,25 @@ def test_cpu_tensor_is_refused_by_the_device_half():
 
 
 # ---- the `python -O` property
-FIRST_ENGINE_WRAPPER = 'pp_scores'      # the in-scope half of hip.py starts here and runs to the end of the file
-
-
 def _calls(fn):
     return {n.func.id for n in ast.walk(fn) if isinstance(n, ast.Call) and isinstance(n.func, ast.Name)} | \
            {n.func.attr for n in ast.walk(fn) if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute)}
 
 
-def test_no_assert_in_an_engine_wrapper_that_reaches_call():
+def test_no_assert_anywhere_in_the_binding():
     path = os.path.join(os.path.dirname(os.path.abspath(hip.__file__)), 'hip.py')
     tree = ast.parse(open(path).read())
     fns = {}
     for node in ast.walk(tree):
         if isinstance(node, (ast.FunctionDef, ast.AsyncFunctionDef)):
             fns.setdefault(node.name, node)
-    start = fns[FIRST_ENGINE_WRAPPER].lineno
-    engine = {name: fn for name, fn in fns.items() if fn.lineno >= start}
-    assert len(engine) > 100, len(engine)
-    # reaches _call: calls it, or calls (by name) an in-scope function that does
-    reach = {name for name, fn in engine.items() if '_call' in _calls(fn)}
+    assert len(fns) > 200, len(fns)
+    # the parse is not empty: it finds the launching entry points of both halves - those that call _call, or call (by name) a function that does
+    reach = {name for name, fn in fns.items() if '_call' in _calls(fn)}
     grew = True
     while grew:
-        more = {name for name, fn in engine.items() if name not in reach and _calls(fn) & reach}
+        more = {name for name, fn in fns.items() if name not in reach and _calls(fn) & reach}
         grew, reach = bool(more), reach | more
-    assert len(reach) >= 70 and {'pp_finalize', 'icp_step', 'depth_errors', 'mesh_area_count'} <= reach, sorted(reach)      # the launching entry points
-    # ... and everything such a wrapper calls on the way: its helpers in that half, and the check itself
-    helpers = {h for name in reach for h in _calls(engine[name]) if h in engine} | reach
-    checked = [engine[n] for n in helpers] + [fns['_check_operand']] + \
-              [n for n in ast.walk(tree) if isinstance(n, ast.ClassDef) and n.name in ('_Operands', 'DepthTable')]
-    bad = [(getattr(fn, 'name', '?'), a.lineno) for fn in checked for a in ast.walk(fn) if isinstance(a, ast.Assert)]
-    assert not bad, 'assert statements that python -O removes: %s' % bad
-    # the two refusals no tensor carries are statements too
-    for name in ('_view_table', 'consist_view_table', 'depth_table'):
-        assert not [a for a in ast.walk(engine[name]) if isinstance(a, ast.Assert)], name
+    assert len(reach) >= 100 and {'pp_finalize', 'icp_step', 'depth_errors', 'mesh_area_count', 'layernorm', 'gemm', 'attention', 'patch_rows'} <= reach, sorted(reach)
+    bad = [a.lineno for a in ast.walk(tree) if isinstance(a, ast.Assert)]
+    assert not bad, 'assert statements that python -O removes, at lines %s' % bad
