@@ -824,7 +824,8 @@ int pst_mesh_interp(const int64_t* face, int ncams, int H, int W, const float* v
  *               face (wait-free union-find: the root is the component's smallest vertex row).  surface_components: component int32 [F] = that root,
  *               size[root] += 1 per face (int32 atomicAdd: a sum of integers).  surface_keep_count / pst_cloud_scan / surface_keep_emit: the faces
  *               with size[component] >= min_faces (>= 1) in their order, one per thread, PST_SURFACE_WG per workgroup: counts int32 [ceil(F / WG)].
- *               status int32 [1], zeroed by the caller: PST_VCC_RANGE (a face index outside [0, M)), PST_VCC_LOOP (a bounded loop ran out) - never on
+ *               status int32 [1], zeroed by the caller: PST_VCC_RANGE (a face index outside [0, M): that face is united with nothing, its component
+ *               is -1 and no size counts it, whichever of its corners it is), PST_VCC_LOOP (a bounded loop ran out: component -1) - never on
  *               the faces of surface_emit.  1 <= F <= 2^31 - 256, 1 <= M <= 2^30. */
 #define PST_SURFACE_WG 256
 int pst_surface_rows(const int64_t* index, int64_t M, int64_t N, int32_t* row, void* stream);

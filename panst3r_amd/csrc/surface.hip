@@ -152,13 +152,15 @@ __global__ __launch_bounds__(SF_T) void surface_link_kernel(const int32_t* __res
   cc_unite(parent, a, c, M, status);
 }
 
-// component[f] = the root of the face's first vertex (the links are final: plain loads, nothing written to parent), one count per face on its root
+// component[f] = the root of the face's first vertex (the links are final: plain loads, nothing written to parent), one count per face on its root.
+// A face with ANY corner outside the rows was joined to nothing by the link: it belongs to no component and is counted on none.
 __global__ __launch_bounds__(SF_T) void surface_root_kernel(const int32_t* __restrict__ faces, int F, int M, const int32_t* __restrict__ parent,
                                                             int32_t* __restrict__ component, int32_t* __restrict__ size, int32_t* __restrict__ status) {
   const int f = blockIdx.x * SF_T + threadIdx.x;
   if (f >= F) return;
   int x = faces[(int64_t)f * 3];
-  if ((unsigned)x >= (unsigned)M) { atomicOr(status, PST_VCC_RANGE); component[f] = -1; return; }
+  const int b = faces[(int64_t)f * 3 + 1], c = faces[(int64_t)f * 3 + 2];
+  if ((unsigned)x >= (unsigned)M || (unsigned)b >= (unsigned)M || (unsigned)c >= (unsigned)M) { atomicOr(status, PST_VCC_RANGE); component[f] = -1; return; }
   int r = parent[x], it = 0;
   for (; it < M && r != x; ++it) { x = r; r = parent[x]; }
   if (r != x) { atomicOr(status, PST_VCC_LOOP); component[f] = -1; return; }
