@@ -1103,7 +1103,8 @@ int pst_plane_icp_step(const float* source, int64_t N, float a00, float a01, flo
  *               same way to column id2row_g[i], or to the VOID COLUMN G.  Ids <= 0, ids beyond the table and ids not listed are all void (as
  *               pst_voxel_accumulate treats them).
  *   2 slabs     slab s holds the pixels [slab_off[s], slab_off[s + 1]) of the flat maps, slab_off int64 [nslabs + 1] on the device, ascending from 0 to
- *               N: one slab with every pixel of every view (scope 'scene'), or one slab per view (scope 'view').
+ *               N: one slab with every pixel of every view (scope 'scene'), or one slab per view (scope 'view').  Equal neighbours are allowed: such
+ *               a slab is EMPTY, holds no pixel wherever it lies (first, between two others, last), and its table stays as the caller cleared it.
  *   3 counts    counts int32 [nslabs, P+1, G+1], cleared by the CALLER: the number of pixels of slab s with (row p, column g).  int32 atomicAdd only,
  *               so the result does not depend on scheduling.  nslabs (P+1) (G+1) <= 2^31 - 1.  `merge` != 0 adds runs of equal keys inside a
  *               wave with one atomic (same results).
@@ -1164,7 +1165,7 @@ int pst_pq_match(const int32_t* counts, int nslabs, int P, int G, const int32_t*
  *               arithmetic on out (panst3r_amd/engine/depth_eval.py).  Log-space metrics are left out: a device log is not bit-identical to numpy's.
  * PST_EINVAL before any launch: a null operand (a null pred or gt address in a row included), nviews < 1, S < 1, K < 0 or K > 4, a stride < 1, npix < 1,
  * a total of pixels >= 2^31, first_block or slab entries that are not the ones step 3 names, a block count that is not nblocks, a hist that is not
- * 16-byte aligned. */
+ * 16-byte aligned, a min_depth that is negative or NaN (all three entry points: a valid g is then > 0, which step 4's bit order rests on). */
 #define PST_DEPTH_VIEW_WORDS 8    /* int64 words per row of the view table */
 #define PST_DEPTH_MOMENTS 16      /* doubles per row of partials and per slab in out */
 int pst_depth_median(const int64_t* views, const int64_t* views_host, int nviews, int nblocks, int nslabs, float min_depth, float max_depth, float conf_thr,

@@ -200,10 +200,17 @@ static int depth_table_ok(const char* what, const int64_t* views, const int64_t*
   return 0;
 }
 
+// the bit pattern of a valid g orders as its value only while g > 0: a negative (or NaN) lower bound would let negative depths through step 1
+static int depth_bounds_ok(const char* what, float min_depth) {
+  if (!(min_depth >= 0.f)) { pst::set_error("%s: min_depth %g; the lower bound is >= 0 (and no NaN)", what, (double)min_depth); return PST_EINVAL; }
+  return 0;
+}
+
 extern "C" int pst_depth_median(const int64_t* views, const int64_t* views_host, int nviews, int nblocks, int nslabs, float min_depth, float max_depth,
                                 float conf_thr, int32_t* hist, uint32_t* prefix, int32_t* rank, int32_t* count, float* median, void* stream) {
   using namespace pst;
   if (depth_table_ok("depth_median", views, views_host, nviews, nblocks, nslabs)) return PST_EINVAL;
+  if (depth_bounds_ok("depth_median", min_depth)) return PST_EINVAL;
   if (!hist || !prefix || !rank || !count || !median) { set_error("depth_median: null operand"); return PST_EINVAL; }
   if (((uintptr_t)hist) & 15) { set_error("depth_median: the histogram workspace must be 16-byte aligned"); return PST_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
@@ -223,6 +230,7 @@ extern "C" int pst_depth_moments(const int64_t* views, const int64_t* views_host
                                  float min_depth, float max_depth, float conf_thr, double* partials, double* out, void* stream) {
   using namespace pst;
   if (depth_table_ok("depth_moments", views, views_host, nviews, nblocks, nslabs)) return PST_EINVAL;
+  if (depth_bounds_ok("depth_moments", min_depth)) return PST_EINVAL;
   if (!slab_rows || !partials || !out) { set_error("depth_moments: null operand"); return PST_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(depth_sum_kernel<false>, dim3((unsigned)nblocks), dim3(ICP_T), 0, st, (const DepthView*)views, nviews, min_depth, max_depth, conf_thr,
@@ -238,6 +246,7 @@ extern "C" int pst_depth_errors(const int64_t* views, const int64_t* views_host,
                                 double* partials, double* out, void* stream) {
   using namespace pst;
   if (depth_table_ok("depth_errors", views, views_host, nviews, nblocks, nslabs)) return PST_EINVAL;
+  if (depth_bounds_ok("depth_errors", min_depth)) return PST_EINVAL;
   if (!slab_rows || !align || !partials || !out) { set_error("depth_errors: null operand"); return PST_EINVAL; }
   if (K < 0 || K > 4) { set_error("depth_errors: %d thresholds; one call takes 0 .. 4", K); return PST_EINVAL; }
   hipStream_t st = (hipStream_t)stream;

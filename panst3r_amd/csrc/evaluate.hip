@@ -2,7 +2,7 @@
 // pq_compute_single_core without iscrowd; restated in tests/eval_ref.py, [restated, parity unpinned]).  With P predicted and G ground-truth segments:
 //   rows     a predicted id i -> row id2row_p[i] if 0 < i < ntab_p and that entry is in [0, P), else the void row P; ground truth likewise -> a column,
 //            or the void column G.
-//   slabs    S slabs of consecutive pixels of the flat maps (scope 'scene': one; scope 'view': one per view), given by S + 1 offsets.
+//   slabs    S slabs of consecutive pixels of the flat maps (scope 'scene': one; scope 'view': one per view), given by S + 1 offsets; equal offsets: an empty slab.
 //   count    counts int32 [S, P+1, G+1] = pixels of slab s with (row p, column g): int32 atomicAdd only, independent of order.
 //   areas    pa[s,p] = sum_g counts[s,p,g], ga[s,g] = sum_p counts[s,p,g], void included; area 0 = the segment is not in the slab.
 //   match    g with ga > 0 and p with pa > 0 of one category: inter = counts[s,p,g], union = pa + ga - inter - counts[s,p,G]; a match iff

@@ -2171,11 +2171,19 @@ def depth_table(views, slabs, device):
     return DepthTable(rows, [int(s) for s in slabs], device, keep)
 
 
-def depth_median(table, min_depth, max_depth, conf_thr, count, median):
-    """count int32 [S], median fp32 [S, 2] = the exact medians (of pred, of gt) over the valid pixels of every slab"""
+def depth_median_workspace(table, device):
+    """the zeroed int32 workspace of depth_median: hist [S, 2, 2, 256], prefix [S, 2, 2] and rank [S, 2, 2] in one allocation; a call leaves it zeroed"""
+    return torch.zeros(table.nslabs * (2 * 2 * 256 + 4 + 4), dtype=torch.int32, device=device)
+
+
+def depth_median(table, min_depth, max_depth, conf_thr, count, median, ws=None):
+    """count int32 [S], median fp32 [S, 2] = the exact medians (of pred, of gt) over the valid pixels of every slab; ws = a `depth_median_workspace`
+    that is all zero (a call leaves it so), or None for a fresh one"""
     b = _Operands('depth_median')
     S, pc = table.nslabs, b('count', count, I32, table.nslabs)
-    ws = torch.zeros(S * (2 * 2 * 256 + 4 + 4), dtype=torch.int32, device=count.device)
+    if ws is None:
+        ws = depth_median_workspace(table, count.device)
+    b('ws', ws, I32, S * 1032)
     hist, prefix, rank = ws[:S * 1024], ws[S * 1024:S * 1028], ws[S * 1028:]
     _call('pst_depth_median', *table._args(b), S, float(min_depth), float(max_depth), float(conf_thr), b('hist', hist, I32, 1024 * S), b('prefix', prefix, I32, 4 * S),
           b('rank', rank, I32, 4 * S), pc, b('median', median, F32, 2 * S))

@@ -77,6 +77,30 @@ def tables(pred_maps, segments_info, gt_maps, gt_segments, scope='scene'):
             'pred_state': state}
 
 
+def tables_of_counts(counts, cat_p, cat_g):
+    """steps 4 - 6 over a GIVEN counts table [S, P+1, G+1] (hand-made ones included, whose cells need not come from any pair of maps) ->
+    dict(pred_area, gt_area, match, iou, pred_state).  Python integers, so nothing wraps; the first matching row of a column is kept."""
+    c = np.asarray(counts).astype(np.int64)
+    S, P, G = c.shape[0], c.shape[1] - 1, c.shape[2] - 1
+    cat_p, cat_g = np.asarray(cat_p, dtype=np.int64).reshape(-1), np.asarray(cat_g, dtype=np.int64).reshape(-1)
+    pa, ga = c[:, :P, :].sum(axis=2), c[:, :, :G].sum(axis=1)
+    match, iou, state = np.full((S, G), -1, dtype=np.int32), np.zeros((S, G), dtype=np.float64), np.zeros((S, P), dtype=np.int32)
+    for s in range(S):
+        for g in range(G):
+            if ga[s, g] == 0:
+                continue
+            for p in np.nonzero((pa[s] > 0) & (cat_p == cat_g[g]))[0]:
+                inter = int(c[s, p, g])
+                union = int(pa[s, p]) + int(ga[s, g]) - inter - int(c[s, p, G])
+                if 2 * inter > union and match[s, g] < 0:
+                    match[s, g], state[s, p] = p, MATCHED
+                    iou[s, g] = np.float64(inter) / np.float64(union)
+        for p in range(P):
+            if pa[s, p] > 0 and state[s, p] == ABSENT:
+                state[s, p] = IGNORED if 2 * int(c[s, p, G]) > int(pa[s, p]) else FP
+    return {'pred_area': pa.astype(np.int32), 'gt_area': ga.astype(np.int32), 'match': match, 'iou': iou, 'pred_state': state}
+
+
 def _mean(xs):
     return sum(xs) / len(xs) if xs else 0.0
 

@@ -169,3 +169,21 @@ def test_the_library_refuses_a_bad_table_without_a_device():
     assert L.pst_depth_errors(fake, good.ctypes.data, 2, 3, fake, 2, 0.0, 9.0, 1.0, fake, 5, 1.1, 1.2, 1.3, 1.4, fake, fake, None) == -1
     assert b'thresholds' in L.pst_last_error()
     assert L.pst_depth_median(fake, good.ctypes.data, 2, 3, 2, 0.0, 9.0, 1.0, fake + 4, fake, fake, fake, fake, None) == -1
+
+
+def test_the_library_refuses_a_negative_or_nan_lower_bound_without_a_device():
+    """a valid g is > min_depth; the median's bit order needs g > 0, so the three entry points refuse min_depth < 0 and NaN themselves, not only
+    the Python entry point; -0.0 is 0 and is accepted as far as the next refusal (a null output)"""
+    from panst3r_amd import hip
+    from panst3r_amd.build import build
+    build(verbose=False)
+    L = hip.lib()
+    fake = 4096
+    good = np.array([[fake, 1, fake, 0, 4097, 0, 0, 0], [fake, 3, fake, fake, 5, 2, 1, 0]], dtype=np.int64)
+    h = good.ctypes.data
+    for lo in (-1.0, -1e-45, float('-inf'), float('nan')):
+        for rc in (L.pst_depth_moments(fake, h, 2, 3, fake, 2, lo, 9.0, 1.0, fake, fake, None),
+                   L.pst_depth_errors(fake, h, 2, 3, fake, 2, lo, 9.0, 1.0, fake, 2, 1.1, 1.2, 1.3, 1.4, fake, fake, None),
+                   L.pst_depth_median(fake, h, 2, 3, 2, lo, 9.0, 1.0, fake, fake, fake, fake, fake, None)):
+            assert rc == -1 and b'min_depth' in L.pst_last_error(), lo
+    assert L.pst_depth_moments(fake, h, 2, 3, fake, 2, -0.0, 9.0, 1.0, fake, None, None) == -1 and b'null operand' in L.pst_last_error()

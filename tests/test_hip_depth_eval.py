@@ -261,6 +261,34 @@ def test_every_library_refusal_returns_without_a_launch():
     assert (out[:, 0] > 0).all() and (count > 0).all() and (ws == 0).all()       # the workspaces of the median are left zeroed
 
 
+def test_a_negative_or_nan_lower_bound_is_refused_without_a_launch():
+    """PST_EINVAL from all three entry points for min_depth < 0 and NaN: the outputs keep their sentinel and the workspaces stay zero; 0 and -0.0 run"""
+    pred, gt, conf = D.random_views([(9, 13)], seed=24, with_conf=False)
+    t = hip.depth_table([(dev(pred)[0], 1, dev(gt)[0], None)], [0], DEV)
+    L, st = hip.lib(), hip._stream()
+    f64 = dict(dtype=torch.float64, device=DEV)
+    partials, out, align = torch.full((1, hip.DEPTH_MOMENTS), -7.0, **f64), torch.full((1, hip.DEPTH_MOMENTS), -7.0, **f64), torch.ones(1, 2, **f64)
+    ws = torch.zeros(1032, dtype=torch.int32, device=DEV)
+    count, median = torch.full((1,), -7, dtype=torch.int32, device=DEV), torch.full((1, 2), -7.0, dtype=torch.float32, device=DEV)
+
+    def call(lo):
+        a = (t.dev.data_ptr(), t.host.ctypes.data, 1, 1)
+        return (L.pst_depth_moments(*a, t.slab_rows.data_ptr(), 1, lo, 9.0, 1.0, partials.data_ptr(), out.data_ptr(), st),
+                L.pst_depth_errors(*a, t.slab_rows.data_ptr(), 1, lo, 9.0, 1.0, align.data_ptr(), 1, 1.25, 0.0, 0.0, 0.0, partials.data_ptr(), out.data_ptr(), st),
+                L.pst_depth_median(*a, 1, lo, 9.0, 1.0, ws[:1024].data_ptr(), ws[1024:1028].data_ptr(), ws[1028:].data_ptr(), count.data_ptr(), median.data_ptr(), st))
+    for lo in (-1.0, -1e-45, float('-inf'), float('nan')):
+        assert call(lo) == (-1, -1, -1) and b'min_depth' in L.pst_last_error(), lo
+    torch.cuda.synchronize()
+    assert (partials == -7).all() and (out == -7).all() and (count == -7).all() and (median == -7).all() and (ws == 0).all()
+    with pytest.raises(RuntimeError, match='min_depth'):
+        hip.depth_median(t, -0.5, 9.0, 1.0, count, median)
+    want = int(D.valid(pred[0], gt[0], None, None, 0.0, 9.0).sum())
+    for lo in (0.0, -0.0):
+        assert call(lo) == (0, 0, 0)
+        torch.cuda.synchronize()
+        assert int(count[0]) == want > 60 and float(out[0, 0]) == want and (ws == 0).all()
+
+
 def test_the_call_copies_back_twice_at_most(monkeypatch):
     """one copy to the host after the alignment stage (none for 'none' or a given scale), one at the end: the call's only host syncs"""
     pred, gt, conf = D.random_views([(37, 51), (48, 64)], seed=23)
