@@ -452,7 +452,8 @@ int pst_retrieval_scores(const int32_t* q_off, const int32_t* q_word, const uint
  *                           index int64 [.]           offset + pixel: the point's position in the concatenated scene
  *                         Every output buffer must hold the scene's total number of points (M is only known on the device).
  *   cloud_segment_median  exact per-axis median of the rows of points_local whose pan id maps to a segment row: row = id2row[id] for 0 < id < ntab
- *                         (int32 [ntab], -1 = none; other ids take part in nothing), nseg rows.  Radix select, four byte passes.  m_ptr = device
+ *                         (int32 [ntab], -1 = none; other ids take part in nothing), nseg rows.  Radix select, four byte passes (csrc/radix_select.h is the one
+ *                         text of the passes, for this select and pst_depth_median's: signed keys here, groups of 3 slots).  m_ptr = device
  *                         pointer to M (base + n), max_points >= M sizes the grid.  Workspaces, all ZEROED by the caller: hist int32
  *                         [nseg, 3, 2, 256] (16-byte aligned; left zeroed), prefix uint32 / rank int32 [nseg, 3, 2], nan_cnt int32 [nseg, 3].
  *                         -> count int32 [nseg] (kept points of the segment), median fp32 [nseg, 3]: the middle element for an odd count,
@@ -1146,7 +1147,8 @@ int pst_pq_match(const int32_t* counts, int nslabs, int P, int G, const int32_t*
  *               (1, 0), a given scale, fp64(median g) / fp64(median p), sum pg / sum pp, or the least-squares pair from n, sum p, sum g, sum pp,
  *               sum pg - solved on the host in fp64 from pst_depth_moments / pst_depth_median.
  *               pst_depth_median: the exact fp32 medians of p and of g over the valid pixels of every slab by a four-pass radix select, most
- *               significant byte first.  Valid values are positive and finite, so their bit patterns order as the values do: the key is the bits,
+ *               significant byte first (csrc/radix_select.h is the one text of the passes, shared with pst_cloud_segment_median: the raw bits as
+ *               keys here, groups of 2 slots).  Valid values are positive and finite, so their bit patterns order as the values do: the key is the bits,
  *               with no rule for NaN or signed zero.  Histograms in LDS, flushed with int32 atomics (order-independent); a one-wave kernel narrows
  *               the two ranks (n - 1) / 2 and n / 2 after every pass.  median fp32 [S, 2] = (of p, of g): the middle element for an odd count,
  *               (a + b) * 0.5f in fp32 for an even one, NaN for n = 0; count int32 [S] = n.  Workspaces int32, ZEROED BY THE CALLER, left zeroed:

@@ -7,13 +7,15 @@
 //             world frame), rgb, pan, blended colour, scene index.  Every output is staged through LDS in slot order, so the global stores are
 //             contiguous runs and not 64 scattered 12-byte rows.
 //   median    exact per-segment, per-axis median of points_local by radix select on the order-preserving key of a float, most significant byte
-//             first, four passes: LDS histograms flushed with INTEGER atomics (order-independent), then a small kernel that narrows the ranks.
+//             first, four passes: LDS histograms flushed with INTEGER atomics (order-independent), then a small kernel that narrows the ranks
+//             (radix_select.h, shared with csrc/depth_eval.hip).
 // The arithmetic of compact is part of the contract (every product and every sum rounded on its own; the move of points_local is pinhole.h's
 // affine34, the workgroup -> view lookup its view_of, both shared with csrc/consistency.hip): contraction is off for the whole file.
 // No float atomics, every result written with plain vector stores.
 #include "common.h"
 #include "../../include/panst3r_hip.h"
 #include "pinhole.h"             // affine34, view_of, PH_VIEW_WG; and through it wave_ops.h: rn_mul, rn_add, wg_rank, wave_scan
+#include "radix_select.h"        // the median's select: keys, tally, flush, the narrow kernel and the loop over the four passes
 
 #pragma clang fp contract(off)
 
@@ -24,7 +26,7 @@ static_assert(CL_WG == PH_VIEW_WG, "first_wg of a pst_cloud_view table counts wo
 constexpr int CL_MAX_COLORS = 4096;                               // colour table rows that fit in LDS next to the staging buffer (48 + 12 KiB)
 constexpr int MD_SB = 8;                                          // segments per workgroup of the histogram pass: 8 x 3 axes x 2 ranks x 256 counters = 48 KiB
 constexpr int MD_SLICE = 32768;                                   // points per workgroup of the histogram pass
-constexpr int MD_ROW = 3 * 2 * 256;                               // counters per segment
+constexpr int MD_ROW = 3 * RS_SLOT;                               // counters per segment: one select slot per axis
 
 // bit k = point i0 + k exists and conf >= thr (a NaN confidence is dropped, as `conf >= thr` drops it in numpy)
 __device__ __forceinline__ int keep_mask(const float* __restrict__ conf, int npix, int i0, float thr) {
@@ -168,14 +170,9 @@ __global__ __launch_bounds__(CL_T) void cloud_compact_kernel(const pst_cloud_vie
   stage_out<2>(stage, ival, m, slot, cnt, (uint32_t*)(index + b0));
 }
 
-// ---------------------------------------------------------------- per-segment median
-// order-preserving key: a < b as floats <=> key(a) < key(b) as unsigned (-0.0 sorts just below +0.0; NaNs sort to the two ends and are counted apart)
-__device__ __forceinline__ uint32_t fkey(uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ uint32_t funkey(uint32_t k) { return (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; }
-
+// ---------------------------------------------------------------- per-segment median (the select itself: radix_select.h, signed keys, groups of 3)
 // grid (point slices, segment blocks).  A workgroup takes MD_SLICE points and the MD_SB segment rows [MD_SB blockIdx.y, ...): it reads pan for every
-// point and the coordinates of its own segments' points only.  pass 0: byte 3 of every key (one histogram per (segment, axis), shared by both ranks)
-// and the NaN counts; pass p: byte 3 - p of the keys whose higher bytes equal the rank's prefix.  LDS counters, flushed with integer atomics.
+// point and the coordinates of its own segments' points only, tallies each into the slot of its (segment, axis) and, in pass 0, counts the NaNs.
 __global__ __launch_bounds__(CL_T) void median_hist_kernel(const float* __restrict__ pts, const int32_t* __restrict__ pan, const int32_t* __restrict__ m_ptr,
                                                            const int32_t* __restrict__ id2row, int ntab, int S, int pass, const uint32_t* __restrict__ prefix,
                                                            int32_t* __restrict__ hist, int32_t* __restrict__ nan_cnt) {
@@ -192,7 +189,6 @@ __global__ __launch_bounds__(CL_T) void median_hist_kernel(const float* __restri
   if (tid < MD_SB * 3) nn[tid] = 0;
   if (tid < MD_SB * 6) pre[tid] = tid < nrow * 6 ? prefix[row0 * 6 + tid] : 0u;
   __syncthreads();
-  const int shift = 24 - 8 * pass;
   for (int i = (int)p0 + tid; i < p1; i += CL_T) {
     const int id = pan[i];
     if (id <= 0 || id >= ntab) continue;                           // void, or an id outside the table: never used as an index
@@ -201,76 +197,15 @@ __global__ __launch_bounds__(CL_T) void median_hist_kernel(const float* __restri
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const uint32_t u = __float_as_uint(pts[(int64_t)i * 3 + a]);
-      const uint32_t key = fkey(u);
-      if (pass == 0) {
-        atomicAdd(&h[(r * 3 + a) * 512 + (key >> 24)], 1);
+      if (pass == 0) {                                             // the NaN count shares the tally's (uniform) branch on the pass
+        select_tally(h, pre, r * 3 + a, select_key<true>(u), 0);
         if ((u & 0x7fffffffu) > 0x7f800000u) atomicAdd(&nn[r * 3 + a], 1);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          if ((key >> (shift + 8)) == (pre[(r * 3 + a) * 2 + j] >> (shift + 8))) atomicAdd(&h[((r * 3 + a) * 2 + j) * 256 + ((key >> shift) & 255)], 1);
-      }
+      } else select_tally(h, pre, r * 3 + a, select_key<true>(u), pass);
     }
   }
   __syncthreads();
-  for (int i = tid; i < nrow * MD_ROW; i += CL_T) {
-    const int c = h[i];
-    if (c) atomicAdd(&hist[(int64_t)row0 * MD_ROW + i], c);
-  }
+  select_flush<CL_T>(h, nrow * MD_ROW, hist + (int64_t)row0 * MD_ROW);
   if (pass == 0 && tid < nrow * 3 && nn[tid]) atomicAdd(&nan_cnt[row0 * 3 + tid], nn[tid]);
-}
-
-// One wave per (segment, axis): walks the two histograms (pass 0: the shared one), moves each rank into its bin, clears the counters for the next
-// pass.  After the last pass the prefix is the key of the order statistic: median = a for an odd count, (a + b) * 0.5f for an even one.
-__global__ __launch_bounds__(64) void median_narrow_kernel(int32_t* __restrict__ hist, uint32_t* __restrict__ prefix, int32_t* __restrict__ rank, int pass,
-                                                           const int32_t* __restrict__ nan_cnt, int32_t* __restrict__ count, float* __restrict__ median) {
-  const int sa = blockIdx.x, lane = threadIdx.x;                   // sa = segment * 3 + axis
-  const int shift = 24 - 8 * pass;
-  int n = 0;
-  uint32_t key[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    int4* hp = (int4*)(hist + ((int64_t)sa * 2 + (pass == 0 ? 0 : j)) * 256) + lane;
-    const int4 c = *hp;
-    const int own = c.x + c.y + c.z + c.w;
-    int s = own;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(s, o);
-      if (lane >= o) s += t;
-    }
-    const int tot = __shfl(s, 63);
-    int k;
-    if (pass == 0) { n = tot; k = j == 0 ? (tot - 1) / 2 : tot / 2; } else k = rank[sa * 2 + j];
-    // the bin that holds rank k: first bin whose inclusive count exceeds k
-    int below = s - own, bin = -1;
-    const int cc[4] = {c.x, c.y, c.z, c.w};
-    if (tot > 0 && k >= below && k < s) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (bin < 0) {
-          if (k < below + cc[q]) bin = 4 * lane + q; else below += cc[q];
-        }
-    }
-    const uint64_t who = __ballot(bin >= 0);
-    const int src = who ? __builtin_ctzll(who) : 0;
-    bin = __shfl(bin, src); below = __shfl(below, src);
-    const uint32_t pfx = (pass == 0 ? 0u : prefix[sa * 2 + j]) | ((uint32_t)max(bin, 0) << shift);
-    key[j] = pfx;
-    if (lane == 0) { prefix[sa * 2 + j] = pfx; rank[sa * 2 + j] = who ? k - below : 0; }
-  }
-  __syncthreads();                                                 // (one wave: both ranks have read the shared pass-0 histogram)
-  const int4 z = {0, 0, 0, 0};
-  ((int4*)(hist + (int64_t)sa * 512))[lane] = z;
-  ((int4*)(hist + (int64_t)sa * 512))[lane + 64] = z;
-  if (pass == 0 && lane == 0 && sa % 3 == 0) count[sa / 3] = n;
-  if (pass == 3 && lane == 0) {
-    const int cnt = count[sa / 3];
-    const float a = __uint_as_float(funkey(key[0])), b = __uint_as_float(funkey(key[1]));
-    float med = (cnt & 1) ? a : rn_mul(rn_add(a, b), 0.5f);
-    if (nan_cnt[sa] > 0 || cnt == 0) med = __uint_as_float(0x7fc00000u);
-    median[sa] = med;
-  }
 }
 
 }  // namespace pst
@@ -320,13 +255,7 @@ extern "C" int pst_cloud_segment_median(const float* points_local, const int32_t
   if (((uintptr_t)hist) & 15) { set_error("cloud_segment_median: the histogram workspace must be 16-byte aligned"); return PST_EINVAL; }
   const dim3 grid((unsigned)((max_points + MD_SLICE - 1) / MD_SLICE), (unsigned)((nseg + MD_SB - 1) / MD_SB));
   hipStream_t st = (hipStream_t)stream;
-  for (int pass = 0; pass < 4; ++pass) {
+  return select_passes<true, 3>("cloud_segment_median (histogram)", "cloud_segment_median (narrow)", [&](int pass) {
     hipLaunchKernelGGL(median_hist_kernel, grid, dim3(CL_T), 0, st, points_local, pan, m_ptr, id2row, ntab, nseg, pass, prefix, hist, nan_cnt);
-    int rc = check_launch("cloud_segment_median (histogram)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(median_narrow_kernel, dim3((unsigned)nseg * 3), dim3(64), 0, st, hist, prefix, rank, pass, nan_cnt, count, median);
-    rc = check_launch("cloud_segment_median (narrow)");
-    if (rc) return rc;
-  }
-  return 0;
+  }, nseg, hist, prefix, rank, nan_cnt, count, median, st);
 }

@@ -2,12 +2,13 @@
 // tests/depth_eval_ref.py, [restated, parity unpinned]).  Three stages over one table of views, so that a mixed-shape scene is one launch per stage:
 //   moments   n, sum p, sum g, sum pp, sum pg over the valid pixels of every slab: what a least-squares scale (and shift) is solved from on the host
 //   median    the exact fp32 medians of p and of g per slab by radix select on the float's bits, most significant byte first, four passes: LDS
-//             histograms flushed with INTEGER atomics (order-independent), then a one-wave kernel that narrows the two ranks
+//             histograms flushed with INTEGER atomics (order-independent), then a one-wave kernel that narrows the two ranks (radix_select.h, shared with csrc/cloud.hip)
 //   errors    with p' = s p + b in fp64: n, sum |d|/g, sum dd/g, sum dd, sum |d| and the inlier counts of up to four thresholds
 // The fp64 sums are added in the fixed order of icp_sum.h: a block of 256 lanes per 4096 pixels of ONE view, lane l its pixels l, l + 256, ...; the
 // butterfly, the four waves in order, one row of partials per block; then one reducer block per slab over the slab's rows.  No float atomics.
 // Every operation is part of the contract: contraction is off for the whole file.
-#include "icp_sum.h"             // icp_block_sum, ICP_T, ICP_ROWS; and through pinhole.h: common.h, wave_ops.h (last_le, rn_add, rn_mul), include/panst3r_hip.h
+#include "icp_sum.h"             // icp_block_sum, ICP_T, ICP_ROWS; and through pinhole.h: common.h, wave_ops.h (last_le), include/panst3r_hip.h
+#include "radix_select.h"        // the medians' select: keys, tally, flush, the narrow kernel and the loop over the four passes
 
 #pragma clang fp contract(off)
 
@@ -19,7 +20,7 @@ struct DepthView {                                                 // a row of t
 static_assert(sizeof(DepthView) == 8 * PST_DEPTH_VIEW_WORDS, "the row the header writes out");
 struct DepthThresholds { double t[4]; int K; };
 constexpr int DE_MOMENTS = PST_DEPTH_MOMENTS, DE_ALIGN = 5, DE_ERR = 9;   // doubles per row; live moments of the two sum kernels
-constexpr int DE_HIST = 2 * 2 * 256;                               // counters per slab: (p, g) x two ranks x 256 bins
+constexpr int DE_HIST = 2 * RS_SLOT;                               // counters per slab: one select slot for p, one for g
 
 __device__ __forceinline__ const DepthView& depth_view_of(const DepthView* __restrict__ views, int nviews, int blk) {
   return views[last_le(nviews, (int64_t)blk, [&](int v) { return views[v].first_block; })];
@@ -90,9 +91,8 @@ __global__ __launch_bounds__(ICP_T) void depth_reduce_kernel(const double* __res
   icp_block_sum<LIVE, DE_MOMENTS>(acc, out + (int64_t)s * DE_MOMENTS);
 }
 
-// ---------------------------------------------------------------- medians
-// One block per PST_ICP_CHUNK pixels of a view (the grid of the sums).  pass 0: byte 3 of the bits of p and of g (one histogram per quantity, shared by
-// both ranks); pass q: byte 3 - q of the values whose higher bytes equal the rank's prefix.  LDS counters, flushed with integer atomics.
+// ---------------------------------------------------------------- medians (the select itself: radix_select.h, the raw bits as keys, groups of 2)
+// One block per PST_ICP_CHUNK pixels of a view (the grid of the sums): tallies the bits of p and of g of every valid pixel into the slab's two slots.
 __global__ __launch_bounds__(ICP_T) void depth_hist_kernel(const DepthView* __restrict__ views, int nviews, float lo, float hi, float thr, int pass,
                                                            const uint32_t* __restrict__ prefix, int32_t* __restrict__ hist) {
   __shared__ int h[DE_HIST];
@@ -102,7 +102,6 @@ __global__ __launch_bounds__(ICP_T) void depth_hist_kernel(const DepthView* __re
   for (int i = tid; i < DE_HIST; i += ICP_T) h[i] = 0;
   if (tid < 4) pre[tid] = prefix[v.slab * 4 + tid];
   __syncthreads();
-  const int shift = 24 - 8 * pass;
   const int64_t i0 = ((int64_t)blk - v.first_block) * PST_ICP_CHUNK + tid;
   for (int j = 0; j < ICP_ROWS; ++j) {
     const int64_t i = i0 + (int64_t)j * ICP_T;
@@ -110,69 +109,10 @@ __global__ __launch_bounds__(ICP_T) void depth_hist_kernel(const DepthView* __re
     if (i >= v.npix || !depth_valid(v, i, lo, hi, thr, pf, gf)) continue;
     const uint32_t u[2] = {__float_as_uint(pf), __float_as_uint(gf)};
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      if (pass == 0) atomicAdd(&h[q * 512 + (u[q] >> 24)], 1);
-      else {
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-          if ((u[q] >> (shift + 8)) == (pre[q * 2 + r] >> (shift + 8))) atomicAdd(&h[(q * 2 + r) * 256 + ((u[q] >> shift) & 255)], 1);
-      }
-    }
+    for (int q = 0; q < 2; ++q) select_tally(h, pre, q, select_key<false>(u[q]), pass);
   }
   __syncthreads();
-  for (int i = tid; i < DE_HIST; i += ICP_T) {
-    const int c = h[i];
-    if (c) atomicAdd(&hist[v.slab * DE_HIST + i], c);
-  }
-}
-
-// One wave per (slab, quantity): walks the two histograms (pass 0: the shared one), moves each rank into its bin, clears the counters for the next
-// pass.  After the last pass the prefix is the bit pattern of the order statistic: median = a for an odd count, (a + b) * 0.5f for an even one.
-__global__ __launch_bounds__(64) void depth_narrow_kernel(int32_t* __restrict__ hist, uint32_t* __restrict__ prefix, int32_t* __restrict__ rank, int pass,
-                                                          int32_t* __restrict__ count, float* __restrict__ median) {
-  const int sq = blockIdx.x, lane = threadIdx.x;                   // sq = slab * 2 + quantity
-  const int shift = 24 - 8 * pass;
-  int n = 0;
-  uint32_t key[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int4 c = ((const int4*)(hist + ((int64_t)sq * 2 + (pass == 0 ? 0 : r)) * 256))[lane];
-    const int own = c.x + c.y + c.z + c.w;
-    const int s = wave_scan(own, lane);
-    const int tot = __shfl(s, 63);
-    int k;
-    if (pass == 0) { n = tot; k = r == 0 ? (tot - 1) / 2 : tot / 2; } else k = rank[sq * 2 + r];
-    // the bin that holds rank k: the first bin whose inclusive count exceeds k
-    int below = s - own, bin = -1;
-    const int cc[4] = {c.x, c.y, c.z, c.w};
-    if (tot > 0 && k >= below && k < s) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (bin < 0) {
-          if (k < below + cc[q]) bin = 4 * lane + q; else below += cc[q];
-        }
-    }
-    const uint64_t who = __ballot(bin >= 0);
-    const int src = who ? __builtin_ctzll(who) : 0;
-    bin = __shfl(bin, src); below = __shfl(below, src);
-    const uint32_t pfx = (pass == 0 ? 0u : prefix[sq * 2 + r]) | ((uint32_t)max(bin, 0) << shift);
-    key[r] = pfx;
-    if (lane == 0) { prefix[sq * 2 + r] = pfx; rank[sq * 2 + r] = who ? k - below : 0; }
-  }
-  __syncthreads();                                                 // (one wave: both ranks have read the shared pass-0 histogram)
-  const int4 z = {0, 0, 0, 0};
-  ((int4*)(hist + (int64_t)sq * 512))[lane] = z;
-  ((int4*)(hist + (int64_t)sq * 512))[lane + 64] = z;
-  if (pass == 0 && lane == 0 && (sq & 1) == 0) count[sq >> 1] = n;
-  if (pass == 3 && lane == 0) {
-    const int cnt = count[sq >> 1];                                // written by pass 0, three launches ago
-    const float a = __uint_as_float(key[0]), b = __uint_as_float(key[1]);
-    float med = (cnt & 1) ? a : rn_mul(rn_add(a, b), 0.5f);
-    if (cnt == 0) med = __uint_as_float(0x7fc00000u);
-    median[sq] = med;
-    prefix[sq * 2] = 0u; prefix[sq * 2 + 1] = 0u;                  // the workspaces are left as they came: zeroed
-    rank[sq * 2] = 0; rank[sq * 2 + 1] = 0;
-  }
+  select_flush<ICP_T>(h, DE_HIST, hist + v.slab * DE_HIST);
 }
 
 }  // namespace pst
@@ -214,16 +154,10 @@ extern "C" int pst_depth_median(const int64_t* views, const int64_t* views_host,
   if (!hist || !prefix || !rank || !count || !median) { set_error("depth_median: null operand"); return PST_EINVAL; }
   if (((uintptr_t)hist) & 15) { set_error("depth_median: the histogram workspace must be 16-byte aligned"); return PST_EINVAL; }
   hipStream_t st = (hipStream_t)stream;
-  for (int pass = 0; pass < 4; ++pass) {
+  return select_passes<false, 2>("depth_median (histogram)", "depth_median (narrow)", [&](int pass) {
     hipLaunchKernelGGL(depth_hist_kernel, dim3((unsigned)nblocks), dim3(ICP_T), 0, st, (const DepthView*)views, nviews, min_depth, max_depth, conf_thr, pass,
                        prefix, hist);
-    int rc = check_launch("depth_median (histogram)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(depth_narrow_kernel, dim3((unsigned)nslabs * 2), dim3(64), 0, st, hist, prefix, rank, pass, count, median);
-    rc = check_launch("depth_median (narrow)");
-    if (rc) return rc;
-  }
-  return 0;
+  }, nslabs, hist, prefix, rank, nullptr, count, median, st);
 }
 
 extern "C" int pst_depth_moments(const int64_t* views, const int64_t* views_host, int nviews, int nblocks, const int32_t* slab_rows, int nslabs,

@@ -253,6 +253,11 @@ def _wgs(n, wg=1024):       # workgroups of wg items (CLOUD_WG by default) over 
     return (n + wg - 1) // wg
 
 
+def _select_workspace(slots, device, nan=0, ws=None):       # csrc/radix_select.h's int32 workspace, zeroed (or the caller's ws) -> ws, hist [slots, 2, 256], prefix, rank [slots, 2], nan [slots * nan]
+    ws = torch.zeros(slots * (516 + nan), dtype=torch.int32, device=device) if ws is None else ws
+    return (ws, *ws.tensor_split([slots * 512, slots * 514, slots * 516]))
+
+
 class KernelTimer:
     """Optional per-launch HIP-event timing of the two MFMA kernels (bench.py roofline leg).  Events are recorded on
     torch's current stream, which is the stream the kernels are launched on."""
@@ -1315,8 +1320,7 @@ def cloud_segment_median(points_local, pan, m_ptr, id2row, nseg, count, median):
     device tensor holding M"""
     b = _Operands('cloud_segment_median')
     pp, pi = b.ge('pan', pan, I32, 0), b.ge('id2row', id2row, I32, 0)
-    ws = torch.zeros(nseg * (3 * 2 * 256 + 6 + 6 + 3), dtype=torch.int32, device=pan.device)
-    hist, prefix, rank, nan = ws[:nseg * 1536], ws[nseg * 1536:nseg * 1542], ws[nseg * 1542:nseg * 1548], ws[nseg * 1548:]
+    _, hist, prefix, rank, nan = _select_workspace(3 * nseg, pan.device, nan=1)
     _call('pst_cloud_segment_median', b('points_local', points_local, F32, 3 * pan.numel()), pp, b.ge('m_ptr', m_ptr, I32, 1), pan.numel(), pi, id2row.numel(),
           nseg, b('hist', hist, I32, 1536 * nseg), b('prefix', prefix, I32, 6 * nseg), b('rank', rank, I32, 6 * nseg), b('nan', nan, I32, 3 * nseg),
           b('count', count, I32, nseg), b('median', median, F32, 3 * nseg))
@@ -2173,7 +2177,7 @@ def depth_table(views, slabs, device):
 
 def depth_median_workspace(table, device):
     """the zeroed int32 workspace of depth_median: hist [S, 2, 2, 256], prefix [S, 2, 2] and rank [S, 2, 2] in one allocation; a call leaves it zeroed"""
-    return torch.zeros(table.nslabs * (2 * 2 * 256 + 4 + 4), dtype=torch.int32, device=device)
+    return _select_workspace(2 * table.nslabs, device)[0]
 
 
 def depth_median(table, min_depth, max_depth, conf_thr, count, median, ws=None):
@@ -2181,10 +2185,8 @@ def depth_median(table, min_depth, max_depth, conf_thr, count, median, ws=None):
     that is all zero (a call leaves it so), or None for a fresh one"""
     b = _Operands('depth_median')
     S, pc = table.nslabs, b('count', count, I32, table.nslabs)
-    if ws is None:
-        ws = depth_median_workspace(table, count.device)
-    b('ws', ws, I32, S * 1032)
-    hist, prefix, rank = ws[:S * 1024], ws[S * 1024:S * 1028], ws[S * 1028:]
+    b('ws', ws, I32, S * 1032, optional=True)
+    _, hist, prefix, rank, _ = _select_workspace(2 * S, count.device, ws=ws)
     _call('pst_depth_median', *table._args(b), S, float(min_depth), float(max_depth), float(conf_thr), b('hist', hist, I32, 1024 * S), b('prefix', prefix, I32, 4 * S),
           b('rank', rank, I32, 4 * S), pc, b('median', median, F32, 2 * S))
 

@@ -77,7 +77,7 @@ def median_ref(case, min_depth=0.0, max_depth=np.inf):
 
 
 def radix_median(b, m=None):
-    """the radix select of depth_hist_kernel / depth_narrow_kernel over the bits of the valid values of one (slab, quantity) -> the median's bits.
+    """the radix select of depth_hist_kernel / select_narrow_kernel over the bits of the valid values of one (slab, quantity) -> the median's bits.
     m = 'rank0_hist': rank 1 walks rank 0's histogram from pass 1 on; 'below_own_lane': `below` is not taken from the lane that holds the bin"""
     b = np.asarray(b, dtype=np.uint64)
     n = len(b)
