@@ -16,11 +16,13 @@
 
 namespace pst {
 
-#ifdef PST_ABL
-#define PST_ABL_E PST_ABL
-#else
-#define PST_ABL_E 0
+// Measurement builds only (tools/pp_ablate.sh; their results are garbage, only time matters).  PST_ABL, the persistent kernel's K loop: 1 no DMA,
+// 2 no LDS reads, 4 no barriers, 8 no MFMAs.  PST_ABL_E, the same bits as its epilogues read them: 16 no 16-bit stores, 32 no GELU, 64 no residual
+// loads, 128 no fp32 stores, 256 no 16-bit copy.
+#ifndef PST_ABL
+#define PST_ABL 0
 #endif
+#define PST_ABL_E PST_ABL
 #ifndef PST_RES_LA
 #define PST_RES_LA 2         // residual row fragments in flight ahead of the one being finished (3: 7-20 spilled registers, 4: 55-66; measurement builds override)
 #endif
@@ -402,7 +404,7 @@ __device__ __forceinline__ float mul_add_2r(float a, float b, float c) {
 // 4-column chunks summed in order, chunk pairs, quads, octets, halves.
 // TRANS: C^T (the attention V^T operand) -- the MFMA operands swap roles, so a lane owns one output column and, with perm_row8 on the A rows
 // instead of the W rows, 8 consecutive ROWS of it: 16-byte stores along V^T's contiguous axis.
-// PP (ping-pong, the default): the two 4-wave groups wm = 0 / 1 (one wave of each per SIMD) run the K loop ONE BARRIER APART.  A K tile is 4
+// THE K LOOP (ping-pong): the two 4-wave groups wm = 0 / 1 (one wave of each per SIMD) run the K loop ONE BARRIER APART.  A K tile is 4
 // phases of [L: ds_read the phase's fragments + issue LDS-DMA, wait for the reads | barrier | M: 16 MFMAs, nothing else | barrier]; while one
 // group is in an M segment the other is in an L segment, so every SIMD's matrix pipe is fed by one wave at a time with the other wave's LDS
 // reads, DMA issue and waits hidden behind it (guide: "256^2 8-phase template", the wr == 1 stagger).  Whole K tiles are prefetched TWO tiles
@@ -413,7 +415,7 @@ __device__ __forceinline__ float mul_add_2r(float a, float b, float c) {
 //   group 1:     L0 M0 L1 M1 L2 M2 L3 | M3 L0' ...       M0: (m0,n0)  M1: (m0,n1)  M2: (m1,n1)  M3: (m1,n0)      -- same K order: same bits
 // The kernel body: workgroup `bid` of the `nblk` workgroups that walk problem `p` (its `ntiles` tiles).  One problem per launch: (blockIdx.x, gridDim.x);
 // two problems per launch (gemm256p2_kernel below): each problem gets a contiguous range of the launch's workgroups.
-template <bool F16, bool RES, bool TRANS, bool PP, bool ROPE>
+template <bool F16, bool RES, bool TRANS, bool ROPE>
 __device__ __forceinline__ void gemm256p_body(const pst_gemm_params& p, const int ntiles, const int tiles_m, const int tiles_n, const int bid, const int nblk, char* smem) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -488,10 +490,7 @@ __device__ __forceinline__ void gemm256p_body(const pst_gemm_params& p, const in
       static_for<0, 2>([&](auto kk) { ds_read128<(ni * 32 + j * 16) * 128>(bfr[ni][j][kk], buf + (uint32_t)(b_off ^ (kk << 6))); });
     });
   };
-  // 16 MFMAs of quadrant (mi, ni), row fragment i outer (per accumulator the K halves stay in the order kk = 0, 1: same bits as ever).
-  //   mma_a: right after the A fragments were read (reads in the order B(ni) [earlier], A i = 0..3, then `pend` further reads): group i waits
-  //          until at most pend + 2 (3 - i) reads are outstanding, i.e. for af[i][*] only - the first MFMAs start after 2 of the 8 A reads;
-  //   mma_b: A valid already, waits for everything outstanding (the B fragments of this quadrant);   mma_n: all operands valid.
+  // 16 MFMAs of quadrant (mi, ni), row fragment i outer (per accumulator the K halves stay in the order kk = 0, 1: same bits as ever); all operands valid
   auto mma_group = [&](auto mi, auto ni, auto i) {
     static_for<0, 2>([&](auto kk) {
       static_for<0, 2>([&](auto j) {
@@ -500,23 +499,6 @@ __device__ __forceinline__ void gemm256p_body(const pst_gemm_params& p, const in
       });
     });
     __builtin_amdgcn_sched_barrier(0);
-  };
-  auto mma_a = [&](auto mi, auto ni, auto pend) {
-    __builtin_amdgcn_s_setprio(1);
-    static_for<0, 4>([&](auto i) {
-      lgkm_wait<pend + 2 * (3 - i)>(af[i][1]);
-      lds_tie(af[i][0]);
-      if constexpr (i == 0) static_for<0, 2>([&](auto j) { static_for<0, 2>([&](auto kk) { lds_tie(bfr[ni][j][kk]); }); });
-      mma_group(mi, ni, i);
-    });
-    __builtin_amdgcn_s_setprio(0);
-  };
-  auto mma_b = [&](auto mi, auto ni) {
-    __builtin_amdgcn_s_setprio(1);
-    lgkm_wait<0>(bfr[ni][0][0]);
-    lds_tie(bfr[ni][0][1]); lds_tie(bfr[ni][1][0]); lds_tie(bfr[ni][1][1]);
-    static_for<0, 4>([&](auto i) { mma_group(mi, ni, i); });
-    __builtin_amdgcn_s_setprio(0);
   };
   auto mma_n = [&](auto mi, auto ni) {
     __builtin_amdgcn_s_setprio(1);
@@ -611,108 +593,74 @@ __device__ __forceinline__ void gemm256p_body(const pst_gemm_params& p, const in
     float2* lnst = lnst_all + par * 256;
     float* coltab = coltab_all + par * 768;
     int2* postab = postab_all + par * 256;
-    if constexpr (PP) {
-      // ---- all of K tile 1 behind K tile 0: with the in-order vmcnt, "all but the 8 newest" = everything of K tile 0 (and every older store)
-      stage(2, 1); stage(3, 1); stage(0, 1); stage(1, 1);
-      if (nk > 1) PST_VMCNT(8); else PST_VMCNT(0);
-    } else {
-      // ---- B of K tile 1 last: with the in-order vmcnt, "all but the 4 newest" = everything of K tile 0 (and every older store)
-      stage(2, 1); stage(3, 1);
-      if (nk > 1) PST_VMCNT(4); else PST_VMCNT(0);
-    }
+    // ---- all of K tile 1 behind K tile 0: with the in-order vmcnt, "all but the 8 newest" = everything of K tile 0 (and every older store)
+    stage(2, 1); stage(3, 1); stage(0, 1); stage(1, 1);
+    if (nk > 1) PST_VMCNT(8); else PST_VMCNT(0);
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    if constexpr (PP) {
-      constexpr std::integral_constant<int, 0> c0{};
-      constexpr std::integral_constant<int, 1> c1{};
-#ifndef PST_ABL
-#define PST_ABL 0                          // measurement builds only (tools/pp_ablate.sh): 1 no DMA, 2 no LDS reads, 4 no barriers, 8 no MFMAs in the K loop
-#endif
-      auto seg_end = [&]() {               // end of an L or M segment: nothing moves across it
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(PST_ABL & 4)) __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      auto stage_l = [&](int which, int kt) { if (!(PST_ABL & 1)) stage(which, kt); };
-      auto read_a_l = [&](uint32_t b, auto mi) { if (!(PST_ABL & 2)) read_a(b, mi); };
-      auto read_b_l = [&](uint32_t b, auto ni) { if (!(PST_ABL & 2)) read_b(b, ni); };
-      auto mma_l = [&](auto mi, auto ni) { if (!(PST_ABL & 8)) mma_n(mi, ni); };
-      auto reads_done_a = [&]() {          // every outstanding LDS read of this wave has returned (the A fragments among them)
-        lgkm_wait<0>(af[0][0]);
-        static_for<0, 4>([&](auto i) { static_for<0, 2>([&](auto kk) { lds_tie(af[i][kk]); }); });
-      };
-      auto reads_done_b = [&](auto ni) {
-        lgkm_wait<0>(bfr[ni][0][0]);
-        static_for<0, 2>([&](auto j) { static_for<0, 2>([&](auto kk) { lds_tie(bfr[ni][j][kk]); }); });
-      };
-      // One K tile; F = the n half its FIRST quadrant takes (S = the other).  The B fragments of that half are already in bfr[F]: they were read in slot L3 of the
-      // previous K tile (bfr[F] of this tile = bfr[S] of that one, dead since its M2) - the L segments read 8 / 4 / 8 / 4 fragments instead of 12 / 4 / 8 / 0,
-      // none longer than an M segment (16 MFMAs = 256 cycles against 4 waves x 8 KB = 256 cycles of LDS).  Consecutive K tiles alternate F; every accumulator
-      // still receives its K products in ascending order: same bits.  For that early read, B(kt + 1) must have landed at the END of L2 (counted wait: all but
-      // A(kt + 1) and the B(kt + 2) pieces just issued; the barriers that end L2 and M2 carry the other waves' shares), A(kt + 1) at L3 as before.
-      auto ktile = [&](int kt, auto F) {
-        constexpr std::integral_constant<int, 1 - F> S{};
-        const uint32_t buf = lds0 + (uint32_t)((kt & 1) * BUF_BYTES), nbuf = lds0 + (uint32_t)(((kt + 1) & 1) * BUF_BYTES);
-        if (kt == 0) read_b_l(buf, F);       // L0 (the first K tile of an output tile has nothing preloaded)
-        read_a_l(buf, c0);
-        reads_done_a();
-        if (kt == 0) reads_done_b(F);
-        seg_end();
-        mma_l(c0, F);                      // M0
-        seg_end();
-        read_b_l(buf, S);                    // L1
-        reads_done_b(S);
-        seg_end();
-        mma_l(c0, S);                      // M1
-        seg_end();
-        read_a_l(buf, c1);                   // L2: the B halves of this buffer are dead (both groups' B reads retired two barriers ago)
-        stage_l(2, kt + 2); stage_l(3, kt + 2);
-        reads_done_a();
-        if (kt + 2 < nk) PST_VMCNT(8); else if (kt + 1 < nk) PST_VMCNT(4);
-        seg_end();
-        mma_l(c1, S);                      // M2
-        seg_end();
-        if (kt + 2 < nk) PST_VMCNT(4); else PST_VMCNT(0);      // L3: K tile kt + 1 has landed (this wave's share); A of this buffer is dead
-        stage_l(0, kt + 2); stage_l(1, kt + 2);
-        if (kt + 1 < nk) { read_b_l(nbuf, S); reads_done_b(S); }     // the next K tile's first half
-        seg_end();
-        mma_l(c1, F);                      // M3
-        seg_end();
-      };
-      if (wm == 1) seg_end();              // group 1 runs one barrier behind group 0
-      for (int kt = 0; kt < nk; kt += 2) {
-        ktile(kt, c0);
-        if (kt + 1 < nk) ktile(kt + 1, c1);
-      }
-      if (wm == 0) seg_end();              // re-align the groups for the epilogue
-    } else
-    for (int kt = 0; kt < nk; ++kt) {
-      const uint32_t buf = lds0 + (uint32_t)((kt & 1) * BUF_BYTES);
-      constexpr std::integral_constant<int, 0> c0{};
-      constexpr std::integral_constant<int, 1> c1{};
-      constexpr std::integral_constant<int, 4> c4{};
-      // phase 0 / 1: quadrants (m0,n0), (m0,n1); B(n1) is fetched while (m0,n0) is multiplied
-      read_b(buf, c0);
-      read_a(buf, c0);
-      stage(0, kt + 1);
-      read_b(buf, c1);
-      mma_a(c0, c0, c4);                   // 4 = the B(n1) reads issued behind the A reads
-      stage(1, kt + 1);
-      mma_b(c0, c1);
-      __builtin_amdgcn_s_barrier();        // every wave has finished its B reads of this buffer -> B halves may be refilled
-      // phase 2 / 3: quadrants (m1,n1), (m1,n0)
-      read_a(buf, c1);
-      stage(2, kt + 2);
-      mma_a(c1, c1, c0);
-      stage(3, kt + 2);
-      mma_n(c1, c0);
-      if (kt + 2 < nk) PST_VMCNT(4); else PST_VMCNT(0);
-      __builtin_amdgcn_s_barrier();
+    constexpr std::integral_constant<int, 0> c0{};
+    constexpr std::integral_constant<int, 1> c1{};
+    auto seg_end = [&]() {               // end of an L or M segment: nothing moves across it
+      __builtin_amdgcn_sched_barrier(0);
+      if (!(PST_ABL & 4)) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    auto stage_l = [&](int which, int kt) { if (!(PST_ABL & 1)) stage(which, kt); };
+    auto read_a_l = [&](uint32_t b, auto mi) { if (!(PST_ABL & 2)) read_a(b, mi); };
+    auto read_b_l = [&](uint32_t b, auto ni) { if (!(PST_ABL & 2)) read_b(b, ni); };
+    auto mma_l = [&](auto mi, auto ni) { if (!(PST_ABL & 8)) mma_n(mi, ni); };
+    auto reads_done_a = [&]() {          // every outstanding LDS read of this wave has returned (the A fragments among them)
+      lgkm_wait<0>(af[0][0]);
+      static_for<0, 4>([&](auto i) { static_for<0, 2>([&](auto kk) { lds_tie(af[i][kk]); }); });
+    };
+    auto reads_done_b = [&](auto ni) {
+      lgkm_wait<0>(bfr[ni][0][0]);
+      static_for<0, 2>([&](auto j) { static_for<0, 2>([&](auto kk) { lds_tie(bfr[ni][j][kk]); }); });
+    };
+    // One K tile; F = the n half its FIRST quadrant takes (S = the other).  The B fragments of that half are already in bfr[F]: they were read in slot L3 of the
+    // previous K tile (bfr[F] of this tile = bfr[S] of that one, dead since its M2) - the L segments read 8 / 4 / 8 / 4 fragments instead of 12 / 4 / 8 / 0,
+    // none longer than an M segment (16 MFMAs = 256 cycles against 4 waves x 8 KB = 256 cycles of LDS).  Consecutive K tiles alternate F; every accumulator
+    // still receives its K products in ascending order: same bits.  For that early read, B(kt + 1) must have landed at the END of L2 (counted wait: all but
+    // A(kt + 1) and the B(kt + 2) pieces just issued; the barriers that end L2 and M2 carry the other waves' shares), A(kt + 1) at L3 as before.
+    auto ktile = [&](int kt, auto F) {
+      constexpr std::integral_constant<int, 1 - F> S{};
+      const uint32_t buf = lds0 + (uint32_t)((kt & 1) * BUF_BYTES), nbuf = lds0 + (uint32_t)(((kt + 1) & 1) * BUF_BYTES);
+      if (kt == 0) read_b_l(buf, F);       // L0 (the first K tile of an output tile has nothing preloaded)
+      read_a_l(buf, c0);
+      reads_done_a();
+      if (kt == 0) reads_done_b(F);
+      seg_end();
+      mma_l(c0, F);                      // M0
+      seg_end();
+      read_b_l(buf, S);                    // L1
+      reads_done_b(S);
+      seg_end();
+      mma_l(c0, S);                      // M1
+      seg_end();
+      read_a_l(buf, c1);                   // L2: the B halves of this buffer are dead (both groups' B reads retired two barriers ago)
+      stage_l(2, kt + 2); stage_l(3, kt + 2);
+      reads_done_a();
+      if (kt + 2 < nk) PST_VMCNT(8); else if (kt + 1 < nk) PST_VMCNT(4);
+      seg_end();
+      mma_l(c1, S);                      // M2
+      seg_end();
+      if (kt + 2 < nk) PST_VMCNT(4); else PST_VMCNT(0);      // L3: K tile kt + 1 has landed (this wave's share); A of this buffer is dead
+      stage_l(0, kt + 2); stage_l(1, kt + 2);
+      if (kt + 1 < nk) { read_b_l(nbuf, S); reads_done_b(S); }     // the next K tile's first half
+      seg_end();
+      mma_l(c1, F);                      // M3
+      seg_end();
+    };
+    if (wm == 1) seg_end();              // group 1 runs one barrier behind group 0
+    for (int kt = 0; kt < nk; kt += 2) {
+      ktile(kt, c0);
+      if (kt + 1 < nk) ktile(kt + 1, c1);
     }
+    if (wm == 0) seg_end();              // re-align the groups for the epilogue
 
     const int cm0 = m0, cn0 = n0;
     slot += nblk;
@@ -998,29 +946,10 @@ __device__ __forceinline__ void gemm256p_body(const pst_gemm_params& p, const in
   }
 }
 
-// DE-PHASING (PST_TUNE_DEPHASE, round 6).  Every workgroup of a persistent launch alternates a K loop (matrix pipe, operands from L2 / MALL) with an epilogue
-// (HBM: stores, residual loads), and with equal tile costs the whole chip does so IN STEP: profiles/r6_gemm_k1024.txt - the per-tile fixed part of a launch is
-// exactly its epilogue bytes x 256 CUs at the ~5.2 TB/s the box sustains (plain 16-bit store 6.7 us, fp32 residual class 31.4 us per round), with the matrix
-// cores idle meanwhile.  With the workgroups in G phase groups (group = (index / 8) % G: every XCD holds every phase) that start e / G apart - e = that
-// all-CU epilogue time - only 1 / G of the chip is in its epilogue at any time, each epilogue takes e / G, and the offsets persist (steady state).  Cost: the
-// last group ends (G - 1) e / G late; gain: (rounds - 1) (G - 1) e / G.
-__device__ __forceinline__ void dephase_wait(int bid, int dephase_g, int dephase_ticks) {
-  if (dephase_g > 1) {
-    const int grp = (bid >> 3) % dephase_g;
-    if (grp) {
-      const uint64_t t0 = wall_clock64();
-      const int64_t ticks = (int64_t)grp * dephase_ticks;
-      while ((int64_t)(wall_clock64() - t0) < ticks) __builtin_amdgcn_s_sleep(8);
-    }
-  }
-}
-
-template <bool F16, bool RES, bool TRANS, bool PP, bool ROPE>
-__global__ __launch_bounds__(512, 1) void gemm256p_kernel(const pst_gemm_params p, const int ntiles, const int tiles_m, const int tiles_n, const int dephase_g,
-                                                          const int dephase_ticks) {
+template <bool F16, bool RES, bool TRANS, bool ROPE>
+__global__ __launch_bounds__(512, 1) void gemm256p_kernel(const pst_gemm_params p, const int ntiles, const int tiles_m, const int tiles_n) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  dephase_wait(blockIdx.x, dephase_g, dephase_ticks);
-  gemm256p_body<F16, RES, TRANS, PP, ROPE>(p, ntiles, tiles_m, tiles_n, blockIdx.x, gridDim.x, smem);
+  gemm256p_body<F16, RES, TRANS, ROPE>(p, ntiles, tiles_m, tiles_n, blockIdx.x, gridDim.x, smem);
 }
 
 // TWO independent problems of the same class in one launch (pst_gemm_pair): workgroups [0, g0) walk problem 0, [g0, gridDim.x) problem 1.  Tile
@@ -1032,25 +961,14 @@ struct gemm256p2_args {
   pst_gemm_params p[2];
   int ntiles[2], tiles_m[2], tiles_n[2];
   int g0;
-  int delay_ticks;        // start delay of problem 1's workgroups in 100 MHz ticks (0: none), see gemm256p_pair_delay_us
-  int dephase_g, dephase_ticks;      // phase groups within each problem (dephase_wait)
 };
-template <bool F16, bool RES, bool TRANS, bool PP, bool ROPE>
+template <bool F16, bool RES, bool TRANS, bool ROPE>
 __global__ __launch_bounds__(512, 1) void gemm256p2_kernel(const gemm256p2_args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int which = (int)blockIdx.x >= a.g0 ? 1 : 0;
   const int bid = which ? (int)blockIdx.x - a.g0 : (int)blockIdx.x;
   const int nblk = which ? (int)gridDim.x - a.g0 : a.g0;
-  // DE-PHASING: every workgroup of a persistent launch alternates a K loop (matrix pipe, operands from L2) with an epilogue (HBM: stores, residual
-  // loads), and with equal tile costs the whole chip does so in step - the epilogue bursts meet a saturated HBM while the matrix cores idle, then the
-  // reverse (profiles/r3_gemm_pp_ablation.txt: 92 us of loop + 86 us of epilogue traffic that do not overlap).  With two problems in the launch, the
-  // second one's workgroups start half a tile period late: its epilogues fall into the first one's K loops for the rest of the launch.
-  if (which && a.delay_ticks > 0) {
-    const uint64_t t0 = wall_clock64();
-    while ((int64_t)(wall_clock64() - t0) < (int64_t)a.delay_ticks) __builtin_amdgcn_s_sleep(32);
-  }
-  dephase_wait(bid, a.dephase_g, a.dephase_ticks);
-  gemm256p_body<F16, RES, TRANS, PP, ROPE>(a.p[which], a.ntiles[which], a.tiles_m[which], a.tiles_n[which], bid, nblk, smem);
+  gemm256p_body<F16, RES, TRANS, ROPE>(a.p[which], a.ntiles[which], a.tiles_m[which], a.tiles_n[which], bid, nblk, smem);
 }
 
 constexpr int LDS256 = 2 * BUF_BYTES + 256 * (int)sizeof(float2);      // operand buffers + the LayerNorm-fold row table
@@ -1090,60 +1008,25 @@ int gemm256_persistent_class(const pst_gemm_params& p) {
 }
 bool gemm256_persistent_ok(const pst_gemm_params& p) { return gemm256_persistent_class(p) != 0; }
 
-// PST_TUNE_G256_PP: 1 (default) = the ping-pong K loop, 0 = the lock-step loop of rounds 2-3 (A/B measurements; bit-identical)
-static int g_g256_pp = 1;
-int gemm256_pp(int set) {
-  const int prev = g_g256_pp;
-  if (set == 0 || set == 1) g_g256_pp = set;
-  return prev;
+// The one place that picks an instantiation of the persistent kernels: class `cls` (gemm256_persistent_class), 16-bit format, and - plain class only - the
+// variant that can rotate.  `go` gets the four template arguments <F16, RES, TRANS, ROPE> as integral constants; the single-problem and the pair
+// launcher share it.
+template <class Go>
+static void with_256p_variant(int cls, bool f16, bool rope, Go go) {
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  auto of_format = [&](auto res, auto trans, auto rot) {
+    if (f16) go(yes, res, trans, rot); else go(no, res, trans, rot);
+  };
+  if (cls == 3) of_format(no, yes, no);
+  else if (cls == 2) of_format(yes, no, no);
+  else if (rope) of_format(no, no, yes);
+  else of_format(no, no, no);
 }
-
-// PST_TUNE_DEPHASE: G * 1000 + percent (of the modelled step e / G); 0 = off.  e = epilogue bytes of one tile x workgroups of the launch / 5.2 TB/s.
-static int g_dephase = 0;
-int gemm256p_dephase(int set) {
-  const int prev = g_dephase;
-  if (set >= 0 && set < 64000) g_dephase = set;
-  return prev;
-}
-static inline double epilogue_bytes(const pst_gemm_params& p, int cls) {
-  return cls == 2 ? 256.0 * 256.0 * 8.0 + (p.xcopy ? 256.0 * 256.0 * 2.0 : 0.0) : 256.0 * 256.0 * 2.0;
-}
-// (groups, ticks between groups) of a launch whose `wgs` workgroups move `bytes` per round of epilogues; rounds < 2: nothing to gain
-static inline void dephase_plan(double bytes, double rounds, int* g, int* ticks) {
-  *g = 0; *ticks = 0;
-  const int G = g_dephase / 1000, pct = g_dephase % 1000;
-  if (G < 2 || pct <= 0 || rounds < 1.5) return;
-  const double e_us = bytes / 5.2e6;                       // all workgroups in their epilogue at once, at 5.2 TB/s
-  *g = G;
-  *ticks = (int)(e_us / G * pct / 100.0 * 100.0);         // microseconds -> 100 MHz ticks
-}
-
-template <bool F16, bool RES, bool TRANS, bool PP, bool ROPE>
-static void launch_256p_r(const pst_gemm_params& p, hipStream_t s, int grid, int tiles, int tiles_m, int tiles_n) {
+template <auto Kernel>
+static void allow_lds256p() {          // once per device and instantiation
   static unsigned long long attr_seen = 0;
-  once_per_device(attr_seen, [] { (void)hipFuncSetAttribute((const void*)gemm256p_kernel<F16, RES, TRANS, PP, ROPE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS256P); });
-  int dg, dt;
-  dephase_plan(epilogue_bytes(p, RES ? 2 : 1) * grid, (double)tiles / grid, &dg, &dt);
-  hipLaunchKernelGGL((gemm256p_kernel<F16, RES, TRANS, PP, ROPE>), dim3(grid), dim3(512), LDS256P, s, p, tiles, tiles_m, tiles_n, dg, dt);
-}
-template <bool F16, bool RES, bool TRANS, bool PP>
-static void launch_256p_t(const pst_gemm_params& p, hipStream_t s, int grid, int tiles, int tiles_m, int tiles_n) {
-  if constexpr (!RES && !TRANS) {
-    if (p.rope_hd == 64) { launch_256p_r<F16, RES, TRANS, PP, true>(p, s, grid, tiles, tiles_m, tiles_n); return; }
-  }
-  launch_256p_r<F16, RES, TRANS, PP, false>(p, s, grid, tiles, tiles_m, tiles_n);
-}
-
-template <bool RES, bool TRANS>
-static void launch_256p_c(const pst_gemm_params& p, hipStream_t s, int grid, int tiles, int tiles_m, int tiles_n) {
-  const bool h = p.dtype16 == DT_F16;
-  if (g_g256_pp) {
-    if (h) launch_256p_t<true, RES, TRANS, true>(p, s, grid, tiles, tiles_m, tiles_n);
-    else launch_256p_t<false, RES, TRANS, true>(p, s, grid, tiles, tiles_m, tiles_n);
-  } else {
-    if (h) launch_256p_t<true, RES, TRANS, false>(p, s, grid, tiles, tiles_m, tiles_n);
-    else launch_256p_t<false, RES, TRANS, false>(p, s, grid, tiles, tiles_m, tiles_n);
-  }
+  once_per_device(attr_seen, [] { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS256P); });
 }
 
 // Time model of the persistent kernel (microseconds; fitted to profiles/r3_shape_profile.txt and r3_gemm_pp_ablation.txt): a 256 x 256 tile costs
@@ -1177,53 +1060,8 @@ double gemm256p_single_us(const pst_gemm_params& p, int cus) {
   return ((t + cus - 1) / cus) * tile_us(p, gemm256_persistent_class(p));
 }
 
-template <bool F16, bool RES, bool TRANS, bool PP, bool ROPE>
-static void launch_256p2_r(const gemm256p2_args& a, hipStream_t s, int grid) {
-  static unsigned long long attr_seen = 0;
-  once_per_device(attr_seen, [] { (void)hipFuncSetAttribute((const void*)gemm256p2_kernel<F16, RES, TRANS, PP, ROPE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS256P); });
-  hipLaunchKernelGGL((gemm256p2_kernel<F16, RES, TRANS, PP, ROPE>), dim3(grid), dim3(512), LDS256P, s, a);
-}
-template <bool F16, bool RES, bool TRANS, bool PP>
-static void launch_256p2_t(const gemm256p2_args& a, hipStream_t s, int grid) {
-  if constexpr (!RES && !TRANS) {          // the rotating variant when either problem carries positions
-    if (a.p[0].rope_hd == 64 || a.p[1].rope_hd == 64) { launch_256p2_r<F16, RES, TRANS, PP, true>(a, s, grid); return; }
-  }
-  launch_256p2_r<F16, RES, TRANS, PP, false>(a, s, grid);
-}
-template <bool RES, bool TRANS>
-static void launch_256p2_c(const gemm256p2_args& a, hipStream_t s, int grid) {
-  const bool h = a.p[0].dtype16 == DT_F16;
-  if (g_g256_pp) {
-    if (h) launch_256p2_t<true, RES, TRANS, true>(a, s, grid); else launch_256p2_t<false, RES, TRANS, true>(a, s, grid);
-  } else {
-    if (h) launch_256p2_t<true, RES, TRANS, false>(a, s, grid); else launch_256p2_t<false, RES, TRANS, false>(a, s, grid);
-  }
-}
-
-// PST_TUNE_PAIR_DELAY: start delay of the second problem of a shared launch in % of a tile period (0 = off, the default).  Applied when the model says
-// it could pay: the delayed problem ends `delay` later, each of its rounds overlaps about half an epilogue - worth it when rounds x epilogue / 2 > delay.
-// MEASURED (profiles/r4_pair_ab.txt, same box, 10 graph-replayed scenes each, twice): 0 % 304.1 / 303.7 frames/s, 25 % 303.2, 50 % 302.0 / 302.8,
-// 75 % 301.7 - the delay costs more at the end of the launch than the de-phased epilogues give back (tried, negative, kept as a knob).
-static int g_pair_delay_pct = 0;
-int gemm256p_pair_delay(int set) {
-  const int prev = g_pair_delay_pct;
-  if (set >= 0 && set <= 200) g_pair_delay_pct = set;
-  return prev;
-}
-static int pair_delay_ticks(const pst_gemm_params& pa, const pst_gemm_params& pb, int cus, int g0) {
-  if (g_pair_delay_pct <= 0) return 0;
-  const int cls = gemm256_persistent_class(pb);
-  const double tile = tile_us(pb, cls), epi = 1.94 * (cls == 2 ? 15 : 8), delay = tile * g_pair_delay_pct / 100.0;
-  const long tb = (long)((pb.M + 255) / 256) * ((pb.N + 255) / 256);
-  const long rounds = (tb + (cus - g0) - 1) / (cus - g0);
-  if (rounds * epi * 0.5 <= delay * 1.2) return 0;
-  (void)pa;
-  return (int)(delay * 100.0);          // microseconds -> 100 MHz ticks
-}
-
 int launch_gemm256p_pair(const pst_gemm_params& pa, const pst_gemm_params& pb, hipStream_t s, int cus, int g0) {
   gemm256p2_args a;
-  a.delay_ticks = pair_delay_ticks(pa, pb, cus, g0);
   a.p[0] = pa; a.p[1] = pb;
   const pst_gemm_params* ps[2] = {&pa, &pb};
   for (int i = 0; i < 2; ++i) {
@@ -1232,12 +1070,12 @@ int launch_gemm256p_pair(const pst_gemm_params& pa, const pst_gemm_params& pb, h
     a.ntiles[i] = a.tiles_m[i] * a.tiles_n[i];
   }
   a.g0 = g0;
-  const int cls = gemm256_persistent_class(pa);
-  dephase_plan(epilogue_bytes(pa, cls) * g0 + epilogue_bytes(pb, cls) * (cus - g0), std::min((double)a.ntiles[0] / g0, (double)a.ntiles[1] / (cus - g0)), &a.dephase_g,
-               &a.dephase_ticks);
-  if (cls == 3) launch_256p2_c<false, true>(a, s, cus);
-  else if (cls == 2) launch_256p2_c<true, false>(a, s, cus);
-  else launch_256p2_c<false, false>(a, s, cus);
+  // (the rotating variant when either problem carries positions)
+  with_256p_variant(gemm256_persistent_class(pa), pa.dtype16 == DT_F16, pa.rope_hd == 64 || pb.rope_hd == 64, [&](auto f16, auto res, auto trans, auto rope) {
+    constexpr auto kernel = gemm256p2_kernel<f16, res, trans, rope>;
+    allow_lds256p<kernel>();
+    hipLaunchKernelGGL(kernel, dim3(cus), dim3(512), LDS256P, s, a);
+  });
   return check_launch("gemm256p (pair)");
 }
 
@@ -1245,10 +1083,11 @@ int launch_gemm256p(const pst_gemm_params& p, hipStream_t s, int cus) {
   const int tiles_m = (p.M + 255) / 256, tiles_n = (p.N + 255) / 256;
   const int tiles = tiles_m * tiles_n;
   const int grid = tiles < cus ? tiles : cus;
-  const int cls = gemm256_persistent_class(p);
-  if (cls == 3) launch_256p_c<false, true>(p, s, grid, tiles, tiles_m, tiles_n);
-  else if (cls == 2) launch_256p_c<true, false>(p, s, grid, tiles, tiles_m, tiles_n);
-  else launch_256p_c<false, false>(p, s, grid, tiles, tiles_m, tiles_n);
+  with_256p_variant(gemm256_persistent_class(p), p.dtype16 == DT_F16, p.rope_hd == 64, [&](auto f16, auto res, auto trans, auto rope) {
+    constexpr auto kernel = gemm256p_kernel<f16, res, trans, rope>;
+    allow_lds256p<kernel>();
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), LDS256P, s, p, tiles, tiles_m, tiles_n);
+  });
   return check_launch("gemm256p");
 }
 

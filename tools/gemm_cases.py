@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """GEMM cases of the scene's big shapes with realistic epilogue arguments (LayerNorm fold consumer / producer outputs, fused RoPE, GELU,
-fp32 residual stream, transposed store), shared by the GEMM measurement tools (tools/dispatch_bench.py, pp_bench.py, ...).  GPU box only."""
+fp32 residual stream, transposed store), shared by the GEMM measurement tools (tools/dispatch_bench.py, pp_time.py, ...).  GPU box only."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

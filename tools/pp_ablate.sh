@@ -1,8 +1,8 @@
 #!/bin/bash
-# Measurement builds of gemm256.hip (ablations / schedule experiments of the ping-pong K loop).  Results of ablation builds are garbage, only time matters.
+# Measurement builds of gemm256.hip (ablations / schedule experiments of the persistent kernel's K loop and epilogues).  Results of ablation builds are garbage, only time matters.
 #   tools/pp_ablate.sh build name1:-DPST_ABL=1 name2:-DPST_PPV=1 ...     (here, no GPU needed; -> panst3r_amd/lib/abl/lib_<name>.so)
-#   tools/pp_ablate.sh run "name1 name2" M N K kind                        (GPU box)
-# PST_ABL bits: 1 no DMA, 2 no LDS reads, 4 no barriers, 8 no MFMAs in the K loop.
+#   tools/pp_ablate.sh run "name1 name2" M N K kind [workgroups]           (GPU box; the arguments of tools/pp_time.py)
+# PST_ABL bits: 1 no DMA, 2 no LDS reads, 4 no barriers, 8 no MFMAs in the K loop; the epilogue bits are listed at the top of gemm256.hip.
 set -e
 ROOT=$(cd $(dirname $0)/.. && pwd); L=$ROOT/panst3r_amd/lib
 if [ "$1" = build ]; then
